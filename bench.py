@@ -2,6 +2,7 @@
 """Benchmark of the MPPI hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--graph ITERATIONS]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one MPPI iteration: sample control noise -> roll every control
 sample through the horizon with traction-grid lookups -> min-subtract +
@@ -37,6 +38,13 @@ problem of N*world samples (noise is keyed by the global sample index).
 Prints ONE JSON line (rank 0).  If the RCCL communicator cannot be created the ranks
 exchange their packets through the host (the TCP hub) instead and the JSON says so
 (config.exchange).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds
+everything else the line can carry: the repeated regions (ms_per_step_median / _min;
+15 unless --regions says otherwise), the event-bracketed stages and per-kernel
+durations with the roofline built on them, the CPU baselines (`bb`: also the notebook's
+5 x 5 %timeit).  `--dump-outputs DIR` writes what the last timed step computed --
+the control sequence `u` and the rollout costs `costs`, float32 -- as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -169,6 +177,27 @@ def batch_problems(count, rng):
                    axis=1).astype(np.float32)
     goals = np.stack([rng.uniform(4, 60, count), rng.uniform(4, 60, count)], axis=1).astype(np.float32)
     return x0s, goals
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs`: every array as directory/<name>.npy in float32.  An array that would take the dump past
+    DUMP_BUDGET_BYTES is replaced by a fixed, seeded sample of its flattened elements (<name>.npy) and the sample's
+    positions (<name>_index.npy, float64), so that two runs with the same arguments write the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > left:
+            k = max(0, (left - 8 * 4096) // 12)  # 4 bytes per sampled value + 8 per position, room for the headers
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def algorithmic_bytes(w, n, rp, cp, rollout_writes_noise=True, fused=False):
@@ -353,15 +382,8 @@ def bench_barebone(args, result_fd):
         useq = planner.solve()
     elapsed = time.perf_counter() - t0
     assert useq.shape == (t, 2) and np.isfinite(useq).all()
-    runs = []
-    for _ in range(5):  # %timeit -n 5 -r 5
-        t1 = time.perf_counter()
-        for _ in range(5):
-            planner.solve()
-        runs.append((time.perf_counter() - t1) / 5)
-    # per-kernel durations of the three launches of a solve (begin / end timestamps of the dispatches)
-    us_roll, us_upd = C.c_float(), C.c_float()
-    _lib.call("mppi_planner_time_kernels", planner._handle, None, None, 200, C.byref(us_roll), C.byref(us_upd))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"u": useq, "costs": planner.costs_d.copy_to_host()})
     kernel = C.create_string_buffer(512)
     _lib.call("mppi_planner_describe_last_rollout", planner._handle, kernel, 512)
     ms_per_step = 1e3 * elapsed / args.steps
@@ -376,22 +398,34 @@ def bench_barebone(args, result_fd):
                                "a step = one solve() call wall-clocked on the host, as the notebook's %timeit",
                    "rollouts_per_gpu": n, "horizon_steps": t, "rollout_kernel": kernel.value.decode(),
                    "rng": "Philox4x32-10 counters (rocRAND-identical engine) + hardware Box-Muller", "math": "exact"},
-        "solve_ms_timeit_5x5": {"mean": 1e3 * float(np.mean(runs)), "std": 1e3 * float(np.std(runs)),
-                                "how": "5 runs of 5 solve() calls each, mean +- std of the per-call time over the runs (%timeit -n 5 -r 5)"},
         "reference_published": BB_PUBLISHED,
         "speedup_vs_published": BB_PUBLISHED["value_ms"] / ms_per_step,
         "speedup_note": "other hardware (the reference publishes no MI355X number): a ratio of wall times per solve() call, "
                         "dominated on both sides by launch and host overhead, not by arithmetic",
-        "kernel_us_in_loop": {"rollout": us_roll.value, "update": us_upd.value},
-        "roofline": {"bound": "hbm", "kernel": kernel.value.decode().split(" ")[0], "achieved": bytes_roll / (us_roll.value * 1e-6) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bytes_roll / (us_roll.value * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                     "traffic": None, "algorithmic_bytes_per_launch": bytes_roll,
-                     "note": "16 waves of one lane per rollout walking 50 dependent steps: a latency measurement, not a bandwidth one"},
         "roofline_iteration": {"bound": "hbm", "achieved": bytes_iter / (ms_per_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                                "unit": "GB/s", "frac": bytes_iter / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                "algorithmic_bytes_per_step": bytes_iter},
     }
-    if not args.no_cpu_baseline:
+    if args.full:
+        runs = []
+        for _ in range(5):  # %timeit -n 5 -r 5
+            t1 = time.perf_counter()
+            for _ in range(5):
+                planner.solve()
+            runs.append((time.perf_counter() - t1) / 5)
+        # per-kernel durations of the three launches of a solve (begin / end timestamps of the dispatches)
+        us_roll, us_upd = C.c_float(), C.c_float()
+        _lib.call("mppi_planner_time_kernels", planner._handle, None, None, 200, C.byref(us_roll), C.byref(us_upd))
+        out.update({
+            "solve_ms_timeit_5x5": {"mean": 1e3 * float(np.mean(runs)), "std": 1e3 * float(np.std(runs)),
+                                    "how": "5 runs of 5 solve() calls each, mean +- std of the per-call time over the runs (%timeit -n 5 -r 5)"},
+            "kernel_us_in_loop": {"rollout": us_roll.value, "update": us_upd.value},
+            "roofline": {"bound": "hbm", "kernel": kernel.value.decode().split(" ")[0], "achieved": bytes_roll / (us_roll.value * 1e-6) / 1e9,
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bytes_roll / (us_roll.value * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                         "traffic": None, "algorithmic_bytes_per_launch": bytes_roll,
+                         "note": "16 waves of one lane per rollout walking 50 dependent steps: a latency measurement, not a bandwidth one"},
+        })
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         p = O.make_params(params, 1.0, [0, 0], [0, 0], [0.0, 1.0], [0.0, 1.0], default_obs_cost=1e3, default_dist_weight=10)
         pos, rad = params["obstacle_positions"], params["obstacle_radius"]
@@ -436,9 +470,14 @@ def main():
     ap.add_argument("--problems", type=int, default=None, help="c5: problems per GPU (default 64)")
     ap.add_argument("--math", default="exact", choices=["exact", "fast"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--regions", type=int, default=15,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure everything else the line can carry: repeated regions, "
+                         "event-bracketed stages, per-kernel durations and the roofline, the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", dest="dump_outputs",
+                    help="after the timed steps, write what the last one computed (u, costs; float32) as DIR/<name>.npy")
+    ap.add_argument("--regions", type=int, default=None,
                     help="repeat the K-step timed region this many more times (ms_per_step stays the FIRST region; "
-                         "median / min over all regions are reported beside it)")
+                         "median / min over all regions are reported beside it).  Default 15 with --full, else 0")
     ap.add_argument("--debug-flags", type=int, default=0,
                     help="developer switches (include/mppi_hip.h MPPI_DEBUG_*): which kernel variant runs (experiments)")
     ap.add_argument("--graph", type=int, default=0, metavar="ITERATIONS",
@@ -465,6 +504,8 @@ def main():
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N from ONE process driving N devices (mppi_group_*) instead of one process per GPU")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 15 if args.full else 0
 
     from mppi_numba_amd import launch
     if args.gpus > 1 and not args.single_process and not launch.launched_by_a_launcher():
@@ -775,6 +816,8 @@ def main():
     per_rank = region["per_rank"]
     elapsed = region["elapsed"]
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:  # what the last timed step computed, before anything else runs on the handle
+        dump_outputs(args.dump_outputs, {"u": planner.u_cur_d.copy_to_host(), "costs": planner.costs_d.copy_to_host()})
     # The contract's number is the region above, one shot (K x ~17 us at C2: a fraction of a millisecond).  The
     # same region again, `--regions` times, each bracketed the same way: the spread IS the measurement's noise.
     region_ms = [ms_per_step]
@@ -795,21 +838,24 @@ def main():
     rccl_ranks = planner.comm_count()
 
     # ---- per-kernel durations with HIP events on the planner's stream ---------------
-    planner.set_profiling(True)
     stage = dict(noise=0.0, rollout=0.0, update=0.0, collective=0.0)
-    reps = 0 if ((world > 1 and args.exchange == "host" and not problems) or group_size > 1 or args.no_kernel_timing) else 50
-    for _ in range(reps):
-        planner.iterate_async(3)  # the middle iteration is profiled: steady state
-        planner.synchronize()
-        for k, v in planner.stage_times_ms().items():
-            stage[k] += v / reps
-    planner.set_profiling(False)
+    reps = 0 if ((world > 1 and args.exchange == "host" and not problems) or group_size > 1 or args.no_kernel_timing
+                 or not args.full) else 50
+    if args.full:
+        planner.set_profiling(True)
+        for _ in range(reps):
+            planner.iterate_async(3)  # the middle iteration is profiled: steady state
+            planner.synchronize()
+            for k, v in planner.stage_times_ms().items():
+                stage[k] += v / reps
+        planner.set_profiling(False)
     # the dominant kernels inside the ordinary loop: every launch carries its own start / stop HIP
     # events, which the runtime fills with the dispatch's begin / end timestamps (what rocprofv3
     # --kernel-trace reports); nothing is inserted between the kernels
     # (every rank runs it: with RCCL the iterations it times contain the all-gather, a collective)
     kernel_us = None
-    if group_size == 1 and not args.graph and not (world > 1 and args.exchange == "host" and not problems) and not args.no_kernel_timing:
+    if args.full and group_size == 1 and not args.graph and not (world > 1 and args.exchange == "host" and not problems) \
+            and not args.no_kernel_timing:
         kernel_us = planner.time_kernels(200)
         if kernel_us[0] <= 0.0:  # (a loop on two streams whose rollout kernel does not stamp its launch: not timed in the loop)
             kernel_us = None
@@ -825,11 +871,12 @@ def main():
                                                rollout_writes_noise=(kernel_name in ("k_rollout_pipe",)),
                                                fused=fused)
     traffic = None
-    try:  # HBM bytes per launch of the dominant kernel, from the committed rocprofv3 PMC passes
-        with open(os.path.join(ROOT, "profiles", "traffic.json")) as fh:
-            traffic = json.load(fh).get(traffic_key(args.workload, n_local, args.math), {}).get("dominant_kernel_hbm_bytes_per_launch")
-    except (OSError, ValueError):
-        pass
+    if args.full:
+        try:  # HBM bytes per launch of the dominant kernel, from the committed rocprofv3 PMC passes
+            with open(os.path.join(ROOT, "profiles", "traffic.json")) as fh:
+                traffic = json.load(fh).get(traffic_key(args.workload, n_local, args.math), {}).get("dominant_kernel_hbm_bytes_per_launch")
+        except (OSError, ValueError):
+            pass
     roll_s = kernel_us[0] * 1e-6 if kernel_us else stage["rollout"] * 1e-3
     # (host-staged exchange / device group: the loop is driven stage by stage from Python, no kernel is timed)
     achieved = bytes_roll / roll_s / 1e9 if roll_s > 0 else None
@@ -881,50 +928,53 @@ def main():
         "closing_barrier_ms": 1e3 * closing_barrier_s,
         "timing_note": "ms_per_step = the slowest rank's wall time of its own K steps (stream drained), over K; the closing "
                        "barrier is outside the timed region and reported beside it",
-        "event_bracketed_ms": stage,
-        "event_bracketed_ms_note": "each stage of ONE iteration bracketed by its own HIP events on the planner's stream; every "
-                          "bracket adds ~3 us of event overhead, so the stages sum to more than ms_per_step (which has "
-                          "no events inside the loop); kernel_us_in_loop has no such overhead",
-        "kernel_us_in_loop": None if not kernel_us else
-            {"rollout": kernel_us[0], "update": kernel_us[1],
-             "how": "200 ordinary iterations of one call; every rollout / update launch carries its own start / stop HIP "
-                    "events (hipExtLaunchKernelGGL: the dispatch's begin / end timestamps, as rocprofv3 --kernel-trace "
-                    "reports them; averages agree with profiles/).  A loop that runs the next iteration's noise on a second "
-                    "stream (N*T >= 4M: ns, c4) is timed WITHOUT events -- they shift such a loop (mppi_api.hip, "
-                    "mppi_planner_time_kernels) -- by its kernels themselves: first wave in to last wave out on the device's "
-                    "100 MHz clock.  `update` is the update launches' time per ITERATION: "
-                    "when the next rollout launch applies the update itself (rollout_kernel says applies_update=1) only "
-                    "the last iteration of a call has an update launch and its time is spread over all of them"},
-        # the line must follow from its parts: the dominant launches of an iteration cannot last longer than the iteration
-        "accounting": None if not kernel_us else
-            {"rollout_plus_update_us": kernel_us[0] + kernel_us[1], "step_us": 1e3 * ms_per_step,
-             "ok": bool(kernel_us[0] + kernel_us[1] <= 1.05 * 1e3 * max(ms_per_step, float(np.median(region_ms))))},
-        "roofline": {"bound": "hbm",
-                     "kernel": kernel_name + (" (rollout + next iteration's noise)" if kernel_name in ("k_rollout_pipe",) else
-                                              " (noise + rollout + per-tile update sums)" if fused else ""),
-                     "fused": fused,
-                     "fused_note": ("the launch samples the noise, rolls out and reduces the update per tile; the noise never "
-                                    "exists in memory, so `traffic` is a small fraction of `algorithmic_bytes_per_launch` and "
-                                    "the kernel is bound by instruction issue and by the walks of the float32-rounded running "
-                                    "sums, not by HBM (priced against the reference's dataflow as SURVEY.md 8d prescribes)") if fused else None,
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": None if achieved is None else achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     # (for a fused launch `achieved` is a speed-of-job index, not bus utilisation)
-                     "algorithmic_equivalent_GBps": achieved,
-                     "hbm_GBps_measured": None if (traffic is None or roll_s <= 0) else traffic / roll_s / 1e9,
-                     "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                       "kernel on this workload (committed; not re-measured in this run)",
-                     "algorithmic_bytes_per_launch": bytes_roll,
-                     "launch_ms": roll_s * 1e3 if roll_s > 0 else None,
-                     "duration_source": "kernel_us_in_loop.rollout" if kernel_us else
-                                        ("event_bracketed_ms.rollout" if roll_s > 0 else
-                                         "not measured in this mode (stage-level loop driven from Python: --exchange host / --single-process)")},
         "roofline_iteration": {"bound": "hbm", "achieved": bytes_iter / (ms_per_step * 1e-3) / 1e9,
                                "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": bytes_iter / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                "algorithmic_bytes_per_step": bytes_iter},
     }
-    if not args.no_cpu_baseline and world * group_size == 1:
+    if args.full:
+        out.update({
+            "event_bracketed_ms": stage,
+            "event_bracketed_ms_note": "each stage of ONE iteration bracketed by its own HIP events on the planner's stream; every "
+                              "bracket adds ~3 us of event overhead, so the stages sum to more than ms_per_step (which has "
+                              "no events inside the loop); kernel_us_in_loop has no such overhead",
+            "kernel_us_in_loop": None if not kernel_us else
+                {"rollout": kernel_us[0], "update": kernel_us[1],
+                 "how": "200 ordinary iterations of one call; every rollout / update launch carries its own start / stop HIP "
+                        "events (hipExtLaunchKernelGGL: the dispatch's begin / end timestamps, as rocprofv3 --kernel-trace "
+                        "reports them; averages agree with profiles/).  A loop that runs the next iteration's noise on a second "
+                        "stream (N*T >= 4M: ns, c4) is timed WITHOUT events -- they shift such a loop (mppi_api.hip, "
+                        "mppi_planner_time_kernels) -- by its kernels themselves: first wave in to last wave out on the device's "
+                        "100 MHz clock.  `update` is the update launches' time per ITERATION: "
+                        "when the next rollout launch applies the update itself (rollout_kernel says applies_update=1) only "
+                        "the last iteration of a call has an update launch and its time is spread over all of them"},
+            # the line must follow from its parts: the dominant launches of an iteration cannot last longer than the iteration
+            "accounting": None if not kernel_us else
+                {"rollout_plus_update_us": kernel_us[0] + kernel_us[1], "step_us": 1e3 * ms_per_step,
+                 "ok": bool(kernel_us[0] + kernel_us[1] <= 1.05 * 1e3 * max(ms_per_step, float(np.median(region_ms))))},
+            "roofline": {"bound": "hbm",
+                         "kernel": kernel_name + (" (rollout + next iteration's noise)" if kernel_name in ("k_rollout_pipe",) else
+                                                  " (noise + rollout + per-tile update sums)" if fused else ""),
+                         "fused": fused,
+                         "fused_note": ("the launch samples the noise, rolls out and reduces the update per tile; the noise never "
+                                        "exists in memory, so `traffic` is a small fraction of `algorithmic_bytes_per_launch` and "
+                                        "the kernel is bound by instruction issue and by the walks of the float32-rounded running "
+                                        "sums, not by HBM (priced against the reference's dataflow as SURVEY.md 8d prescribes)") if fused else None,
+                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": None if achieved is None else achieved / HBM_PEAK_GBS, "traffic": traffic,
+                         # (for a fused launch `achieved` is a speed-of-job index, not bus utilisation)
+                         "algorithmic_equivalent_GBps": achieved,
+                         "hbm_GBps_measured": None if (traffic is None or roll_s <= 0) else traffic / roll_s / 1e9,
+                         "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                           "kernel on this workload (committed; not re-measured in this run)",
+                         "algorithmic_bytes_per_launch": bytes_roll,
+                         "launch_ms": roll_s * 1e3 if roll_s > 0 else None,
+                         "duration_source": "kernel_us_in_loop.rollout" if kernel_us else
+                                            ("event_bracketed_ms.rollout" if roll_s > 0 else
+                                             "not measured in this mode (stage-level loop driven from Python: --exchange host / --single-process)")},
+        })
+    if args.full and not args.no_cpu_baseline and world * group_size == 1:
         # (the CPU legs are timed at N = 1 only: with several ranks the others would sit at the closing barrier for it)
         with quiet:
             out["cpu_baseline"] = cpu_baseline(w, params, lin, ang, planner)

@@ -2,10 +2,11 @@
 for config / mppi / terrain and finds the reference's host-side helpers (density,
 visualization, utils) in a reference checkout; without one they do not resolve (they are out of
 this repository's scope) and the ImportError says where to point MPPI_NUMBA_REFERENCE.
-Reference notebooks' first cell: /root/reference/test.ipynb cell 1 (all five notebooks start
-with the same imports)."""
+IMPORT_CELL: the mppi_numba imports of the reference notebooks' first cell (all five notebooks
+start with the same imports)."""
 import importlib
 import os
+import shutil
 import subprocess
 import sys
 
@@ -13,8 +14,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
-HAVE_REFERENCE = os.path.isfile(os.path.join(REFERENCE, "mppi_numba", "density.py"))
 
 IMPORT_CELL = """
 from mppi_numba.density import Density, GaussianMixture
@@ -64,37 +63,25 @@ def test_the_test_suites_stand_ins_resolve_through_the_same_hook():
     assert lines[1] == os.path.join(ROOT, "mppi_numba_amd", "mppi.py")
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference checkout on this box")
+@pytest.fixture
+def reference_checkout(tmp_path):
+    """A directory laid out like a checkout of the reference -- its `mppi_numba` package with the host-side helper
+    modules -- holding the suite's stand-ins (tests/standins/): what is tested is where the helpers are taken from."""
+    pkg = tmp_path / "mppi_numba"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("")
+    for name in ("density", "visualization", "utils"):
+        shutil.copy(os.path.join(ROOT, "tests", "standins", name + ".py"), str(pkg / (name + ".py")))
+    return str(tmp_path)
+
+
 @pytest.mark.parametrize("how", ["pythonpath", "env"])
-def test_import_cell_with_reference_forwards_the_host_helpers(how):
-    if how == "pythonpath":   # the verdict's reproduction: PYTHONPATH=/root/repo:/root/reference
-        lines = run_py(IMPORT_CELL, ROOT + ":" + REFERENCE)
+def test_import_cell_with_reference_forwards_the_host_helpers(how, reference_checkout):
+    if how == "pythonpath":   # the checkout behind this repository on PYTHONPATH
+        lines = run_py(IMPORT_CELL, ROOT + ":" + reference_checkout)
     else:
-        lines = run_py(IMPORT_CELL, ROOT, {"MPPI_NUMBA_REFERENCE": REFERENCE})
-    assert lines[0] == os.path.join(REFERENCE, "mppi_numba", "density.py")
+        lines = run_py(IMPORT_CELL, ROOT, {"MPPI_NUMBA_REFERENCE": reference_checkout})
+    assert lines[0] == os.path.join(reference_checkout, "mppi_numba", "density.py")
     # the engine modules are never the reference's (they would need numba + CUDA)
     assert lines[1] == os.path.join(ROOT, "mppi_numba_amd", "mppi.py")
     assert lines[2] == "mppi_numba_amd.mppi mppi_numba_amd.terrain mppi_numba_amd.config"
-
-
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference checkout on this box")
-@pytest.mark.parametrize("notebook", ["test.ipynb", "planner_example_vis_gif.ipynb", "benchmark_vis.ipynb"])
-def test_reference_notebook_import_cells_execute(notebook):
-    """Cell 1 (imports) of the reference's notebooks, unmodified, against the alias."""
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from tools.run_reference_notebook import run\n"
-            "ns = run(%r, cells={1})\n"
-            "print(ns['MPPI_Numba'].__module__)\n" % (ROOT, os.path.join(REFERENCE, notebook)))
-    assert run_py(code, ROOT + ":" + REFERENCE)[-1] == "mppi_numba_amd.mppi"
-
-
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference checkout on this box")
-def test_reference_notebook_terrain_cell_executes():
-    """test.ipynb cell 2: terrain densities, PMFs, Terrain objects and the density plots --
-    the reference's helpers working on this repository's Terrain class."""
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from tools.run_reference_notebook import run\n"
-            "ns = run(%r, cells={1, 2})\n"
-            "print(type(ns['bush']).__module__, len(ns['b_lin_pmf']), round(float(ns['b_lin_pmf'].sum()), 6))\n"
-            % (ROOT, os.path.join(REFERENCE, "test.ipynb")))
-    assert run_py(code, ROOT + ":" + REFERENCE)[-1] == "mppi_numba_amd.terrain 22 1.0"

@@ -81,7 +81,7 @@ def test_bench_line_with_the_peer_exchange():
     line is the peer exchange's and says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MPPI_RDZV_FILE")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "2048", "--steps", "20",
-                          "--warmup", "5", "--regions", "2", "--no-cpu-baseline"], capture_output=True, text=True,
+                          "--warmup", "5", "--regions", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True,
                          timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

@@ -1,42 +1,24 @@
-"""The oracle against the REFERENCE ITSELF on worlds that are not among the committed
-fixtures: where /root/reference and the numba interpreter exist (the build container, not the
-GPU box), a few fixtures are regenerated with other random maps by running the reference's
-kernels under the CUDA simulator (oracle/gen_golden.py, GOLDEN_SEED_OFFSET), and the C
-restatement has to reproduce them bit for bit like the committed ones."""
+"""The oracle against the REFERENCE ITSELF on worlds that are not among the main fixtures: the
+reference's kernels were run under the CUDA simulator with other random maps (oracle/gen_golden.py
+with GOLDEN_SEED_OFFSET=303, `--only` each of NAMES, `--out tests/golden/seed303`), and the C
+restatement has to reproduce what they recorded bit for bit, like the main fixtures."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from helpers import iterations, params_from_golden, ulp_diff_f32
+from helpers import GOLDEN_DIR, iterations, params_from_golden, ulp_diff_f32
 from oracle import oracle as O
 from test_oracle_golden import map_params, solve_of_iteration
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NUMBA_PYTHON = "/opt/conda/bin/python3.9"
-NAMES = ["det_odd_units", "speedmap_odd_units", "tdm_odd_units"]  # (the quick ones: ~5 s each under the simulator)
-
-pytestmark = pytest.mark.skipif(
-    not (os.path.isdir("/root/reference/mppi_numba") and os.path.exists(NUMBA_PYTHON)),
-    reason="needs the reference and its numba interpreter (build container only)")
+NAMES = ["det_odd_units", "speedmap_odd_units", "tdm_odd_units"]
 
 
 @pytest.fixture(scope="module", params=[303])
-def live_fixtures(request, tmp_path_factory):
-    out = tmp_path_factory.mktemp("live_golden_%d" % request.param)
-    cmd = [NUMBA_PYTHON, os.path.join(ROOT, "oracle", "gen_golden.py"), "--out", str(out)]
-    for name in NAMES:
-        cmd += ["--only", name]
-    env = dict(os.environ, GOLDEN_SEED_OFFSET=str(request.param))
-    try:
-        subprocess.run(cmd, check=True, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
-    except (subprocess.SubprocessError, OSError) as e:  # the simulator environment, not the oracle, failed
-        pytest.skip("could not run the reference under the simulator here: %r" % (e,))
+def live_fixtures(request):
     loaded = {}
     for name in NAMES:
-        with np.load(os.path.join(str(out), name + ".npz")) as z:
+        with np.load(os.path.join(GOLDEN_DIR, "seed%d" % request.param, name + ".npz")) as z:
             loaded[name] = {k: z[k] for k in z.files}
     return loaded
 

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for w in $WL; do
-  BENCH="python $ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline --workload $w"
+  BENCH="python $ROOT/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --workload $w"
   rocprofv3 --kernel-trace --stats -d $OUT/prof_${TAG}_${w}_trace -o trace -- $BENCH > $OUT/prof_${TAG}_${w}_trace.log 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_${TAG}_${w}_fetch -o fetch -- $BENCH > $OUT/prof_${TAG}_${w}_fetch.log 2>&1
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/prof_${TAG}_${w}_write -o write -- $BENCH > $OUT/prof_${TAG}_${w}_write.log 2>&1

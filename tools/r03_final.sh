@@ -9,7 +9,7 @@ timeout 420 python -m pytest tests -m gpu -q -p no:cacheprovider --timeout=120 -
 echo "pytest -m gpu rc=$?"; grep -E "passed|failed|FAILED|Timeout" $OUT/pytest_gpu.log | tail -8 | cut -c1-200
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3
 for M in exact fast; do
-  timeout 120 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --math $M > $OUT/bench_${M}_c2.json 2> $OUT/bench_${M}_c2.err
+  timeout 120 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --math $M > $OUT/bench_${M}_c2.json 2> $OUT/bench_${M}_c2.err
   python - <<PY
 import json
 try:

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 for item in "$@"; do
   w=${item%%:*}; m=${item##*:}
   name=${TAG}_${w}; [ "$m" = fast ] && name=${name}_fast
-  BENCH="python $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --workload $w --math $m"
+  BENCH="python $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --workload $w --math $m"
   timeout 150 $BENCH > $OUT/${name/_$w/_bench_$w}.json 2> $RAW/${name}_bench.err
   for pass in trace fetch write; do
     case $pass in

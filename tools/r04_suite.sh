@@ -9,7 +9,7 @@ timeout ${SUITE_LIMIT:-900} python -m pytest tests -m gpu -q -p no:cacheprovider
 echo "pytest -m gpu rc=$?"; grep -E "passed|failed|FAILED|ERROR|Timeout" $OUT/pytest_gpu.log | tail -${TAIL:-30} | cut -c1-230
 if [ -z "${NO_SMOKE:-}" ]; then timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3; fi
 if [ -z "${NO_BENCH:-}" ]; then
-timeout 200 python bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 200 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 python - <<PY
 import json
 try:

@@ -18,7 +18,7 @@ for v in ${VARIANTS:-}; do
     classes*) envs="MPPI_REDUCE_CLASSES=${v#classes}";;
     *) lib=$ROOT/build/libmppi_$v.so;;
   esac
-  env $envs MPPI_HIP_LIB=$lib timeout 90 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline ${BENCH_ARGS:-} 2>$OUT/bench_$v.err | python -c "
+  env $envs MPPI_HIP_LIB=$lib timeout 90 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline ${BENCH_ARGS:-} 2>$OUT/bench_$v.err | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', round(d['ms_per_step']*1e3,2), round(d['kernel_us_in_loop']['rollout'],2), round(d['kernel_us_in_loop']['update'],2), d['config'].get('rollout_kernel','')[:90])

@@ -15,8 +15,8 @@ if [ -f $ROOT/build/libmppi_bounded.so ]; then
   MPPI_HIP_LIB=$ROOT/build/libmppi_bounded.so timeout 900 python -m pytest tests/test_gpu_scan.py tests/test_gpu_fuzz.py tests/test_gpu_reduce_fold.py tests/test_gpu_semantic.py tests/test_gpu_soak.py tests/test_gpu_fold_failsoft.py -m gpu -q -p no:cacheprovider --timeout=200 > $OUT/pytest_bounded.log 2>&1
   echo "bounded build rc=$?"; tail -2 $OUT/pytest_bounded.log | cut -c1-200
 fi
-timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err
-timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err
+timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 for f in bench_driver_style bench_c2; do
 python - <<PY
 import json

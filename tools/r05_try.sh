@@ -17,7 +17,7 @@ for item in "${ITEMS[@]}"; do
   for v in ${VARIANTS:-default}; do
     lib=$ROOT/mppi_numba_amd/libmppi_hip.so
     [ "$v" != default ] && lib=$ROOT/build/libmppi_$v.so
-    MPPI_HIP_LIB=$lib timeout 120 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --regions 5 $bargs 2>$OUT/bench_${label}_$v.err | tee $OUT/bench_${label}_$v.json | python -c "
+    MPPI_HIP_LIB=$lib timeout 120 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --regions 5 $bargs 2>$OUT/bench_${label}_$v.err | tee $OUT/bench_${label}_$v.json | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$label $v', 'us/step first %.2f median %.2f min %.2f' % (d['ms_per_step']*1e3, d['ms_per_step_median']*1e3, d['ms_per_step_min']*1e3), 'rollout %.2f update %.2f' % (d['kernel_us_in_loop']['rollout'], d['kernel_us_in_loop']['update']), d['config'].get('rollout_kernel','')[:80])

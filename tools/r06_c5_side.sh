@@ -4,7 +4,7 @@ set -u
 ROOT=${GRAFT_REPO_ROOT:-$PWD}; OUT=$ROOT/gpurun_out/${TAG:-r06c5s}; mkdir -p $OUT; cd $ROOT
 for mode in default side16; do
   if [ $mode = side16 ]; then export MPPI_SIDE_STREAM_MAX_WAVES=16; else unset MPPI_SIDE_STREAM_MAX_WAVES; fi
-  timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c5_$mode.json 2> $OUT/c5_$mode.err
+  timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c5_$mode.json 2> $OUT/c5_$mode.err
   python - <<PY
 import json
 try:

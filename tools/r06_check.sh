@@ -13,7 +13,7 @@ fi
 for item in ${BENCH:-}; do
   wl=${item%%:*}; extra=""
   case $item in *:*) extra=$(echo ${item#*:} | tr '+' ' ');; esac
-  timeout 300 python bench.py --workload $wl $extra --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --regions 5 > $OUT/bench_$(echo $item | tr ':+' '__').json 2> $OUT/bench_$(echo $item | tr ':+' '__').err
+  timeout 300 python bench.py --full --workload $wl $extra --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --regions 5 > $OUT/bench_$(echo $item | tr ':+' '__').json 2> $OUT/bench_$(echo $item | tr ':+' '__').err
   python - <<PY
 import json
 f="$OUT/bench_$(echo $item | tr ':+' '__')"

@@ -5,7 +5,7 @@ set -u
 ROOT=${GRAFT_REPO_ROOT:-$PWD}; OUT=$ROOT/gpurun_out/${TAG:-r06fam}; mkdir -p $OUT; cd $ROOT
 run() {  # label, env, bench args
   local label=$1 envv=$2; shift 2
-  env $envv timeout 200 python bench.py "$@" --steps 200 --warmup 20 --no-cpu-baseline --regions 5 > $OUT/fam_$label.json 2> $OUT/fam_$label.err
+  env $envv timeout 200 python bench.py --full "$@" --steps 200 --warmup 20 --no-cpu-baseline --regions 5 > $OUT/fam_$label.json 2> $OUT/fam_$label.err
   python - <<PY
 import json
 try:

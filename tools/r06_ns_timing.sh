@@ -10,7 +10,7 @@ for variant in default nosidestream; do
     default) ENVV="";;
     nosidestream) ENVV="MPPI_NO_SIDE_STREAM=1";;
   esac
-  env $ENVV timeout 200 python $ROOT/bench.py --workload $WL --steps 200 --warmup 20 --no-cpu-baseline --regions 3 > $OUT/bench_${WL}_$variant.json 2> $OUT/bench_${WL}_$variant.err
+  env $ENVV timeout 200 python $ROOT/bench.py --full --workload $WL --steps 200 --warmup 20 --no-cpu-baseline --regions 3 > $OUT/bench_${WL}_$variant.json 2> $OUT/bench_${WL}_$variant.err
   python - <<PY
 import json
 d=json.loads(open("$OUT/bench_${WL}_$variant.json").read().strip().splitlines()[-1])

@@ -4,8 +4,8 @@
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$PWD}; OUT=$ROOT/gpurun_out/${TAG:-r06ov}; mkdir -p $OUT; cd $ROOT
 for rep in 1 2; do
-  timeout 120 python bench.py --workload c2 --steps 2000 --warmup 50 --no-cpu-baseline --no-kernel-timing > $OUT/plain_$rep.json 2> $OUT/plain_$rep.err
-  MPPI_EXPERIMENT_ALT_STREAMS=1 timeout 120 python bench.py --workload c2 --steps 2000 --warmup 50 --no-cpu-baseline --no-kernel-timing > $OUT/alt_$rep.json 2> $OUT/alt_$rep.err
+  timeout 120 python bench.py --full --workload c2 --steps 2000 --warmup 50 --no-cpu-baseline --no-kernel-timing > $OUT/plain_$rep.json 2> $OUT/plain_$rep.err
+  MPPI_EXPERIMENT_ALT_STREAMS=1 timeout 120 python bench.py --full --workload c2 --steps 2000 --warmup 50 --no-cpu-baseline --no-kernel-timing > $OUT/alt_$rep.json 2> $OUT/alt_$rep.err
 done
 python - <<PY
 import json,glob

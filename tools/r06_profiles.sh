@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for item in "$@"; do
   label=${item%%:*}; bargs=${item#*:}
   name=${TAG}_${label}
-  BENCH="python $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --regions 5 $bargs"
+  BENCH="python $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --regions 5 $bargs"
   timeout 150 $BENCH > $OUT/${TAG}_bench_${label}.json 2> $RAW/${name}_bench.err
   for pass in ${PASSES:-trace fetch write}; do
     # (counter passes execute one kernel at a time: the two-stream loops then order their streams with events, as rounds
