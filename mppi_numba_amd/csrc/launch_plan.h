@@ -92,8 +92,7 @@ static int reserve_cells(mppi_planner* p, const mppi_tdm* lin, int M) {
 // the ordinary sample + pack path has to run.
 static bool sample_into_cells(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, double alpha_dyn, int* rc) {
   *rc = MPPI_OK;
-  static const bool disabled = getenv("MPPI_NO_FUSED_SAMPLING") != nullptr;  // developer switch (ablation)
-  if (disabled || p->cfg.mode != MPPI_MODE_TDM || lin == ang) return false;
+  if (p->cfg.mode != MPPI_MODE_TDM || lin == ang) return false;
   if (lin->cfg.rng != MPPI_RNG_PHILOX || ang->cfg.rng != MPPI_RNG_PHILOX) return false;
   if (lin->bins > 64 || ang->bins > 64 || !(alpha_dyn > 0.0)) return false;
   if (lin->first_sample != ang->first_sample) return false;
@@ -220,6 +219,16 @@ static NoiseJob make_noise_job(mppi_planner* p, float2* target) {
   return j;
 }
 
+// the next iteration's noise, by `extra` workgroups appended to a rollout launch; none: an empty job
+static NoiseJob next_noise_job(mppi_planner* p, int extra) {
+  NoiseJob j;
+  memset(&j, 0, sizeof(j));
+  if (extra <= 0) return j;
+  j = make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]);
+  p->next_noise_done = true;
+  return j;
+}
+
 static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nullptr) {
   long total = (long)noise_items(p->n_local, p->cfg.num_steps, p->cfg.rng == MPPI_RNG_PHILOX);  // one thread per item
   NoiseJob job = make_noise_job(p, target);
@@ -325,6 +334,24 @@ static bool unclamped_lookup_ok(const mppi_planner* p, const DevParams& d) {
   return yi0 - reach > 0.0 && yi0 + reach + 1.0 < (double)d.rows && xi0 - reach > 0.0 && xi0 + reach + 1.0 < (double)d.cols;
 }
 
+// Incremental trig, (cos, sin) advanced by rotation: the host bounds the heading increment |dt * w * traction| by 0.36 rad
+// (barebone mode: traction 1) and the horizon by 2000 steps.
+static bool rotation_ok(const mppi_planner* p, const DevParams& d) {
+  const mppi_params& a = p->params;
+  const double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
+  const double trmax = p->cfg.mode == MPPI_MODE_BAREBONE
+                           ? 1.0
+                           : std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
+  const double dmax = (double)a.dt * wmax * trmax;
+  return std::isfinite(dmax) && dmax <= 0.36 && p->cfg.num_steps <= 2000;
+}
+
+// res == 2^k exactly: four-instruction cell coordinates
+static bool res_is_pow2(const mppi_planner* p) {
+  int res_exp = 0;
+  return std::frexp((double)p->params.res, &res_exp) == 0.5;
+}
+
 // Waves (tiles of 64 rollouts) per workgroup of the one-wave-per-tile kernels that keep the map
 // window in LDS.  The window makes it one workgroup per CU, so the workgroup is sized to cover
 // the problem in one round: at least 4 waves (one per SIMD, and enough lanes to copy the
@@ -373,8 +400,13 @@ static void settle_noise_wait(mppi_planner* p) {
 // ... the kernels that do (DevParams::noise_flag; their DevParams through noise_flag_params)
 #define MPPI_KLAUNCH_WAITS_ITSELF(kernel, grid, block, lds, stream, ...) \
   hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, p->kev_start, p->kev_stop, 0, __VA_ARGS__)
+// MPPI_NO_NOISE_FLAG: the streams are ordered by events only, the wait of rounds 1-5
+static bool noise_flag_disabled() {
+  static const bool disabled = getenv("MPPI_NO_NOISE_FLAG") != nullptr;
+  return disabled;
+}
 static DevParams noise_flag_params(mppi_planner* p, DevParams d) {
-  static const bool no_flag = getenv("MPPI_NO_NOISE_FLAG") != nullptr;  // developer switch (ablation): the event wait of rounds 1-5
+  const bool no_flag = noise_flag_disabled();
   d.flag_fault = p->flag_fault_dev;
   if (p->noise_wait_pending && p->noise_flag_dev && !no_flag && !p->stream_flags_off) {
     d.noise_flag = p->noise_flag_dev;
@@ -446,8 +478,7 @@ static bool scan_plan(const mppi_planner* p, ScanPlan* out) {
 }
 
 static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
-  static const bool disabled = getenv("MPPI_NO_SCAN") != nullptr;  // developer switch (ablation)
-  if (disabled || (p->debug_flags & MPPI_DEBUG_NO_SCAN_KERNEL)) return false;
+  if (p->debug_flags & MPPI_DEBUG_NO_SCAN_KERNEL) return false;
   // (round 6) the speed-map mode too: its dynamics run on nominal traction -- the walks' assumption by construction --
   // and the risk byte comes with the (32-bit) cell; exact arithmetic only, no direct form (rollout_scan_exact_kernel.h)
   const bool speed = p->cfg.mode == MPPI_MODE_SPEED_MAP;
@@ -459,8 +490,7 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
   const bool stopped = p->speculation_off && !(p->debug_flags & MPPI_DEBUG_KEEP_SPECULATING);
   if (stopped && p->cfg.math != MPPI_MATH_EXACT) return false;  // (the tolerance kernel has no exact schedule inside)
   const bool direct = (stopped || (p->debug_flags & MPPI_DEBUG_NO_SPECULATION)) && p->cfg.math == MPPI_MATH_EXACT;
-  static const bool no_direct = getenv("MPPI_NO_SCAN_DIRECT") != nullptr;  // developer switch (ablation): k_rollout_pipe as in round 4
-  if (direct && (no_direct || (p->debug_flags & MPPI_DEBUG_NO_SCAN_DIRECT) || p->cfg.math != MPPI_MATH_EXACT ||
+  if (direct && ((p->debug_flags & MPPI_DEBUG_NO_SCAN_DIRECT) || p->cfg.math != MPPI_MATH_EXACT ||
                  !p->packed_lin || !p->packed_ang || speed))
     return false;
   const int T = p->cfg.num_steps;
@@ -481,8 +511,7 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
   // (the accumulating wave reads up to two groups of records past the last one: keep that inside the allocation)
   plan.lds = std::max(plan.lds, (size_t)40 * 1024);
   if (plan.lds > (size_t)p->lds_per_cu - 1024) return false;
-  int res_exp = 0;
-  plan.pow2res = std::frexp((double)p->params.res, &res_exp) == 0.5;  // res == 2^k exactly
+  plan.pow2res = res_is_pow2(p);
   // (the template flag also selects the unclamped address of the exact schedule inside the kernel -- direct launches
   //  and re-executed tiles: only where no rollout can leave the map)
   const DevParams d0 = make_dev_params(p, p->packed_lin, p->packed_ang);
@@ -513,9 +542,7 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
 
 // the iteration loop may let the rollout launch generate its own noise: Philox counters only
 static bool scan_generates_noise(const mppi_planner* p) {
-  static const bool disabled = getenv("MPPI_SCAN_READ_NOISE") != nullptr;  // developer switch (ablation)
-  return !disabled && !(p->debug_flags & MPPI_DEBUG_SCAN_READ_NOISE) && p->cfg.rng == MPPI_RNG_PHILOX &&
-         scan_plan(p, nullptr);
+  return !(p->debug_flags & MPPI_DEBUG_SCAN_READ_NOISE) && p->cfg.rng == MPPI_RNG_PHILOX && scan_plan(p, nullptr);
 }
 
 // the noise of the last iteration into noise_buf when it exists as counters only
@@ -571,24 +598,19 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
   ScanPackets pk;
   pk.tiles = p->tile_packets[p->tpk_cur ^ 1];  // (the other one may be read by this very launch: reduce_pending)
   pk.n_tiles = tiles;
-  NoiseJob gen_job, next_job;
+  NoiseJob gen_job;
   memset(&gen_job, 0, sizeof(gen_job));
-  memset(&next_job, 0, sizeof(next_job));
   int extra = 0;
   if (gen) {
     gen_job = make_noise_job(p, nullptr);  // (advances the Philox epoch: this iteration's block)
-  } else {
-    // a loop that stores its noise (debug switch; the stage-level calls): CUs without a workgroup
+  } else if (p->next_noise_wanted && tiles < p->num_cus && p->cfg.rng == MPPI_RNG_PHILOX && !plan.exact) {
+    // a loop that stores its noise (debug flag; the stage-level calls): CUs without a workgroup
     // produce the next iteration's, as in k_rollout_pipe.  (Producing it in the launch's own tail, by
     // the waves that idle while one wave accumulates the costs, was measured: the stage gained is lost
     // again to the slower accumulation and the noise reads -- profiles/r03_scan_notes.md.)
-    static const bool no_fused_noise = getenv("MPPI_NO_FUSED_NOISE") != nullptr;  // developer switch
-    if (p->next_noise_wanted && tiles < p->num_cus && !no_fused_noise && p->cfg.rng == MPPI_RNG_PHILOX && !plan.exact) {
-      extra = p->num_cus - tiles;
-      next_job = make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]);
-      p->next_noise_done = true;
-    }
+    extra = p->num_cus - tiles;
   }
+  const NoiseJob next_job = next_noise_job(p, extra);
   // a sharded iteration whose update has not been applied yet: this launch does it (PendingApply)
   PendingApply pend;
   memset(&pend, 0, sizeof(pend));
@@ -624,30 +646,17 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
   // controls, 16-bit map window and one chunk ring in the LDS of the walks' groups and positions, dead by then --
   // or behind everything when the horizon is too short for that region to hold them.
   ScanFallback fallback = {-1, 0, 0, 0, 0};
-  {  // the exact-increment rotation of the state role applies (as launch_rollout_det's rot_ok)
-    const mppi_params& a = p->params;
-    const double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-    const double trmax = std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-    const double dmax = (double)a.dt * wmax * trmax;
-    fallback.rot_ok = (std::isfinite(dmax) && dmax <= 0.36) ? 1 : 0;
-  }
-  static const bool no_fast_fallback = getenv("MPPI_SCAN_SLOW_FALLBACK") != nullptr;  // developer switch (ablation)
+  fallback.rot_ok = rotation_ok(p, d) ? 1 : 0;  // the exact-increment rotation of the state role (as launch_rollout_det's)
   if (plan.direct) {
     REQUIRE(have_window && plan.fallback_offset >= 0, MPPI_ERR_STATE, "internal: direct exact schedule without its map window");
     fallback.offset = plan.fallback_offset;
     fallback.map_bytes = plan.fallback_map_bytes;
     fallback.small_offset = plan.small_offset;
     fallback.direct = 1;
-  } else if (plan.exact && have_window && !no_fast_fallback && !speed) {  // (speed-map: 32-bit cells, no exact schedule inside)
+  } else if (plan.exact && have_window && !speed) {  // (speed-map: 32-bit cells, no exact schedule inside)
     const size_t lds = scan_fallback_place(p, d, plan.chunk_waves, plan.lds, &fallback.offset, &fallback.map_bytes);
     if (lds) plan.lds = lds;
   }
-  // Developer experiment (profiles/r06_overlap_notes.md; TIMING ONLY -- the launches race on the tile packets): every
-  // other launch goes to the second stream with nothing ordering it behind its predecessor, i.e. the upper bound of what
-  // "launch k+1 before launch k ends"  could hide.
-  static const bool alt_streams = getenv("MPPI_EXPERIMENT_ALT_STREAMS") != nullptr;
-  static unsigned alt_toggle = 0;
-  hipStream_t scan_stream = (alt_streams && (alt_toggle++ & 1)) ? p->noise_stream : p->stream;
 #define MPPI_LAUNCH_SCAN_EXACT(P2, GEN)                                                                    \
   do {                                                                                                    \
     auto kern = speed ? k_rollout_scan_exact<P2, GEN, false, true>                                        \
@@ -655,7 +664,7 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
     if (plan.lds > 64 * 1024)                                                                             \
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));            \
-    MPPI_KLAUNCH(kern, dim3(tiles), dim3(64 * plan.waves), plan.lds, scan_stream, d, p->cells16, p->cells, \
+    MPPI_KLAUNCH(kern, dim3(tiles), dim3(64 * plan.waves), plan.lds, p->stream, d, p->cells16, p->cells,   \
                  p->noise, gen_job, p->u, p->costs, p->w_rel, pk, pend, fallback,                          \
                  (const int8_t*)(speed ? p->risk_ref : nullptr));                                          \
   } while (0)
@@ -731,14 +740,12 @@ struct DetRegime {
   bool rot_ok_fast;       // ... the same bound under MPPI_MATH_FAST (k_rollout_fused<one pass>)
 };
 
-template <bool EXACT>
 static int try_launch_pipe(mppi_planner* p, DevParams& d, const DetRegime& r, bool* launched) {
   *launched = false;
   const int N = p->n_local, T = p->cfg.num_steps;
-  [[maybe_unused]] const bool have_window = r.have_window, rot_ok = r.rot_ok, pow2res = r.pow2res_unclamped;
-  [[maybe_unused]] const size_t lds_win = r.lds_win;
-  static const bool no_pipe = getenv("MPPI_NO_PIPE") != nullptr;  // developer switch (ablation)
-  if (have_window && rot_ok && !no_pipe) {
+  const bool pow2res = r.pow2res_unclamped;
+  const size_t lds_win = r.lds_win;
+  if (r.have_window && r.rot_ok) {
     // pipelined kernel: the map window in LDS + the incremental trig
     const size_t map_bytes = lds_win - sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);
     int pairs = ceil_div(ceil_div(N, 64), p->num_cus);  // wave triples per workgroup
@@ -773,16 +780,9 @@ static int try_launch_pipe(mppi_planner* p, DevParams& d, const DetRegime& r, bo
       const size_t lds_total = lds_win + ring_bytes(chunk) + (cc_lds ? cc_bytes : 0);
       const int block = 192 * pairs;
       const int grid = ceil_div(N, 64 * pairs);
-      // spare CUs generate the next iteration's noise inside this launch
-      NoiseJob next_job;
-      memset(&next_job, 0, sizeof(next_job));
-      int extra = 0;
-      static const bool no_fused_noise = getenv("MPPI_NO_FUSED_NOISE") != nullptr;  // developer switch
-      if (p->next_noise_wanted && grid < p->num_cus && !no_fused_noise) {  // (no spare CU otherwise: in line)
-        extra = p->num_cus - grid;
-        next_job = make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]);
-        p->next_noise_done = true;
-      }
+      // spare CUs generate the next iteration's noise inside this launch (no spare CU: in line)
+      const int extra = p->next_noise_wanted && grid < p->num_cus ? p->num_cus - grid : 0;
+      const NoiseJob next_job = next_noise_job(p, extra);
       if (!cc_lds && !p->cc_scratch) TRY(dev_alloc(&p->cc_scratch, (size_t)ceil_div(N, 64) * 64 * T));
 #define MPPI_LAUNCH_PIPE(CH, P2, CL)                                                                  \
   do {                                                                                                \
@@ -827,32 +827,28 @@ else MPPI_LAUNCH_PIPE(2, P2, CL);                 \
 template <bool EXACT, bool BOUNDED>
 static int launch_windowed_or_general(mppi_planner* p, DevParams& d, const DetRegime& r) {
   const int N = p->n_local, T = p->cfg.num_steps;
-  [[maybe_unused]] const bool have_window = r.have_window, rot_ok = r.rot_ok, pow2res = r.pow2res;
-  [[maybe_unused]] const size_t lds_win = r.lds_win;
+  const bool pow2res = r.pow2res;
+  const size_t lds_win = r.lds_win;
   const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
-  static const bool no_window = getenv("MPPI_NO_WINDOW") != nullptr;  // developer switch (ablation)
-  if (have_window && !no_window) {
+  if (r.have_window) {
     // the window makes it one workgroup per CU: size the workgroup so that the grid
     // is at most one wave of workgroups over the CUs
     // (at least 4 waves: one per SIMD, and four times the lanes to copy the window)
     const int waves = fused_waves_per_workgroup(p, N);
     int block = 64 * waves;
-    static const bool no_fused = getenv("MPPI_NO_FUSED") != nullptr;  // developer switch (ablation)
-    if ((rot_ok || r.rot_ok_fast) && !no_fused) {
+    if (r.rot_ok || r.rot_ok_fast) {
       // (MPPI_MATH_FAST: one pass over the noise, the control cost added once)
       // (round 6: workgroups of at most four waves -- nobody hides a wave's trips to memory: k_rollout_fused, LONE)
-      static const bool no_lone = getenv("MPPI_NO_FUSED_LONE") != nullptr;  // developer switch (ablation)
-      const bool lone = EXACT && waves <= 4 && !no_lone;
+      const bool lone = EXACT && waves <= 4;
       auto fused = EXACT ? (lone ? (pow2res ? k_rollout_fused<true, false, false, true> : k_rollout_fused<false, false, false, true>)
                                  : (pow2res ? k_rollout_fused<true> : k_rollout_fused<false>))
                          : (pow2res ? k_rollout_fused<true, false, true> : k_rollout_fused<false, false, true>);
       // Round 6 (exact mode reads the noise twice): what the window leaves of the CU's LDS keeps the noise of the first
       // steps for the second pass -- one workgroup per CU either way (DevParams::stash_steps; N = 65536, T = 100: 56 of
       // the 100 steps of each of the four waves)
-      static const bool no_stash = getenv("MPPI_NO_NOISE_STASH") != nullptr;  // developer switch (ablation)
       size_t lds_fused = lds_win;
       d.stash_steps = d.stash_offset = 0;
-      if (EXACT && !no_stash) {
+      if (EXACT) {
         const size_t off = (lds_win + 15) & ~(size_t)15, limit = (size_t)p->lds_per_cu - 1024;
         if (limit > off) {
           const int fit = (int)((limit - off) / ((size_t)waves * 64 * sizeof(float2)));
@@ -899,7 +895,6 @@ static int launch_windowed_or_general(mppi_planner* p, DevParams& d, const DetRe
 
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_det(mppi_planner* p, DevParams d) {
-  const int T = p->cfg.num_steps;
   p->tile_packets_fresh = false;
   size_t lds_win = 0;
   bool have_window = plan_lds_window(p, d, &lds_win);
@@ -908,23 +903,15 @@ static int launch_rollout_det(mppi_planner* p, DevParams d) {
     ScanPlan plan;
     if (scan_plan(p, &plan)) return launch_scan(p, d, plan, have_window);
   }
-  // incremental trig: needs a heading increment |dt*w*traction| <= 0.36 rad and T <= 2000
-  bool rot_ok = false, rot_ok_fast = false, pow2res = false;
-  {
-    const mppi_params& a = p->params;
-    double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-    double trmax = std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-    double dmax = (double)a.dt * wmax * trmax;
-    rot_ok = EXACT && BOUNDED && std::isfinite(dmax) && dmax <= 0.36 && T <= 2000;
-    rot_ok_fast = !EXACT && p->theta_bounded && std::isfinite(dmax) && dmax <= 0.36 && T <= 2000;
-    int res_exp = 0;
-    pow2res = std::frexp((double)a.res, &res_exp) == 0.5;  // res == 2^k exactly
-  }
+  const bool rot = rotation_ok(p, d);
   DetRegime r;
-  r.have_window = have_window; r.lds_win = lds_win; r.rot_ok = rot_ok; r.rot_ok_fast = rot_ok_fast; r.pow2res = pow2res;
-  r.pow2res_unclamped = pow2res && unclamped_lookup_ok(p, d);
+  r.have_window = have_window; r.lds_win = lds_win;
+  r.rot_ok = EXACT && BOUNDED && rot;
+  r.rot_ok_fast = !EXACT && p->theta_bounded && rot;
+  r.pow2res = res_is_pow2(p);
+  r.pow2res_unclamped = r.pow2res && unclamped_lookup_ok(p, d);
   bool launched = false;
-  TRY(try_launch_pipe<EXACT>(p, d, r, &launched));
+  TRY(try_launch_pipe(p, d, r, &launched));
   if (!launched) TRY((launch_windowed_or_general<EXACT, BOUNDED>(p, d, r)));
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
@@ -933,9 +920,7 @@ static int launch_rollout_det(mppi_planner* p, DevParams d) {
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_speed_map(mppi_planner* p, DevParams d) {
   const int N = p->n_local, T = p->cfg.num_steps;
-  [[maybe_unused]] const int M = p->cfg.num_grid_samples;
-  [[maybe_unused]] size_t lds = sizeof(double2) * (size_t)T;
-  [[maybe_unused]] const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
+  const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
   p->tile_packets_fresh = false;
   size_t lds_win = 0;
   const bool have_window = plan_lds_window(p, d, &lds_win);  // 32-bit cells: 16 bits + risk byte
@@ -948,15 +933,9 @@ static int launch_rollout_speed_map(mppi_planner* p, DevParams d) {
       return launch_scan(p, d, plan, have_window);
     }
   }
-  const mppi_params& a = p->params;
-  double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-  double trmax = std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-  double dmax = (double)a.dt * wmax * trmax;
-  static const bool no_fused = getenv("MPPI_NO_FUSED") != nullptr;  // developer switch (ablation)
-  if (have_window && (BOUNDED || (!EXACT && p->theta_bounded)) && std::isfinite(dmax) && dmax <= 0.36 && T <= 2000 && !no_fused) {
+  if (have_window && (BOUNDED || (!EXACT && p->theta_bounded)) && rotation_ok(p, d)) {
     const int waves = fused_waves_per_workgroup(p, N);
-    int res_exp = 0;
-    const bool pow2res = std::frexp((double)a.res, &res_exp) == 0.5;
+    const bool pow2res = res_is_pow2(p);
     auto fused = EXACT ? (pow2res ? k_rollout_fused<true, true> : k_rollout_fused<false, true>)
                        : (pow2res ? k_rollout_fused<true, true, true> : k_rollout_fused<false, true, true>);
     if (lds_win > 64 * 1024)
@@ -983,9 +962,8 @@ static int launch_rollout_speed_map(mppi_planner* p, DevParams d) {
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   const int N = p->n_local, T = p->cfg.num_steps;
-  [[maybe_unused]] const int M = p->cfg.num_grid_samples;
-  [[maybe_unused]] size_t lds = sizeof(double2) * (size_t)T;
-  [[maybe_unused]] const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
+  const int M = p->cfg.num_grid_samples;
+  size_t lds = sizeof(double2) * (size_t)T;
   int mp2 = next_pow2(M);
   int threads = ceil_div(M, 64) * 64;
   if (threads > 1024) threads = 1024;
@@ -1002,28 +980,17 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   p->tile_packets_fresh = false;
   TRY(upload_instances(p));
   {
-    const mppi_params& a = p->params;
-    double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-    double trmax = std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-    double dmax = (double)a.dt * wmax * trmax;
     const size_t lds_fast = (sizeof(double2) + sizeof(double)) * (size_t)T + sizeof(float) * (size_t)mp2;
-    if ((BOUNDED || (!EXACT && p->theta_bounded)) && std::isfinite(dmax) && dmax <= 0.36 && T <= 2000 && lds_fast <= 64 * 1024) {
-      int res_exp = 0;
-      const bool pow2res = std::frexp((double)a.res, &res_exp) == 0.5;
+    if ((BOUNDED || (!EXACT && p->theta_bounded)) && rotation_ok(p, d) && lds_fast <= 64 * 1024) {
+      const bool pow2res = res_is_pow2(p);
       float* sc_out = sc_dst;
       // the next iteration's noise by workgroups appended to the grid (they run in the launch's tail)
-      NoiseJob next_job;
-      memset(&next_job, 0, sizeof(next_job));
       int extra = 0;
-      static const bool no_fused_noise = getenv("MPPI_NO_FUSED_NOISE") != nullptr;  // developer switch
-      if (p->next_noise_wanted && !no_fused_noise && p->cfg.rng == MPPI_RNG_PHILOX) {
+      if (p->next_noise_wanted && p->cfg.rng == MPPI_RNG_PHILOX) {
         const long rows = (long)(noise_items(p->n_local, T, true) >> 6);
         extra = (int)std::min<long>(2L * p->num_cus, ceil_div(rows, (long)(threads / 64) * 4));
-        if (extra > 0) {
-          next_job = make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]);
-          p->next_noise_done = true;
-        }
       }
+      const NoiseJob next_job = next_noise_job(p, extra);
       if (pow2res)
         MPPI_KLAUNCH((k_rollout_tdm_fast<true, !EXACT>), dim3(N + extra), dim3(threads), lds_fast, p->stream, d, p->cells,
                            p->noise, p->u, p->costs, sc_out, mp2, N, next_job);
@@ -1055,16 +1022,13 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
       const int N = p->n_local;
       p->tile_packets_fresh = false;
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
-      const mppi_params& a = p->params;
-      const double dmax = (double)a.dt * std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-      const bool rot = EXACT && std::isfinite(dmax) && dmax <= 0.36 && p->cfg.num_steps <= 2000;
+      const bool rot = EXACT && rotation_ok(p, d);
       const size_t lds_bb = sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)std::max(1, p->n_obstacles);
       REQUIRE(lds_bb <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", p->n_obstacles, p->cfg.num_steps);
-      static const bool no_kd = getenv("MPPI_BAREBONE_NO_KD") != nullptr;  // developer switch (ablation)
-      if (rot && !no_kd && p->n_obstacles <= 2)
+      if (rot && p->n_obstacles <= 2)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 2 * sizeof(float4),
                      p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
-      else if (rot && !no_kd && p->n_obstacles <= 4)
+      else if (rot && p->n_obstacles <= 4)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 4 * sizeof(float4),
                      p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
       else if (rot)
@@ -1251,8 +1215,7 @@ static int launch_apply(mppi_planner* p) {
 
 // Whether the NEXT rollout launch of this handle can apply a sharded update itself (PendingApply).
 static bool next_rollout_applies_updates(const mppi_planner* p) {
-  static const bool disabled = getenv("MPPI_NO_FOLDED_APPLY") != nullptr;  // developer switch (ablation)
-  return !disabled && !(p->debug_flags & MPPI_DEBUG_NO_FOLDED_APPLY) && p->B == 1 && !p->inst_set && p->m_count == 1 &&
+  return !(p->debug_flags & MPPI_DEBUG_NO_FOLDED_APPLY) && p->B == 1 && !p->inst_set && p->m_count == 1 &&
          p->cfg.world_size <= kMaxFoldedRanks && p->cfg.mode == MPPI_MODE_DET && !p->mirror_now && scan_plan(p, nullptr);
 }
 
@@ -1266,9 +1229,8 @@ static bool p2p_usable(const mppi_planner* p) {
 
 // Whether the NEXT rollout launch can combine and apply the tile packets of this one (no update kernel).
 static bool next_rollout_reduces_tiles(const mppi_planner* p) {
-  static const bool disabled = getenv("MPPI_NO_REDUCE_FOLD") != nullptr;  // developer switch (ablation)
   ScanPlan plan;
-  return !disabled && !p->fold_off && !(p->debug_flags & (MPPI_DEBUG_NO_FOLDED_APPLY | MPPI_DEBUG_NO_REDUCE_FOLD)) && p->B == 1 && !p->inst_set &&
+  return !p->fold_off && !(p->debug_flags & (MPPI_DEBUG_NO_FOLDED_APPLY | MPPI_DEBUG_NO_REDUCE_FOLD)) && p->B == 1 && !p->inst_set &&
          p->m_count == 1 && ((p->cfg.world_size == 1 && !p->comm) || p2p_usable(p)) &&
          (p->cfg.mode == MPPI_MODE_DET || p->cfg.mode == MPPI_MODE_SPEED_MAP) && !p->mirror_now &&
          scan_plan(p, &plan) && plan.tile == p->scan_tile &&
@@ -1330,13 +1292,12 @@ static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false
 static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_noise, bool want_next, bool prof,
                             bool defer_exchange = false, bool may_leave_apply = false) {
   // (below ~4M rollout-steps the generator takes less than the ~12 us a cross-stream dependency costs)
-  static const bool no_side_stream = getenv("MPPI_NO_SIDE_STREAM") != nullptr;  // developer switch
   // and above 8 rollout waves per CU the register file has room for one generator wave per SIMD only: the generator
   // crawls beside the rollout, slows it, and still collides with the update (measured in round 1, profiles/r01_ablation.md,
-  // and again in round 6 with MPPI_SIDE_STREAM_MAX_WAVES=16: C5 187 us against 178, profiles/r06_ns_notes.md section 3)
-  static const int side_max_waves = getenv("MPPI_SIDE_STREAM_MAX_WAVES") ? atoi(getenv("MPPI_SIDE_STREAM_MAX_WAVES")) : 8;  // developer switch
+  // and again in round 6 with a bound of 16: C5 187 us against 178, profiles/r06_ns_notes.md section 3)
+  constexpr int kSideStreamMaxWaves = 8;
   const bool side_stream_pays = (long)p->n_local * p->cfg.num_steps >= 4L * 1000 * 1000 &&
-                                ceil_div(ceil_div(p->n_local, 64), p->num_cus) <= side_max_waves && !no_side_stream;
+                                ceil_div(ceil_div(p->n_local, 64), p->num_cus) <= kSideStreamMaxWaves;
   const bool ktime_stamps = p->ktime_index >= 0 && p->ktime_dev && p->ktime_use_stamps;  // (mppi_planner_time_kernels)
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[0], p->stream));
   // MPPI_MATH_FAST over a map the time-parallel kernel takes: the rollout launch computes its noise
@@ -1430,10 +1391,8 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
   // Where the rollout fills the SIMDs by itself (more than 8 of its waves per CU: the batched handles, C5) a generator
   // beside it only takes its issue slots; but the update behind it is bound by memory: there the next iteration's noise is
   // generated beside the UPDATE launch -- which runs slim (k_update_rows<.., 256>: a quarter of the waves, the same bytes
-  // in flight) and signals its start to the generator's gate kernel.
-  static const bool no_beside_update = getenv("MPPI_NO_NOISE_BESIDE_UPDATE") != nullptr ||  // developer switch (ablation)
-                                       getenv("MPPI_NO_NOISE_FLAG") != nullptr;             // (no flags: no second stream here)
-  const bool beside_update = want_next && !have_noise && !side_stream_pays && !no_side_stream && !no_beside_update && !p->graph_on &&
+  // in flight) and signals its start to the generator's gate kernel.  (MPPI_NO_NOISE_FLAG: no flags, no second stream here)
+  const bool beside_update = want_next && !have_noise && !side_stream_pays && !noise_flag_disabled() && !p->graph_on &&
                              !prof && !defer_exchange && p->noise_flag_dev && p->progress_dev && !p->stream_flags_off &&
                              p->cfg.rng == MPPI_RNG_PHILOX && (long)p->n_local * p->cfg.num_steps >= 4L * 1000 * 1000 &&
                              !p->scan_packets_fresh && p->cfg.world_size == 1 && !p->comm && p->m_count == 1 &&
@@ -1643,11 +1602,6 @@ static int run_iterations(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, int ite
     }
     for (; k < iterations; ++k) TRY(launch_iteration(p, d, have_noise, true, false, false, k + 1 < iterations));
     p->primed = have_noise;
-  }
-  static const bool alt_streams = getenv("MPPI_EXPERIMENT_ALT_STREAMS") != nullptr;
-  if (alt_streams) {  // (developer experiment, launch_scan: the second stream joins here)
-    HIP_TRY(hipEventRecord(p->ev_noise_ready, p->noise_stream));
-    HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_noise_ready, 0));
   }
   if (timed) {
     HIP_TRY(hipEventRecord(p->ev_end, p->stream));
