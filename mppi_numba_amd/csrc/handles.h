@@ -30,9 +30,10 @@ struct mppi_tdm {
   bool compact_ok = false;  // masks are 0/1 and every traction byte is in [0,127]: 16-bit cells usable
   int table_max = 127;      // largest traction byte the sampler can write
   double lo = 0.0, ratio = 0.0;
-  uint64_t epoch = 0;         // Philox call counter
-  uint64_t maps_version = 0;  // bumped by set_maps
-  uint64_t grid_version = 0;  // bumped whenever `grid` changes
+  uint64_t epoch = 0;  // Philox call counter
+  // generations (next_generation): a number unique across all TDMs for the lifetime of the process, 0: never set
+  uint64_t maps_version = 0;  // renewed by set_maps
+  uint64_t grid_version = 0;  // renewed whenever `grid` changes
   uint64_t sampled_maps_version = ~0ULL;
   double sampled_alpha = -1.0;
   // solve() of a CVaR planner samples straight into the planner's cell words (Philox only):
@@ -50,6 +51,24 @@ struct mppi_tdm {
   // samples sharded over GPUs (mppi_tdm_set_sample_shard): this handle's G grids are samples
   // [first_sample, first_sample + G) of the unsharded set; even, a Philox block serves a pair
   int first_sample = 0;
+};
+
+// the next map or grid generation of any TDM (mppi_tdm::maps_version, grid_version): never reused in this process, so
+// a planner can tell map states apart by number alone, whichever TDM they belonged to and whether it still exists
+static uint64_t next_generation() {
+  static std::atomic<uint64_t> last{0};
+  return ++last;
+}
+
+// What a planner's cell words were packed from (launch_plan.h: note_packed): the generations of both TDMs and the map
+// facts the launches derive from them.  A planner never reads a TDM after packing it.
+struct PackedMaps {
+  uint64_t lin_maps = 0, lin_grid = 0, ang_maps = 0, ang_grid = 0;  // 0: nothing packed yet
+  double lin_lo = 0.0, lin_ratio = 0.0, ang_lo = 0.0, ang_ratio = 0.0;
+  int rows = 0, cols = 0;
+  int lin_max_byte = 0, ang_max_byte = 0;  // largest traction byte of the packed grids (tdm_max_byte)
+  int sink_ring = 0;                       // zero-traction border rings of lin's packed grids (mppi_tdm::maps_sink_ring)
+  const int8_t* risk = nullptr;            // lin's risk map (speed-map mode)
 };
 
 // ---- k_rollout_scan / k_rollout_scan_exact: the launch geometry (launch_plan.h: scan_plan) --------
@@ -195,7 +214,6 @@ struct mppi_planner {
   bool cells16_with_risk = false;  // cells16 holds 32-bit cells with the risk byte (speed-map mode)
   int num_cus = 256;
   int lds_per_cu = 160 * 1024;
-  int8_t* risk_ref = nullptr;
   float* sample_costs = nullptr;  // [n_local][M], allocated on first request
   bool want_sample_costs = false;
   uint64_t* states = nullptr;  // xoroshiro-compatible generator only
@@ -209,9 +227,7 @@ struct mppi_planner {
   mppi_params params;
   bool params_set = false;
   uint64_t noise_epoch = 0;
-  const mppi_tdm* packed_lin = nullptr;
-  const mppi_tdm* packed_ang = nullptr;
-  uint64_t packed_lin_grid = ~0ULL, packed_ang_grid = ~0ULL, packed_lin_maps = ~0ULL;
+  PackedMaps packed;
   // timing
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   hipEvent_t ev_stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -27,8 +27,10 @@ static int check_tdms(const mppi_planner* p, const mppi_tdm* lin, const mppi_tdm
   return MPPI_OK;
 }
 
-static DevParams make_dev_params(const mppi_planner* p, const mppi_tdm* lin, const mppi_tdm* ang) {
+// the map fields come from what the cell words were packed from (zeros before that, and in barebone mode)
+static DevParams make_dev_params(const mppi_planner* p) {
   const mppi_params& a = p->params;
+  const PackedMaps& m = p->packed;
   DevParams d;
   memset(&d, 0, sizeof(d));
   d.x0 = a.x0[0]; d.y0 = a.x0[1]; d.th0 = a.x0[2];
@@ -50,13 +52,13 @@ static DevParams make_dev_params(const mppi_planner* p, const mppi_tdm* lin, con
   // (samples sharded over GPUs: the local kernel's own reduction is not used; cvar_numel())
   d.dist_weight = a.dist_weight;
   d.v_post_den = (double)a.v_post_rollout + 1e-6;
-  if (lin) { d.lin_lo = lin->lo; d.lin_ratio = lin->ratio; d.rows = lin->rows; d.cols = lin->cols; }
-  if (ang) { d.ang_lo = ang->lo; d.ang_ratio = ang->ratio; }
+  d.lin_lo = m.lin_lo; d.lin_ratio = m.lin_ratio; d.rows = m.rows; d.cols = m.cols;
+  d.ang_lo = m.ang_lo; d.ang_ratio = m.ang_ratio;
   d.lin_zero_byte = -1;
-  for (int b = 0; b < 128 && lin; ++b)
+  for (int b = 0; b < 128 && m.lin_grid; ++b)
     if (std::fma(d.lin_ratio, (double)b, d.lin_lo) == 0.0) { d.lin_zero_byte = b; break; }
-  d.lin_max_byte = lin ? tdm_max_byte(lin) : 0;
-  d.ang_max_byte = ang ? tdm_max_byte(ang) : 0;
+  d.lin_max_byte = m.lin_max_byte;
+  d.ang_max_byte = m.ang_max_byte;
   d.s0sq = (double)a.u_std[0] * (double)a.u_std[0];
   d.s1sq = (double)a.u_std[1] * (double)a.u_std[1];
   d.n_local = p->n_local;
@@ -84,6 +86,19 @@ static int reserve_cells(mppi_planner* p, const mppi_tdm* lin, int M) {
     p->cells_capacity = need;
   }
   return MPPI_OK;
+}
+
+// the cell words now hold these TDMs' grids: what the launches need to know of them (the only writer of p->packed)
+static void note_packed(mppi_planner* p, const mppi_tdm* lin, const mppi_tdm* ang) {
+  PackedMaps& m = p->packed;
+  if (m.lin_maps != lin->maps_version) p->speculation_off = false;  // a new map: speculate again
+  m.lin_maps = lin->maps_version; m.lin_grid = lin->grid_version;
+  m.ang_maps = ang->maps_version; m.ang_grid = ang->grid_version;
+  m.lin_lo = lin->lo; m.lin_ratio = lin->ratio; m.ang_lo = ang->lo; m.ang_ratio = ang->ratio;
+  m.rows = lin->rows; m.cols = lin->cols;
+  m.lin_max_byte = tdm_max_byte(lin); m.ang_max_byte = tdm_max_byte(ang);
+  m.sink_ring = lin->injected ? lin->injected_sink_ring : lin->maps_sink_ring;
+  m.risk = lin->risk;
 }
 
 // solve() of a CVaR planner, Philox generators: both TDMs sampled straight into the cell words
@@ -124,16 +139,10 @@ static bool sample_into_cells(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, dou
     t->sampled_maps_version = t->maps_version;
     t->grid_stale = true;  // the int8 grids of these draws do not exist yet
     t->injected = false;
-    ++t->grid_version;
+    t->grid_version = next_generation();
   }
   p->cells16_valid = false;
-  p->risk_ref = lin->risk;
-  p->packed_lin = lin;
-  p->packed_ang = ang;
-  p->packed_lin_grid = lin->grid_version;
-  p->packed_ang_grid = ang->grid_version;
-  if (p->packed_lin_maps != lin->maps_version) p->speculation_off = false;  // a new map: speculate again
-  p->packed_lin_maps = lin->maps_version;
+  note_packed(p, lin, ang);
   return true;
 }
 
@@ -143,8 +152,9 @@ static int ensure_packed(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {
   // solve() samples the traction grids itself; the stage-level entry points use what is there
   REQUIRE(lin->grid_version > 0 && ang->grid_version > 0, MPPI_ERR_STATE,
           "traction grids have never been sampled: call mppi_tdm_sample_grids (or mppi_planner_solve) first");
-  if (p->packed_lin == lin && p->packed_ang == ang && p->packed_lin_grid == lin->grid_version &&
-      p->packed_ang_grid == ang->grid_version && p->packed_lin_maps == lin->maps_version)
+  const PackedMaps& m = p->packed;
+  if (m.lin_maps == lin->maps_version && m.lin_grid == lin->grid_version && m.ang_maps == ang->maps_version &&
+      m.ang_grid == ang->grid_version)
     return MPPI_OK;
   const int M = p->cfg.num_grid_samples;
   TRY(reserve_cells(p, lin, M));
@@ -189,13 +199,15 @@ static int ensure_packed(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {
                        p->cells);
   }
   HIP_TRY(hipGetLastError());
-  p->risk_ref = lin->risk;
-  p->packed_lin = lin;
-  p->packed_ang = ang;
-  p->packed_lin_grid = lin->grid_version;
-  p->packed_ang_grid = ang->grid_version;
-  if (p->packed_lin_maps != lin->maps_version) p->speculation_off = false;  // a new map: speculate again
-  p->packed_lin_maps = lin->maps_version;
+  note_packed(p, lin, ang);
+  return MPPI_OK;
+}
+
+// the TDMs checked, their maps packed if they changed, and the launches' parameters
+static int prepare_launch(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, DevParams* d) {
+  TRY(check_tdms(p, lin, ang));
+  TRY(ensure_packed(p, lin, ang));
+  *d = make_dev_params(p);
   return MPPI_OK;
 }
 
@@ -318,15 +330,11 @@ static bool plan_lds_window(mppi_planner* p, DevParams& d, size_t* lds_bytes) {
 // exact floor division and the clamp, i.e. the border cell, like k_rollout_map and k_rollout_fused.
 static bool unclamped_lookup_ok(const mppi_planner* p, const DevParams& d) {
   const mppi_params& a = p->params;
-  const mppi_tdm* lin = p->packed_lin;
   const double vmax = std::fmax(std::fabs((double)a.vrange[0]), std::fabs((double)a.vrange[1]));
   const double trmax = std::fmax(std::fabs(d.lin_lo), std::fabs(d.lin_lo + (double)d.lin_max_byte * d.lin_ratio));
   const double step_cells = (double)a.dt * vmax * trmax / (double)a.res;
   if (!std::isfinite(step_cells)) return false;
-  if (lin) {
-    const int ring = lin->injected ? lin->injected_sink_ring : lin->maps_sink_ring;
-    if ((double)ring >= std::ceil(step_cells + 1e-3)) return true;
-  }
+  if (p->packed.lin_grid && (double)p->packed.sink_ring >= std::ceil(step_cells + 1e-3)) return true;
   if (p->inst_set) return false;  // (per-problem windows are shifted inwards at the border)
   const double reach = std::ceil((double)p->cfg.num_steps * step_cells) + 2.0;
   const double xi0 = std::floor(((double)a.x0[0] - (double)a.xlo) / (double)a.res);
@@ -457,15 +465,14 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out);
 static bool scan_plan(const mppi_planner* p, ScanPlan* out) {
   struct Key {
     mppi_params params;
-    const void *lin, *ang;
-    uint64_t lin_grid, ang_grid, lin_maps;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid;
     int debug_flags, speculation_off, cells16_valid, cells16_with_risk, params_set, pad;
   } key;
   if (p->inst_set) return scan_plan_compute(p, out);
   memset(&key, 0, sizeof(key));
   key.params = p->params;
-  key.lin = p->packed_lin; key.ang = p->packed_ang;
-  key.lin_grid = p->packed_lin_grid; key.ang_grid = p->packed_ang_grid; key.lin_maps = p->packed_lin_maps;
+  key.lin_maps = p->packed.lin_maps; key.lin_grid = p->packed.lin_grid;
+  key.ang_maps = p->packed.ang_maps; key.ang_grid = p->packed.ang_grid;
   key.debug_flags = p->debug_flags; key.speculation_off = p->speculation_off; key.cells16_valid = p->cells16_valid;
   key.cells16_with_risk = p->cells16_with_risk; key.params_set = p->params_set;
   mppi_planner* q = const_cast<mppi_planner*>(p);  // (the cache only)
@@ -491,7 +498,7 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
   if (stopped && p->cfg.math != MPPI_MATH_EXACT) return false;  // (the tolerance kernel has no exact schedule inside)
   const bool direct = (stopped || (p->debug_flags & MPPI_DEBUG_NO_SPECULATION)) && p->cfg.math == MPPI_MATH_EXACT;
   if (direct && ((p->debug_flags & MPPI_DEBUG_NO_SCAN_DIRECT) || p->cfg.math != MPPI_MATH_EXACT ||
-                 !p->packed_lin || !p->packed_ang || speed))
+                 !p->packed.lin_grid || speed))
     return false;
   const int T = p->cfg.num_steps;
   ScanPlan plan;
@@ -514,9 +521,9 @@ static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
   plan.pow2res = res_is_pow2(p);
   // (the template flag also selects the unclamped address of the exact schedule inside the kernel -- direct launches
   //  and re-executed tiles: only where no rollout can leave the map)
-  const DevParams d0 = make_dev_params(p, p->packed_lin, p->packed_ang);
+  const DevParams d0 = make_dev_params(p);
   // (the speed-map form has no exact schedule inside: its lookups all clamp)
-  plan.pow2res = plan.pow2res && (speed || (p->packed_lin && unclamped_lookup_ok(p, d0)));
+  plan.pow2res = plan.pow2res && (speed || (p->packed.lin_grid && unclamped_lookup_ok(p, d0)));
   if (plan.direct) {
     // the exact schedule needs the 16-bit window of the cells reachable within the horizon in LDS, next to the noise,
     // and the exact-increment rotation (|dt * w * traction| <= 0.36 rad): else k_rollout_pipe / the general kernels
@@ -666,7 +673,7 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));            \
     MPPI_KLAUNCH(kern, dim3(tiles), dim3(64 * plan.waves), plan.lds, p->stream, d, p->cells16, p->cells,   \
                  p->noise, gen_job, p->u, p->costs, p->w_rel, pk, pend, fallback,                          \
-                 (const int8_t*)(speed ? p->risk_ref : nullptr));                                          \
+                 (const int8_t*)(speed ? p->packed.risk : nullptr));                                       \
   } while (0)
 #define MPPI_LAUNCH_SCAN(RR, P2, GEN)                                                                      \
   do {                                                                                                    \
@@ -952,7 +959,7 @@ static int launch_rollout_speed_map(mppi_planner* p, DevParams d) {
     return MPPI_OK;
   }
   MPPI_KLAUNCH((k_rollout_map<MAP_SPEED, EXACT, BOUNDED, false>), dim3(ceil_div(N, 64)), dim3(64),
-                     lds_map, p->stream, d, p->cells, (const uint16_t*)nullptr, (const int8_t*)p->risk_ref,
+                     lds_map, p->stream, d, p->cells, (const uint16_t*)nullptr, (const int8_t*)p->packed.risk,
                      p->noise, p->u, p->costs);
   p->last_rollout = "k_rollout_map speed_map global_cells exact=" + std::to_string((int)EXACT);
   HIP_TRY(hipGetLastError());
@@ -1442,13 +1449,12 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
 
 // Everything the launches of an iteration take by value or derive on the host: a captured graph
 // may be replayed only while none of it has changed.
-static void graph_signature(const mppi_planner* p, const DevParams& d, const mppi_tdm* lin, const mppi_tdm* ang,
-                            std::vector<unsigned char>& out) {
+static void graph_signature(const mppi_planner* p, const DevParams& d, std::vector<unsigned char>& out) {
   struct Sig {
     DevParams d;
     mppi_params params;
-    const void *lin, *ang, *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_grid, ang_grid, lin_maps, epoch_bias;
+    const void *cells, *cells16, *cc, *sample_costs, *u;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1459,9 +1465,10 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, const mpp
     memset(sig.params.x0, 0, sizeof(sig.params.x0));
     memset(sig.params.xgoal, 0, sizeof(sig.params.xgoal));
   }
-  sig.lin = lin; sig.ang = ang; sig.cells = p->cells; sig.cells16 = p->cells16; sig.cc = p->cc_scratch;
+  sig.cells = p->cells; sig.cells16 = p->cells16; sig.cc = p->cc_scratch;
   sig.sample_costs = p->sample_costs; sig.u = p->u;
-  sig.lin_grid = p->packed_lin_grid; sig.ang_grid = p->packed_ang_grid; sig.lin_maps = p->packed_lin_maps;
+  sig.lin_maps = p->packed.lin_maps; sig.lin_grid = p->packed.lin_grid;
+  sig.ang_maps = p->packed.ang_maps; sig.ang_grid = p->packed.ang_grid;
   sig.epoch_bias = p->noise_epoch - p->bumps_launched;
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
@@ -1507,9 +1514,8 @@ static void review_speculation(mppi_planner* p) {
 static int run_iterations(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, int iterations, bool timed = true,
                           bool mirror_last = false, bool part_of_group_loop = false, bool more_follow = false) {
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
-  TRY(check_tdms(p, lin, ang));
-  TRY(ensure_packed(p, lin, ang));
-  DevParams d = make_dev_params(p, lin, ang);
+  DevParams d;
+  TRY(prepare_launch(p, lin, ang, &d));
   p->iterations_since_wait += iterations;
   timed = (timed || p->profile_stages) && !part_of_group_loop;
   if (timed) HIP_TRY(hipEventRecord(p->ev_begin, p->stream));
@@ -1556,7 +1562,7 @@ static int run_iterations(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, int ite
     const int chunk = p->graph_chunk;  // iterations per graph: even (noise double buffer)
     while (iterations - k >= chunk) {
       std::vector<unsigned char> sig;
-      graph_signature(p, d, lin, ang, sig);
+      graph_signature(p, d, sig);
       sig.push_back(have_noise ? 1 : 0);
       const int slot = (p->noise_cur & 1) | ((p->u_parity & 1) << 1) | ((p->tpk_cur & 1) << 2);
       if (!p->graph_exec[slot] || sig != p->graph_sig[slot]) {

@@ -9,13 +9,13 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -71,22 +71,8 @@ extern "C" int mppi_device_props_get(int device, mppi_device_props* out) {
 }
 
 
-// live planners of this process: a planner remembers which TDMs its cell words were packed from (packed_lin / packed_ang,
-// dereferenced again by scan_plan); a TDM that goes away takes those notes with it
-static std::vector<mppi_planner*> g_planners;
-static std::mutex g_planners_mutex;  // (handles are single-threaded each; the registry is shared)
-
 extern "C" int mppi_tdm_destroy(mppi_tdm* t) {
   if (!t) return MPPI_OK;
-  {
-    std::lock_guard<std::mutex> lock(g_planners_mutex);
-    for (mppi_planner* p : g_planners) {
-      if (p->packed_lin == t || p->packed_ang == t) {
-        p->packed_lin = p->packed_ang = nullptr;
-        p->packed_lin_grid = p->packed_ang_grid = p->packed_lin_maps = ~0ULL;
-      }
-    }
-  }
   (void)hipSetDevice(t->cfg.device);
   dev_free(t->grid);
   dev_free(t->pmf);
@@ -205,7 +191,7 @@ extern "C" int mppi_tdm_set_maps(mppi_tdm* t, const int8_t* pmf, int bins, int r
   t->ratio = traction_ratio;
   t->maps_set = true;
   t->injected_sink_ring = 0;  // (judged with the old traction bounds)
-  ++t->maps_version;
+  t->maps_version = next_generation();
   return MPPI_OK;
 }
 
@@ -317,7 +303,7 @@ extern "C" int mppi_tdm_set_maps_from_pmf(mppi_tdm* t, int kind, const int8_t* p
   t->ratio = traction_ratio;
   t->maps_set = true;
   t->injected_sink_ring = 0;  // (judged with the old traction bounds)
-  ++t->maps_version;
+  t->maps_version = next_generation();
   return MPPI_OK;
 }
 
@@ -397,7 +383,7 @@ static int tdm_sample_on(mppi_tdm* t, double alpha_dyn, hipStream_t stream) {
   HIP_TRY(hipGetLastError());
   t->sampled_maps_version = t->maps_version;
   t->sampled_alpha = alpha_dyn;
-  ++t->grid_version;
+  t->grid_version = next_generation();
   t->injected = false;
   return MPPI_OK;
 }
@@ -444,7 +430,7 @@ extern "C" int mppi_tdm_set_sampled_grids(mppi_tdm* t, const int8_t* grids, int 
       if (std::fma(t->ratio, (double)grids[((size_t)g * rows + r) * cols + c], t->lo) != 0.0) return false;
     return true;
   });
-  ++t->grid_version;
+  t->grid_version = next_generation();
   t->sampled_maps_version = ~0ULL;  // injected grids are not a cached sample
   t->grid_stale = false;             // (a lazy sample, if any, is superseded)
   t->injected = true;                // arbitrary bytes: the 16-bit cell format is not guaranteed
@@ -489,10 +475,6 @@ extern "C" int mppi_comm_unique_id(char id[MPPI_COMM_ID_BYTES]) {
 
 extern "C" int mppi_planner_destroy(mppi_planner* p) {
   if (!p) return MPPI_OK;
-  {
-    std::lock_guard<std::mutex> lock(g_planners_mutex);
-    g_planners.erase(std::remove(g_planners.begin(), g_planners.end(), p), g_planners.end());
-  }
   (void)hipSetDevice(p->cfg.device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   if (p->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(p->comm);
@@ -696,10 +678,6 @@ extern "C" int mppi_planner_create(const mppi_planner_cfg* cfg, mppi_planner** o
     mppi_planner_destroy(p);
     g_last_error = keep;
     return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lock(g_planners_mutex);
-    g_planners.push_back(p);
   }
   *out = p;
   return MPPI_OK;
@@ -1188,8 +1166,8 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
   memset(&L, 0, sizeof(L));
   auto plan_loop = [&]() -> int {
     // the window plan the host would make for every new start state, handed to the step kernel
-    TRY(ensure_packed(p, lin, ang));
-    DevParams plan = make_dev_params(p, lin, ang);
+    DevParams plan;
+    TRY(prepare_launch(p, lin, ang, &plan));
     size_t lds_unused = 0;
     const bool windowed = plan_lds_window(p, plan, &lds_unused);
     TRY(upload_instances(p));
@@ -1308,9 +1286,8 @@ extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* an
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   HIP_TRY(hipSetDevice(p->cfg.device));
-  TRY(check_tdms(p, lin, ang));
-  TRY(ensure_packed(p, lin, ang));
-  DevParams d = make_dev_params(p, lin, ang);
+  DevParams d;
+  TRY(prepare_launch(p, lin, ang, &d));
   TRY(launch_rollout(p, d));
   if (p->m_count > 1) {
     // samples sharded over ranks: with a communicator the slabs are exchanged and reduced here, as
@@ -1449,12 +1426,11 @@ extern "C" int mppi_planner_update_apply_and_rollout(mppi_planner* p, const doub
   //  mppi_planner_rollout / sample_costs_local / sample_costs_apply / update)
   REQUIRE(p->m_count == 1, MPPI_ERR_STATE, "update_apply_and_rollout serves handles that shard their control samples");
   HIP_TRY(hipSetDevice(p->cfg.device));
-  TRY(check_tdms(p, lin, ang));
-  TRY(ensure_packed(p, lin, ang));
+  DevParams d;
+  TRY(prepare_launch(p, lin, ang, &d));
   const int len = p->B * packet_len(p->cfg.num_steps);
   HIP_TRY(hipMemcpyAsync(p->packets, packets, sizeof(double) * (size_t)len * (size_t)count,
                          hipMemcpyHostToDevice, p->stream));
-  DevParams d = make_dev_params(p, lin, ang);
   // the rollout launch applies the update when it is one that can (launch_rollout settles it otherwise)
   if (next_rollout_applies_updates(p)) p->apply_pending = true;
   else TRY(launch_apply(p));
@@ -1488,10 +1464,9 @@ extern "C" int mppi_planner_get_instance_state_rollout(mppi_planner* p, mppi_tdm
   REQUIRE(instance >= 0 && instance < p->B, MPPI_ERR_INVALID, "instance %d of %d", instance, p->B);
   REQUIRE(p->B == 1 || p->inst_set, MPPI_ERR_STATE, "instances not set");
   HIP_TRY(hipSetDevice(p->cfg.device));
-  TRY(check_tdms(p, lin, ang));
-  TRY(ensure_packed(p, lin, ang));  // uses the already sampled grids (mppi.py:572-573)
+  DevParams d;
+  TRY(prepare_launch(p, lin, ang, &d));  // uses the already sampled grids (mppi.py:572-573)
   TRY(materialize_noise(p));
-  DevParams d = make_dev_params(p, lin, ang);
   // one problem of a batched handle: its start state, its controls, its slice of the noise
   struct Rebased {
     float2 *noise, *u, *u_prev;
@@ -1879,9 +1854,7 @@ extern "C" int mppi_group_iterate_async(mppi_planner** ps, mppi_tdm** lins, mppi
     REQUIRE(p->params_set, MPPI_ERR_STATE, "planner %d: params not set", g);
     REQUIRE(!p->graph_on, MPPI_ERR_STATE, "graph replay and group iteration do not combine");
     HIP_TRY(hipSetDevice(p->cfg.device));
-    TRY(check_tdms(p, lins[g], angs[g]));
-    TRY(ensure_packed(p, lins[g], angs[g]));
-    d[(size_t)g] = make_dev_params(p, lins[g], angs[g]);
+    TRY(prepare_launch(p, lins[g], angs[g], &d[(size_t)g]));
     have[(size_t)g] = p->primed;
     HIP_TRY(hipEventRecord(p->ev_begin, p->stream));
   }

@@ -17,6 +17,7 @@ import pytest
 import bench
 from mppi_numba_amd import _lib
 from oracle import oracle as O
+from test_gpu_scale import custom_world
 
 pytestmark = pytest.mark.gpu
 
@@ -274,3 +275,93 @@ def test_graph_replay_of_the_generating_loop():
     assert b.graph_stats()["replays"] >= 3
     np.testing.assert_array_equal(a.u_cur_d.copy_to_host(), b.u_cur_d.copy_to_host())
     np.testing.assert_array_equal(a.noise_samples_d.copy_to_host(), b.noise_samples_d.copy_to_host())
+
+
+
+
+def swap_cfg(pad_speed=6.0):
+    from mppi_numba_amd.config import Config
+    return Config(T=4.05, dt=0.1, num_grid_samples=1, num_control_rollouts=1024, max_speed_padding=pad_speed,
+                  num_vis_state_rollouts=1, max_map_dim=(70, 70), seed=11, enforce_recommended_limits=False,
+                  use_det_dynamics=True)
+
+
+def swap_tdms(rows, cols, pad_speed, origin, seed):
+    """Det-dynamics TDMs of a custom world: 0.25 m cells from `origin`, a padding ring of zero traction (bin 0)
+    ceil(pad_speed * 0.1 / 0.25) cells wide."""
+    from mppi_numba_amd.terrain import TDM_Numba
+    pmf, obstacle, unknown, td = custom_world(rows, cols, 0.25, seed)
+    td = dict(td, xlimits=(origin, origin + cols * 0.25), ylimits=(origin, origin + rows * 0.25))
+    lin, ang = TDM_Numba(swap_cfg(pad_speed)), TDM_Numba(swap_cfg(pad_speed))
+    lin.set_TDM_from_PMF_grid(pmf, td, obstacle, unknown)
+    ang.set_TDM_from_PMF_grid(pmf[:, :, ::-1].copy(), td, obstacle, unknown)
+    return lin, ang
+
+
+def launch_geometry(desc):
+    """The kernel and launch geometry a rollout kernel description names."""
+    words = desc.split()
+    return [words[0]] + [w for w in words if w.split("=")[0] in ("tile", "waves", "pow2res", "lds", "direct")]
+
+
+@pytest.mark.parametrize("flags,graph", [(0, False), (_lib.DEBUG_NO_SPECULATION, False),
+                                         (_lib.DEBUG_NO_SPECULATION, True)])
+def test_maps_of_new_tdms_get_their_own_plan(flags, graph):
+    """The usual map update: the old TDMs are destroyed, new ones created (the allocator may hand out the freed
+    memory again) with other dims, set and sampled once -- same params, padded origin included.  The planner must
+    plan for the new maps: a plan kept from the old ones would form unclamped addresses (pow2res) on a map whose
+    ring does not hold a step, and size the direct launch's window for the old dims.  With graph replay the loop is
+    captured anew, with the same results as without."""
+    import gc
+    from mppi_numba_amd.mppi import MPPI_Numba
+    # a step is up to 1.2 cells (3 m/s, 0.1 s, 0.25 m); x0 16 cells from the padded border, heading for it
+    params = bench.make_params("c2")
+    params.update(x0=np.array([-0.75 + 16.5 * 0.25, 6.0, 3.0]), xgoal=np.array([1.0, 9.0]), lambda_weight=3.0)
+    planners = [MPPI_Numba(swap_cfg()) for _ in range(2 if graph else 1)]  # (the second one: no graph replay)
+    # A: a ring of 3 cells (the reference's padding for 6 m/s), a power-of-two resolution: unclamped addresses
+    lin, ang = swap_tdms(60, 50, 6.0, 0.0, seed=21)
+    for p in planners:
+        p.set_debug_flags(flags)
+        p.setup(params, lin, ang)
+    if graph:
+        planners[0].set_graph_replay(True, 2)
+    for p in planners:
+        p.solve()
+        p.iterate_async(5)
+        p.synchronize()
+        assert "pow2res=1" in p.last_rollout_kernel(), p.last_rollout_kernel()
+    captures = planners[0].graph_stats()["captures"]
+    assert captures >= 1 or not graph
+    for p in planners:
+        p.set_tdm(None, None)
+    del lin, ang
+    gc.collect()
+    # B: other dims, a ring of 1 cell -- narrower than a step -- and a reach bound (50 cells) that leaves the map
+    lin, ang = swap_tdms(48, 56, 2.5, -0.5, seed=22)
+    assert np.array_equal(lin.padded_xlimits[:1], [-0.75]) and np.array_equal(lin.padded_ylimits[:1], [-0.75])
+    lin.sample_grids()
+    ang.sample_grids()
+    for p in planners:
+        p.set_tdm(lin, ang)
+    if graph:
+        for p in planners:
+            p.iterate_async(5)
+            p.synchronize()
+        assert planners[0].graph_stats()["captures"] > captures, planners[0].graph_stats()
+        for name in ("costs_d", "u_cur_d", "noise_samples_d"):
+            np.testing.assert_array_equal(getattr(planners[0], name).copy_to_host(), getattr(planners[1], name).copy_to_host())
+    planner = planners[0]
+    planner.sample_noise()
+    noise, u_in = planner.noise_samples_d.copy_to_host(), planner.u_cur_d.copy_to_host()
+    planner.rollout()
+    got = planner.last_rollout_kernel()
+    np.testing.assert_array_equal(planner.costs_d.copy_to_host(), oracle_costs(params, lin, ang, noise, u_in))
+    fresh = MPPI_Numba(swap_cfg())
+    fresh.set_debug_flags(flags)
+    fresh.setup(params, lin, ang)
+    fresh.sample_noise()
+    fresh.rollout()
+    want = fresh.last_rollout_kernel()
+    assert want.startswith("k_rollout_scan_exact") and "pow2res=0" in want, want
+    assert ("direct=1" in want) == bool(flags), want
+    assert launch_geometry(got) == launch_geometry(want), (got, want)
