@@ -214,10 +214,21 @@ int mppi_planner_set_disc_obstacles(mppi_planner* p, const float* positions, con
  * minimum cost and normaliser.  Instance b is bit-identical to a single-instance
  * handle given the same noise.  Array shapes with B > 1: u (B,T,2), costs and
  * weights (B,N_local), noise (B*N_local,T,2), packets B*(2T+2) doubles per rank.
- * Needs N/world_size to be a multiple of 64; not available in MPPI_MODE_BAREBONE.
+ * Needs N/world_size to be a multiple of 64.  MPPI_MODE_BAREBONE: the problems share the disc set
+ * of mppi_planner_set_disc_obstacles, or each has its own (below); world_size must be 1.
  * x0: (count,3) float32, xgoal: (count,2) float32; count must equal B.  A handle with B = 1
  * also takes count = 0 (x0, xgoal ignored): back to the start / goal of mppi_params. */
 int mppi_planner_set_instances(mppi_planner* p, int count, const float* x0, const float* xgoal);
+
+/* MPPI_MODE_BAREBONE only: one disc set per problem.  count must equal B; disc_counts [B] >= 0,
+ * positions (sum of the counts, 2) float32 and radii (sum) float32, problem b's discs following
+ * problem b-1's.  Problem b's costs are bit-identical to a single-problem handle given its discs
+ * (in the same order) through mppi_planner_set_disc_obstacles.  count = 0: every problem back to
+ * the shared set.  Unchanged arrays cost a comparison and no synchronisation; a change drops the
+ * captured graphs.  MPPI_ERR_INVALID for a map mode, a negative count, count not 0 and not B, or
+ * a largest set whose discs and the T control ratios need more than 64 KiB of LDS (16*T + 16*K). */
+int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int count, const int* disc_counts,
+                                             const float* positions, const float* radii);
 
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
@@ -372,7 +383,9 @@ int mppi_world_sample_true_dist(mppi_world* w, const int32_t* terrain_of_cell, i
  *   xhist  [B][max_steps+1][3] float64, row 0 = start, rows never reached = NaN
  *   uhist  [B][max_steps][2]   float32, the control applied at every step (NaN likewise)
  *   steps_taken [B]            steps until the goal test passed (or the number of steps run)
- * Afterwards the handle is where the notebook's loop would have left it (start states, shifted u). */
+ * Afterwards the handle is where the notebook's loop would have left it (start states, shifted u).
+ * MPPI_MODE_BAREBONE: lin = ang = w = NULL, the barebone notebook's loop (cell 7): the nominal
+ * unicycle, x += dt*cos(th)*u0, y += dt*sin(th)*u0, th += dt*u1 in float64.  The map modes need w. */
 int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, mppi_world* w, int max_steps,
                              double dt, double goal_tolerance, const double* x_init, double* xhist, float* uhist,
                              int* steps_taken);

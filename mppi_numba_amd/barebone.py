@@ -66,6 +66,7 @@ class MPPI_Numba(object):
 
     def __init__(self, cfg):
         self.cfg = cfg
+        self.num_instances = int(getattr(self, "num_instances", 1))  # (MPPI_Batch sets it first)
         self.T = cfg.T
         self.dt = cfg.dt
         self.num_steps = cfg.num_steps
@@ -110,17 +111,20 @@ class MPPI_Numba(object):
             num_grid_samples=1, num_vis_state_rollouts=int(self.num_vis_state_rollouts),
             rng=_lib.RNG_XOROSHIRO if getattr(self.cfg, "rng", "philox") == "xoroshiro" else _lib.RNG_PHILOX,
             math=_lib.MATH_FAST if getattr(self.cfg, "math", "exact") == "fast" else _lib.MATH_EXACT,
-            rank=0, world_size=1, seed=int(self.seed))
+            rank=0, world_size=1, num_instances=self.num_instances, seed=int(self.seed))
         handle = C.c_void_p()
         _lib.call("mppi_planner_create", C.byref(cfg), C.byref(handle))
         self._handle = handle
-        n, t, v = self.num_control_rollouts, self.num_steps, self.num_vis_state_rollouts
+        B, t, v = self.num_instances, self.num_steps, self.num_vis_state_rollouts
+        n = B * self.num_control_rollouts
+        lead = () if B == 1 else (B,)
+        ushape, cshape = lead + (t, 2), lead + (self.num_control_rollouts,)
         self.noise_samples_d = DeviceArray((n, t, 2), np.float32, lambda: self._fetch("mppi_planner_get_noise", (n, t, 2)))
-        self.u_cur_d = DeviceArray((t, 2), np.float32, lambda: self._fetch("mppi_planner_get_u", (t, 2)))
-        self._u_prev_view = DeviceArray((t, 2), np.float32, lambda: self._fetch("mppi_planner_get_u_prev", (t, 2)))
+        self.u_cur_d = DeviceArray(ushape, np.float32, lambda: self._fetch("mppi_planner_get_u", ushape))
+        self._u_prev_view = DeviceArray(ushape, np.float32, lambda: self._fetch("mppi_planner_get_u_prev", ushape))
         self.u_prev_d = self._u_prev_view
-        self.costs_d = DeviceArray((n,), np.float32, lambda: self._fetch("mppi_planner_get_costs", (n,)))
-        self.weights_d = DeviceArray((n,), np.float32, lambda: self._fetch("mppi_planner_get_weights", (n,)))
+        self.costs_d = DeviceArray(cshape, np.float32, lambda: self._fetch("mppi_planner_get_costs", cshape))
+        self.weights_d = DeviceArray(cshape, np.float32, lambda: self._fetch("mppi_planner_get_weights", cshape))
         self._last_state_rollout = np.zeros((v, t + 1, 3), dtype=np.float32)
         self.state_rollout_batch_d = DeviceArray((v, t + 1, 3), np.float32, lambda: self._last_state_rollout.copy())
         self.device_var_initialized = True
@@ -193,7 +197,7 @@ class MPPI_Numba(object):
 
     def solve_with_nominal_dynamics(self):
         self.move_mppi_task_vars_to_device()
-        useq = np.empty((self.num_steps, 2), dtype=np.float32)
+        useq = np.empty(((self.num_instances,) if self.num_instances > 1 else ()) + (self.num_steps, 2), dtype=np.float32)
         _lib.call("mppi_planner_solve", self._handle, None, None, _lib.ptr(useq, C.c_float))
         self.u_prev_d = self._u_prev_view
         return useq
@@ -219,13 +223,65 @@ class MPPI_Numba(object):
         self._last_state_rollout = out
         return out.copy()
 
+    def closed_loop(self, max_steps, goal_tolerance=None, x_init=None):
+        """The notebook's control loop (barebone_mppi_numba.ipynb cell 7) on the device: max_steps times {solve, float64
+        Euler step of the nominal unicycle with useq[0], shift_and_update, goal check}, without a host round trip per
+        control step.  Returns (xhist (max_steps+1, 3) float64, uhist (max_steps, 2) float32, steps_taken) -- with a
+        leading problem axis for a batch; rows never reached are NaN, as in the notebook.  Afterwards params['x0'] and
+        the device's control sequence are where the loop left them (see mppi.MPPI_Numba.closed_loop)."""
+        if not self.check_solve_conditions():
+            print("MPPI solve condition not met. Cannot solve. Return")
+            return
+        B, single = self.num_instances, self.num_instances == 1
+        self.move_mppi_task_vars_to_device()
+        if single:
+            x0 = np.asarray(self.params["x0"], dtype=np.float64).reshape(1, 3) if x_init is None \
+                else np.asarray(x_init, dtype=np.float64).reshape(1, 3)
+            x0_f32 = np.ascontiguousarray(x0.astype(np.float32))
+            goal = np.ascontiguousarray(np.asarray(self.params["xgoal"], dtype=np.float64).astype(np.float32)).reshape(1, 2)
+            _lib.call("mppi_planner_set_instances", self._handle, 1, _lib.ptr(x0_f32, C.c_float),
+                      _lib.ptr(goal, C.c_float))
+            x_init = x0
+        tol = float(self.params["goal_tolerance"] if goal_tolerance is None else goal_tolerance)
+        xhist = np.empty((B, max_steps + 1, 3), dtype=np.float64)
+        uhist = np.empty((B, max_steps, 2), dtype=np.float32)
+        steps = np.zeros(B, dtype=np.int32)
+        xi = None
+        if x_init is not None:
+            xi = np.ascontiguousarray(np.asarray(x_init, dtype=np.float64).reshape(B, 3))
+        try:
+            _lib.call("mppi_planner_closed_loop", self._handle, None, None, None, int(max_steps), float(self.cfg.dt), tol,
+                      None if xi is None else _lib.ptr(xi, C.c_double), _lib.ptr(xhist, C.c_double),
+                      _lib.ptr(uhist, C.c_float), _lib.ptr(steps, C.c_int))
+        finally:
+            if single:
+                _lib.call("mppi_planner_set_instances", self._handle, 0, None, None)
+        self.u_prev_d = self._u_prev_view
+        last = np.stack([xhist[b, steps[b]] for b in range(B)])
+        if single:
+            self.params["x0"] = last[0].copy()
+            return xhist[0], uhist[0], int(steps[0])
+        self.x0s = np.ascontiguousarray(last.astype(np.float32))
+        self.params["x0"] = last[0].copy()
+        return xhist, uhist, steps
+
+    def set_graph_replay(self, enabled=True, iterations_per_graph=2):
+        """hipGraph replay of the iteration loop (include/mppi_hip.h); same results."""
+        _lib.call("mppi_planner_set_graph_replay", self._handle, int(iterations_per_graph) if enabled else 0)
+
+    def graph_stats(self):
+        captures, replays = C.c_long(0), C.c_long(0)
+        _lib.call("mppi_planner_graph_stats", self._handle, C.byref(captures), C.byref(replays))
+        return dict(captures=int(captures.value), replays=int(replays.value))
+
     # --- stage-level hooks for parity tests (not in the notebook) ---
     def set_u(self, u):
-        u = np.ascontiguousarray(u, dtype=np.float32).reshape(self.num_steps, 2)
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(self.num_instances * self.num_steps, 2)
         _lib.call("mppi_planner_set_u", self._handle, _lib.ptr(u, C.c_float))
 
     def set_noise(self, noise):
-        noise = np.ascontiguousarray(noise, dtype=np.float32).reshape(self.num_control_rollouts, self.num_steps, 2)
+        noise = np.ascontiguousarray(noise, dtype=np.float32).reshape(
+            self.num_instances * self.num_control_rollouts, self.num_steps, 2)
         _lib.call("mppi_planner_set_noise", self._handle, _lib.ptr(noise, C.c_float))
 
     def sample_noise(self):
@@ -237,7 +293,7 @@ class MPPI_Numba(object):
         _lib.call("mppi_planner_rollout", self._handle, None, None)
 
     def set_costs(self, costs):
-        costs = np.ascontiguousarray(costs, dtype=np.float32).reshape(self.num_control_rollouts)
+        costs = np.ascontiguousarray(costs, dtype=np.float32).reshape(self.num_instances * self.num_control_rollouts)
         _lib.call("mppi_planner_set_costs", self._handle, _lib.ptr(costs, C.c_float))
 
     def update(self):
@@ -254,3 +310,107 @@ class MPPI_Numba(object):
     def set_debug_flags(self, flags):
         """Developer switches (_lib.DEBUG_*): which rollout kernel variant runs; never the costs."""
         _lib.call("mppi_planner_set_debug_flags", self._handle, int(flags))
+
+
+class MPPI_Batch(MPPI_Numba):
+
+    """B independent barebone problems in one handle (not in the reference; see batch.MPPI_Batch for the map modes).
+    One problem of the notebook's shape (N = 1000, T = 50) keeps 16 waves busy; a batch fills the device with one launch
+    over (problem, rollout).  Each problem has its own start, goal, control sequence and, optionally, its own disc set
+    (e.g. the other robots' predicted positions); its result is bit-identical to a single-problem MPPI_Numba given the
+    same discs, controls and noise.
+
+        batch = MPPI_Batch(cfg, num_instances=64)          # cfg.num_control_rollouts: a multiple of 64
+        batch.setup(params, x0s, goals, obstacle_sets)     # params as for MPPI_Numba
+        useqs = batch.solve()                              # (B, T, 2) float32
+        batch.shift_and_update(new_x0s, useqs, num_shifts=1)
+
+    Everything in `params` except 'x0', 'xgoal' (and the discs, when obstacle_sets is given) is shared."""
+
+    def __init__(self, cfg, num_instances):
+        num_instances = int(num_instances)
+        assert num_instances >= 1, "num_instances must be >= 1"
+        self.num_instances = num_instances
+        self.x0s = None
+        self.goals = None
+        self.obstacle_sets = None
+        super().__init__(cfg)
+
+    def reset(self):
+        super().reset()
+        self.u_seq0 = np.zeros((self.num_instances, self.num_steps, 2), dtype=np.float32)
+
+    # ------------------------------------------------------------------ task set-up
+    def setup(self, params, x0s=None, goals=None, obstacle_sets=None):
+        if x0s is None:
+            x0s = np.tile(np.asarray(params["x0"], dtype=np.float32), (self.num_instances, 1))
+        if goals is None:
+            goals = np.tile(np.asarray(params["xgoal"], dtype=np.float32), (self.num_instances, 1))
+        params = dict(params)
+        params["x0"] = np.asarray(x0s[0]).copy()
+        params["xgoal"] = np.asarray(goals[0]).copy()
+        self.set_params(params)
+        self.set_instances(x0s, goals)
+        self.set_obstacle_sets(obstacle_sets)
+
+    def set_instances(self, x0s, goals=None):
+        """(B,3) start states and (B,2) goals (goals=None keeps the current ones)."""
+        x0s = np.ascontiguousarray(np.asarray(x0s, dtype=np.float64).astype(np.float32)).reshape(self.num_instances, 3)
+        if goals is None:
+            goals = self.goals
+        goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).astype(np.float32)).reshape(self.num_instances, 2)
+        self.x0s, self.goals = x0s, goals
+        _lib.call("mppi_planner_set_instances", self._handle, self.num_instances,
+                  _lib.ptr(x0s, C.c_float), _lib.ptr(goals, C.c_float))
+
+    def set_obstacle_sets(self, obstacle_sets):
+        """One disc set per problem: a list of B (positions (K_b, 2), radii (K_b,)) pairs, K_b >= 0 -- or None: every
+        problem has the shared set of params['obstacle_positions'] / ['obstacle_radius']."""
+        if obstacle_sets is None:
+            _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
+            self.obstacle_sets = None
+            return
+        assert len(obstacle_sets) == self.num_instances, "one disc set per problem"
+        pos = [_f32(np.asarray(op)).reshape(-1, 2) for op, _ in obstacle_sets]
+        rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in obstacle_sets]
+        for b in range(self.num_instances):
+            assert len(pos[b]) == len(rad[b]), "problem {}: positions and radii differ in length".format(b)
+        counts = np.ascontiguousarray([len(r) for r in rad], dtype=np.int32)
+        pos_all = np.ascontiguousarray(np.concatenate(pos) if counts.sum() else np.zeros((0, 2), np.float32))
+        rad_all = np.ascontiguousarray(np.concatenate(rad) if counts.sum() else np.zeros(0, np.float32))
+        _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, self.num_instances,
+                  _lib.ptr(counts, C.c_int), _lib.ptr(pos_all, C.c_float), _lib.ptr(rad_all, C.c_float))
+        self.obstacle_sets = [(p.copy(), r.copy()) for p, r in zip(pos, rad)]
+
+    def check_solve_conditions(self):
+        if self.x0s is None:
+            print("Batch instances are not set. Cannot solve")
+            return False
+        return super().check_solve_conditions()
+
+    # ------------------------------------------------------------------ control loop
+    def shift_and_update(self, new_x0s, u_cur, num_shifts=1):
+        """Per problem: x0 <- new_x0s[b]; u[b, :-k] = u[b, k:] (tail kept), uploaded."""
+        self.set_instances(new_x0s)
+        self.params["x0"] = np.asarray(new_x0s[0]).copy()
+        self.shift_optimal_control_sequence(u_cur, num_shifts)
+
+    def shift_and_update_on_device(self, new_x0s, num_shifts=1):
+        self.set_instances(new_x0s)
+        self.params["x0"] = np.asarray(new_x0s[0]).copy()
+        _lib.call("mppi_planner_shift_u", self._handle, int(num_shifts))
+
+    def shift_optimal_control_sequence(self, u_cur, num_shifts=1):
+        shifted = np.array(u_cur, dtype=np.float32).reshape(self.num_instances, self.num_steps, 2)
+        shifted[:, :-num_shifts] = shifted[:, num_shifts:].copy()
+        self.set_u(shifted)
+
+    def get_state_rollout(self, instance=0):
+        """(V, T+1, 3) state sequences of one problem (see MPPI_Numba.get_state_rollout)."""
+        assert self.params_set, "MPPI parameters are not set"
+        self.move_mppi_task_vars_to_device()
+        out = np.empty((self.num_vis_state_rollouts, self.num_steps + 1, 3), dtype=np.float32)
+        _lib.call("mppi_planner_get_instance_state_rollout", self._handle, None, None, int(instance),
+                  _lib.ptr(out, C.c_float))
+        self._last_state_rollout = out
+        return out.copy()

@@ -222,6 +222,14 @@ struct mppi_planner {
   float* obs_r = nullptr;
   int n_obstacles = 0;
   std::vector<float> obs_pos_host, obs_r_host;  // what the device arrays hold (mppi_planner_set_disc_obstacles)
+  // barebone batch, one disc set per problem (mppi_planner_set_instance_disc_obstacles): the sets one after the other;
+  // each problem's range is in its BatchInst (disc0, n_discs).  inst_obs_on == false: every problem has the shared set
+  bool inst_obs_on = false;
+  float2* inst_obs_pos = nullptr;
+  float* inst_obs_r = nullptr;
+  int inst_obs_max = 0;  // the largest problem's count
+  std::vector<int> inst_obs_counts_host;
+  std::vector<float> inst_obs_pos_host, inst_obs_r_host;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

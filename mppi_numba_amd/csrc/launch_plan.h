@@ -1017,6 +1017,39 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   return MPPI_OK;
 }
 
+// The barebone mode on a batched handle: one launch over the B problems, one workgroup per tile of one problem
+// (k_rollout_barebone<..., BATCHED>).  Every problem's discs are a range of one pair of arrays -- the shared set, or the
+// concatenated per-problem sets -- named by its BatchInst (note_instance_discs).  The KD forms are chosen by the LARGEST
+// problem's count; a smaller problem's slots past its own count hold the far, radius-0 disc (+0.0 added), so every
+// problem keeps the bits of its own single-problem launch.
+template <bool EXACT>
+static int launch_rollout_barebone_batch(mppi_planner* p, const DevParams& d, bool rot) {
+  TRY(upload_instances(p));
+  const int N = p->n_local, T = p->cfg.num_steps;
+  const bool own = p->inst_obs_on;
+  const int kmax = own ? p->inst_obs_max : p->n_obstacles;
+  const float2* pos = own ? p->inst_obs_pos : p->obs_pos;
+  const float* rad = own ? p->inst_obs_r : p->obs_r;
+  const int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
+  // LDS: [T] double2 control ratios | one float4 per disc slot, the size launched
+  const size_t lds = sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, kd > 0 ? kd : kmax);
+  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, T);
+  const dim3 grid(ceil_div(N, 64)), block(64);
+  if (kd == 2)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
+  else if (kd == 4)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
+  else if (rot)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
+  else
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
+  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
+                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
+                    (own ? " own_discs=1" : "") + " problems=" + std::to_string(p->B);
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_t(mppi_planner* p, DevParams d) {
   p->scan_packets_fresh = false;
@@ -1030,20 +1063,26 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
       p->tile_packets_fresh = false;
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
       const bool rot = EXACT && rotation_ok(p, d);
-      const size_t lds_bb = sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)std::max(1, p->n_obstacles);
-      REQUIRE(lds_bb <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", p->n_obstacles, p->cfg.num_steps);
-      if (rot && p->n_obstacles <= 2)
+      if (p->inst_set) return launch_rollout_barebone_batch<EXACT>(p, d, rot);
+      // (one problem given its own set through mppi_planner_set_instance_disc_obstacles: the launch with that set)
+      const int K = p->inst_obs_on ? p->inst_obs_max : p->n_obstacles;
+      const float2* pos = p->inst_obs_on ? p->inst_obs_pos : p->obs_pos;
+      const float* rad = p->inst_obs_on ? p->inst_obs_r : p->obs_r;
+      d.n_obstacles = K;
+      const size_t lds_bb = sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)std::max(1, K);
+      REQUIRE(lds_bb <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", K, p->cfg.num_steps);
+      if (rot && K <= 2)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 2 * sizeof(float4),
-                     p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
-      else if (rot && p->n_obstacles <= 4)
+                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
+      else if (rot && K <= 4)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 4 * sizeof(float4),
-                     p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
+                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
       else if (rot)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true>), dim3(ceil_div(N, 64)), dim3(64), lds_bb,
-                     p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
+                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
       else
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, false>), dim3(ceil_div(N, 64)), dim3(64), lds_bb,
-                     p->stream, d, p->obs_pos, p->obs_r, p->noise, p->u, p->costs);
+                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
       p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot);
       break;
     }

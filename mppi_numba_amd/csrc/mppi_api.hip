@@ -509,6 +509,8 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->states);
   dev_free(p->obs_pos);
   dev_free(p->obs_r);
+  dev_free(p->inst_obs_pos);
+  dev_free(p->inst_obs_r);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -652,9 +654,10 @@ extern "C" int mppi_planner_create(const mppi_planner_cfg* cfg, mppi_planner** o
   const int n_inst = cfg->num_control_rollouts / cfg->world_size;
   REQUIRE(cfg->num_instances >= 0 && n_problems <= 65535, MPPI_ERR_INVALID, "bad num_instances %d",
           cfg->num_instances);
-  REQUIRE(n_problems == 1 || (n_inst % 64 == 0 && cfg->mode != MPPI_MODE_BAREBONE), MPPI_ERR_INVALID,
-          "num_instances > 1 needs num_control_rollouts/world_size (%d) to be a multiple of 64 and a map mode",
-          n_inst);
+  REQUIRE(n_problems == 1 || n_inst % 64 == 0, MPPI_ERR_INVALID,
+          "num_instances > 1 needs num_control_rollouts/world_size (%d) to be a multiple of 64", n_inst);
+  REQUIRE(n_problems == 1 || cfg->mode != MPPI_MODE_BAREBONE || cfg->world_size == 1, MPPI_ERR_INVALID,
+          "a barebone batch (num_instances %d) is not sharded over ranks: world_size must be 1", n_problems);
   REQUIRE((long)n_problems * n_inst <= (1L << 30), MPPI_ERR_INVALID, "too many rollouts per GPU");
   const int n_local = n_problems * n_inst;
   const int device_cus = pr.compute_units, device_lds = pr.lds_bytes_per_cu;
@@ -712,6 +715,20 @@ extern "C" int mppi_planner_set_params(mppi_planner* p, const mppi_params* param
   return MPPI_OK;
 }
 
+// Barebone mode: every problem's range of the disc arrays its launch gets (BatchInst::disc0, n_discs) -- its own set
+// (mppi_planner_set_instance_disc_obstacles) or the shared one.  Uploaded with the start states.
+static void note_instance_discs(mppi_planner* p) {
+  if (p->cfg.mode != MPPI_MODE_BAREBONE) return;
+  int k0 = 0;
+  for (int b = 0; b < p->B; ++b) {
+    BatchInst& I = p->inst_host[(size_t)b];
+    I.disc0 = p->inst_obs_on ? k0 : 0;
+    I.n_discs = p->inst_obs_on ? p->inst_obs_counts_host[(size_t)b] : p->n_obstacles;
+    k0 += I.n_discs;
+  }
+  p->inst_dirty = true;
+}
+
 extern "C" int mppi_planner_set_disc_obstacles(mppi_planner* p, const float* positions, const float* radii,
                                                int count) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
@@ -738,7 +755,64 @@ extern "C" int mppi_planner_set_disc_obstacles(mppi_planner* p, const float* pos
     p->obs_r_host.assign(radii, radii + (size_t)count);
   }
   p->n_obstacles = count;
+  note_instance_discs(p);
   drop_graphs(p);  // (the count is a by-value argument of the captured launches)
+  return MPPI_OK;
+}
+
+// Barebone batch: one disc set per problem.  Like set_disc_obstacles, unchanged arrays cost a comparison (the Python
+// mirror may hand them over with every solve); a change synchronises, reallocates and drops the captured graphs, whose
+// launches hold the arrays and the largest count.  count == 0: every problem back to the shared set.
+extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int count, const int* disc_counts,
+                                                        const float* positions, const float* radii) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc obstacles belong to the barebone mode (mode %d)",
+          p->cfg.mode);
+  REQUIRE(count == 0 || count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 or num_instances %d", count, p->B);
+  long total = 0;
+  int kmax = 0;
+  if (count > 0) {
+    REQUIRE(disc_counts, MPPI_ERR_INVALID, "NULL disc_counts");
+    for (int b = 0; b < count; ++b) {
+      REQUIRE(disc_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative disc count %d", b, disc_counts[b]);
+      total += disc_counts[b];
+      kmax = std::max(kmax, disc_counts[b]);
+    }
+    REQUIRE(total <= (1L << 30), MPPI_ERR_INVALID, "too many discs (%ld)", total);
+    REQUIRE(total == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
+    // what a launch holds in LDS: the control ratios and the largest problem's discs (launch_rollout_barebone_batch)
+    REQUIRE(sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)kmax <= 64 * 1024, MPPI_ERR_INVALID,
+            "a problem with %d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, p->cfg.num_steps);
+  }
+  if (count == 0 ? !p->inst_obs_on
+                 : (p->inst_obs_on && memcmp(disc_counts, p->inst_obs_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
+                    (total == 0 || (memcmp(positions, p->inst_obs_pos_host.data(), sizeof(float) * 2 * (size_t)total) == 0 &&
+                                    memcmp(radii, p->inst_obs_r_host.data(), sizeof(float) * (size_t)total) == 0))))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  dev_free(p->inst_obs_pos);
+  dev_free(p->inst_obs_r);
+  p->inst_obs_on = false;
+  p->inst_obs_max = 0;
+  p->inst_obs_counts_host.clear();
+  p->inst_obs_pos_host.clear();
+  p->inst_obs_r_host.clear();
+  drop_graphs(p);  // (the arrays and the largest count are arguments of the captured launches)
+  if (count > 0) {
+    TRY(dev_alloc(&p->inst_obs_pos, (size_t)total));
+    TRY(dev_alloc(&p->inst_obs_r, (size_t)total));
+    if (total > 0) {
+      HIP_TRY(hipMemcpy(p->inst_obs_pos, positions, sizeof(float2) * (size_t)total, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(p->inst_obs_r, radii, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
+    }
+    p->inst_obs_on = true;
+    p->inst_obs_max = kmax;
+    p->inst_obs_counts_host.assign(disc_counts, disc_counts + count);
+    p->inst_obs_pos_host.assign(positions, positions + 2 * (size_t)total);
+    p->inst_obs_r_host.assign(radii, radii + (size_t)total);
+  }
+  note_instance_discs(p);
   return MPPI_OK;
 }
 
@@ -799,7 +873,6 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
   }
   REQUIRE(x0 && xgoal, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d != num_instances %d of this handle", count, p->B);
-  REQUIRE(p->cfg.mode != MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "no instances in the barebone mode");
   for (int b = 0; b < count; ++b) {
     BatchInst& I = p->inst_host[(size_t)b];
     I.x0 = x0[3 * b]; I.y0 = x0[3 * b + 1]; I.th0 = x0[3 * b + 2];
@@ -808,6 +881,7 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
                 std::isfinite(I.yg),
             MPPI_ERR_INVALID, "instance %d: non-finite start or goal", b);
   }
+  note_instance_discs(p);
   p->inst_set = true;
   p->inst_dirty = true;
   return MPPI_OK;
@@ -1113,11 +1187,15 @@ extern "C" int mppi_world_sample_true_dist(mppi_world* w, const int32_t* terrain
 extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, mppi_world* w, int max_steps,
                                         double dt, double goal_tolerance, const double* x_init, double* xhist, float* uhist,
                                         int* steps_taken) {
-  REQUIRE(p && w && xhist && uhist && steps_taken, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p && xhist && uhist && steps_taken, MPPI_ERR_INVALID, "NULL argument");
+  const bool nominal = p->cfg.mode == MPPI_MODE_BAREBONE;  // the barebone notebook's world: traction 1 everywhere
+  REQUIRE(nominal ? w == nullptr : w != nullptr, MPPI_ERR_INVALID,
+          nominal ? "the barebone mode's world is the nominal unicycle: w must be NULL" : "NULL world");
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   REQUIRE(p->inst_set, MPPI_ERR_STATE, "closed_loop needs per-problem start states (mppi_planner_set_instances)");
   REQUIRE(p->cfg.world_size == 1, MPPI_ERR_STATE, "closed_loop drives an unsharded handle");
-  REQUIRE(w->device == p->cfg.device, MPPI_ERR_INVALID, "world on device %d, planner on %d", w->device, p->cfg.device);
+  REQUIRE(nominal || w->device == p->cfg.device, MPPI_ERR_INVALID, "world on device %d, planner on %d", w->device,
+          p->cfg.device);
   REQUIRE(max_steps >= 1 && max_steps <= (1 << 20), MPPI_ERR_INVALID, "max_steps %d", max_steps);
   HIP_TRY(hipSetDevice(p->cfg.device));
   TraceRange tr("mppi:closed_loop");
@@ -1169,7 +1247,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     DevParams plan;
     TRY(prepare_launch(p, lin, ang, &plan));
     size_t lds_unused = 0;
-    const bool windowed = plan_lds_window(p, plan, &lds_unused);
+    const bool windowed = !nominal && plan_lds_window(p, plan, &lds_unused);  // (barebone: no map, no window)
     TRY(upload_instances(p));
     L.state = p->loop_state; L.xhist = p->loop_xhist; L.uhist = p->loop_uhist; L.done = p->loop_done;
     L.done_count = p->loop_done_count_dev;
@@ -1190,7 +1268,9 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     }
     return MPPI_OK;
   };
-  const WorldGrid G = world_grid(w);
+  WorldGrid G;
+  memset(&G, 0, sizeof(G));  // (nominal: no grid, k_world_step takes traction 1)
+  if (!nominal) G = world_grid(w);
   const int check_every = 16;
   HIP_TRY(hipEventRecord(p->ev_begin, p->stream));
   int launched = 0;

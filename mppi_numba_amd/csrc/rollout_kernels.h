@@ -112,7 +112,14 @@ struct DevParams {
 struct BatchInst {
   float x0, y0, th0;
   float xg, yg;
-  int win_r0, win_c0;  // the LDS window is planned around each start state
+  union {
+    struct {
+      int win_r0, win_c0;  // map modes: the LDS window is planned around each start state
+    };
+    struct {
+      int disc0, n_discs;  // barebone mode: the problem's discs are obs_pos / obs_r [disc0, disc0 + n_discs)
+    };
+  };
   int pad;
 };
 
@@ -1465,7 +1472,11 @@ __global__ void k_cvar_reduce(const float* __restrict__ slabs, int count, int n_
 // KD (round 6): the disc count as a compile-time bound -- >= 0: exactly the discs 0 .. KD-1 are tested, slots past
 // n_obstacles hold a disc nobody can touch (the same additions of +0.0) -- so that a batch of eight steps is ONE basic
 // block and the scheduler may run step t's cost beside step t+1's state; -1: the run-time loop.
-template <bool EXACT, bool ROT = false, int KD = -1>
+// BATCHED: a launch over the B problems of a batched handle (P.inst set), one workgroup = one tile of one problem,
+// b = blockIdx.x / inst_tiles: its start, goal and controls (select_instance) and its discs, obs_pos / obs_r
+// [disc0, disc0 + n_discs) of its BatchInst.  KD is then a bound on the largest problem's count: a smaller problem's
+// slots past its own count hold the far disc above, so every problem keeps the bits of its own single-problem launch.
+template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false>
 __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const float2* __restrict__ obs_pos,
                                                          const float* __restrict__ obs_r,
                                                          const float2* __restrict__ noise,
@@ -1473,6 +1484,14 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
                                                          float* __restrict__ costs) {
   extern __shared__ double2 uos[];
   ktime_begin(P);
+  if constexpr (BATCHED) {
+    const int b = (int)blockIdx.x / P.inst_tiles;  // (uniform over the workgroup)
+    u = select_instance(P, u, b);
+    const BatchInst I = P.inst[b];
+    obs_pos += I.disc0;
+    obs_r += I.disc0;
+    P.n_obstacles = I.n_discs;
+  }
   // LDS: [T] double2 control ratios | [K] {float x, y, r, -} discs (a step looked each of them up in memory before:
   // two dependent scalar loads per disc and step on a wave that has nothing else to run)
   float4* discs = reinterpret_cast<float4*>(uos + P.n_steps);

@@ -18,7 +18,9 @@
 namespace mppi {
 
 struct WorldGrid {
-  const double* lin;  // [rows][cols] float64, as TractionGrid.lin_traction (terrain.py:757-762)
+  // [rows][cols] float64, as TractionGrid.lin_traction (terrain.py:757-762); nullptr: the nominal world of the barebone
+  // notebook (traction 1 everywhere: dt * 1.0 * cos(th) * u0 has the bits of its dt * cos(th) * u0)
+  const double* lin;
   const double* ang;
   int rows, cols;
   double res, xlo, ylo;
@@ -92,7 +94,8 @@ struct WorldLoop {
   double xlo, ylo, res;
 };
 
-// One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4):
+// One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4; barebone_mppi_numba.ipynb
+// cell 7 is the same with traction 1, G.lin == nullptr):
 //   u_curr = useq[0]; (lt, at) = traction_grid.get(x, y)
 //   x += dt*lt*cos(th)*u_curr[0]; y += dt*lt*sin(th)*u_curr[0]; th += dt*at*u_curr[1]   (float64)
 //   shift_and_update(x_new, useq, 1)   (mppi.py:534-542: x0 <- x_new, u[:-1] = u[1:])
@@ -112,8 +115,8 @@ __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ i
     const double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
     const float2 u0 = shifted[0];
     L.uhist[(size_t)b * L.max_steps + step] = u0;
-    double lt, at;
-    world_lookup(G, x, y, lt, at);
+    double lt = 1.0, at = 1.0;
+    if (G.lin) world_lookup(G, x, y, lt, at);
     const double x1 = x + L.dt * lt * cos(th) * (double)u0.x;
     const double y1 = y + L.dt * lt * sin(th) * (double)u0.x;
     const double th1 = th + L.dt * at * (double)u0.y;
