@@ -230,6 +230,28 @@ int mppi_planner_set_instances(mppi_planner* p, int count, const float* x0, cons
 int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int count, const int* disc_counts,
                                              const float* positions, const float* radii);
 
+/* MPPI_MODE_BAREBONE only: discs that move.  A track is `rows` >= 1 predicted centres of a disc,
+ * row j its centre at time j*dt from "now"; tracks is (sum of the counts, rows, 2) float32, radii
+ * (sum) float32.  count = 1: disc_counts[0] discs shared by every problem; count = B: one set per
+ * problem, laid out as for mppi_planner_set_instance_disc_obstacles.  Each problem has a track
+ * offset s >= 0 ("now" is row s; below).  In a rollout the state after step t (t = 0 .. T-1) is
+ * tested against row min(s + t + 1, rows - 1) of every disc of its problem: the disc where it will
+ * be when the robot gets there, at its last predicted place once the track has ended.  The test,
+ * the cost and their roundings are those of the static discs, so tracks whose rows are all equal
+ * give the bits of the static set.  While tracks are set they take the place of both static sets;
+ * count = 0 (or disc_counts NULL) clears them and the static sets apply again.  Unchanged arrays
+ * cost a comparison; a change drops the captured graphs and sets every offset to 0.
+ * MPPI_ERR_INVALID for a map mode, rows < 1, a negative count, count not 0 / 1 / B, or a largest
+ * set that needs more than 64 KiB of LDS (16*T + 16*T*K bytes). */
+int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const int* disc_counts, int rows,
+                                 const float* tracks, const float* radii);
+/* offsets [B] int >= 0, count must equal B.  An offset travels with its problem's start state (no
+ * synchronisation; graph replay needs no new capture for it on a handle with instances set).
+ * mppi_planner_closed_loop advances the offset of every problem that is still running by one per
+ * control step, on the device; afterwards get returns offset_before + steps_taken[b]. */
+int mppi_planner_set_track_offsets(mppi_planner* p, int count, const int* offsets);
+int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

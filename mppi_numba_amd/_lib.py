@@ -104,6 +104,9 @@ SIGNATURES = {
     "mppi_planner_set_params": [_vp, C.POINTER(Params)],
     "mppi_planner_set_disc_obstacles": [_vp, _f32p, _f32p, C.c_int],
     "mppi_planner_set_instance_disc_obstacles": [_vp, C.c_int, C.POINTER(C.c_int), _f32p, _f32p],
+    "mppi_planner_set_disc_tracks": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p],
+    "mppi_planner_set_track_offsets": [_vp, C.c_int, C.POINTER(C.c_int)],
+    "mppi_planner_get_track_offsets": [_vp, C.c_int, C.POINTER(C.c_int)],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

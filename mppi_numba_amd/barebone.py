@@ -6,6 +6,11 @@ keys ('obstacle_positions', 'obstacle_radius', 'obs_penalty', 'dist_weight').
 
 Stage cost dist_weight*d^2, terminal cost (1-reached)*d^2, obstacle penalty
 when the POST-step position lies inside a disc (notebook cell 3).
+
+Not in the notebook: discs that move.  params['obstacle_tracks'] (K, L, 2) in
+place of 'obstacle_positions' gives every disc L predicted centres, row j its
+centre at time j*dt from "now"; "now" is row `track_offset`, and the state
+after step t of a rollout is tested against row min(track_offset + t + 1, L - 1).
 """
 import copy
 import ctypes as C
@@ -58,6 +63,22 @@ def _f32(values):
     return np.asarray(values, dtype=np.float64).astype(np.float32)
 
 
+def constant_velocity_tracks(positions, velocities, dt, rows):
+    """(K, rows, 2) float32 tracks of discs that keep their velocity: row j is positions + velocities * (j*dt),
+    evaluated in float64 and rounded once to float32 (row 0 is float32(positions))."""
+    rows = int(rows)
+    assert rows >= 1, "a track has at least one row"
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 1, 2)
+    vel = np.asarray(velocities, dtype=np.float64).reshape(-1, 1, 2)
+    assert len(pos) == len(vel), "positions and velocities differ in length"
+    times = (np.arange(rows, dtype=np.float64) * float(dt)).reshape(1, rows, 1)
+    return np.ascontiguousarray((pos + vel * times).astype(np.float32))
+
+
+def _is_track_set(obstacle_set):
+    return np.asarray(obstacle_set[0]).ndim == 3
+
+
 class MPPI_Numba(object):
 
     """Information-theoretic MPPI (Williams et al., Alg. 2) without maps.
@@ -84,6 +105,8 @@ class MPPI_Numba(object):
         self.state_rollout_batch_d = None
         self.device_var_initialized = False
         self._discs_key = None  # what the device's disc arrays hold (None: nothing handed over yet)
+        self._tracks_from_params = False  # ... and whether they are the tracks of params['obstacle_tracks']
+        self._own_tracks = False          # MPPI_Batch: per-problem tracks are set (they win over params')
         self.reset()
 
     def __del__(self):
@@ -100,6 +123,54 @@ class MPPI_Numba(object):
         self.params_set = False
         self.u_prev_d = None
         self.init_device_vars_before_solving()
+        self.set_track_offset(0)
+
+    # ------------------------------------------------------------------ discs that move
+    @property
+    def track_offset(self):
+        """The row of the disc tracks that is "now": an int, a (B,) int32 array for a batch."""
+        return int(self._track_offset[0]) if self.num_instances == 1 else self._track_offset.copy()
+
+    def set_track_offset(self, offset):
+        """An int (every problem) or one per problem; >= 0.  Past the last row: the discs stay at their last place."""
+        off = np.ascontiguousarray(np.broadcast_to(np.asarray(offset, dtype=np.int64), (self.num_instances,)), dtype=np.int32)
+        assert (off >= 0).all(), "track offsets are >= 0"
+        _lib.call("mppi_planner_set_track_offsets", self._handle, self.num_instances, _lib.ptr(off, C.c_int))
+        self._track_offset = off
+
+    def _fetch_track_offset(self):
+        off = np.zeros(self.num_instances, dtype=np.int32)
+        _lib.call("mppi_planner_get_track_offsets", self._handle, self.num_instances, _lib.ptr(off, C.c_int))
+        self._track_offset = off
+
+    def _tracks_on(self):
+        return self._tracks_from_params or self._own_tracks
+
+    def _hand_over_tracks(self, sets):
+        """sets: one (tracks (K, L, 2), radii (K,)) pair for every problem, or one per problem; None clears."""
+        if sets is None:
+            _lib.call("mppi_planner_set_disc_tracks", self._handle, 0, None, 0, None, None)
+            return
+        tracks = [np.asarray(tr) for tr, _ in sets]
+        rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in sets]
+        rows = None
+        for b, tr in enumerate(tracks):
+            if tr.ndim != 3 or tr.shape[2] != 2:
+                raise ValueError("set {}: tracks have shape (K, L, 2), got {}".format(b, tr.shape))
+            if tr.shape[1] < 1:
+                raise ValueError("set {}: a track has at least one row (L = 0)".format(b))
+            if len(tr) != len(rad[b]):
+                raise ValueError("set {}: {} tracks and {} radii".format(b, len(tr), len(rad[b])))
+            if rows not in (None, tr.shape[1]):
+                raise ValueError("set {}: {} rows, other sets of this call have {}".format(b, tr.shape[1], rows))
+            rows = tr.shape[1]
+        counts = np.ascontiguousarray([len(r) for r in rad], dtype=np.int32)
+        flat = [_f32(tr).reshape(-1, 2) for tr in tracks if len(tr)]
+        pos_all = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 2), np.float32))
+        rad_all = np.ascontiguousarray(np.concatenate(rad) if counts.sum() else np.zeros(0, np.float32))
+        _lib.call("mppi_planner_set_disc_tracks", self._handle, len(sets), _lib.ptr(counts, C.c_int), int(rows),
+                  _lib.ptr(pos_all, C.c_float), _lib.ptr(rad_all, C.c_float))
+        self._track_offset = np.zeros(self.num_instances, dtype=np.int32)  # (new tracks: row 0 is "now")
 
     def init_device_vars_before_solving(self):
         if self.device_var_initialized:
@@ -175,6 +246,21 @@ class MPPI_Numba(object):
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
         # the discs: handed over when they have changed (the notebook uploads them with every solve)
+        if "obstacle_tracks" in p:
+            if "obstacle_positions" in p:
+                raise ValueError("params hold both 'obstacle_positions' and 'obstacle_tracks': discs are static or have "
+                                 "tracks, give one of the two")
+            tr, orad = np.asarray(p['obstacle_tracks']), np.asarray(p['obstacle_radius'])
+            key = ("tracks", tr.dtype.str, tr.shape, tr.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
+            if key != self._discs_key and not self._own_tracks:
+                self._hand_over_tracks([(tr, orad)])
+                self._discs_key, self._tracks_from_params = key, True
+            return
+        if self._tracks_from_params:  # (the params no longer hold tracks: the static discs below apply again)
+            self._hand_over_tracks(None)
+            self._tracks_from_params = False
+            self._discs_key = None
+            self._track_offset = np.zeros(self.num_instances, dtype=np.int32)
         if "obstacle_positions" in p and "obstacle_radius" in p:
             op, orad = np.asarray(p['obstacle_positions']), np.asarray(p['obstacle_radius'])
             key = (op.dtype.str, op.shape, op.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
@@ -205,6 +291,11 @@ class MPPI_Numba(object):
     def shift_and_update(self, new_x0, u_cur, num_shifts=1):
         self.params["x0"] = new_x0.copy()
         self.shift_optimal_control_sequence(u_cur, num_shifts)
+        self._advance_tracks(num_shifts)
+
+    def _advance_tracks(self, num_shifts):
+        if self._tracks_on():  # num_shifts control steps later "now" is that many rows further
+            self.set_track_offset(self._track_offset.astype(np.int64) + int(num_shifts))
 
     def shift_optimal_control_sequence(self, u_cur, num_shifts=1):
         shifted = u_cur.copy()
@@ -257,6 +348,7 @@ class MPPI_Numba(object):
             if single:
                 _lib.call("mppi_planner_set_instances", self._handle, 0, None, None)
         self.u_prev_d = self._u_prev_view
+        self._fetch_track_offset()  # (advanced on the device, one row per control step of a problem still running)
         last = np.stack([xhist[b, steps[b]] for b in range(B)])
         if single:
             self.params["x0"] = last[0].copy()
@@ -365,12 +457,33 @@ class MPPI_Batch(MPPI_Numba):
 
     def set_obstacle_sets(self, obstacle_sets):
         """One disc set per problem: a list of B (positions (K_b, 2), radii (K_b,)) pairs, K_b >= 0 -- or None: every
-        problem has the shared set of params['obstacle_positions'] / ['obstacle_radius']."""
+        problem has the shared set of params['obstacle_positions'] / ['obstacle_radius'].  A set whose first element
+        is 3-D, (K_b, L, 2), is a set of tracks (discs that move; L common to the sets of a call); one call is all
+        static or all tracks."""
+        if self._own_tracks and (obstacle_sets is None or not _is_track_set(obstacle_sets[0])):
+            self._hand_over_tracks(None)  # (per-problem tracks go; shared ones of the params are handed over again)
+            self._own_tracks = False
+            self._discs_key = None
+            self._track_offset = np.zeros(self.num_instances, dtype=np.int32)
         if obstacle_sets is None:
             _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
             self.obstacle_sets = None
             return
         assert len(obstacle_sets) == self.num_instances, "one disc set per problem"
+        kinds = {_is_track_set(s) for s in obstacle_sets}
+        if len(kinds) > 1:
+            raise ValueError("obstacle_sets mix static sets and track sets: one call is all static or all tracks")
+        if kinds == {True}:
+            same = self._own_tracks and self.obstacle_sets is not None and all(
+                np.array_equal(_f32(np.asarray(a[0])), b[0]) and np.array_equal(_f32(np.asarray(a[1])).reshape(-1), b[1])
+                for a, b in zip(obstacle_sets, self.obstacle_sets))
+            if same:
+                return  # (unchanged: "now" stays where it is)
+            self._hand_over_tracks(list(obstacle_sets))
+            _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
+            self._own_tracks, self._tracks_from_params, self._discs_key = True, False, None
+            self.obstacle_sets = [(_f32(np.asarray(tr)).copy(), _f32(np.asarray(r)).reshape(-1).copy()) for tr, r in obstacle_sets]
+            return
         pos = [_f32(np.asarray(op)).reshape(-1, 2) for op, _ in obstacle_sets]
         rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in obstacle_sets]
         for b in range(self.num_instances):
@@ -394,11 +507,13 @@ class MPPI_Batch(MPPI_Numba):
         self.set_instances(new_x0s)
         self.params["x0"] = np.asarray(new_x0s[0]).copy()
         self.shift_optimal_control_sequence(u_cur, num_shifts)
+        self._advance_tracks(num_shifts)
 
     def shift_and_update_on_device(self, new_x0s, num_shifts=1):
         self.set_instances(new_x0s)
         self.params["x0"] = np.asarray(new_x0s[0]).copy()
         _lib.call("mppi_planner_shift_u", self._handle, int(num_shifts))
+        self._advance_tracks(num_shifts)
 
     def shift_optimal_control_sequence(self, u_cur, num_shifts=1):
         shifted = np.array(u_cur, dtype=np.float32).reshape(self.num_instances, self.num_steps, 2)

@@ -230,6 +230,17 @@ struct mppi_planner {
   int inst_obs_max = 0;  // the largest problem's count
   std::vector<int> inst_obs_counts_host;
   std::vector<float> inst_obs_pos_host, inst_obs_r_host;
+  // discs that move (mppi_planner_set_disc_tracks): trk_rows predicted centres per disc, [disc][row]; one set for every
+  // problem (trk_counts_host has one entry) or one per problem, the sets one after the other as above.  While trk_on,
+  // the launches take these and neither static set; the row that is "now" is BatchInst::track_off of inst_host
+  // (problem 0's for the classic single launch: make_dev_params)
+  bool trk_on = false;
+  float2* trk_pos = nullptr;
+  float* trk_r = nullptr;
+  int trk_rows = 0;
+  int trk_max = 0;  // the largest problem's count
+  std::vector<int> trk_counts_host;
+  std::vector<float> trk_pos_host, trk_r_host;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;
@@ -319,6 +330,11 @@ static int count_sink_rings(int rows, int cols, F&& sink) {
     if (!all) break;
   }
   return rings;
+}
+
+// LDS of a barebone launch with disc tracks: [T] double2 control ratios | [T][slots] float4, a row of disc slots per step
+static size_t barebone_track_lds(int T, int slots) {
+  return sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)T * (size_t)std::max(1, slots);
 }
 
 static void drop_graphs(mppi_planner* p) {

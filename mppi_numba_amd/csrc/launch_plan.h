@@ -65,6 +65,9 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.n_steps = p->cfg.num_steps;
   d.n_grids = p->cfg.num_grid_samples;
   d.n_obstacles = p->n_obstacles;
+  // (discs that move: a batch reads each problem's offset from its BatchInst, as it reads the start state)
+  d.track_rows = p->trk_on ? p->trk_rows : 0;
+  d.track_off = p->trk_on && !p->inst_set ? p->inst_host[0].track_off : 0;
   d.inst = p->inst_set ? p->inst_dev : nullptr;
   d.inst_tiles = p->inst_tiles;
   d.n_inst = p->n_inst;
@@ -1022,9 +1025,39 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
 // concatenated per-problem sets -- named by its BatchInst (note_instance_discs).  The KD forms are chosen by the LARGEST
 // problem's count; a smaller problem's slots past its own count hold the far, radius-0 disc (+0.0 added), so every
 // problem keeps the bits of its own single-problem launch.
+// Discs that move (mppi_planner_set_disc_tracks): the track forms of k_rollout_barebone, one launch over the problems
+// of an instance handle or the classic single launch.  LDS: [T] double2 control ratios | [T][slots] float4, one row of
+// disc slots per step (barebone_track_lds); the KD forms where they fit, else the run-time loop over the largest
+// problem's count.
+template <bool EXACT, bool BATCHED>
+static int launch_rollout_barebone_tracks(mppi_planner* p, DevParams d, bool rot) {
+  const int N = p->n_local, T = p->cfg.num_steps, kmax = p->trk_max;
+  int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
+  if (kd > 0 && barebone_track_lds(T, kd) > 64 * 1024) kd = -1;  // (a long horizon: the padded row does not fit, the problem's own may)
+  const size_t lds = barebone_track_lds(T, kd > 0 ? kd : kmax);  // the size launched
+  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, T, lds);
+  if (!BATCHED) d.n_obstacles = kmax;
+  const dim3 grid(ceil_div(N, 64)), block(64);
+  if (kd == 2)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
+  else if (kd == 4)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
+  else if (rot)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
+  else
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
+  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
+                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
+                    " tracks=" + std::to_string(p->trk_rows) +
+                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string());
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
 template <bool EXACT>
 static int launch_rollout_barebone_batch(mppi_planner* p, const DevParams& d, bool rot) {
   TRY(upload_instances(p));
+  if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, true>(p, d, rot);
   const int N = p->n_local, T = p->cfg.num_steps;
   const bool own = p->inst_obs_on;
   const int kmax = own ? p->inst_obs_max : p->n_obstacles;
@@ -1064,6 +1097,7 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
       const bool rot = EXACT && rotation_ok(p, d);
       if (p->inst_set) return launch_rollout_barebone_batch<EXACT>(p, d, rot);
+      if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, false>(p, d, rot);
       // (one problem given its own set through mppi_planner_set_instance_disc_obstacles: the launch with that set)
       const int K = p->inst_obs_on ? p->inst_obs_max : p->n_obstacles;
       const float2* pos = p->inst_obs_on ? p->inst_obs_pos : p->obs_pos;

@@ -511,6 +511,8 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->obs_r);
   dev_free(p->inst_obs_pos);
   dev_free(p->inst_obs_r);
+  dev_free(p->trk_pos);
+  dev_free(p->trk_r);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -722,8 +724,14 @@ static void note_instance_discs(mppi_planner* p) {
   int k0 = 0;
   for (int b = 0; b < p->B; ++b) {
     BatchInst& I = p->inst_host[(size_t)b];
-    I.disc0 = p->inst_obs_on ? k0 : 0;
-    I.n_discs = p->inst_obs_on ? p->inst_obs_counts_host[(size_t)b] : p->n_obstacles;
+    if (p->trk_on) {  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
+      const bool own = p->trk_counts_host.size() > 1;
+      I.disc0 = own ? k0 : 0;
+      I.n_discs = p->trk_counts_host[own ? (size_t)b : 0];
+    } else {
+      I.disc0 = p->inst_obs_on ? k0 : 0;
+      I.n_discs = p->inst_obs_on ? p->inst_obs_counts_host[(size_t)b] : p->n_obstacles;
+    }
     k0 += I.n_discs;
   }
   p->inst_dirty = true;
@@ -813,6 +821,91 @@ extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int cou
     p->inst_obs_r_host.assign(radii, radii + (size_t)total);
   }
   note_instance_discs(p);
+  return MPPI_OK;
+}
+
+// Barebone mode: discs that move.  `rows` predicted centres per disc (row j: where it is j * dt from "now"), one set shared
+// by every problem (count == 1) or one per problem (count == B), laid out like the static per-problem sets.  Unchanged
+// arrays cost a comparison; a change synchronises, reallocates, drops the captured graphs and makes row 0 "now" again.
+extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const int* disc_counts, int rows,
+                                            const float* tracks, const float* radii) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
+          p->cfg.mode);
+  if (disc_counts == nullptr) count = 0;
+  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
+          "count %d: must be 0, 1 (one set for every problem) or num_instances %d", count, p->B);
+  long total = 0;
+  int kmax = 0;
+  if (count > 0) {
+    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
+    for (int b = 0; b < count; ++b) {
+      REQUIRE(disc_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative disc count %d", b, disc_counts[b]);
+      total += disc_counts[b];
+      kmax = std::max(kmax, disc_counts[b]);
+    }
+    REQUIRE(total * (long)rows <= (1L << 30), MPPI_ERR_INVALID, "too many track rows (%ld discs x %d)", total, rows);
+    REQUIRE(total == 0 || (tracks && radii), MPPI_ERR_INVALID, "NULL tracks or radii");
+    // what a launch holds in LDS at the least: the control ratios and a row of the largest problem's discs per step
+    const size_t lds = barebone_track_lds(p->cfg.num_steps, kmax);
+    REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID,
+            "a problem with %d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, p->cfg.num_steps, lds);
+  }
+  const size_t n_pos = (size_t)total * (size_t)rows;
+  if (count == 0 ? !p->trk_on
+                 : (p->trk_on && rows == p->trk_rows && (size_t)count == p->trk_counts_host.size() &&
+                    memcmp(disc_counts, p->trk_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
+                    (total == 0 || (memcmp(tracks, p->trk_pos_host.data(), sizeof(float) * 2 * n_pos) == 0 &&
+                                    memcmp(radii, p->trk_r_host.data(), sizeof(float) * (size_t)total) == 0))))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  dev_free(p->trk_pos);
+  dev_free(p->trk_r);
+  p->trk_on = false;
+  p->trk_rows = p->trk_max = 0;
+  p->trk_counts_host.clear();
+  p->trk_pos_host.clear();
+  p->trk_r_host.clear();
+  drop_graphs(p);  // (the arrays, the row count and the kernel form are arguments of the captured launches)
+  if (count > 0) {
+    TRY(dev_alloc(&p->trk_pos, std::max<size_t>(1, n_pos)));
+    TRY(dev_alloc(&p->trk_r, std::max<size_t>(1, (size_t)total)));
+    if (total > 0) {
+      HIP_TRY(hipMemcpy(p->trk_pos, tracks, sizeof(float2) * n_pos, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(p->trk_r, radii, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
+    }
+    p->trk_on = true;
+    p->trk_rows = rows;
+    p->trk_max = kmax;
+    p->trk_counts_host.assign(disc_counts, disc_counts + count);
+    p->trk_pos_host.assign(tracks, tracks + 2 * n_pos);
+    p->trk_r_host.assign(radii, radii + (size_t)total);
+  }
+  for (BatchInst& I : p->inst_host) I.track_off = 0;
+  note_instance_discs(p);
+  return MPPI_OK;
+}
+
+// The row of every problem's tracks that is "now".  It travels with the start state: a kernel argument of the classic
+// single launch, the problem's BatchInst otherwise -- no synchronisation, and nothing a captured graph holds.
+extern "C" int mppi_planner_set_track_offsets(mppi_planner* p, int count, const int* offsets) {
+  REQUIRE(p && offsets, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
+          p->cfg.mode);
+  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d != num_instances %d of this handle", count, p->B);
+  for (int b = 0; b < count; ++b) REQUIRE(offsets[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative track offset %d", b, offsets[b]);
+  for (int b = 0; b < count; ++b) p->inst_host[(size_t)b].track_off = offsets[b];
+  p->inst_dirty = true;
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets) {
+  REQUIRE(p && offsets, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
+          p->cfg.mode);
+  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d != num_instances %d of this handle", count, p->B);
+  for (int b = 0; b < count; ++b) offsets[b] = p->inst_host[(size_t)b].track_off;
   return MPPI_OK;
 }
 
@@ -1256,6 +1349,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.dt = dt > 0.0 ? dt : (double)p->params.dt;
     L.goal_tolerance = goal_tolerance;
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
+    L.advance_tracks = p->trk_on ? 1 : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)

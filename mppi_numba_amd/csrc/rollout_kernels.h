@@ -106,6 +106,10 @@ struct DevParams {
   // MPPI_ERR_BUSY and the handle orders its streams with events from then on.  (What it takes: a tool that runs one kernel
   // at a time -- rocprofv3 --pmc does -- so that the generator cannot run beside the launch that waits for it.)
   unsigned int* flag_fault;
+  // barebone mode, discs that move (k_rollout_barebone<..., TRACKS>): every disc has `track_rows` predicted centres, row j
+  // its centre at time j * dt from "now", and "now" is row `track_off` (single-problem launches; a batch reads its
+  // problems' offsets from their BatchInst).  0 rows: static discs
+  int track_rows, track_off;
 };
 
 // What differs between the problems of a batched handle (mppi_planner_set_instances).
@@ -120,7 +124,7 @@ struct BatchInst {
       int disc0, n_discs;  // barebone mode: the problem's discs are obs_pos / obs_r [disc0, disc0 + n_discs)
     };
   };
-  int pad;
+  int track_off;  // barebone mode: the row of the problem's disc tracks that is "now" (DevParams::track_rows)
 };
 
 // every wave of a workgroup, before its first load of the noise (see DevParams::noise_flag).  Every wave looks once; when
@@ -1476,7 +1480,12 @@ __global__ void k_cvar_reduce(const float* __restrict__ slabs, int count, int n_
 // b = blockIdx.x / inst_tiles: its start, goal and controls (select_instance) and its discs, obs_pos / obs_r
 // [disc0, disc0 + n_discs) of its BatchInst.  KD is then a bound on the largest problem's count: a smaller problem's
 // slots past its own count hold the far disc above, so every problem keeps the bits of its own single-problem launch.
-template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false>
+// TRACKS: discs that move.  obs_pos is then [disc][P.track_rows] predicted centres, row j a disc's centre at time j * dt from
+// "now" = row s (P.track_off; BATCHED: the problem's BatchInst::track_off), and the post-step state of step t is tested
+// against row min(s + t + 1, rows - 1): the disc where it will be when the robot gets there, at its last predicted place
+// once the track has ended.  The rows are picked when the launch stages its LDS -- one row of disc slots per step,
+// [T][slots] -- so a step does what it does for static discs on operands that change with t: same operations, same order.
+template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false, bool TRACKS = false>
 __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const float2* __restrict__ obs_pos,
                                                          const float* __restrict__ obs_r,
                                                          const float2* __restrict__ noise,
@@ -1488,19 +1497,35 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
     const int b = (int)blockIdx.x / P.inst_tiles;  // (uniform over the workgroup)
     u = select_instance(P, u, b);
     const BatchInst I = P.inst[b];
-    obs_pos += I.disc0;
+    obs_pos += TRACKS ? (size_t)I.disc0 * (size_t)P.track_rows : (size_t)I.disc0;
     obs_r += I.disc0;
     P.n_obstacles = I.n_discs;
+    if constexpr (TRACKS) P.track_off = I.track_off;
   }
   // LDS: [T] double2 control ratios | [K] {float x, y, r, -} discs (a step looked each of them up in memory before:
   // two dependent scalar loads per disc and step on a wave that has nothing else to run)
+  // TRACKS: [T][slots] of them, row t what step t tests
   float4* discs = reinterpret_cast<float4*>(uos + P.n_steps);
-  for (int k = threadIdx.x; k < P.n_obstacles; k += 64) {
-    const float2 op = obs_pos[k];
-    discs[k] = make_float4(op.x, op.y, obs_r[k], 0.0f);
+  const int slots = KD > 0 ? KD : P.n_obstacles;  // (TRACKS: the pitch of a row)
+  if constexpr (TRACKS) {
+    const int last = P.track_rows - 1, now = min(max(P.track_off, 0), last);  // (an offset past the end: the last row)
+    for (int i = threadIdx.x; i < P.n_steps * slots; i += 64) {
+      const int t = i / slots, k = i - t * slots;
+      float4 d = make_float4(1e18f, 1e18f, 0.0f, 0.0f);  // (slots past the last disc, in every row: see below)
+      if (k < P.n_obstacles) {
+        const float2 op = obs_pos[(size_t)k * (size_t)P.track_rows + (size_t)min(now + t + 1, last)];
+        d = make_float4(op.x, op.y, obs_r[k], 0.0f);
+      }
+      discs[i] = d;
+    }
+  } else {
+    for (int k = threadIdx.x; k < P.n_obstacles; k += 64) {
+      const float2 op = obs_pos[k];
+      discs[k] = make_float4(op.x, op.y, obs_r[k], 0.0f);
+    }
+    if (KD > 0)  // (slots past the last disc: far away, radius 0 -- `diff > 0`, no hit, +0.0 added)
+      for (int k = P.n_obstacles + (int)threadIdx.x; k < KD; k += 64) discs[k] = make_float4(1e18f, 1e18f, 0.0f, 0.0f);
   }
-  if (KD > 0)  // (slots past the last disc: far away, radius 0 -- `diff > 0`, no hit, +0.0 added)
-    for (int k = P.n_obstacles + (int)threadIdx.x; k < KD; k += 64) discs[k] = make_float4(1e18f, 1e18f, 0.0f, 0.0f);
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
   const int n = blockIdx.x * 64 + threadIdx.x;
   const bool live = n < P.n_local;
@@ -1513,7 +1538,8 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
   [[maybe_unused]] double rs = 0.0, rc = 1.0;
   if (ROT) sincos_f64<false>((double)th, rs, rc);
   const float2* col = noise + tile_index(0, nn, T);  // this lane's column; rows are 64 apart
-  auto step = [&](float2 ut, float2 e) {
+  auto step = [&](float2 ut, float2 e, [[maybe_unused]] int t) {
+    const float4* row = TRACKS ? discs + t * slots : discs;  // the discs where they are after this step
     float v = clip_f32(ut.x + e.x, P.v_lo, P.v_hi);
     float w = clip_f32(ut.y + e.y, P.w_lo, P.w_hi);
     float nx, ny, nth;
@@ -1537,7 +1563,7 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
     float c1 = (float)((double)cost + P.dist_weight * nd2);
 #pragma unroll
     for (int k = 0; k < (KD >= 0 ? KD : P.n_obstacles); ++k) {
-      const float4 op = discs[k];
+      const float4 op = row[k];
       double ex = (double)(nx - op.x), ey = (double)(ny - op.y);
       double rr = (double)op.z * (double)op.z;
       double diff = fma(ex, ex, ey * ey) - rr;
@@ -1602,9 +1628,10 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
           const double dx = (double)(P.xg - nxa[j]), dy = (double)(P.yg - nya[j]);
           nd2a[j] = fma(dx, dx, dy * dy);
           add0[j] = P.dist_weight * nd2a[j];
+          [[maybe_unused]] const float4* row = TRACKS ? discs + (t0 + j) * KD : discs;
 #pragma unroll
           for (int k = 0; k < KD; ++k) {
-            const float4 op = discs[k];
+            const float4 op = row[k];
             const double ex = (double)(nxa[j] - op.x), ey = (double)(nya[j] - op.y);
             const double rr = (double)op.z * (double)op.z;
             const double diff = fma(ex, ex, ey * ey) - rr;
@@ -1626,7 +1653,7 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
         }
       } else {
 #pragma unroll
-        for (int j = 0; j < kNoiseBatch; ++j) step(u[t0 + j], e_cur[j]);
+        for (int j = 0; j < kNoiseBatch; ++j) step(u[t0 + j], e_cur[j], t0 + j);
       }
 #pragma unroll
       for (int j = 0; j < kNoiseBatch; ++j) e_cur[j] = e_nxt[j];
@@ -1634,13 +1661,13 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
     }
     if (!__all(done))
       for (int t = t0; t < T; ++t) {  // (batch registers shifted down, not indexed: see k_rollout_fused)
-        step(u[t], e_cur[0]);
+        step(u[t], e_cur[0], t);
 #pragma unroll
         for (int j = 0; j + 1 < kNoiseBatch; ++j) e_cur[j] = e_cur[j + 1];
       }
   } else {
     for (int t = 0; t < T; ++t) {
-      step(u[t], col[(size_t)t * 64]);
+      step(u[t], col[(size_t)t * 64], t);
       if (__all(done)) break;
     }
   }

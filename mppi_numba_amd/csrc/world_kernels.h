@@ -92,6 +92,8 @@ struct WorldLoop {
   // the LDS window plan of the planner (plan_lds_window): origin per problem around its start cell
   int win_active, reach, win_rows, win_cols, map_rows, map_pitch;
   double xlo, ylo, res;
+  // barebone mode with disc tracks: a control step later "now" is the tracks' next row (BatchInst::track_off)
+  int advance_tracks;
 };
 
 // One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4; barebone_mppi_numba.ipynb
@@ -136,6 +138,7 @@ __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ i
       I.win_r0 = (int)(r0 < rmax ? r0 : rmax);
       I.win_c0 = (int)(c0 < cmax ? c0 : cmax);
     }
+    if (L.advance_tracks && I.track_off < 0x7fffffff) ++I.track_off;
     inst[b] = I;
     const double dx = x1 - (double)I.xg, dy = y1 - (double)I.yg;
     if (sqrt(dx * dx + dy * dy) <= L.goal_tolerance) {
