@@ -252,6 +252,17 @@ int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const int* disc_cou
 int mppi_planner_set_track_offsets(mppi_planner* p, int count, const int* offsets);
 int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets);
 
+/* MPPI_MODE_BAREBONE only (any other mode: MPPI_ERR_INVALID): crowd mode, off by default.  While it
+ * is on, the three disc hand-overs above and the launch take any disc count that device memory
+ * holds -- the 64 KiB limits do not apply -- and the rollout of a set with kCrowdMinDiscs discs or
+ * more (launch_plan.h) runs k_rollout_barebone_crowd, which reads the discs from memory, counts the
+ * hits of every step in parallel over the horizon and then adds obs_cost once per hit: the bits
+ * of the default forms.  Everything else is unchanged.  Turning it off while the handle holds a
+ * set the default forms cannot launch returns MPPI_ERR_INVALID (the message names the set) and
+ * the handle stays in crowd mode with what it had.  A change drops the captured graphs. */
+int mppi_planner_set_crowd(mppi_planner* p, int on);
+int mppi_planner_get_crowd(mppi_planner* p, int* on);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

@@ -11,6 +11,9 @@ Not in the notebook: discs that move.  params['obstacle_tracks'] (K, L, 2) in
 place of 'obstacle_positions' gives every disc L predicted centres, row j its
 centre at time j*dt from "now"; "now" is row `track_offset`, and the state
 after step t of a rollout is tested against row min(track_offset + t + 1, L - 1).
+
+Crowd mode, Config(crowd=True) / set_crowd(True): disc sets of any size (the default forms keep a row of disc slots per
+step in 64 KiB of LDS: 39 moving discs at 100 steps); same results bit for bit.
 """
 import copy
 import ctypes as C
@@ -34,7 +37,7 @@ class Config:
     """ Configurations that are typically fixed throughout execution. """
 
     def __init__(self, T=10, dt=0.1, num_control_rollouts=1024, num_vis_state_rollouts=20, seed=1,
-                 enforce_recommended_limits=True, rng="philox", math="exact", device=0):
+                 enforce_recommended_limits=True, rng="philox", math="exact", device=0, crowd=False):
         assert T > 0
         assert dt > 0
         assert T > dt
@@ -45,6 +48,7 @@ class Config:
         assert self.num_steps > 0
         self.max_threads_per_block = _config.max_threads_per_block
         self.rng, self.math, self.device = rng, math, device
+        self.crowd = bool(crowd)  # crowd mode: no LDS limit on the disc sets (set_crowd)
 
         self.num_control_rollouts = num_control_rollouts
         if enforce_recommended_limits:
@@ -143,6 +147,20 @@ class MPPI_Numba(object):
         _lib.call("mppi_planner_get_track_offsets", self._handle, self.num_instances, _lib.ptr(off, C.c_int))
         self._track_offset = off
 
+    # ------------------------------------------------------------------ crowd mode
+    @property
+    def crowd(self):
+        """Whether the handle is in crowd mode (set_crowd)."""
+        on = C.c_int(0)
+        _lib.call("mppi_planner_get_crowd", self._handle, C.byref(on))
+        return bool(on.value)
+
+    def set_crowd(self, on):
+        """Crowd mode: disc sets of any size -- the 64 KiB LDS limits of the default forms do not apply -- and, above a
+        handful of discs, a rollout kernel that counts every step's hits in parallel; same results bit for bit.
+        Turning it off raises MppiError (and stays on) while the handle holds a set the default forms cannot launch."""
+        _lib.call("mppi_planner_set_crowd", self._handle, int(bool(on)))
+
     def _tracks_on(self):
         return self._tracks_from_params or self._own_tracks
 
@@ -186,6 +204,8 @@ class MPPI_Numba(object):
         handle = C.c_void_p()
         _lib.call("mppi_planner_create", C.byref(cfg), C.byref(handle))
         self._handle = handle
+        if getattr(self.cfg, "crowd", False):
+            self.set_crowd(True)
         B, t, v = self.num_instances, self.num_steps, self.num_vis_state_rollouts
         n = B * self.num_control_rollouts
         lead = () if B == 1 else (B,)

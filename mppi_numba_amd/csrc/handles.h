@@ -241,6 +241,11 @@ struct mppi_planner {
   int trk_max = 0;  // the largest problem's count
   std::vector<int> trk_counts_host;
   std::vector<float> trk_pos_host, trk_r_host;
+  // crowd mode (mppi_planner_set_crowd): no LDS limit on the disc sets; k_rollout_barebone_crowd reads them from memory.
+  // trk_pos_rows: the tracks once more as [row][disc] (all problems' discs side by side), kept while crowd && trk_on, so
+  // that the discs a step tests are contiguous
+  bool crowd = false;
+  float2* trk_pos_rows = nullptr;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

@@ -1029,9 +1029,69 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
 // of an instance handle or the classic single launch.  LDS: [T] double2 control ratios | [T][slots] float4, one row of
 // disc slots per step (barebone_track_lds); the KD forms where they fit, else the run-time loop over the largest
 // problem's count.
+// Crowd mode (mppi_planner_set_crowd; rollout_crowd_kernel.h): from this many discs on -- the largest problem's count --
+// the rollout runs k_rollout_barebone_crowd.  Every form gives the same bits, so the crossover is a timing decision, to be
+// taken from tools/barebone_crowd_timing.py (solve() at N = 1000, T = 50, crowd off and on side by side; profiles/HISTORY.md,
+// "Barebone crowd mode").  NOT MEASURED YET: 5 is the lowest value the design allows -- up to four discs under rotation the
+// KD forms are a single basic block -- and tests/test_gpu_barebone_crowd.py expects the crowd kernel from five discs on.
+// Below it the default forms run (they fit: a set this small needs 16 * T * (1 + K) bytes at the most -- and where a long
+// horizon's tracks do not, the crowd kernel runs).
+constexpr int kCrowdMinDiscs = 5;
+
+// W waves per workgroup and C steps per chunk.  One tile is one workgroup whatever W is, so few tiles (N = 1000: 16 on
+// 256 CUs) get the whole 16 waves -- 14 counters -- and a launch that fills the device on its own gets fewer: about 32
+// waves per CU in all.  C: the largest multiple of the counters within kCrowdChunkMax, every counter the same share.
+static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
+  const int tiles = ceil_div(p->n_local, 64);
+  const int W = std::min(kCrowdWavesMax, std::max(4, (32 * p->num_cus) / tiles));
+  *waves = W;
+  *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
+}
+
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
+static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
+  int W = 0, C = 0;
+  crowd_shape(p, &W, &C);
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C);
+  auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS>;
+  if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MPPI_KLAUNCH(kern, dim3(ceil_div(p->n_local, 64)), dim3(64 * W), lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch);
+  p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)ROT) +
+                    " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
+                    (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string());
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+// The disc set a crowd launch reads: the tracks ([row][disc] copy), a problem's own static set, or the shared one.
+template <bool EXACT, bool BATCHED>
+static int launch_rollout_barebone_crowd(mppi_planner* p, DevParams d, bool rot) {
+  if (p->trk_on) {
+    if (!BATCHED) d.n_obstacles = p->trk_max;
+    const int pitch = (int)p->trk_r_host.size();
+    if (rot) return launch_crowd_kernel<EXACT, EXACT, BATCHED, true>(p, d, p->trk_pos_rows, p->trk_r, pitch);
+    return launch_crowd_kernel<EXACT, false, BATCHED, true>(p, d, p->trk_pos_rows, p->trk_r, pitch);
+  }
+  const bool own = p->inst_obs_on;
+  if (!BATCHED) d.n_obstacles = own ? p->inst_obs_max : p->n_obstacles;
+  const float2* pos = own ? p->inst_obs_pos : p->obs_pos;
+  const float* rad = own ? p->inst_obs_r : p->obs_r;
+  if (rot) return launch_crowd_kernel<EXACT, EXACT, BATCHED, false>(p, d, pos, rad, 0);
+  return launch_crowd_kernel<EXACT, false, BATCHED, false>(p, d, pos, rad, 0);
+}
+
+// Crowd mode: does this launch go to the crowd kernel?  kmax: the largest problem's disc count; default_lds: what the
+// default form would hold in LDS.
+static bool crowd_launch(const mppi_planner* p, int kmax, size_t default_lds) {
+  return p->crowd && (kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
+}
+
 template <bool EXACT, bool BATCHED>
 static int launch_rollout_barebone_tracks(mppi_planner* p, DevParams d, bool rot) {
   const int N = p->n_local, T = p->cfg.num_steps, kmax = p->trk_max;
+  if (crowd_launch(p, kmax, barebone_track_lds(T, kmax))) return launch_rollout_barebone_crowd<EXACT, BATCHED>(p, d, rot);
   int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
   if (kd > 0 && barebone_track_lds(T, kd) > 64 * 1024) kd = -1;  // (a long horizon: the padded row does not fit, the problem's own may)
   const size_t lds = barebone_track_lds(T, kd > 0 ? kd : kmax);  // the size launched
@@ -1063,6 +1123,8 @@ static int launch_rollout_barebone_batch(mppi_planner* p, const DevParams& d, bo
   const int kmax = own ? p->inst_obs_max : p->n_obstacles;
   const float2* pos = own ? p->inst_obs_pos : p->obs_pos;
   const float* rad = own ? p->inst_obs_r : p->obs_r;
+  if (crowd_launch(p, kmax, sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, kmax)))
+    return launch_rollout_barebone_crowd<EXACT, true>(p, d, rot);
   const int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
   // LDS: [T] double2 control ratios | one float4 per disc slot, the size launched
   const size_t lds = sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, kd > 0 ? kd : kmax);
@@ -1104,6 +1166,7 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
       const float* rad = p->inst_obs_on ? p->inst_obs_r : p->obs_r;
       d.n_obstacles = K;
       const size_t lds_bb = sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)std::max(1, K);
+      if (crowd_launch(p, K, lds_bb)) return launch_rollout_barebone_crowd<EXACT, false>(p, d, rot);
       REQUIRE(lds_bb <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", K, p->cfg.num_steps);
       if (rot && K <= 2)
         MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 2 * sizeof(float4),

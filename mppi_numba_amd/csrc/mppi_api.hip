@@ -21,6 +21,7 @@
 
 #include "rng_kernels.h"
 #include "rollout_kernels.h"
+#include "rollout_crowd_kernel.h"
 #include "rollout_scan_kernel.h"
 #include "rollout_scan_exact_kernel.h"
 #include "map_kernels.h"
@@ -512,6 +513,7 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->inst_obs_pos);
   dev_free(p->inst_obs_r);
   dev_free(p->trk_pos);
+  dev_free(p->trk_pos_rows);
   dev_free(p->trk_r);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
@@ -789,7 +791,7 @@ extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int cou
     REQUIRE(total <= (1L << 30), MPPI_ERR_INVALID, "too many discs (%ld)", total);
     REQUIRE(total == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
     // what a launch holds in LDS: the control ratios and the largest problem's discs (launch_rollout_barebone_batch)
-    REQUIRE(sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)kmax <= 64 * 1024, MPPI_ERR_INVALID,
+    REQUIRE(p->crowd || sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)kmax <= 64 * 1024, MPPI_ERR_INVALID,
             "a problem with %d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, p->cfg.num_steps);
   }
   if (count == 0 ? !p->inst_obs_on
@@ -824,6 +826,20 @@ extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int cou
   return MPPI_OK;
 }
 
+// Crowd mode: the tracks the handle holds ([disc][row], trk_pos_host) once more as [row][disc] on the device.
+static int upload_track_rows(mppi_planner* p) {
+  dev_free(p->trk_pos_rows);
+  const size_t rows = (size_t)p->trk_rows, total = p->trk_r_host.size();
+  TRY(dev_alloc(&p->trk_pos_rows, std::max<size_t>(1, rows * total)));
+  if (rows * total == 0) return MPPI_OK;
+  std::vector<float2> by_row(rows * total);
+  for (size_t k = 0; k < total; ++k)
+    for (size_t r = 0; r < rows; ++r)
+      by_row[r * total + k] = make_float2(p->trk_pos_host[2 * (k * rows + r)], p->trk_pos_host[2 * (k * rows + r) + 1]);
+  HIP_TRY(hipMemcpy(p->trk_pos_rows, by_row.data(), sizeof(float2) * by_row.size(), hipMemcpyHostToDevice));
+  return MPPI_OK;
+}
+
 // Barebone mode: discs that move.  `rows` predicted centres per disc (row j: where it is j * dt from "now"), one set shared
 // by every problem (count == 1) or one per problem (count == B), laid out like the static per-problem sets.  Unchanged
 // arrays cost a comparison; a change synchronises, reallocates, drops the captured graphs and makes row 0 "now" again.
@@ -848,7 +864,7 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
     REQUIRE(total == 0 || (tracks && radii), MPPI_ERR_INVALID, "NULL tracks or radii");
     // what a launch holds in LDS at the least: the control ratios and a row of the largest problem's discs per step
     const size_t lds = barebone_track_lds(p->cfg.num_steps, kmax);
-    REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID,
+    REQUIRE(p->crowd || lds <= 64 * 1024, MPPI_ERR_INVALID,
             "a problem with %d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, p->cfg.num_steps, lds);
   }
   const size_t n_pos = (size_t)total * (size_t)rows;
@@ -861,6 +877,7 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   dev_free(p->trk_pos);
+  dev_free(p->trk_pos_rows);
   dev_free(p->trk_r);
   p->trk_on = false;
   p->trk_rows = p->trk_max = 0;
@@ -881,9 +898,43 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
     p->trk_counts_host.assign(disc_counts, disc_counts + count);
     p->trk_pos_host.assign(tracks, tracks + 2 * n_pos);
     p->trk_r_host.assign(radii, radii + (size_t)total);
+    if (p->crowd) TRY(upload_track_rows(p));
   }
   for (BatchInst& I : p->inst_host) I.track_off = 0;
   note_instance_discs(p);
+  return MPPI_OK;
+}
+
+// Crowd mode (include/mppi_hip.h).  Off -> on: the [row][disc] copy of the tracks the handle holds.  On -> off: only when
+// the default forms can launch every set the handle holds (the checks of the hand-overs and of the launches).
+extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  if ((on != 0) == p->crowd) return MPPI_OK;
+  const int T = p->cfg.num_steps;
+  if (!on) {
+    REQUIRE(!p->trk_on || barebone_track_lds(T, p->trk_max) <= 64 * 1024, MPPI_ERR_INVALID,
+            "crowd mode stays on: the disc tracks held (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
+            p->trk_max, T, barebone_track_lds(T, p->trk_max));
+    REQUIRE(!p->inst_obs_on || sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)p->inst_obs_max <= 64 * 1024, MPPI_ERR_INVALID,
+            "crowd mode stays on: the per-problem disc obstacles held (%d discs, %d steps) need more than 64 KiB of LDS",
+            p->inst_obs_max, T);
+    REQUIRE(sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, p->n_obstacles) <= 64 * 1024, MPPI_ERR_INVALID,
+            "crowd mode stays on: the disc obstacles held (%d discs, %d steps) need more than 64 KiB of LDS", p->n_obstacles, T);
+  }
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (on && p->trk_on) TRY(upload_track_rows(p));
+  if (!on) dev_free(p->trk_pos_rows);
+  p->crowd = on != 0;
+  drop_graphs(p);  // (the kernel form is part of the captured launches)
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_crowd(mppi_planner* p, int* on) {
+  REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  *on = p->crowd ? 1 : 0;
   return MPPI_OK;
 }
 

@@ -1,0 +1,200 @@
+// Crowd mode of the barebone rollout (mppi_planner_set_crowd): disc sets of any size, read from memory.
+//
+// k_rollout_barebone keeps a row of disc slots per step in LDS (64 KiB: 39 moving discs at T = 100) and, above four discs,
+// appends one float32-rounded addition per disc and step to the one dependent chain of a lone wave.  Three facts let the
+// discs leave that chain without changing a bit of the result:
+//   - a rollout's state never depends on the discs,
+//   - a disc that is not hit adds +0.0 -- the identity: the running cost is never -0.0 (it starts at +0.0, and a sum is
+//     -0.0 only when both terms are),
+//   - every disc that is hit adds the same (double)obs_cost.
+// So the cost after step t depends on the discs only through HOW MANY of them the post-step position touches, an integer
+// that any number of waves may count in any order.  (obs_cost = +-inf is where the forms part: 0.0 * inf is NaN there.)
+//
+// One workgroup of W >= 3 waves serves one tile of 64 rollouts of one problem and walks the horizon in chunks of C steps.
+// The three phases of a chunk run on different waves, and the chunks are pipelined through double-buffered LDS -- in
+// interval i of the loop (one barrier per interval):
+//   walk   wave 0       chunk i      the state step of k_rollout_barebone (barebone_next_pose), state in registers across
+//                                    chunks; post-step (x, y) -> LDS [step][lane]
+//   count  waves 2..W-1 chunk i-1    counter q takes the chunk's steps j = q, q + (W-2), ...: the lane's position against
+//                                    every disc of the problem at that step (tracks: row min(now + t + 1, last) of the
+//                                    [row][disc] copy, so a step's discs are contiguous) with the double-precision test
+//                                    of k_rollout_barebone; int32 hit count and the goal distance -> LDS [step][lane].
+//                                    A (step, lane) pair has one owner: no atomics.  64 discs at a time: every lane loads
+//                                    one disc (a coalesced load, the next tile's in flight during the tests), the tests
+//                                    read them lane by lane as wave-uniform values.
+//   cost   wave 1       chunk i-2    the reference's chain: the distance term, then `hits` rounded additions of obs_cost
+//                                    (a wave-uniform loop to the wave's largest count, predicated per lane), then the freeze
+//                                    at the goal
+// and after the last chunk wave 1 adds the terminal term and the T control-cost terms as k_rollout_barebone does.
+// When every rollout of the tile has reached the goal the workgroup stops (what is left of the horizon adds nothing).
+#pragma once
+#include "rollout_kernels.h"
+
+namespace mppi {
+
+constexpr int kCrowdChunkMax = 16;   // steps per chunk at the most (the walker keeps a chunk's noise in registers)
+constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
+// dynamic LDS: [T] double2 control ratios | [2][C][64] double goal distance | [2][C][64] float2 position |
+// [2][C][64] int hits | two "tile done" words
+__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C) {
+  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * (sizeof(double) + sizeof(float2) + sizeof(int)) + 2 * sizeof(int);
+}
+
+__device__ __forceinline__ float crowd_lane_f32(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ double crowd_lane_f64(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
+__global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
+    DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
+    const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch) {
+  extern __shared__ double2 uos[];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, NC = ((int)blockDim.x >> 6) - 2;
+  if (P.ktime && threadIdx.x == 0) P.ktime[blockIdx.x] = (unsigned long long)wall_clock64();  // (one slot per tile)
+  if constexpr (BATCHED) {
+    const int b = (int)blockIdx.x / P.inst_tiles;  // (uniform over the workgroup)
+    u = select_instance(P, u, b);
+    const BatchInst I = P.inst[b];
+    obs_pos += I.disc0;
+    obs_r += I.disc0;
+    P.n_obstacles = I.n_discs;
+    if constexpr (TRACKS) P.track_off = I.track_off;
+  }
+  const int T = P.n_steps, K = P.n_obstacles;
+  double* nd2s = reinterpret_cast<double*>(uos + T);
+  float2* poss = reinterpret_cast<float2*>(nd2s + 2 * C * 64);
+  int* cnts = reinterpret_cast<int*>(poss + 2 * C * 64);
+  int* tile_done = cnts + 2 * C * 64;  // [2], used in turn: a wave still looks at one while wave 1 writes the other
+  if (threadIdx.x < 2) tile_done[threadIdx.x] = 0;
+  stage_control_ratios(P, u, uos);  // (ends with a barrier)
+  const int n = blockIdx.x * 64 + lane;
+  const bool live = n < P.n_local;
+  const int nn = live ? n : P.n_local - 1;
+  const float2* col = noise + tile_index(0, nn, T);  // this lane's column; rows are 64 apart
+  const int n_chunks = (T + C - 1) / C;
+  // the walker's
+  float x = P.x0, y = P.y0, th = P.th0;
+  [[maybe_unused]] double rs = 0.0, rc = 1.0;
+  float2 e_cur[kCrowdChunkMax];
+  if (wave == 0) {
+    if (ROT) sincos_f64<false>((double)th, rs, rc);
+#pragma unroll
+    for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = col[(size_t)min(j, T - 1) * 64];
+  }
+  // the cost wave's
+  float cost = 0.0f;
+  double d2 = 1e9;
+  bool done = false, reached = false;
+  [[maybe_unused]] const int last = P.track_rows - 1, now = min(max(P.track_off, 0), last);  // (an offset past the end: the last row)
+
+  for (int ph = 0; ph < n_chunks + 2; ++ph) {
+    if (wave == 0) {
+      if (ph < n_chunks) {  // ---- walk chunk ph
+        const int c0 = ph * C, cl = min(C, T - c0);
+        float2 e_nxt[kCrowdChunkMax];
+#pragma unroll
+        for (int j = 0; j < kCrowdChunkMax; ++j) e_nxt[j] = col[(size_t)min(c0 + C + j, T - 1) * 64];
+        float2* out = poss + (size_t)((ph & 1) * C) * 64 + lane;
+#pragma unroll
+        for (int j = 0; j < kCrowdChunkMax; ++j) {
+          if (j < cl) {
+            float nx, ny, nth;
+            barebone_next_pose<EXACT, ROT>(P, u[c0 + j], e_cur[j], x, y, th, rs, rc, nx, ny, nth);
+            if (ROT) rotate_sincos_f64((double)nth - (double)th, rs, rc);  // exact increment of the ROUNDED heading
+            x = nx; y = ny; th = nth;  // (past the goal the state goes on -- nobody looks at it: the cost wave freezes)
+            out[j * 64] = make_float2(nx, ny);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = e_nxt[j];
+      }
+    } else if (wave == 1) {
+      if (ph >= 2) {  // ---- cost of chunk ph - 2
+        const int c = ph - 2, c0 = c * C, cl = min(C, T - c0);
+        const size_t at = (size_t)((c & 1) * C) * 64 + lane;
+        for (int j = 0; j < cl; ++j) {
+          const double nd2 = nd2s[at + j * 64];
+          const int hits = cnts[at + j * 64];
+          float c1 = (float)((double)cost + P.dist_weight * nd2);
+          for (int h = 0; __any(h < hits); ++h)
+            if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
+          const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
+          cost = act ? c1 : cost;
+          d2 = act ? nd2 : d2;
+          reached = reached || (act && hit_goal);
+          done = done || hit_goal;
+        }
+        if (__all(done) && lane == 0) tile_done[ph & 1] = 1;
+      }
+    } else {
+      const int c = ph - 1;
+      if (c >= 0 && c < n_chunks) {  // ---- count chunk ph - 1
+        const int c0 = c * C, cl = min(C, T - c0);
+        const size_t at = (size_t)((c & 1) * C) * 64 + lane;
+        // this lane's disc of the tile [base, base + 64) as step c0 + j sees it; past the problem's last disc: a disc
+        // nobody can touch (k_rollout_barebone's far slot)
+        auto load_disc = [&](int j, int base, float2& op, double& rr) {
+          const int k = base + lane;
+          op = make_float2(1e18f, 1e18f);
+          float r = 0.0f;
+          if (j < cl && k < K) {
+            const float2* row = TRACKS ? obs_pos + (size_t)min(now + c0 + j + 1, last) * (size_t)disc_pitch : obs_pos;
+            op = row[k];
+            r = obs_r[k];
+          }
+          rr = (double)r * (double)r;
+        };
+        int j = wave - 2, base = 0, hits = 0;
+        float2 op;
+        double rr;
+        load_disc(j, base, op, rr);
+        while (j < cl) {
+          int nj = j, nbase = base + 64;
+          if (nbase >= K) { nj = j + NC; nbase = 0; }
+          float2 op_nxt;
+          double rr_nxt;
+          load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
+          const float2 pos = poss[at + j * 64];
+          const int kt = min(64, K - base);
+          for (int l0 = 0; l0 < kt; l0 += 4) {
+#pragma unroll
+            for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+              const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
+              const double rrl = crowd_lane_f64(rr, l);
+              const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+              const double diff = fma(ex, ex, ey * ey) - rrl;
+              hits += (diff > 0.0) ? 0 : 1;
+            }
+          }
+          if (nj != j) {  // the step's last tile
+            cnts[at + j * 64] = hits;
+            nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+            hits = 0;
+          }
+          j = nj; base = nbase; op = op_nxt; rr = rr_nxt;
+        }
+      }
+    }
+    __syncthreads();
+    if (tile_done[ph & 1]) break;  // (uniform: every rollout of the tile is at its goal)
+  }
+  if (wave != 1) return;
+  cost = (float)((double)cost + (reached ? 0.0 : 1.0) * d2);
+  int t0 = 0;
+  for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {  // loads and products batched, the float32-rounded additions in order
+    double cc[kNoiseBatch];
+#pragma unroll
+    for (int j = 0; j < kNoiseBatch; ++j) cc[j] = control_cost(P, uos[t0 + j], col[(size_t)(t0 + j) * 64]);
+#pragma unroll
+    for (int j = 0; j < kNoiseBatch; ++j) cost = (float)((double)cost + cc[j]);
+  }
+  for (int t = t0; t < T; ++t) cost = (float)((double)cost + control_cost(P, uos[t], col[(size_t)t * 64]));
+  if (live) costs[n] = cost;
+  if (P.ktime && lane == 0) P.ktime[P.ktime_waves + blockIdx.x] = (unsigned long long)wall_clock64();
+}
+
+}  // namespace mppi

@@ -1485,6 +1485,36 @@ __global__ void k_cvar_reduce(const float* __restrict__ slabs, int count, int n_
 // against row min(s + t + 1, rows - 1): the disc where it will be when the robot gets there, at its last predicted place
 // once the track has ended.  The rows are picked when the launch stages its LDS -- one row of disc slots per step,
 // [T][slots] -- so a step does what it does for static discs on operands that change with t: same operations, same order.
+// One state step of the barebone rollout, shared by k_rollout_barebone's step() and the walk of
+// k_rollout_barebone_crowd (rollout_crowd_kernel.h): the clipped controls and the pose after the step, with the
+// reference's float32 roundings.  ROT: (rs, rc) are (sin, cos) of `th`, kept by the caller by rotation.
+template <bool EXACT, bool ROT>
+__device__ __forceinline__ void barebone_next_pose(const DevParams& P, float2 ut, float2 e, float x, float y, float th,
+                                                   [[maybe_unused]] double rs, [[maybe_unused]] double rc, float& nx,
+                                                   float& ny, float& nth) {
+  float v = clip_f32(ut.x + e.x, P.v_lo, P.v_hi);
+  float w = clip_f32(ut.y + e.y, P.w_lo, P.w_hi);
+  float dtv = P.dt * v;  // float32 * float32 first (cell 3: dt_d*v_noisy*math.cos(...))
+  if (EXACT) {
+    double sn, cs;
+    if (ROT) { sn = rs; cs = rc; }
+    else sincos_f64<false>((double)th, sn, cs);
+    nx = (float)fma((double)dtv, cs, (double)x);
+    ny = (float)fma((double)dtv, sn, (double)y);
+  } else {
+    float sn, cs;
+    sincosf(th, &sn, &cs);
+    nx = fmaf(dtv, cs, x);
+    ny = fmaf(dtv, sn, y);
+  }
+  nth = th + P.dt * w;
+}
+// ... and the squared distance to the goal of the post-step position
+__device__ __forceinline__ double barebone_goal_d2(const DevParams& P, float nx, float ny) {
+  double dx = (double)(P.xg - nx), dy = (double)(P.yg - ny);
+  return fma(dx, dx, dy * dy);
+}
+
 template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false, bool TRACKS = false>
 __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const float2* __restrict__ obs_pos,
                                                          const float* __restrict__ obs_r,
@@ -1540,26 +1570,9 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
   const float2* col = noise + tile_index(0, nn, T);  // this lane's column; rows are 64 apart
   auto step = [&](float2 ut, float2 e, [[maybe_unused]] int t) {
     const float4* row = TRACKS ? discs + t * slots : discs;  // the discs where they are after this step
-    float v = clip_f32(ut.x + e.x, P.v_lo, P.v_hi);
-    float w = clip_f32(ut.y + e.y, P.w_lo, P.w_hi);
     float nx, ny, nth;
-    double nd2;
-    float dtv = P.dt * v;  // float32 * float32 first (cell 3: dt_d*v_noisy*math.cos(...))
-    if (EXACT) {
-      double sn, cs;
-      if (ROT) { sn = rs; cs = rc; }
-      else sincos_f64<false>((double)th, sn, cs);
-      nx = (float)fma((double)dtv, cs, (double)x);
-      ny = (float)fma((double)dtv, sn, (double)y);
-    } else {
-      float sn, cs;
-      sincosf(th, &sn, &cs);
-      nx = fmaf(dtv, cs, x);
-      ny = fmaf(dtv, sn, y);
-    }
-    nth = th + P.dt * w;
-    double dx = (double)(P.xg - nx), dy = (double)(P.yg - ny);
-    nd2 = fma(dx, dx, dy * dy);
+    barebone_next_pose<EXACT, ROT>(P, ut, e, x, y, th, rs, rc, nx, ny, nth);
+    const double nd2 = barebone_goal_d2(P, nx, ny);
     float c1 = (float)((double)cost + P.dist_weight * nd2);
 #pragma unroll
     for (int k = 0; k < (KD >= 0 ? KD : P.n_obstacles); ++k) {
