@@ -263,6 +263,24 @@ int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets);
 int mppi_planner_set_crowd(mppi_planner* p, int on);
 int mppi_planner_get_crowd(mppi_planner* p, int* on);
 
+/* MPPI_MODE_BAREBONE in crowd mode only: wall obstacles.  A wall is a segment A -> B with a
+ * half-width h >= 0; segments is (count, 4) float32 -- ax ay bx by -- and halfwidths (count)
+ * float32.  Step t of a rollout (t = 0 .. T-1) moves the robot from P (the position before the
+ * step, the start state for t = 0) to Q; it hits the wall iff the distance between the closed
+ * segments PQ and AB is <= h, so a step that jumps a thin wall is a hit.  Every wall hit counts
+ * like a disc hit of that step: obs_cost once more, nothing after the freeze at the goal; walls do
+ * not stop a rollout, and a position inside a wall is counted at the step that ends there and at
+ * the step that starts there.  The test is division-free and runs in double on the widened
+ * float32 inputs (rollout_crowd_kernel.h, crowd_wall_hit; tests/wall_model.py is its numpy form).
+ * The walls are static and shared by every problem of a batched handle; per-problem wall sets and
+ * walls that move are not provided.  A handle that holds walls launches
+ * k_rollout_barebone_crowd's WALLS form whatever its disc count (mppi_planner_describe_last_rollout
+ * ends in " walls=<count>"), and mppi_planner_set_crowd(p, 0) returns MPPI_ERR_INVALID until they
+ * are cleared.  count = 0 clears them (segments, halfwidths ignored).  Unchanged arrays cost a
+ * comparison; a change drops the captured graphs.  MPPI_ERR_INVALID for a map mode, a handle that
+ * is not in crowd mode, a negative or non-finite half-width, or a non-finite endpoint. */
+int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* halfwidths, int count);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

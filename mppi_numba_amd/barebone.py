@@ -14,6 +14,12 @@ after step t of a rollout is tested against row min(track_offset + t + 1, L - 1)
 
 Crowd mode, Config(crowd=True) / set_crowd(True): disc sets of any size (the default forms keep a row of disc slots per
 step in 64 KiB of LDS: 39 moving discs at 100 steps); same results bit for bit.
+
+Walls (crowd mode only): params['wall_segments'] (W, 2, 2), [[ax, ay], [bx, by]] per wall, and params['wall_halfwidth'],
+a scalar or (W,).  Step t of a rollout moves the robot from P to Q (P of step 0 is x0); it hits a wall iff the distance
+between the closed segments PQ and AB is <= the half-width -- a step that jumps a thin wall is a hit -- and every hit adds
+obs_penalty once, like a disc hit of that step.  Static, and shared by the problems of an MPPI_Batch.  polyline_walls()
+turns a room outline into segments.
 """
 import copy
 import ctypes as C
@@ -79,6 +85,20 @@ def constant_velocity_tracks(positions, velocities, dt, rows):
     return np.ascontiguousarray((pos + vel * times).astype(np.float32))
 
 
+def polyline_walls(points, closed=False):
+    """(W, 2, 2) float32 wall segments [[ax, ay], [bx, by]] along a polyline of (P, 2) points: W = P - 1, or P with
+    closed=True (a polygon: the last point is joined to the first; fewer than three points close nothing).  Fewer than two
+    points: no walls."""
+    pts = _f32(points).reshape(-1, 2)
+    if len(pts) < 2:
+        return np.zeros((0, 2, 2), dtype=np.float32)
+    ends = pts[1:]
+    starts = pts[:-1]
+    if closed and len(pts) >= 3:
+        starts, ends = pts, np.roll(pts, -1, axis=0)
+    return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.float32)
+
+
 def _is_track_set(obstacle_set):
     return np.asarray(obstacle_set[0]).ndim == 3
 
@@ -111,6 +131,7 @@ class MPPI_Numba(object):
         self._discs_key = None  # what the device's disc arrays hold (None: nothing handed over yet)
         self._tracks_from_params = False  # ... and whether they are the tracks of params['obstacle_tracks']
         self._own_tracks = False          # MPPI_Batch: per-problem tracks are set (they win over params')
+        self._walls_key = ()  # what the device's wall arrays hold (): none
         self.reset()
 
     def __del__(self):
@@ -160,6 +181,28 @@ class MPPI_Numba(object):
         handful of discs, a rollout kernel that counts every step's hits in parallel; same results bit for bit.
         Turning it off raises MppiError (and stays on) while the handle holds a set the default forms cannot launch."""
         _lib.call("mppi_planner_set_crowd", self._handle, int(bool(on)))
+
+    # ------------------------------------------------------------------ walls
+    def _hand_over_walls(self, p):
+        """params['wall_segments'] / ['wall_halfwidth']: handed over when they have changed, cleared when the keys have
+        gone.  Without crowd mode the library refuses them (MppiError)."""
+        if "wall_segments" not in p:
+            if self._walls_key != ():
+                _lib.call("mppi_planner_set_walls", self._handle, None, None, 0)
+                self._walls_key = ()
+            return
+        seg, hw = np.asarray(p['wall_segments']), np.asarray(p.get('wall_halfwidth', 0.0))
+        key = (seg.dtype.str, seg.shape, seg.tobytes(), hw.dtype.str, hw.shape, hw.tobytes())
+        if key == self._walls_key:
+            return
+        if seg.size and seg.shape[1:] != (2, 2):
+            raise ValueError("params['wall_segments'] has shape (W, 2, 2), got {}".format(seg.shape))
+        segs = np.ascontiguousarray(_f32(seg).reshape(-1, 4))
+        if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(segs)):
+            raise ValueError("params['wall_halfwidth'] is a scalar or has shape ({},), got {}".format(len(segs), hw.shape))
+        half = np.ascontiguousarray(np.broadcast_to(_f32(hw), (len(segs),)))
+        _lib.call("mppi_planner_set_walls", self._handle, _lib.ptr(segs, C.c_float), _lib.ptr(half, C.c_float), len(segs))
+        self._walls_key = key
 
     def _tracks_on(self):
         return self._tracks_from_params or self._own_tracks
@@ -265,6 +308,7 @@ class MPPI_Numba(object):
         c.alpha_dyn = 1.0
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
+        self._hand_over_walls(p)
         # the discs: handed over when they have changed (the notebook uploads them with every solve)
         if "obstacle_tracks" in p:
             if "obstacle_positions" in p:

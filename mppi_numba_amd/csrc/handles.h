@@ -246,6 +246,14 @@ struct mppi_planner {
   // that the discs a step tests are contiguous
   bool crowd = false;
   float2* trk_pos_rows = nullptr;
+  // walls (mppi_planner_set_walls; crowd mode only): segments (ax, ay, bx, by) and half-widths, static and shared by every
+  // problem.  n_walls > 0: every rollout launch is the crowd kernel's WALLS form.  wall_gen: next_generation() at every
+  // change, 0 without walls -- what the graph signature holds of them
+  float4* wall_seg = nullptr;
+  float* wall_hw = nullptr;
+  int n_walls = 0;
+  uint64_t wall_gen = 0;
+  std::vector<float> wall_seg_host, wall_hw_host;  // what the device arrays hold
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

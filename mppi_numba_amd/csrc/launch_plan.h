@@ -1048,21 +1048,40 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
   *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
 }
 
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
-static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS>
+static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C);
-  auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS>;
-  if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MPPI_KLAUNCH(kern, dim3(ceil_div(p->n_local, 64)), dim3(64 * W), lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch);
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, WALLS);  // the size launched
+  if constexpr (WALLS)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
+    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
+  const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
+  if constexpr (WALLS) {
+    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls>;
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const CrowdWalls walls{p->wall_seg, p->wall_hw, p->n_walls};
+    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls);
+  } else {  // (the kernel and its arguments as they were before there were walls)
+    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS>;
+    if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch);
+  }
   p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)ROT) +
                     " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
                     (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
-                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string());
+                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
+                    (WALLS ? " walls=" + std::to_string(p->n_walls) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
+}
+
+// A handle that holds walls (mppi_planner_set_walls) launches the WALLS form, whatever its discs are.
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
+static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
+  if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, true>(p, d, pos, rad, pitch);
+  return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, false>(p, d, pos, rad, pitch);
 }
 
 // The disc set a crowd launch reads: the tracks ([row][disc] copy), a problem's own static set, or the shared one.
@@ -1083,9 +1102,9 @@ static int launch_rollout_barebone_crowd(mppi_planner* p, DevParams d, bool rot)
 }
 
 // Crowd mode: does this launch go to the crowd kernel?  kmax: the largest problem's disc count; default_lds: what the
-// default form would hold in LDS.
+// default form would hold in LDS.  Walls are the crowd kernel's alone: a handle that holds any always goes there.
 static bool crowd_launch(const mppi_planner* p, int kmax, size_t default_lds) {
-  return p->crowd && (kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
+  return p->crowd && (p->n_walls > 0 || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
 }
 
 template <bool EXACT, bool BATCHED>
@@ -1590,7 +1609,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1606,6 +1625,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.lin_maps = p->packed.lin_maps; sig.lin_grid = p->packed.lin_grid;
   sig.ang_maps = p->packed.ang_maps; sig.ang_grid = p->packed.ang_grid;
   sig.epoch_bias = p->noise_epoch - p->bumps_launched;
+  sig.wall_gen = p->wall_gen;  // (the walls' generation, not their address: a new set may land where the old one was)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

@@ -515,6 +515,8 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->trk_pos);
   dev_free(p->trk_pos_rows);
   dev_free(p->trk_r);
+  dev_free(p->wall_seg);
+  dev_free(p->wall_hw);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -913,6 +915,8 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   if ((on != 0) == p->crowd) return MPPI_OK;
   const int T = p->cfg.num_steps;
   if (!on) {
+    REQUIRE(p->n_walls == 0, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
     REQUIRE(!p->trk_on || barebone_track_lds(T, p->trk_max) <= 64 * 1024, MPPI_ERR_INVALID,
             "crowd mode stays on: the disc tracks held (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
             p->trk_max, T, barebone_track_lds(T, p->trk_max));
@@ -928,6 +932,47 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   if (!on) dev_free(p->trk_pos_rows);
   p->crowd = on != 0;
   drop_graphs(p);  // (the kernel form is part of the captured launches)
+  return MPPI_OK;
+}
+
+// Walls (include/mppi_hip.h): crowd mode only -- they are one more source of hits for the count waves of
+// k_rollout_barebone_crowd<..., WALLS> and nothing the default forms know.  Unchanged arrays cost a comparison; a change
+// synchronises, reallocates, takes a new generation (the graph signature's view of the walls) and drops the captured graphs.
+extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* halfwidths, int count) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "walls belong to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(count >= 0 && count <= (1 << 24) && (count == 0 || (segments && halfwidths)), MPPI_ERR_INVALID, "bad wall arrays (count %d)", count);
+  REQUIRE(count == 0 || p->crowd, MPPI_ERR_INVALID,
+          "walls need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
+  for (int k = 0; k < count; ++k) {
+    const float h = halfwidths[k];
+    REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "wall %d: half-width %g is negative or not finite", k, (double)h);
+    for (int i = 0; i < 4; ++i)
+      REQUIRE(std::isfinite(segments[4 * (size_t)k + i]), MPPI_ERR_INVALID, "wall %d: an endpoint coordinate is not finite", k);
+  }
+  if (count == p->n_walls &&
+      (count == 0 || (memcmp(segments, p->wall_seg_host.data(), sizeof(float) * 4 * (size_t)count) == 0 &&
+                      memcmp(halfwidths, p->wall_hw_host.data(), sizeof(float) * (size_t)count) == 0)))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  dev_free(p->wall_seg);
+  dev_free(p->wall_hw);
+  p->n_walls = 0;
+  p->wall_gen = 0;
+  p->wall_seg_host.clear();
+  p->wall_hw_host.clear();
+  drop_graphs(p);  // (the arrays, the count and the kernel form are arguments of the captured launches)
+  if (count > 0) {
+    TRY(dev_alloc(&p->wall_seg, (size_t)count));
+    TRY(dev_alloc(&p->wall_hw, (size_t)count));
+    HIP_TRY(hipMemcpy(p->wall_seg, segments, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->wall_hw, halfwidths, sizeof(float) * (size_t)count, hipMemcpyHostToDevice));
+    p->wall_seg_host.assign(segments, segments + 4 * (size_t)count);
+    p->wall_hw_host.assign(halfwidths, halfwidths + (size_t)count);
+    p->n_walls = count;
+    p->wall_gen = next_generation();
+  }
   return MPPI_OK;
 }
 

@@ -27,6 +27,21 @@
 //                                    at the goal
 // and after the last chunk wave 1 adds the terminal term and the T control-cost terms as k_rollout_barebone does.
 // When every rollout of the tile has reached the goal the workgroup stops (what is left of the horizon adds nothing).
+//
+// WALLS (mppi_planner_set_walls): one more source of hits for the count waves, nothing else.  A wall is a segment A -> B
+// with a half-width h >= 0 (float32); step t moves the robot from P (the position before the step, x0 for t = 0) to Q, and
+// it hits the wall iff the distance between the closed segments PQ and AB is <= h: a step that jumps a thin wall is a hit
+// (no tunnelling).  crowd_wall_hit is the test: division-free, every operation in double on the widened float32 inputs, no
+// fma -- tests/wall_model.py is the same arithmetic in numpy, and tests/test_wall_model.py compares it with exact rational
+// arithmetic.  A wall hit counts like a disc hit: it goes into the same cnts[step][lane], and the cost wave adds obs_cost
+// once more.  The counter that owns a step goes on through the walls after the step's discs, 64 walls at a time: every lane
+// loads one wall and forms its constants (d = B - A, d.d, h*h), the tests read them lane by lane as wave-uniform values.
+// The counters need P as well as Q, and the position before a chunk's first step lies in the buffer the walker is
+// overwriting in that very interval -- so with WALLS a position buffer has C + 1 slots per lane: the walker stores the
+// chunk's entry position (x0 ahead of chunk 0) in slot 0 and the post-step positions behind it.
+// The walls are static and shared by the problems of a batch (one building, many robots): per-problem wall sets and walls
+// that move are not built.  WALLS = false is the kernel as it was: same arguments, same LDS layout, and -- compared in the compiler's gfx950
+// assembly, all twelve forms -- the same instructions.
 #pragma once
 #include "rollout_kernels.h"
 
@@ -35,10 +50,18 @@ namespace mppi {
 constexpr int kCrowdChunkMax = 16;   // steps per chunk at the most (the walker keeps a chunk's noise in registers)
 constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
 // dynamic LDS: [T] double2 control ratios | [2][C][64] double goal distance | [2][C][64] float2 position |
-// [2][C][64] int hits | two "tile done" words
-__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C) {
-  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * (sizeof(double) + sizeof(float2) + sizeof(int)) + 2 * sizeof(int);
+// [2][C][64] int hits | two "tile done" words.  walls: [2][C + 1][64] positions (slot 0: the chunk's entry position)
+__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false) {
+  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * (sizeof(double) + sizeof(int)) +
+         (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int);
 }
+
+// The walls of a launch (WALLS): seg[k] = (ax, ay, bx, by), halfwidth[k]; shared by every problem of a batch.
+struct CrowdWalls {
+  const float4* seg;
+  const float* halfwidth;
+  int count;
+};
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -47,11 +70,45 @@ __device__ __forceinline__ double crowd_lane_f64(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
+// near(X; U, dU, LL): is the point X = U + (wx, wy) within sqrt(hh) of the segment U -> U + dU, LL = dU.dU?  By the sign
+// of the projection s: before U, past U + dU, or beside the segment (squared cross product against hh * LL; no division).
+// A degenerate segment (dU = 0) has s = 0: the first branch.
+__device__ __forceinline__ bool crowd_near(double wx, double wy, double ux, double uy, double LL, double hh) {
+  const double s = wx * ux + wy * uy;
+  if (s <= 0.0) return wx * wx + wy * wy <= hh;
+  if (s >= LL) {
+    const double vx = wx - ux, vy = wy - uy;
+    return vx * vx + vy * vy <= hh;
+  }
+  const double c = wx * uy - wy * ux;
+  return c * c <= hh * LL;
+}
+
+// Does the step P -> Q hit the wall A -> B (d = B - A, LLd = d.d, hh = h * h)?  The segments cross (strictly opposite
+// signs of the orientations, both ways) or an endpoint of one is within h of the other.
+__device__ __forceinline__ bool crowd_wall_hit(double px, double py, double qx, double qy, double ax, double ay, double bx,
+                                               double by, double dx, double dy, double LLd, double hh) {
+  const double ex = qx - px, ey = qy - py, LLe = ex * ex + ey * ey;
+  const double pax = px - ax, pay = py - ay, qax = qx - ax, qay = qy - ay;  // P - A, Q - A
+  const double apx = ax - px, apy = ay - py, bpx = bx - px, bpy = by - py;  // A - P, B - P
+  const double o1 = dx * pay - dy * pax, o2 = dx * qay - dy * qax;
+  const double o3 = ex * apy - ey * apx, o4 = ex * bpy - ey * bpx;
+  const bool crossing = ((o1 > 0.0 && o2 < 0.0) || (o1 < 0.0 && o2 > 0.0)) && ((o3 > 0.0 && o4 < 0.0) || (o3 < 0.0 && o4 > 0.0));
+  return crossing || crowd_near(pax, pay, dx, dy, LLd, hh) || crowd_near(qax, qay, dx, dy, LLd, hh) ||
+         crowd_near(apx, apy, ex, ey, LLe, hh) || crowd_near(bpx, bpy, ex, ey, LLe, hh);
+}
+
 // obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
+__device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
+
+// WallArgs: nothing (WALLS = false: the kernel's arguments are what they were) or one CrowdWalls (WALLS = true).
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
-    const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch) {
+    const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch, WallArgs... wall_args) {
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0), "WALLS: one CrowdWalls argument; else none");
+  [[maybe_unused]] const CrowdWalls walls = crowd_walls_of(wall_args...);
   extern __shared__ double2 uos[];
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, NC = ((int)blockDim.x >> 6) - 2;
   if (P.ktime && threadIdx.x == 0) P.ktime[blockIdx.x] = (unsigned long long)wall_clock64();  // (one slot per tile)
@@ -66,8 +123,10 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   }
   const int T = P.n_steps, K = P.n_obstacles;
   double* nd2s = reinterpret_cast<double*>(uos + T);
+  constexpr int kEntry = WALLS ? 1 : 0;  // position slots ahead of a chunk's first step
+  const int CP = C + kEntry;
   float2* poss = reinterpret_cast<float2*>(nd2s + 2 * C * 64);
-  int* cnts = reinterpret_cast<int*>(poss + 2 * C * 64);
+  int* cnts = reinterpret_cast<int*>(poss + 2 * CP * 64);
   int* tile_done = cnts + 2 * C * 64;  // [2], used in turn: a wave still looks at one while wave 1 writes the other
   if (threadIdx.x < 2) tile_done[threadIdx.x] = 0;
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
@@ -98,7 +157,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         float2 e_nxt[kCrowdChunkMax];
 #pragma unroll
         for (int j = 0; j < kCrowdChunkMax; ++j) e_nxt[j] = col[(size_t)min(c0 + C + j, T - 1) * 64];
-        float2* out = poss + (size_t)((ph & 1) * C) * 64 + lane;
+        float2* out = poss + (size_t)((ph & 1) * CP + kEntry) * 64 + lane;
+        if constexpr (WALLS) out[-64] = make_float2(x, y);  // where the chunk's first step starts
 #pragma unroll
         for (int j = 0; j < kCrowdChunkMax; ++j) {
           if (j < cl) {
@@ -135,6 +195,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
       if (c >= 0 && c < n_chunks) {  // ---- count chunk ph - 1
         const int c0 = c * C, cl = min(C, T - c0);
         const size_t at = (size_t)((c & 1) * C) * 64 + lane;
+        const size_t atp = (size_t)((c & 1) * CP + kEntry) * 64 + lane;  // poss[atp + j * 64]: the position after step c0 + j
         // this lane's disc of the tile [base, base + 64) as step c0 + j sees it; past the problem's last disc: a disc
         // nobody can touch (k_rollout_barebone's far slot)
         auto load_disc = [&](int j, int base, float2& op, double& rr) {
@@ -148,6 +209,24 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
           }
           rr = (double)r * (double)r;
         };
+        // this lane's wall of the tile [wbase, wbase + 64) with its constants; past the last wall: a wall nobody can touch.
+        // The walls do not change with the step: the first tile is loaded once per chunk
+        [[maybe_unused]] auto load_wall = [&](int wbase, float4& sg, double& dx, double& dy, double& LLd, double& hh) {
+          const int k = wbase + lane;
+          sg = make_float4(1e18f, 1e18f, 1e18f, 1e18f);
+          float h = 0.0f;
+          if (k < walls.count) {
+            sg = walls.seg[k];
+            h = walls.halfwidth[k];
+          }
+          dx = (double)sg.z - (double)sg.x;
+          dy = (double)sg.w - (double)sg.y;
+          LLd = dx * dx + dy * dy;
+          hh = (double)h * (double)h;
+        };
+        [[maybe_unused]] float4 sg0;
+        [[maybe_unused]] double dx0, dy0, LLd0, hh0;
+        if constexpr (WALLS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
         int j = wave - 2, base = 0, hits = 0;
         float2 op;
         double rr;
@@ -158,7 +237,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
           float2 op_nxt;
           double rr_nxt;
           load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
-          const float2 pos = poss[at + j * 64];
+          const float2 pos = poss[atp + j * 64];
           const int kt = min(64, K - base);
           for (int l0 = 0; l0 < kt; l0 += 4) {
 #pragma unroll
@@ -171,6 +250,26 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             }
           }
           if (nj != j) {  // the step's last tile
+            if constexpr (WALLS) {  // ... then the walls, against the step's segment P -> Q
+              const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
+              const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+              float4 sg = sg0;
+              double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
+              for (int wbase = 0; wbase < walls.count; wbase += 64) {
+                float4 sg_nxt;
+                double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                const int wt = min(64, walls.count - wbase);
+                for (int l = 0; l < wt; ++l) {
+                  const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                  const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                  hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                         crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                              ? 1 : 0;
+                }
+                sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+              }
+            }
             cnts[at + j * 64] = hits;
             nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
             hits = 0;
