@@ -272,14 +272,38 @@ int mppi_planner_get_crowd(mppi_planner* p, int* on);
  * not stop a rollout, and a position inside a wall is counted at the step that ends there and at
  * the step that starts there.  The test is division-free and runs in double on the widened
  * float32 inputs (rollout_crowd_kernel.h, crowd_wall_hit; tests/wall_model.py is its numpy form).
- * The walls are static and shared by every problem of a batched handle; per-problem wall sets and
- * walls that move are not provided.  A handle that holds walls launches
+ * These walls are static and shared by every problem of a batched handle (walls that move and
+ * per-problem sets: mppi_planner_set_wall_tracks below).  A handle that holds walls launches
  * k_rollout_barebone_crowd's WALLS form whatever its disc count (mppi_planner_describe_last_rollout
  * ends in " walls=<count>"), and mppi_planner_set_crowd(p, 0) returns MPPI_ERR_INVALID until they
  * are cleared.  count = 0 clears them (segments, halfwidths ignored).  Unchanged arrays cost a
  * comparison; a change drops the captured graphs.  MPPI_ERR_INVALID for a map mode, a handle that
  * is not in crowd mode, a negative or non-finite half-width, or a non-finite endpoint. */
 int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* halfwidths, int count);
+
+/* MPPI_MODE_BAREBONE in crowd mode only: walls that move, and a wall set per problem.  count = 1:
+ * one set for every problem; count = B: one per problem, wall_counts[b] >= 0 walls each; the sets
+ * lie one after the other in problem order, segments (sum W_b, rows, 4) float32 -- ax ay bx by --
+ * and halfwidths (sum W_b) float32, static per wall.  Row j of a wall is the segment it occupies
+ * during control interval j, from j*dt to (j+1)*dt after "now".  Step t of a rollout is interval
+ * s + t -- s: the problem's track offset (mppi_planner_set_track_offsets; one "now" per problem,
+ * shared with the disc tracks) -- and is tested as mppi_planner_set_walls describes against row
+ * min(s + t, rows - 1) of every wall of its problem.  (A disc row is an instant: the post-step
+ * position meets row s + t + 1.  Each kind clamps against its own row count.)  rows = 1, or equal
+ * rows, is a static wall to the bit.  A wall that itself jumps over the robot between two rows is
+ * seen only if its rows are sweeps of the wall's motion; the sweep of a translating segment, a
+ * parallelogram, is not provided.
+ * While a handle holds such a set, the walls of mppi_planner_set_walls rest; count = 0 clears it
+ * and they apply again.  The launches are k_rollout_barebone_crowd's CrowdWallTracks form
+ * (mppi_planner_describe_last_rollout ends in " walls=<largest count> wall_rows=<rows>"),
+ * mppi_planner_closed_loop advances s with every control step when rows > 1, and
+ * mppi_planner_set_crowd(p, 0) returns MPPI_ERR_INVALID until the set is cleared.  Unchanged
+ * arrays cost a comparison; a change drops the captured graphs and, when rows > 1, sets every
+ * offset to 0 (clearing does so unless disc tracks are held).  MPPI_ERR_INVALID -- the handle
+ * keeps what it had -- for a map mode, a handle that is not in crowd mode, rows < 1, a negative
+ * count, count not 0 / 1 / B, a negative or non-finite half-width, or a non-finite endpoint. */
+int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_counts, int rows,
+                                 const float* segments, const float* halfwidths);
 
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);

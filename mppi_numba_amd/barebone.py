@@ -18,8 +18,15 @@ step in 64 KiB of LDS: 39 moving discs at 100 steps); same results bit for bit.
 Walls (crowd mode only): params['wall_segments'] (W, 2, 2), [[ax, ay], [bx, by]] per wall, and params['wall_halfwidth'],
 a scalar or (W,).  Step t of a rollout moves the robot from P to Q (P of step 0 is x0); it hits a wall iff the distance
 between the closed segments PQ and AB is <= the half-width -- a step that jumps a thin wall is a hit -- and every hit adds
-obs_penalty once, like a disc hit of that step.  Static, and shared by the problems of an MPPI_Batch.  polyline_walls()
-turns a room outline into segments.
+obs_penalty once, like a disc hit of that step.  polyline_walls() turns a room outline into segments.
+
+Walls that move: params['wall_tracks'] (W, L, 2, 2) in place of 'wall_segments' gives every wall L segments, row j the
+segment it occupies during control interval j, from j*dt to (j+1)*dt after "now".  Step t of a rollout is interval
+track_offset + t and is tested against row min(track_offset + t, L - 1): a wall row is an interval where a disc row is an
+instant, and each kind of track clamps against its own row count.  The half-widths stay static per wall.  A wall that itself
+jumps over the robot between two rows is seen only if its rows are sweeps of its motion (swept_walls() makes those of a
+disc; the sweep of a translating segment, a parallelogram, is not provided).  constant_velocity_walls() makes the rows of
+walls that keep their velocity.  MPPI_Batch.set_wall_sets() gives every problem of a batch its own walls or wall tracks.
 """
 import copy
 import ctypes as C
@@ -85,6 +92,37 @@ def constant_velocity_tracks(positions, velocities, dt, rows):
     return np.ascontiguousarray((pos + vel * times).astype(np.float32))
 
 
+def constant_velocity_walls(segments, velocities, dt, rows, at=0.5):
+    """(W, rows, 2, 2) float32 wall tracks of walls that keep their velocity: row j is the wall translated by
+    velocities * ((j + at) * dt) -- at = 0.5: where it is in the middle of control interval j -- evaluated in float64 and
+    rounded once to float32 (at = 0: row 0 is float32(segments)).  segments (W, 2, 2), velocities (W, 2).  A row is tested
+    where it lies: a wall fast enough to jump over the robot within one interval is not seen."""
+    rows = int(rows)
+    assert rows >= 1, "a track has at least one row"
+    seg = np.asarray(segments, dtype=np.float64).reshape(-1, 1, 2, 2)
+    vel = np.asarray(velocities, dtype=np.float64).reshape(-1, 1, 1, 2)
+    assert len(seg) == len(vel), "segments and velocities differ in length"
+    times = ((np.arange(rows, dtype=np.float64) + float(at)) * float(dt)).reshape(1, rows, 1, 1)
+    return np.ascontiguousarray((seg + vel * times).astype(np.float32))
+
+
+def swept_walls(tracks):
+    """(K, max(L - 1, 1), 2, 2) float32 wall tracks from (K, L, 2) disc tracks: row j is the segment [c_j, c_{j+1}] the
+    disc's centre covers during control interval j (L = 1: the degenerate segment [c_0, c_0]).  With half-width
+    r_other + r_own it is the capsule another robot sweeps in that interval, tested against the segment this robot covers
+    in the same interval -- which closes the hole of the disc tracks, whose rows are instants: two robots that swap places
+    within one control step pass each other unseen there.  Conservative: two bodies that move linearly within the
+    interval and come within the half-width of each other at some instant of it always hit (their positions at that
+    instant lie on the two segments), and so do some near misses -- bodies that pass the same place at different instants
+    of the interval."""
+    tr = _f32(tracks)
+    if tr.ndim != 3 or tr.shape[2] != 2 or tr.shape[1] < 1:
+        raise ValueError("tracks have shape (K, L, 2) with L >= 1, got {}".format(tr.shape))
+    starts = tr[:, :-1] if tr.shape[1] > 1 else tr
+    ends = tr[:, 1:] if tr.shape[1] > 1 else tr
+    return np.ascontiguousarray(np.stack([starts, ends], axis=2), dtype=np.float32)
+
+
 def polyline_walls(points, closed=False):
     """(W, 2, 2) float32 wall segments [[ax, ay], [bx, by]] along a polyline of (P, 2) points: W = P - 1, or P with
     closed=True (a polygon: the last point is joined to the first; fewer than three points close nothing).  Fewer than two
@@ -101,6 +139,10 @@ def polyline_walls(points, closed=False):
 
 def _is_track_set(obstacle_set):
     return np.asarray(obstacle_set[0]).ndim == 3
+
+
+def _is_wall_track_set(wall_set):
+    return np.asarray(wall_set[0]).ndim == 4
 
 
 class MPPI_Numba(object):
@@ -132,6 +174,9 @@ class MPPI_Numba(object):
         self._tracks_from_params = False  # ... and whether they are the tracks of params['obstacle_tracks']
         self._own_tracks = False          # MPPI_Batch: per-problem tracks are set (they win over params')
         self._walls_key = ()  # what the device's wall arrays hold (): none
+        self._wall_tracks_key = None  # the wall tracks of params['wall_tracks'] the library holds (None: none)
+        self._own_walls = False       # MPPI_Batch: per-problem wall sets are set (they win over the walls of params)
+        self._wall_rows = 0           # rows of the wall tracks held, whoever set them (0: none, 1: static sets)
         self.reset()
 
     def __del__(self):
@@ -186,6 +231,21 @@ class MPPI_Numba(object):
     def _hand_over_walls(self, p):
         """params['wall_segments'] / ['wall_halfwidth']: handed over when they have changed, cleared when the keys have
         gone.  Without crowd mode the library refuses them (MppiError)."""
+        if "wall_tracks" in p:
+            if "wall_segments" in p:
+                raise ValueError("params hold both 'wall_segments' and 'wall_tracks': walls are static or have tracks, "
+                                 "give one of the two")
+            tr, hw = np.asarray(p['wall_tracks']), np.asarray(p.get('wall_halfwidth', 0.0))
+            key = (tr.dtype.str, tr.shape, tr.tobytes(), hw.dtype.str, hw.shape, hw.tobytes())
+            if tr.ndim != 4:
+                raise ValueError("params['wall_tracks'] has shape (W, L, 2, 2), got {}".format(tr.shape))
+            if key != self._wall_tracks_key and not self._own_walls:
+                self._hand_over_wall_tracks([(tr, hw)], "params['wall_tracks']")
+                self._wall_tracks_key = key
+        elif self._wall_tracks_key is not None:  # (the params no longer hold wall tracks)
+            if not self._own_walls:
+                self._hand_over_wall_tracks(None)
+            self._wall_tracks_key = None
         if "wall_segments" not in p:
             if self._walls_key != ():
                 _lib.call("mppi_planner_set_walls", self._handle, None, None, 0)
@@ -204,8 +264,44 @@ class MPPI_Numba(object):
         _lib.call("mppi_planner_set_walls", self._handle, _lib.ptr(segs, C.c_float), _lib.ptr(half, C.c_float), len(segs))
         self._walls_key = key
 
+    def _hand_over_wall_tracks(self, sets, what="wall set"):
+        """sets: one (tracks (W, L, 2, 2) or segments (W, 2, 2), half-widths: a scalar or (W,)) pair for every problem, or
+        one per problem; None clears, and the walls of mppi_planner_set_walls apply again."""
+        if sets is None:
+            _lib.call("mppi_planner_set_wall_tracks", self._handle, 0, None, 0, None, None)
+            self._wall_rows = 0
+            self._fetch_track_offset()  # (walls that moved have gone: row 0 is "now", unless disc tracks count the rows)
+            return
+        segs, halves, rows = [], [], None
+        for b, (tr, hw) in enumerate(sets):
+            tr, hw = np.asarray(tr), np.asarray(hw)
+            if tr.ndim == 3:  # a static set: tracks of one row
+                tr = tr.reshape(len(tr), 1, *tr.shape[1:])
+            if tr.ndim != 4 or (tr.size and tr.shape[2:] != (2, 2)):
+                raise ValueError("{} {}: shape (W, L, 2, 2) -- or (W, 2, 2) for static walls --, got {}".format(
+                    what, b, np.asarray(sets[b][0]).shape))
+            if tr.shape[1] < 1:
+                raise ValueError("{} {}: a wall track has at least one row (L = 0)".format(what, b))
+            if rows not in (None, tr.shape[1]):
+                raise ValueError("{} {}: {} rows, other sets of this call have {}".format(what, b, tr.shape[1], rows))
+            rows = tr.shape[1]
+            if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(tr)):
+                raise ValueError("{} {}: the half-width is a scalar or has shape ({},), got {}".format(what, b, len(tr), hw.shape))
+            segs.append(_f32(tr).reshape(-1, 4))
+            halves.append(np.broadcast_to(_f32(hw), (len(tr),)))
+        counts = np.ascontiguousarray([len(h) for h in halves], dtype=np.int32)
+        seg_all = np.ascontiguousarray(np.concatenate(segs), dtype=np.float32)
+        half_all = np.ascontiguousarray(np.concatenate(halves), dtype=np.float32)
+        _lib.call("mppi_planner_set_wall_tracks", self._handle, len(sets), _lib.ptr(counts, C.c_int), int(rows),
+                  _lib.ptr(seg_all, C.c_float), _lib.ptr(half_all, C.c_float))
+        self._wall_rows = int(rows)
+        self._fetch_track_offset()  # (new walls that move: row 0 is "now"; a set of one row is static and leaves it alone)
+
     def _tracks_on(self):
         return self._tracks_from_params or self._own_tracks
+
+    def _wall_tracks_on(self):
+        return self._wall_rows > 1
 
     def _hand_over_tracks(self, sets):
         """sets: one (tracks (K, L, 2), radii (K,)) pair for every problem, or one per problem; None clears."""
@@ -358,7 +454,7 @@ class MPPI_Numba(object):
         self._advance_tracks(num_shifts)
 
     def _advance_tracks(self, num_shifts):
-        if self._tracks_on():  # num_shifts control steps later "now" is that many rows further
+        if self._tracks_on() or self._wall_tracks_on():  # num_shifts control steps later "now" is that many rows further
             self.set_track_offset(self._track_offset.astype(np.int64) + int(num_shifts))
 
     def shift_optimal_control_sequence(self, u_cur, num_shifts=1):
@@ -490,6 +586,7 @@ class MPPI_Batch(MPPI_Numba):
         self.x0s = None
         self.goals = None
         self.obstacle_sets = None
+        self.wall_sets = None
         super().__init__(cfg)
 
     def reset(self):
@@ -497,7 +594,7 @@ class MPPI_Batch(MPPI_Numba):
         self.u_seq0 = np.zeros((self.num_instances, self.num_steps, 2), dtype=np.float32)
 
     # ------------------------------------------------------------------ task set-up
-    def setup(self, params, x0s=None, goals=None, obstacle_sets=None):
+    def setup(self, params, x0s=None, goals=None, obstacle_sets=None, wall_sets=None):
         if x0s is None:
             x0s = np.tile(np.asarray(params["x0"], dtype=np.float32), (self.num_instances, 1))
         if goals is None:
@@ -508,6 +605,7 @@ class MPPI_Batch(MPPI_Numba):
         self.set_params(params)
         self.set_instances(x0s, goals)
         self.set_obstacle_sets(obstacle_sets)
+        self.set_wall_sets(wall_sets)
 
     def set_instances(self, x0s, goals=None):
         """(B,3) start states and (B,2) goals (goals=None keeps the current ones)."""
@@ -558,6 +656,29 @@ class MPPI_Batch(MPPI_Numba):
         _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, self.num_instances,
                   _lib.ptr(counts, C.c_int), _lib.ptr(pos_all, C.c_float), _lib.ptr(rad_all, C.c_float))
         self.obstacle_sets = [(p.copy(), r.copy()) for p, r in zip(pos, rad)]
+
+    def set_wall_sets(self, sets):
+        """One wall set per problem (crowd mode): a list of B (segments (W_b, 2, 2), half-width: a scalar or (W_b,)) pairs,
+        W_b >= 0 -- or None: every problem has the shared walls of params again.  A set whose first element is 4-D,
+        (W_b, Lw, 2, 2), is a set of wall tracks (Lw common to the sets of a call); one call is all static or all tracks.
+        Per-problem sets win over the walls of params.  New tracks make row 0 "now"; unchanged ones leave it alone."""
+        if sets is None:
+            if self._own_walls:
+                self._hand_over_wall_tracks(None)  # (shared wall tracks of the params are handed over again)
+                self._own_walls, self._wall_tracks_key = False, None
+            self.wall_sets = None
+            return
+        assert len(sets) == self.num_instances, "one wall set per problem"
+        kinds = {_is_wall_track_set(s) for s in sets}
+        if len(kinds) > 1:
+            raise ValueError("wall sets mix static sets and track sets: one call is all static or all tracks")
+        held = [(_f32(np.asarray(seg)).copy(), _f32(np.asarray(hw)).copy()) for seg, hw in sets]
+        if self._own_walls and self.wall_sets is not None and all(
+                np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(held, self.wall_sets)):
+            return  # (unchanged: "now" stays where it is)
+        self._hand_over_wall_tracks(list(sets))
+        self._own_walls, self._wall_tracks_key = True, None
+        self.wall_sets = held
 
     def check_solve_conditions(self):
         if self.x0s is None:

@@ -254,6 +254,21 @@ struct mppi_planner {
   int n_walls = 0;
   uint64_t wall_gen = 0;
   std::vector<float> wall_seg_host, wall_hw_host;  // what the device arrays hold
+  // walls that move and per-problem wall sets (mppi_planner_set_wall_tracks; crowd mode only): wtrk_rows segments per
+  // wall, one set for every problem (wtrk_counts_host has one entry) or one per problem, the sets one after the other.
+  // While wtrk_on the launches are the crowd kernel's CrowdWallTracks form and the static walls above rest.  wtrk_seg_rows:
+  // the segments as [row][wall] (all problems' walls side by side: a step's walls are contiguous); wtrk_range: {wall0,
+  // count} per problem (per-problem sets only).  The row that is "now" is the disc tracks' BatchInst::track_off.
+  // wtrk_gen: next_generation() at every change, 0 while off
+  bool wtrk_on = false;
+  float4* wtrk_seg_rows = nullptr;
+  float* wtrk_hw = nullptr;
+  int2* wtrk_range = nullptr;
+  int wtrk_rows = 0;
+  int wtrk_max = 0;  // the largest problem's count
+  uint64_t wtrk_gen = 0;
+  std::vector<int> wtrk_counts_host;
+  std::vector<float> wtrk_seg_host, wtrk_hw_host;  // what was handed over ([wall][row])
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

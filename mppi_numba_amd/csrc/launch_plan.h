@@ -67,7 +67,8 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.n_obstacles = p->n_obstacles;
   // (discs that move: a batch reads each problem's offset from its BatchInst, as it reads the start state)
   d.track_rows = p->trk_on ? p->trk_rows : 0;
-  d.track_off = p->trk_on && !p->inst_set ? p->inst_host[0].track_off : 0;
+  // (wall tracks share the offset: rollout_crowd_kernel.h clamps it against the walls' own row count)
+  d.track_off = (p->trk_on || p->wtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
   d.inst = p->inst_set ? p->inst_dev : nullptr;
   d.inst_tiles = p->inst_tiles;
   d.n_inst = p->n_inst;
@@ -1048,15 +1049,25 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
   *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
 }
 
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS>
+// WALLS: 0 none, 1 static walls shared by the problems (CrowdWalls), 2 wall tracks / per-problem sets (CrowdWallTracks)
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, int WALLS>
 static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, WALLS);  // the size launched
-  if constexpr (WALLS)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, WALLS != 0);  // the size launched
+  if constexpr (WALLS != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
-  if constexpr (WALLS) {
+  if constexpr (WALLS == 2) {
+    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks>;
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // (the classic single launch has one problem: the first set, which starts at wall 0)
+    const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
+    const CrowdWallTracks walls{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
+                                own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size()};
+    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls);
+  } else if constexpr (WALLS == 1) {
     auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls>;
     if (lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1072,16 +1083,19 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
                     " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
                     (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
                     (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                    (WALLS ? " walls=" + std::to_string(p->n_walls) : std::string());
+                    (WALLS == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
+                    (WALLS == 2 ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
 
-// A handle that holds walls (mppi_planner_set_walls) launches the WALLS form, whatever its discs are.
+// A handle that holds walls (mppi_planner_set_walls) launches the WALLS form, whatever its discs are; wall tracks and
+// per-problem sets (mppi_planner_set_wall_tracks) come first: while they are held the static walls rest.
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
 static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
-  if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, true>(p, d, pos, rad, pitch);
-  return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, false>(p, d, pos, rad, pitch);
+  if (p->wtrk_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2>(p, d, pos, rad, pitch);
+  if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1>(p, d, pos, rad, pitch);
+  return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0>(p, d, pos, rad, pitch);
 }
 
 // The disc set a crowd launch reads: the tracks ([row][disc] copy), a problem's own static set, or the shared one.
@@ -1104,7 +1118,7 @@ static int launch_rollout_barebone_crowd(mppi_planner* p, DevParams d, bool rot)
 // Crowd mode: does this launch go to the crowd kernel?  kmax: the largest problem's disc count; default_lds: what the
 // default form would hold in LDS.  Walls are the crowd kernel's alone: a handle that holds any always goes there.
 static bool crowd_launch(const mppi_planner* p, int kmax, size_t default_lds) {
-  return p->crowd && (p->n_walls > 0 || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
+  return p->crowd && (p->n_walls > 0 || p->wtrk_on || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
 }
 
 template <bool EXACT, bool BATCHED>
@@ -1609,7 +1623,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1626,6 +1640,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.ang_maps = p->packed.ang_maps; sig.ang_grid = p->packed.ang_grid;
   sig.epoch_bias = p->noise_epoch - p->bumps_launched;
   sig.wall_gen = p->wall_gen;  // (the walls' generation, not their address: a new set may land where the old one was)
+  sig.wtrk_gen = p->wtrk_gen;
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

@@ -517,6 +517,9 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->trk_r);
   dev_free(p->wall_seg);
   dev_free(p->wall_hw);
+  dev_free(p->wtrk_seg_rows);
+  dev_free(p->wtrk_hw);
+  dev_free(p->wtrk_range);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -917,6 +920,8 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   if (!on) {
     REQUIRE(p->n_walls == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
+    REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds wall tracks, which only the crowd kernel tests (clear them first)");
     REQUIRE(!p->trk_on || barebone_track_lds(T, p->trk_max) <= 64 * 1024, MPPI_ERR_INVALID,
             "crowd mode stays on: the disc tracks held (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
             p->trk_max, T, barebone_track_lds(T, p->trk_max));
@@ -972,6 +977,102 @@ extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, co
     p->wall_hw_host.assign(halfwidths, halfwidths + (size_t)count);
     p->n_walls = count;
     p->wall_gen = next_generation();
+  }
+  return MPPI_OK;
+}
+
+// Walls that move, and a wall set per problem (include/mppi_hip.h): crowd mode only, like the static walls.  `rows`
+// segments per wall, one set shared by every problem (count == 1) or one per problem (count == B), the sets one after the
+// other, each [wall][row].  The device keeps them [row][wall] -- a step's walls are contiguous -- with {wall0, count} per
+// problem beside them.  Unchanged arrays cost a comparison; a change synchronises, reallocates, takes a new generation,
+// drops the captured graphs and, for walls that move (rows > 1), makes row 0 "now" again.  Every argument is checked
+// before anything the handle holds is touched.
+extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_counts, int rows,
+                                            const float* segments, const float* halfwidths) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "wall tracks belong to the barebone mode (mode %d)", p->cfg.mode);
+  if (wall_counts == nullptr) count = 0;
+  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
+          "count %d: must be 0, 1 (one set for every problem) or num_instances %d", count, p->B);
+  long total = 0;
+  int wmax = 0;
+  if (count > 0) {
+    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+            "wall tracks need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
+    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a wall track has at least one row", rows);
+    for (int b = 0; b < count; ++b) {
+      REQUIRE(wall_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative wall count %d", b, wall_counts[b]);
+      total += wall_counts[b];
+      wmax = std::max(wmax, wall_counts[b]);
+    }
+    REQUIRE(total <= (1L << 24) && total * (long)rows <= (1L << 28), MPPI_ERR_INVALID, "too many wall track rows (%ld walls x %d)", total, rows);
+    REQUIRE(total == 0 || (segments && halfwidths), MPPI_ERR_INVALID, "NULL segments or halfwidths");
+    for (long k = 0; k < total; ++k) {
+      const float h = halfwidths[k];
+      REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "wall %ld: half-width %g is negative or not finite", k, (double)h);
+    }
+    for (size_t i = 0; i < 4 * (size_t)total * (size_t)rows; ++i)
+      REQUIRE(std::isfinite(segments[i]), MPPI_ERR_INVALID, "wall %zu, row %zu: an endpoint coordinate is not finite",
+              i / 4 / (size_t)rows, i / 4 % (size_t)rows);
+  }
+  const size_t n_seg = (size_t)total * (size_t)rows;
+  if (count == 0 ? !p->wtrk_on
+                 : (p->wtrk_on && rows == p->wtrk_rows && (size_t)count == p->wtrk_counts_host.size() &&
+                    memcmp(wall_counts, p->wtrk_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
+                    (total == 0 || (memcmp(segments, p->wtrk_seg_host.data(), sizeof(float) * 4 * n_seg) == 0 &&
+                                    memcmp(halfwidths, p->wtrk_hw_host.data(), sizeof(float) * (size_t)total) == 0))))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  // the new device arrays first: a failed allocation or copy leaves the handle with what it had
+  float4* seg_rows = nullptr;
+  float* hw = nullptr;
+  int2* range = nullptr;
+  if (count > 0) {
+    std::vector<float4> by_row(std::max<size_t>(1, n_seg));
+    for (size_t k = 0; k < (size_t)total; ++k)
+      for (size_t r = 0; r < (size_t)rows; ++r) {
+        const float* s = segments + 4 * (k * (size_t)rows + r);
+        by_row[r * (size_t)total + k] = make_float4(s[0], s[1], s[2], s[3]);
+      }
+    std::vector<int2> ranges((size_t)count);
+    for (int b = 0, k0 = 0; b < count; k0 += wall_counts[b], ++b) ranges[(size_t)b] = make_int2(k0, wall_counts[b]);
+    auto upload = [&]() -> int {
+      TRY(dev_alloc(&seg_rows, by_row.size()));
+      TRY(dev_alloc(&hw, std::max<size_t>(1, (size_t)total)));
+      TRY(dev_alloc(&range, ranges.size()));
+      HIP_TRY(hipMemcpy(seg_rows, by_row.data(), sizeof(float4) * by_row.size(), hipMemcpyHostToDevice));
+      if (total > 0) HIP_TRY(hipMemcpy(hw, halfwidths, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(range, ranges.data(), sizeof(int2) * ranges.size(), hipMemcpyHostToDevice));
+      return MPPI_OK;
+    };
+    const int rc = upload();
+    if (rc != MPPI_OK) {
+      dev_free(seg_rows);
+      dev_free(hw);
+      dev_free(range);
+      return rc;
+    }
+  }
+  dev_free(p->wtrk_seg_rows);
+  dev_free(p->wtrk_hw);
+  dev_free(p->wtrk_range);
+  p->wtrk_seg_rows = seg_rows;
+  p->wtrk_hw = hw;
+  p->wtrk_range = range;
+  const bool moved = p->wtrk_rows > 1 || (count > 0 && rows > 1);  // (a set of one row is static: it leaves "now" alone)
+  p->wtrk_on = count > 0;
+  p->wtrk_rows = count > 0 ? rows : 0;
+  p->wtrk_max = wmax;
+  p->wtrk_gen = count > 0 ? next_generation() : 0;
+  p->wtrk_counts_host.assign(wall_counts, wall_counts + count);
+  p->wtrk_seg_host.assign(segments, segments + (total > 0 ? 4 * n_seg : 0));
+  p->wtrk_hw_host.assign(halfwidths, halfwidths + (total > 0 ? (size_t)total : 0));
+  drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
+  // new walls that move: row 0 is "now"; cleared: likewise unless disc tracks still count the rows
+  if (moved && (count > 0 || !p->trk_on)) {
+    for (BatchInst& I : p->inst_host) I.track_off = 0;
+    p->inst_dirty = true;
   }
   return MPPI_OK;
 }
@@ -1445,7 +1546,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.dt = dt > 0.0 ? dt : (double)p->params.dt;
     L.goal_tolerance = goal_tolerance;
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
-    L.advance_tracks = p->trk_on ? 1 : 0;
+    L.advance_tracks = p->trk_on || (p->wtrk_on && p->wtrk_rows > 1) ? 1 : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)

@@ -39,10 +39,24 @@
 // The counters need P as well as Q, and the position before a chunk's first step lies in the buffer the walker is
 // overwriting in that very interval -- so with WALLS a position buffer has C + 1 slots per lane: the walker stores the
 // chunk's entry position (x0 ahead of chunk 0) in slot 0 and the post-step positions behind it.
-// The walls are static and shared by the problems of a batch (one building, many robots): per-problem wall sets and walls
-// that move are not built.  WALLS = false is the kernel as it was: same arguments, same LDS layout, and -- compared in the compiler's gfx950
+// WALLS = false is the kernel as it was: same arguments, same LDS layout, and -- compared in the compiler's gfx950
 // assembly, all twelve forms -- the same instructions.
+//
+// WALL TRACKS (mppi_planner_set_wall_tracks): walls that move, and a wall set per problem -- a third form, selected by its
+// argument type (CrowdWallTracks in place of CrowdWalls); static shared walls launch the CrowdWalls form as before.  Every
+// wall has `rows` segments, row j the segment it occupies during control interval j (from j * dt to (j + 1) * dt after
+// "now"); step t of a rollout IS interval s + t (s: the problem's track offset, the one the disc tracks have), so it is
+// tested, with crowd_wall_hit unchanged, against row min(s + t, rows - 1) of every wall.  (A disc row is an instant, and the
+// post-step position is tested against row s + t + 1; a wall row is an interval.  Each kind clamps against its own row
+// count.)  The device copy is [row][wall], all problems' walls side by side, so a step's walls are contiguous; a problem's
+// range of a row is {wall0, count} of the range array (none: one set for every problem).  The walls now change with the
+// step, so the first tile is no longer loaded once per chunk: the counter that owns step c0 + j loads its tiles from that
+// step's row and keeps the next tile -- the first tile of its NEXT step behind a step's last -- in flight during the tests,
+// as it does with the disc tiles.  One row, or equal rows, is a static wall to the bit.  A wall that itself jumps over the
+// robot between two rows is seen only if its rows are sweeps: a row is tested where it lies.
 #pragma once
+#include <type_traits>
+
 #include "rollout_kernels.h"
 
 namespace mppi {
@@ -61,6 +75,17 @@ struct CrowdWalls {
   const float4* seg;
   const float* halfwidth;
   int count;
+};
+
+// The walls of a launch that move or differ from problem to problem (mppi_planner_set_wall_tracks): seg[row * pitch + k],
+// `pitch` walls per row (the sets of all problems side by side), halfwidth[k] static per wall.  range[b] = {wall0, count}:
+// problem b's walls within a row; nullptr: every problem has the walls [0, max_count).
+struct CrowdWallTracks {
+  const float4* seg;
+  const float* halfwidth;
+  const int2* range;
+  int max_count;  // the largest problem's count
+  int rows, pitch;
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -101,14 +126,21 @@ __device__ __forceinline__ bool crowd_wall_hit(double px, double py, double qx, 
 // obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
 __device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls) { return walls; }
+template <typename... WallArgs>
+constexpr bool kCrowdWallTracks = (std::is_same_v<WallArgs, CrowdWallTracks> || ...);
 
-// WallArgs: nothing (WALLS = false: the kernel's arguments are what they were) or one CrowdWalls (WALLS = true).
+// WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
+// shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets).
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
     const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch, WallArgs... wall_args) {
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0), "WALLS: one CrowdWalls argument; else none");
-  [[maybe_unused]] const CrowdWalls walls = crowd_walls_of(wall_args...);
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0), "WALLS: one CrowdWalls or CrowdWallTracks argument; else none");
+  constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
+  [[maybe_unused]] const auto walls = crowd_walls_of(wall_args...);
+  [[maybe_unused]] int wall0 = 0, wcount = 0;  // WTRK: this problem's walls within a row
+  if constexpr (WTRK) wcount = walls.max_count;
   extern __shared__ double2 uos[];
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, NC = ((int)blockDim.x >> 6) - 2;
   if (P.ktime && threadIdx.x == 0) P.ktime[blockIdx.x] = (unsigned long long)wall_clock64();  // (one slot per tile)
@@ -119,7 +151,14 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     obs_pos += I.disc0;
     obs_r += I.disc0;
     P.n_obstacles = I.n_discs;
-    if constexpr (TRACKS) P.track_off = I.track_off;
+    if constexpr (TRACKS || WTRK) P.track_off = I.track_off;
+    if constexpr (WTRK) {
+      if (walls.range) {
+        const int2 r = walls.range[b];
+        wall0 = r.x;
+        wcount = r.y;
+      }
+    }
   }
   const int T = P.n_steps, K = P.n_obstacles;
   double* nd2s = reinterpret_cast<double*>(uos + T);
@@ -149,6 +188,12 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   double d2 = 1e9;
   bool done = false, reached = false;
   [[maybe_unused]] const int last = P.track_rows - 1, now = min(max(P.track_off, 0), last);  // (an offset past the end: the last row)
+  // ... and the walls' "now": the same raw offset against the walls' own row count
+  [[maybe_unused]] int wlast = 0, wnow = 0;
+  if constexpr (WTRK) {
+    wlast = walls.rows - 1;
+    wnow = min(max(P.track_off, 0), wlast);
+  }
 
   for (int ph = 0; ph < n_chunks + 2; ++ph) {
     if (wave == 0) {
@@ -215,9 +260,28 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
           const int k = wbase + lane;
           sg = make_float4(1e18f, 1e18f, 1e18f, 1e18f);
           float h = 0.0f;
-          if (k < walls.count) {
-            sg = walls.seg[k];
-            h = walls.halfwidth[k];
+          if constexpr (WALLS && !WTRK) {
+            if (k < walls.count) {
+              sg = walls.seg[k];
+              h = walls.halfwidth[k];
+            }
+          }
+          dx = (double)sg.z - (double)sg.x;
+          dy = (double)sg.w - (double)sg.y;
+          LLd = dx * dx + dy * dy;
+          hh = (double)h * (double)h;
+        };
+        // WTRK: the walls change with the step -- the tile as step c0 + wj sees it: row min(wnow + c0 + wj, wlast), the
+        // problem's own range of it; the same constants, formed the same way
+        [[maybe_unused]] auto load_wall_row = [&](int wj, int wbase, float4& sg, double& dx, double& dy, double& LLd, double& hh) {
+          const int k = wbase + lane;
+          sg = make_float4(1e18f, 1e18f, 1e18f, 1e18f);
+          float h = 0.0f;
+          if constexpr (WTRK) {
+            if (wj < cl && k < wcount) {
+              sg = walls.seg[(size_t)min(wnow + c0 + wj, wlast) * (size_t)walls.pitch + (size_t)(wall0 + k)];
+              h = walls.halfwidth[wall0 + k];
+            }
           }
           dx = (double)sg.z - (double)sg.x;
           dy = (double)sg.w - (double)sg.y;
@@ -226,7 +290,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         };
         [[maybe_unused]] float4 sg0;
         [[maybe_unused]] double dx0, dy0, LLd0, hh0;
-        if constexpr (WALLS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
+        if constexpr (WTRK) load_wall_row(wave - 2, 0, sg0, dx0, dy0, LLd0, hh0);  // (the first tile of the first step owned)
+        else if constexpr (WALLS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
         int j = wave - 2, base = 0, hits = 0;
         float2 op;
         double rr;
@@ -255,19 +320,38 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
               const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
               float4 sg = sg0;
               double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
-              for (int wbase = 0; wbase < walls.count; wbase += 64) {
-                float4 sg_nxt;
-                double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
-                const int wt = min(64, walls.count - wbase);
-                for (int l = 0; l < wt; ++l) {
-                  const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                  const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                  hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                         crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                              ? 1 : 0;
+              if constexpr (WTRK) {  // this problem's walls as this step sees them
+                for (int wbase = 0; wbase < wcount; wbase += 64) {
+                  float4 sg_nxt;
+                  double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                  const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
+                  load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                  const int wt = min(64, wcount - wbase);
+                  for (int l = 0; l < wt; ++l) {
+                    const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                    const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                    hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                           crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                ? 1 : 0;
+                  }
+                  sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                 }
-                sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+                sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
+              } else {
+                for (int wbase = 0; wbase < walls.count; wbase += 64) {
+                  float4 sg_nxt;
+                  double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                  load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                  const int wt = min(64, walls.count - wbase);
+                  for (int l = 0; l < wt; ++l) {
+                    const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                    const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                    hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                           crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                ? 1 : 0;
+                  }
+                  sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+                }
               }
             }
             cnts[at + j * 64] = hits;

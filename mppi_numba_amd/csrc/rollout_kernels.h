@@ -124,7 +124,7 @@ struct BatchInst {
       int disc0, n_discs;  // barebone mode: the problem's discs are obs_pos / obs_r [disc0, disc0 + n_discs)
     };
   };
-  int track_off;  // barebone mode: the row of the problem's disc tracks that is "now" (DevParams::track_rows)
+  int track_off;  // barebone mode: the row of the problem's disc tracks (DevParams::track_rows) and wall tracks that is "now"
 };
 
 // every wave of a workgroup, before its first load of the noise (see DevParams::noise_flag).  Every wave looks once; when

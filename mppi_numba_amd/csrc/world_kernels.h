@@ -92,7 +92,7 @@ struct WorldLoop {
   // the LDS window plan of the planner (plan_lds_window): origin per problem around its start cell
   int win_active, reach, win_rows, win_cols, map_rows, map_pitch;
   double xlo, ylo, res;
-  // barebone mode with disc tracks: a control step later "now" is the tracks' next row (BatchInst::track_off)
+  // barebone mode with disc tracks or wall tracks: a control step later "now" is the tracks' next row (BatchInst::track_off)
   int advance_tracks;
 };
 
