@@ -305,6 +305,30 @@ int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* 
 int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_counts, int rows,
                                  const float* segments, const float* halfwidths);
 
+/* MPPI_MODE_BAREBONE only (any other mode: MPPI_ERR_INVALID): a goal that moves.  count = 1: one
+ * track for every problem; count = B: one per problem; xy is (count, rows, 2) float32, rows >= 1
+ * common to the call.  Row j is the goal's position at time j*dt from "now" -- an instant, like a
+ * disc row -- and "now" is the problem's track offset s (mppi_planner_set_track_offsets: one "now"
+ * per problem, shared with the disc and wall tracks).  The state after step t of a rollout is
+ * measured against row min(s + t + 1, rows - 1): the stage term dist_weight * d^2, the goal test
+ * d^2 <= goal_tolerance^2 ("reached": within the tolerance of where the goal is at that instant),
+ * the freeze and the terminal term are those of the static goal on a goal that changes with t.
+ * Past its last row the goal stays at its last place; rows = 1, or equal rows, is a static goal to
+ * the bit.  While a handle holds goal tracks, params.xgoal and the goals of
+ * mppi_planner_set_instances rest; count = 0 clears them and the static goals apply again.
+ * The default family then launches its track forms with the goal rows staged in LDS behind the disc
+ * rows (8*T bytes more; a set that no longer fits in 64 KiB goes to the crowd kernel in crowd mode
+ * and is refused with MPPI_ERR_INVALID, naming the bytes, otherwise); the crowd kernel takes the
+ * step's row by a wave-uniform load, with every wall form.  mppi_planner_describe_last_rollout ends
+ * in " goal_rows=<rows>".  mppi_planner_closed_loop advances s with every control step when
+ * rows > 1 and tests the new state against row min(s_new, rows - 1): the goal where it is at the
+ * time of the new state.  Unchanged arrays cost a comparison; a change builds the new device copy
+ * before the old one is freed (a failure leaves the handle as it was), drops the captured graphs
+ * and, when rows > 1, sets every offset to 0 (clearing does so unless disc or wall tracks are
+ * held).  MPPI_ERR_INVALID for a map mode, rows < 1, count not 0 / 1 / B or a non-finite
+ * coordinate. */
+int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows, const float* xy);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

@@ -27,6 +27,16 @@ instant, and each kind of track clamps against its own row count.  The half-widt
 jumps over the robot between two rows is seen only if its rows are sweeps of its motion (swept_walls() makes those of a
 disc; the sweep of a translating segment, a parallelogram, is not provided).  constant_velocity_walls() makes the rows of
 walls that keep their velocity.  MPPI_Batch.set_wall_sets() gives every problem of a batch its own walls or wall tracks.
+
+A goal that moves: params['goal_track'] (L, 2) in place of 'xgoal' gives the goal L positions, row j its position at time
+j*dt from "now" -- an instant, like a disc row, and the same "now": track_offset.  The state after step t of a rollout is
+measured against row min(track_offset + t + 1, L - 1): stage cost, goal test, freeze and terminal cost are the notebook's on
+a goal that changes with t, and "reached" means within goal_tolerance of where the goal is at that instant (intercept,
+rendezvous); a follower sets goal_tolerance = 0 so that nothing freezes.  Past its last row the goal stays at its last
+place; a track of one row, or of equal rows, is a static goal to the bit.  No helper is needed to make one:
+constant_velocity_tracks(p, v, dt, rows)[0] is the goal track of a target that keeps its velocity, and another robot's
+planned states[:, :2] is the goal track of a follower.  goal_now is the goal where it is now; MPPI_Batch.set_goal_tracks()
+gives every problem of a batch its own.
 """
 import copy
 import ctypes as C
@@ -74,6 +84,10 @@ class Config:
                 print("MPPI Config: Clip num_control_rollouts to be recommended min number of {}. (Recommended max={})".format(
                     rec_min_control_rollouts, rec_max_control_rollouts))
         self.num_vis_state_rollouts = max(1, min(num_vis_state_rollouts, self.num_control_rollouts))
+
+
+_TASK_VECTORS = (("x0", 3), ("xgoal", 2), ("vrange", 2), ("wrange", 2), ("u_std", 2))  # params keys -> _lib.Params arrays
+_TASK_VECTORS_GOAL_TRACK = tuple(entry for entry in _TASK_VECTORS if entry[0] != "xgoal")
 
 
 def _f32(values):
@@ -177,6 +191,9 @@ class MPPI_Numba(object):
         self._wall_tracks_key = None  # the wall tracks of params['wall_tracks'] the library holds (None: none)
         self._own_walls = False       # MPPI_Batch: per-problem wall sets are set (they win over the walls of params)
         self._wall_rows = 0           # rows of the wall tracks held, whoever set them (0: none, 1: static sets)
+        self._goal_track_key = None   # the goal track of params['goal_track'] the library holds (None: none)
+        self._own_goals = False       # MPPI_Batch: per-problem goal tracks are set (they win over params['goal_track'])
+        self._goal_tracks = None      # the goal tracks held, whoever set them: (1 or B, L, 2) float32 (None: static goals)
         self.reset()
 
     def __del__(self):
@@ -297,6 +314,69 @@ class MPPI_Numba(object):
         self._wall_rows = int(rows)
         self._fetch_track_offset()  # (new walls that move: row 0 is "now"; a set of one row is static and leaves it alone)
 
+    # ------------------------------------------------------------------ a goal that moves
+    def _hand_over_goal_tracks(self, tracks, what="goal track"):
+        """tracks: one (L, 2) goal track for every problem, or one per problem with a common L; None clears, and the
+        static goals apply again."""
+        if tracks is None:
+            _lib.call("mppi_planner_set_goal_tracks", self._handle, 0, 0, None)
+            self._goal_tracks = None
+            self._fetch_track_offset()  # (a goal that moved has gone: row 0 is "now", unless other tracks count the rows)
+            return
+        held, rows = [], None
+        for b, tr in enumerate(tracks):
+            tr = np.asarray(tr)
+            if tr.ndim != 2 or tr.shape[1] != 2:
+                raise ValueError("{} {}: shape (L, 2), got {}".format(what, b, tr.shape))
+            if tr.shape[0] < 1:
+                raise ValueError("{} {}: a goal track has at least one row (L = 0)".format(what, b))
+            if rows not in (None, tr.shape[0]):
+                raise ValueError("{} {}: {} rows, other tracks of this call have {}".format(what, b, tr.shape[0], rows))
+            rows = tr.shape[0]
+            held.append(_f32(tr))
+        if len(held) not in (1, self.num_instances):
+            raise ValueError("{} goal tracks: one for every problem, or one per problem ({})".format(len(held), self.num_instances))
+        xy = np.ascontiguousarray(np.stack(held), dtype=np.float32)
+        _lib.call("mppi_planner_set_goal_tracks", self._handle, len(held), int(rows), _lib.ptr(xy, C.c_float))
+        self._goal_tracks = xy
+        self._fetch_track_offset()  # (a new goal that moves: row 0 is "now"; a track of one row is static and leaves it alone)
+
+    def _hand_over_goal(self, p):
+        """params['goal_track']: handed over when it has changed, cleared when the key has gone."""
+        if "goal_track" in p:
+            if "xgoal" in p:
+                raise ValueError("params hold both 'xgoal' and 'goal_track': the goal is static or has a track, give one of "
+                                 "the two")
+            tr = np.asarray(p['goal_track'])
+            key = (tr.dtype.str, tr.shape, tr.tobytes())
+            if tr.ndim != 2 or tr.shape[1] != 2:
+                raise ValueError("params['goal_track'] has shape (L, 2), got {}".format(tr.shape))
+            if key != self._goal_track_key and not self._own_goals:
+                self._hand_over_goal_tracks([tr], "params['goal_track']")
+                self._goal_track_key = key
+        elif self._goal_track_key is not None:  # (the params no longer hold a goal track)
+            if not self._own_goals:
+                self._hand_over_goal_tracks(None)
+            self._goal_track_key = None
+
+    def _goal_track_on(self):
+        return self._goal_tracks is not None and self._goal_tracks.shape[1] > 1
+
+    @property
+    def goal_now(self):
+        """The goal where it is now: row min(track_offset, L - 1) of the goal track -- (2,) float32, (B, 2) for a batch --
+        or the static goal when no track is set.  The closed loop's goal test of a new state, after shift_and_update."""
+        tracks = self._goal_tracks
+        if not self._own_goals and self.params is not None:  # (params['goal_track'] may not have been handed over yet)
+            tracks = _f32(self.params['goal_track'])[None] if "goal_track" in self.params else None
+        if tracks is None:
+            if self.num_instances > 1:
+                return np.array(self.goals, dtype=np.float32)
+            return _f32(self.params['xgoal']).reshape(-1)[:2].copy()
+        rows = np.minimum(self._track_offset.astype(np.int64), tracks.shape[1] - 1)
+        now = tracks[np.arange(self.num_instances) % len(tracks), rows]
+        return now[0].copy() if self.num_instances == 1 else now.copy()
+
     def _tracks_on(self):
         return self._tracks_from_params or self._own_tracks
 
@@ -388,10 +468,15 @@ class MPPI_Numba(object):
         whole, `bench.py --workload bb` likewise.)"""
         p = self.params
         c = _lib.Params()
-        for name, count in (("x0", 3), ("xgoal", 2), ("vrange", 2), ("wrange", 2), ("u_std", 2)):
+        moving_goal = "goal_track" in p
+        if moving_goal or self._goal_track_key is not None:  # (the static goal's path pays one lookup for this)
+            self._hand_over_goal(p)
+        for name, count in _TASK_VECTORS_GOAL_TRACK if moving_goal else _TASK_VECTORS:
             src, dst = p[name], getattr(c, name)
             for i in range(count):
                 dst[i] = float(src[i])
+        if moving_goal:  # (the static goal rests: the field holds the track's first row)
+            c.xgoal[0], c.xgoal[1] = float(p['goal_track'][0][0]), float(p['goal_track'][0][1])
         c.dt = float(p['dt'])
         c.goal_tolerance = float(p['goal_tolerance'])
         c.v_post_rollout = 0.0
@@ -454,7 +539,8 @@ class MPPI_Numba(object):
         self._advance_tracks(num_shifts)
 
     def _advance_tracks(self, num_shifts):
-        if self._tracks_on() or self._wall_tracks_on():  # num_shifts control steps later "now" is that many rows further
+        # disc tracks, wall tracks or a goal track: num_shifts control steps later "now" is that many rows further
+        if self._tracks_on() or self._wall_tracks_on() or self._goal_track_on():
             self.set_track_offset(self._track_offset.astype(np.int64) + int(num_shifts))
 
     def shift_optimal_control_sequence(self, u_cur, num_shifts=1):
@@ -489,7 +575,7 @@ class MPPI_Numba(object):
             x0 = np.asarray(self.params["x0"], dtype=np.float64).reshape(1, 3) if x_init is None \
                 else np.asarray(x_init, dtype=np.float64).reshape(1, 3)
             x0_f32 = np.ascontiguousarray(x0.astype(np.float32))
-            goal = np.ascontiguousarray(np.asarray(self.params["xgoal"], dtype=np.float64).astype(np.float32)).reshape(1, 2)
+            goal = np.ascontiguousarray(np.asarray(self.goal_now, dtype=np.float64).astype(np.float32)).reshape(1, 2)
             _lib.call("mppi_planner_set_instances", self._handle, 1, _lib.ptr(x0_f32, C.c_float),
                       _lib.ptr(goal, C.c_float))
             x_init = x0
@@ -577,7 +663,8 @@ class MPPI_Batch(MPPI_Numba):
         useqs = batch.solve()                              # (B, T, 2) float32
         batch.shift_and_update(new_x0s, useqs, num_shifts=1)
 
-    Everything in `params` except 'x0', 'xgoal' (and the discs, when obstacle_sets is given) is shared."""
+    Everything in `params` except 'x0', 'xgoal' (and the discs, when obstacle_sets is given) is shared.  A goal that moves:
+    params['goal_track'] is one track for every problem, set_goal_tracks() one per problem."""
 
     def __init__(self, cfg, num_instances):
         num_instances = int(num_instances)
@@ -587,6 +674,7 @@ class MPPI_Batch(MPPI_Numba):
         self.goals = None
         self.obstacle_sets = None
         self.wall_sets = None
+        self.goal_tracks = None
         super().__init__(cfg)
 
     def reset(self):
@@ -594,18 +682,21 @@ class MPPI_Batch(MPPI_Numba):
         self.u_seq0 = np.zeros((self.num_instances, self.num_steps, 2), dtype=np.float32)
 
     # ------------------------------------------------------------------ task set-up
-    def setup(self, params, x0s=None, goals=None, obstacle_sets=None, wall_sets=None):
+    def setup(self, params, x0s=None, goals=None, obstacle_sets=None, wall_sets=None, goal_tracks=None):
         if x0s is None:
             x0s = np.tile(np.asarray(params["x0"], dtype=np.float32), (self.num_instances, 1))
-        if goals is None:
-            goals = np.tile(np.asarray(params["xgoal"], dtype=np.float32), (self.num_instances, 1))
+        if goals is None:  # (with a shared goal track and no goals: the static goals, which rest, are its first row)
+            first = params["goal_track"][0] if "goal_track" in params else params["xgoal"]
+            goals = np.tile(np.asarray(first, dtype=np.float32), (self.num_instances, 1))
         params = dict(params)
         params["x0"] = np.asarray(x0s[0]).copy()
-        params["xgoal"] = np.asarray(goals[0]).copy()
+        if "goal_track" not in params:
+            params["xgoal"] = np.asarray(goals[0]).copy()
         self.set_params(params)
         self.set_instances(x0s, goals)
         self.set_obstacle_sets(obstacle_sets)
         self.set_wall_sets(wall_sets)
+        self.set_goal_tracks(goal_tracks)
 
     def set_instances(self, x0s, goals=None):
         """(B,3) start states and (B,2) goals (goals=None keeps the current ones)."""
@@ -679,6 +770,25 @@ class MPPI_Batch(MPPI_Numba):
         self._hand_over_wall_tracks(list(sets))
         self._own_walls, self._wall_tracks_key = True, None
         self.wall_sets = held
+
+    def set_goal_tracks(self, tracks):
+        """One goal track per problem: (B, L, 2), or a list of B arrays (L, 2) with a common L -- or None: every problem
+        has its goal of `goals` again (or the shared track of params['goal_track']).  Per-problem tracks win over
+        params['goal_track'].  New tracks of more than one row make row 0 "now"; unchanged ones leave it alone."""
+        if tracks is None:
+            if self._own_goals:
+                self._hand_over_goal_tracks(None)  # (a shared track of the params is handed over again)
+                self._own_goals, self._goal_track_key = False, None
+            self.goal_tracks = None
+            return
+        if len(tracks) != self.num_instances:
+            raise ValueError("{} goal tracks for {} problems: one per problem".format(len(tracks), self.num_instances))
+        held = [_f32(np.asarray(tr)) for tr in tracks]
+        if self._own_goals and self.goal_tracks is not None and all(np.array_equal(a, b) for a, b in zip(held, self.goal_tracks)):
+            return  # (unchanged: "now" stays where it is)
+        self._hand_over_goal_tracks(list(tracks))
+        self._own_goals, self._goal_track_key = True, None
+        self.goal_tracks = held
 
     def check_solve_conditions(self):
         if self.x0s is None:

@@ -269,6 +269,16 @@ struct mppi_planner {
   uint64_t wtrk_gen = 0;
   std::vector<int> wtrk_counts_host;
   std::vector<float> wtrk_seg_host, wtrk_hw_host;  // what was handed over ([wall][row])
+  // a goal that moves (mppi_planner_set_goal_tracks): gtrk_rows positions per track, [track][row]; one track for every
+  // problem (gtrk_count == 1) or one per problem (gtrk_count == B).  While gtrk_on the rollouts measure the state after step
+  // t against row min(track_off + t + 1, gtrk_rows - 1) and params.xgoal / BatchInst::xg, yg rest; the default family
+  // launches its track forms only (static discs as tracks of one row).  gtrk_gen: next_generation() at every change, 0
+  // while off -- what the graph signature holds of the track
+  bool gtrk_on = false;
+  float2* gtrk_xy = nullptr;
+  int gtrk_rows = 0, gtrk_count = 0;
+  uint64_t gtrk_gen = 0;
+  std::vector<float> gtrk_host;  // what was handed over
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;
@@ -364,6 +374,9 @@ static int count_sink_rings(int rows, int cols, F&& sink) {
 static size_t barebone_track_lds(int T, int slots) {
   return sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)T * (size_t)std::max(1, slots);
 }
+
+// ... with a goal track behind the disc rows: [T] float2 more
+static size_t barebone_goal_lds(int T, int slots) { return barebone_track_lds(T, slots) + sizeof(float2) * (size_t)T; }
 
 static void drop_graphs(mppi_planner* p) {
   for (int i = 0; i < mppi_planner::kGraphSlots; ++i) {

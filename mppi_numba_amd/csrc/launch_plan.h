@@ -68,7 +68,8 @@ static DevParams make_dev_params(const mppi_planner* p) {
   // (discs that move: a batch reads each problem's offset from its BatchInst, as it reads the start state)
   d.track_rows = p->trk_on ? p->trk_rows : 0;
   // (wall tracks share the offset: rollout_crowd_kernel.h clamps it against the walls' own row count)
-  d.track_off = (p->trk_on || p->wtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
+  // (... and so does a goal track, against its own)
+  d.track_off = (p->trk_on || p->wtrk_on || p->gtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
   d.inst = p->inst_set ? p->inst_dev : nullptr;
   d.inst_tiles = p->inst_tiles;
   d.n_inst = p->n_inst;
@@ -1049,8 +1050,15 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
   *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
 }
 
+// The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.
+template <bool BATCHED>
+static GoalRows goal_rows_arg(const mppi_planner* p) {
+  return GoalRows{p->gtrk_xy, p->gtrk_rows, BATCHED && p->gtrk_count > 1 ? p->gtrk_rows : 0};
+}
+
 // WALLS: 0 none, 1 static walls shared by the problems (CrowdWalls), 2 wall tracks / per-problem sets (CrowdWallTracks)
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, int WALLS>
+// GOALS: a goal that moves (mppi_planner_set_goal_tracks): one GoalRows argument more, behind the walls'
+template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, int WALLS, bool GOALS = false>
 static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
@@ -1058,7 +1066,26 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
   if constexpr (WALLS != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
-  if constexpr (WALLS == 2) {
+  if constexpr (GOALS) {
+    const GoalRows goal = goal_rows_arg<BATCHED>(p);
+    auto launch = [&](auto kern, auto... walls) -> int {
+      if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls..., goal);
+      return MPPI_OK;
+    };
+    if constexpr (WALLS == 2) {
+      const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
+      const CrowdWallTracks walls{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
+                                  own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size()};
+      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks, GoalRows>, walls));
+    } else if constexpr (WALLS == 1) {
+      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls, GoalRows>,
+                 CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls}));
+    } else {
+      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, false, GoalRows>));
+    }
+  } else if constexpr (WALLS == 2) {
     auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks>;
     if (lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1084,7 +1111,8 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
                     (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
                     (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
                     (WALLS == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
-                    (WALLS == 2 ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string());
+                    (WALLS == 2 ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
+                    (GOALS ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -1093,6 +1121,11 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
 // per-problem sets (mppi_planner_set_wall_tracks) come first: while they are held the static walls rest.
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
 static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
+  if (p->gtrk_on) {  // (a goal that moves: the same three wall forms with the goal rows behind)
+    if (p->wtrk_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2, true>(p, d, pos, rad, pitch);
+    if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1, true>(p, d, pos, rad, pitch);
+    return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0, true>(p, d, pos, rad, pitch);
+  }
   if (p->wtrk_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2>(p, d, pos, rad, pitch);
   if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1>(p, d, pos, rad, pitch);
   return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0>(p, d, pos, rad, pitch);
@@ -1147,9 +1180,48 @@ static int launch_rollout_barebone_tracks(mppi_planner* p, DevParams d, bool rot
   return MPPI_OK;
 }
 
+// A goal that moves (mppi_planner_set_goal_tracks): the default family launches its track forms only, with the goal rows
+// as one more argument.  Static discs are tracks of one row there (DevParams::track_rows = 1: every step's row of slots
+// holds the same discs -- DESIGN.md section 8: a static disc to the bit), so the goal track costs one template flag on the
+// sixteen track forms and no form of its own for static discs.  LDS: barebone_goal_lds, 8 * T bytes more than the track
+// forms'; a set that no longer fits goes to the crowd kernel in crowd mode and is refused otherwise.
+template <bool EXACT, bool BATCHED>
+static int launch_rollout_barebone_goal(mppi_planner* p, DevParams d, bool rot) {
+  const int N = p->n_local, T = p->cfg.num_steps;
+  const bool own = p->inst_obs_on;
+  const int kmax = p->trk_on ? p->trk_max : (own ? p->inst_obs_max : p->n_obstacles);
+  if (crowd_launch(p, kmax, barebone_goal_lds(T, kmax))) return launch_rollout_barebone_crowd<EXACT, BATCHED>(p, d, rot);
+  const float2* pos = p->trk_on ? p->trk_pos : (own ? p->inst_obs_pos : p->obs_pos);
+  const float* rad = p->trk_on ? p->trk_r : (own ? p->inst_obs_r : p->obs_r);
+  if (!p->trk_on) d.track_rows = 1;
+  int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
+  if (kd > 0 && barebone_goal_lds(T, kd) > 64 * 1024) kd = -1;  // (a long horizon: the padded row does not fit, the problem's own may)
+  const size_t lds = barebone_goal_lds(T, kd > 0 ? kd : kmax);  // the size launched
+  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d discs, %d steps and a goal track: %zu bytes, more than 64 KiB of LDS", kmax, T, lds);
+  if (!BATCHED) d.n_obstacles = kmax;
+  const dim3 grid(ceil_div(N, 64)), block(64);
+  const GoalRows goal = goal_rows_arg<BATCHED>(p);
+  if (kd == 2)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
+  else if (kd == 4)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
+  else if (rot)
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
+  else
+    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
+  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
+                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
+                    (p->trk_on ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
+                    " goal_rows=" + std::to_string(p->gtrk_rows);
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
 template <bool EXACT>
 static int launch_rollout_barebone_batch(mppi_planner* p, const DevParams& d, bool rot) {
   TRY(upload_instances(p));
+  if (p->gtrk_on) return launch_rollout_barebone_goal<EXACT, true>(p, d, rot);
   if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, true>(p, d, rot);
   const int N = p->n_local, T = p->cfg.num_steps;
   const bool own = p->inst_obs_on;
@@ -1192,6 +1264,7 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
       const bool rot = EXACT && rotation_ok(p, d);
       if (p->inst_set) return launch_rollout_barebone_batch<EXACT>(p, d, rot);
+      if (p->gtrk_on) return launch_rollout_barebone_goal<EXACT, false>(p, d, rot);
       if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, false>(p, d, rot);
       // (one problem given its own set through mppi_planner_set_instance_disc_obstacles: the launch with that set)
       const int K = p->inst_obs_on ? p->inst_obs_max : p->n_obstacles;
@@ -1623,7 +1696,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1641,6 +1714,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.epoch_bias = p->noise_epoch - p->bumps_launched;
   sig.wall_gen = p->wall_gen;  // (the walls' generation, not their address: a new set may land where the old one was)
   sig.wtrk_gen = p->wtrk_gen;
+  sig.gtrk_gen = p->gtrk_gen;  // (the goal track's likewise)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

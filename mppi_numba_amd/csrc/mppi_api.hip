@@ -520,6 +520,7 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->wtrk_seg_rows);
   dev_free(p->wtrk_hw);
   dev_free(p->wtrk_range);
+  dev_free(p->gtrk_xy);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -930,6 +931,10 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
             p->inst_obs_max, T);
     REQUIRE(sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, p->n_obstacles) <= 64 * 1024, MPPI_ERR_INVALID,
             "crowd mode stays on: the disc obstacles held (%d discs, %d steps) need more than 64 KiB of LDS", p->n_obstacles, T);
+    const int held = p->trk_on ? p->trk_max : (p->inst_obs_on ? p->inst_obs_max : p->n_obstacles);
+    REQUIRE(!p->gtrk_on || barebone_goal_lds(T, held) <= 64 * 1024, MPPI_ERR_INVALID,
+            "crowd mode stays on: the discs held with a goal track (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
+            held, T, barebone_goal_lds(T, held));
   }
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1071,6 +1076,61 @@ extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const in
   drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
   // new walls that move: row 0 is "now"; cleared: likewise unless disc tracks still count the rows
   if (moved && (count > 0 || !p->trk_on)) {
+    for (BatchInst& I : p->inst_host) I.track_off = 0;
+    p->inst_dirty = true;
+  }
+  return MPPI_OK;
+}
+
+// A goal that moves (include/mppi_hip.h): `rows` positions per track, one track for every problem (count == 1) or one per
+// problem (count == B), [track][row].  Unchanged arrays cost a comparison; a change synchronises, builds the new device
+// copy before the old one is freed (a failure leaves the handle as it was), takes a new generation, drops the captured
+// graphs and, for a goal that moves (rows > 1), makes row 0 "now" again.
+extern "C" int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows, const float* xy) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "goal tracks belong to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
+          "count %d: must be 0, 1 (one track for every problem) or num_instances %d", count, p->B);
+  size_t n_xy = 0;
+  if (count > 0) {
+    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a goal track has at least one row", rows);
+    REQUIRE((long)count * (long)rows <= (1L << 28), MPPI_ERR_INVALID, "too many goal track rows (%d tracks x %d)", count, rows);
+    REQUIRE(xy, MPPI_ERR_INVALID, "NULL xy");
+    n_xy = (size_t)count * (size_t)rows;
+    for (size_t i = 0; i < 2 * n_xy; ++i)
+      REQUIRE(std::isfinite(xy[i]), MPPI_ERR_INVALID, "goal track %zu, row %zu: a coordinate is not finite", i / 2 / (size_t)rows,
+              i / 2 % (size_t)rows);
+  }
+  if (count == 0 ? !p->gtrk_on
+                 : (p->gtrk_on && rows == p->gtrk_rows && count == p->gtrk_count &&
+                    memcmp(xy, p->gtrk_host.data(), sizeof(float) * 2 * n_xy) == 0))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  float2* fresh = nullptr;
+  if (count > 0) {  // the new device array first: a failed allocation or copy leaves the handle with what it had
+    auto upload = [&]() -> int {
+      TRY(dev_alloc(&fresh, n_xy));
+      HIP_TRY(hipMemcpy(fresh, xy, sizeof(float2) * n_xy, hipMemcpyHostToDevice));
+      return MPPI_OK;
+    };
+    const int rc = upload();
+    if (rc != MPPI_OK) {
+      dev_free(fresh);
+      return rc;
+    }
+  }
+  dev_free(p->gtrk_xy);
+  p->gtrk_xy = fresh;
+  const bool moved = p->gtrk_rows > 1 || (count > 0 && rows > 1);  // (a track of one row is a static goal: it leaves "now" alone)
+  p->gtrk_on = count > 0;
+  p->gtrk_rows = count > 0 ? rows : 0;
+  p->gtrk_count = count;
+  p->gtrk_gen = count > 0 ? next_generation() : 0;
+  p->gtrk_host.assign(xy, xy + (count > 0 ? 2 * n_xy : 0));
+  drop_graphs(p);  // (the array, the row count and the kernel form are arguments of the captured launches)
+  // a new goal that moves: row 0 is "now"; cleared: likewise unless disc tracks or wall tracks still count the rows
+  if (moved && (count > 0 || !(p->trk_on || (p->wtrk_on && p->wtrk_rows > 1)))) {
     for (BatchInst& I : p->inst_host) I.track_off = 0;
     p->inst_dirty = true;
   }
@@ -1546,7 +1606,10 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.dt = dt > 0.0 ? dt : (double)p->params.dt;
     L.goal_tolerance = goal_tolerance;
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
-    L.advance_tracks = p->trk_on || (p->wtrk_on && p->wtrk_rows > 1) ? 1 : 0;
+    L.advance_tracks = p->trk_on || (p->wtrk_on && p->wtrk_rows > 1) || (p->gtrk_on && p->gtrk_rows > 1) ? 1 : 0;
+    L.goal_xy = p->gtrk_on ? p->gtrk_xy : nullptr;
+    L.goal_rows = p->gtrk_rows;
+    L.goal_stride = p->gtrk_count > 1 ? p->gtrk_rows : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)

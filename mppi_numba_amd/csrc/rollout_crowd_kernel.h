@@ -54,6 +54,11 @@
 // step's row and keeps the next tile -- the first tile of its NEXT step behind a step's last -- in flight during the tests,
 // as it does with the disc tiles.  One row, or equal rows, is a static wall to the bit.  A wall that itself jumps over the
 // robot between two rows is seen only if its rows are sweeps: a row is tested where it lies.
+//
+// A GOAL THAT MOVES (mppi_planner_set_goal_tracks): one GoalRows argument behind the walls' (if any).  The only reader of the
+// goal is the count wave's goal distance, once per (step, lane): the counter that owns step c0 + j takes row
+// min(s + c0 + j + 1, rows - 1) of the problem's goal track -- a wave-uniform load -- where it took P.xg / P.yg.  The cost
+// wave, the walker and the wall code do not know.  Without the argument the kernel is what it was.
 #pragma once
 #include <type_traits>
 
@@ -127,17 +132,24 @@ __device__ __forceinline__ bool crowd_wall_hit(double px, double py, double qx, 
 __device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls) { return walls; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls, const GoalRows&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&) { return walls; }
 template <typename... WallArgs>
 constexpr bool kCrowdWallTracks = (std::is_same_v<WallArgs, CrowdWallTracks> || ...);
 
 // WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
-// shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets).
+// shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets); behind it, with a goal
+// that moves, one GoalRows.
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
     const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch, WallArgs... wall_args) {
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0), "WALLS: one CrowdWalls or CrowdWallTracks argument; else none");
+  constexpr bool GOALS = kGoalRows<WallArgs...>;
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0),
+                "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; else none");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
+  [[maybe_unused]] GoalRows G = goal_rows_of(wall_args...);
   [[maybe_unused]] const auto walls = crowd_walls_of(wall_args...);
   [[maybe_unused]] int wall0 = 0, wcount = 0;  // WTRK: this problem's walls within a row
   if constexpr (WTRK) wcount = walls.max_count;
@@ -151,7 +163,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     obs_pos += I.disc0;
     obs_r += I.disc0;
     P.n_obstacles = I.n_discs;
-    if constexpr (TRACKS || WTRK) P.track_off = I.track_off;
+    if constexpr (TRACKS || WTRK || GOALS) P.track_off = I.track_off;
+    if constexpr (GOALS) G.xy += (size_t)b * (size_t)G.stride;
     if constexpr (WTRK) {
       if (walls.range) {
         const int2 r = walls.range[b];
@@ -193,6 +206,12 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   if constexpr (WTRK) {
     wlast = walls.rows - 1;
     wnow = min(max(P.track_off, 0), wlast);
+  }
+  // ... and the goal track's
+  [[maybe_unused]] int glast = 0, gnow = 0;
+  if constexpr (GOALS) {
+    glast = G.rows - 1;
+    gnow = min(max(P.track_off, 0), glast);
   }
 
   for (int ph = 0; ph < n_chunks + 2; ++ph) {
@@ -355,7 +374,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
               }
             }
             cnts[at + j * 64] = hits;
-            nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+            if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
+            else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
             hits = 0;
           }
           j = nj; base = nbase; op = op_nxt; rr = rr_nxt;

@@ -28,6 +28,7 @@
 // One rollout (or one (rollout, sample) pair) per lane; the cost stays in a
 // register and is written once (the reference does three global RMWs per step).
 #pragma once
+#include <type_traits>
 #include "device_math.h"
 #include "rng_kernels.h"
 #include "update_kernels.h"
@@ -1485,6 +1486,12 @@ __global__ void k_cvar_reduce(const float* __restrict__ slabs, int count, int n_
 // against row min(s + t + 1, rows - 1): the disc where it will be when the robot gets there, at its last predicted place
 // once the track has ended.  The rows are picked when the launch stages its LDS -- one row of disc slots per step,
 // [T][slots] -- so a step does what it does for static discs on operands that change with t: same operations, same order.
+// GoalArgs: nothing (the kernel and its arguments as they were) or one GoalRows (TRACKS forms only): a goal that moves.
+// Row j of the problem's goal track is the goal at time j * dt from "now" = row s, the same raw offset clamped against the
+// goal track's own row count, and the state after step t is measured against row min(s + t + 1, G.rows - 1): stage term,
+// goal test, freeze and terminal term are the static kernel's on a goal that changes with t.  The rows are picked at
+// staging, [T] float2 behind the disc rows, so a step reads its goal at an offset from one base; static discs on such a
+// launch are tracks of one row (P.track_rows = 1: every step's row of slots holds the same discs).
 // One state step of the barebone rollout, shared by k_rollout_barebone's step() and the walk of
 // k_rollout_barebone_crowd (rollout_crowd_kernel.h): the clipped controls and the pose after the step, with the
 // reference's float32 roundings.  ROT: (rs, rc) are (sin, cos) of `th`, kept by the caller by rotation.
@@ -1514,17 +1521,41 @@ __device__ __forceinline__ double barebone_goal_d2(const DevParams& P, float nx,
   double dx = (double)(P.xg - nx), dy = (double)(P.yg - ny);
   return fma(dx, dx, dy * dy);
 }
+// ... to a goal that moves: the same arithmetic against the step's row of the goal track
+__device__ __forceinline__ double barebone_goal_d2(float2 g, float nx, float ny) {
+  double dx = (double)(g.x - nx), dy = (double)(g.y - ny);
+  return fma(dx, dx, dy * dy);
+}
 
-template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false, bool TRACKS = false>
+// The goal tracks of a launch (mppi_planner_set_goal_tracks): xy[b * stride + j], row j of problem b's track; stride is
+// `rows` for one track per problem and 0 for a track every problem shares.
+struct GoalRows {
+  const float2* xy;
+  int rows, stride;
+};
+__device__ __forceinline__ GoalRows goal_rows_of() { return GoalRows{nullptr, 1, 0}; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ GoalRows goal_rows_of(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<First, GoalRows>) return first;
+  else return goal_rows_of(rest...);
+}
+template <typename... Args>
+constexpr bool kGoalRows = (std::is_same_v<Args, GoalRows> || ...);
+
+template <bool EXACT, bool ROT = false, int KD = -1, bool BATCHED = false, bool TRACKS = false, typename... GoalArgs>
 __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const float2* __restrict__ obs_pos,
                                                          const float* __restrict__ obs_r,
                                                          const float2* __restrict__ noise,
                                                          const float2* __restrict__ u,
-                                                         float* __restrict__ costs) {
+                                                         float* __restrict__ costs, GoalArgs... goal_args) {
+  constexpr bool GOALS = kGoalRows<GoalArgs...>;
+  static_assert(sizeof...(GoalArgs) == (GOALS ? 1 : 0) && (TRACKS || !GOALS), "GoalArgs: nothing, or one GoalRows on a TRACKS form");
+  [[maybe_unused]] GoalRows G = goal_rows_of(goal_args...);
   extern __shared__ double2 uos[];
   ktime_begin(P);
   if constexpr (BATCHED) {
     const int b = (int)blockIdx.x / P.inst_tiles;  // (uniform over the workgroup)
+    if constexpr (GOALS) G.xy += (size_t)b * (size_t)G.stride;
     u = select_instance(P, u, b);
     const BatchInst I = P.inst[b];
     obs_pos += TRACKS ? (size_t)I.disc0 * (size_t)P.track_rows : (size_t)I.disc0;
@@ -1556,6 +1587,12 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
     if (KD > 0)  // (slots past the last disc: far away, radius 0 -- `diff > 0`, no hit, +0.0 added)
       for (int k = P.n_obstacles + (int)threadIdx.x; k < KD; k += 64) discs[k] = make_float4(1e18f, 1e18f, 0.0f, 0.0f);
   }
+  // GOALS: [T] float2 behind the disc rows (the host sizes a row at one slot at the least), row t what step t measures against
+  [[maybe_unused]] float2* goals = reinterpret_cast<float2*>(discs + P.n_steps * max(slots, 1));
+  if constexpr (GOALS) {
+    const int glast = G.rows - 1, gnow = min(max(P.track_off, 0), glast);  // (the same raw offset, the goal track's own clamp)
+    for (int t = threadIdx.x; t < P.n_steps; t += 64) goals[t] = G.xy[min(gnow + t + 1, glast)];
+  }
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
   const int n = blockIdx.x * 64 + threadIdx.x;
   const bool live = n < P.n_local;
@@ -1572,7 +1609,9 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
     const float4* row = TRACKS ? discs + t * slots : discs;  // the discs where they are after this step
     float nx, ny, nth;
     barebone_next_pose<EXACT, ROT>(P, ut, e, x, y, th, rs, rc, nx, ny, nth);
-    const double nd2 = barebone_goal_d2(P, nx, ny);
+    double nd2;
+    if constexpr (GOALS) nd2 = barebone_goal_d2(goals[t], nx, ny);
+    else nd2 = barebone_goal_d2(P, nx, ny);
     float c1 = (float)((double)cost + P.dist_weight * nd2);
 #pragma unroll
     for (int k = 0; k < (KD >= 0 ? KD : P.n_obstacles); ++k) {
@@ -1636,9 +1675,12 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
         }
         // what each step adds to the cost -- distance term, one term per disc --: independent of each other
         double nd2a[kNoiseBatch], add0[kNoiseBatch], addk[kNoiseBatch][KD > 0 ? KD : 1];
+        [[maybe_unused]] const float2* grow = goals + t0;  // (GOALS: one base per batch, step j's goal at an immediate offset)
 #pragma unroll
         for (int j = 0; j < kNoiseBatch; ++j) {
-          const double dx = (double)(P.xg - nxa[j]), dy = (double)(P.yg - nya[j]);
+          float gx = P.xg, gy = P.yg;
+          if constexpr (GOALS) { gx = grow[j].x; gy = grow[j].y; }
+          const double dx = (double)(gx - nxa[j]), dy = (double)(gy - nya[j]);
           nd2a[j] = fma(dx, dx, dy * dy);
           add0[j] = P.dist_weight * nd2a[j];
           [[maybe_unused]] const float4* row = TRACKS ? discs + (t0 + j) * KD : discs;

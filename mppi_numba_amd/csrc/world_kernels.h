@@ -92,8 +92,14 @@ struct WorldLoop {
   // the LDS window plan of the planner (plan_lds_window): origin per problem around its start cell
   int win_active, reach, win_rows, win_cols, map_rows, map_pitch;
   double xlo, ylo, res;
-  // barebone mode with disc tracks or wall tracks: a control step later "now" is the tracks' next row (BatchInst::track_off)
+  // barebone mode with disc tracks, wall tracks or a goal track: a control step later "now" is the tracks' next row
+  // (BatchInst::track_off)
   int advance_tracks;
+  // barebone mode with a goal that moves (mppi_planner_set_goal_tracks; nullptr: the goal is BatchInst::xg, yg): problem
+  // b's track is goal_xy[b * goal_stride + j], goal_rows rows.  The new state is tested against the goal where it is at
+  // the time of the new state: row min(track_off, goal_rows - 1) once the offset has advanced
+  const float2* goal_xy;
+  int goal_rows, goal_stride;
 };
 
 // One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4; barebone_mppi_numba.ipynb
@@ -101,7 +107,7 @@ struct WorldLoop {
 //   u_curr = useq[0]; (lt, at) = traction_grid.get(x, y)
 //   x += dt*lt*cos(th)*u_curr[0]; y += dt*lt*sin(th)*u_curr[0]; th += dt*at*u_curr[1]   (float64)
 //   shift_and_update(x_new, useq, 1)   (mppi.py:534-542: x0 <- x_new, u[:-1] = u[1:])
-//   goal check: ||x_new[:2] - goal|| <= goal_tolerance
+//   goal check: ||x_new[:2] - goal|| <= goal_tolerance   (a goal that moves: the goal at the time of the new state)
 // A problem that has reached its goal is left alone (state, controls, log).
 __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ inst, float2* __restrict__ u,
                              int n_steps, int step) {
@@ -140,7 +146,9 @@ __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ i
     }
     if (L.advance_tracks && I.track_off < 0x7fffffff) ++I.track_off;
     inst[b] = I;
-    const double dx = x1 - (double)I.xg, dy = y1 - (double)I.yg;
+    float2 goal = make_float2(I.xg, I.yg);
+    if (L.goal_xy) goal = L.goal_xy[(size_t)b * (size_t)L.goal_stride + (size_t)min(max(I.track_off, 0), L.goal_rows - 1)];
+    const double dx = x1 - (double)goal.x, dy = y1 - (double)goal.y;
     if (sqrt(dx * dx + dy * dy) <= L.goal_tolerance) {
       L.done[b] = step + 1;
       reached_now = 1;
