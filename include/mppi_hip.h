@@ -329,6 +329,50 @@ int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_cou
  * coordinate. */
 int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows, const float* xy);
 
+/* MPPI_MODE_BAREBONE, a batched handle (num_instances B >= 2) in crowd mode: fleet mode -- the
+ * problems are robots that avoid each other's plans.  count = B turns it on, halfwidths (B, B-1)
+ * float32: row a holds reader a's half-width against every other robot b in ascending b, a
+ * skipped (r_a + r_b + margin, formed by the caller); count = 0 turns it off (halfwidths ignored).
+ * While it is on the library rebuilds every reader's wall set from the other robots' CURRENT plans
+ * at the head of every call that starts iterations -- mppi_planner_solve, mppi_planner_rollout,
+ * mppi_planner_iterate_async and each control step of mppi_planner_closed_loop -- once per call,
+ * never between the iterations of a call, on the planner's stream and without the host.  The plan
+ * of robot b is the noise-free rollout c_0 .. c_T of its control sequence from its start state
+ * (the state step of the rollouts with zero noise, the clip to vrange / wrange included: the bits
+ * of mppi_planner_get_instance_state_rollout's row 0 when the controls lie inside the ranges); it
+ * goes on past the goal.  Row j of the wall that stands for b is the segment [c_j, c_{j+1}], the
+ * capsule b sweeps in control interval j, and step t of a rollout of reader a is tested against
+ * row t of every other robot as mppi_planner_set_walls describes: these rows are always counted
+ * from "now", whatever the problem's track offset is, and fleet mode neither reads nor advances
+ * nor resets that offset -- disc tracks and goal tracks keep their meaning beside it.  Behind the
+ * B - 1 others every reader's set holds the static walls of mppi_planner_set_walls with their own
+ * half-widths (they rest while per-problem sets are held, so the library places them itself); the
+ * storage is rebuilt when fleet mode is set or those walls change (new arrays first: a failure
+ * leaves the handle as it was; the captured graphs are dropped), never at a refresh, so graph
+ * replay needs no new capture from one control step to the next.  In mppi_planner_closed_loop a
+ * problem that has reached its goal is parked: its rows are the degenerate segment at its final
+ * float32 position.  A host-driven loop parks a robot by giving it zero controls
+ * (mppi_planner_set_u) where vrange admits 0.  Before the first solve the controls are zero and
+ * every plan stands at its start.  All robots plan at once, each against the others' plans of the
+ * previous control step (shifted): a Jacobi sweep, not the in-turn order of one planner per robot.
+ * The launches are k_rollout_barebone_crowd's CrowdWallTracks form;
+ * mppi_planner_describe_last_rollout holds " walls=<B-1+W> wall_rows=<T> fleet=<B>" (at its end,
+ * or ahead of " goal_rows=<rows>").  One owner of the per-problem sets at a time:
+ * MPPI_ERR_INVALID for mppi_planner_set_wall_tracks with a count while fleet mode is on and for
+ * mppi_planner_set_fleet while wall tracks or per-problem sets are held; also for a map mode, a
+ * handle with B < 2, count not 0 / B, a handle that is not in crowd mode (and
+ * mppi_planner_set_crowd(p, 0) while fleet mode is on), or a negative or non-finite half-width. */
+int mppi_planner_set_fleet(mppi_planner* p, int count, const float* halfwidths);
+/* *on: B while fleet mode is on, else 0 */
+int mppi_planner_get_fleet(mppi_planner* p, int* on);
+/* the refresh alone (for tests and for drawing): the rows from the current controls and start
+ * states, then waits for the stream.  MPPI_ERR_STATE unless fleet mode is on. */
+int mppi_planner_fleet_refresh(mppi_planner* p);
+/* seg (B, B-1, T, 4) float32 -- ax ay bx by --: reader a's others in ascending order, as the last
+ * refresh left them (before the first one: walls nobody can touch, 1e18).  MPPI_ERR_STATE unless
+ * fleet mode is on. */
+int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

@@ -112,6 +112,10 @@ SIGNATURES = {
     "mppi_planner_set_walls": [_vp, _f32p, _f32p, C.c_int],
     "mppi_planner_set_wall_tracks": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p],
     "mppi_planner_set_goal_tracks": [_vp, C.c_int, C.c_int, _f32p],
+    "mppi_planner_set_fleet": [_vp, C.c_int, _f32p],
+    "mppi_planner_get_fleet": [_vp, C.POINTER(C.c_int)],
+    "mppi_planner_fleet_refresh": [_vp],
+    "mppi_planner_get_fleet_walls": [_vp, _f32p],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

@@ -37,6 +37,21 @@ place; a track of one row, or of equal rows, is a static goal to the bit.  No he
 constant_velocity_tracks(p, v, dt, rows)[0] is the goal track of a target that keeps its velocity, and another robot's
 planned states[:, :2] is the goal track of a follower.  goal_now is the goal where it is now; MPPI_Batch.set_goal_tracks()
 gives every problem of a batch its own.
+
+A fleet: MPPI_Batch.set_fleet(radii, margin) makes the B problems of a batch in crowd mode robots that avoid each other's
+plans, without the host in the middle.  At the head of every solve(), rollout() and control step of closed_loop() -- once
+per call, not between the num_opt iterations -- the device rebuilds for every robot a the walls swept_walls() would make of
+the OTHER robots' current plans: the plan of b is the noise-free rollout c_0 .. c_T of its control sequence from its start
+state (the controls clipped to vrange / wrange, the rollouts' own float32 state step; it goes on past the goal), row j of
+its wall the segment [c_j, c_{j+1}], the half-width float32(r_a + r_b + margin).  These rows are always counted from "now":
+step t meets row t whatever track_offset is, and the fleet neither advances nor resets track_offset, so disc tracks and
+goal tracks keep their meaning beside it.  params['wall_segments'] -- a room, a corridor -- stay in force for every robot;
+params['wall_tracks'] and set_wall_sets() are refused while the fleet is on (one owner of the per-problem sets).  All robots
+plan at once, each against the others' plans of the previous control step, shifted: a Jacobi sweep, where one planner per
+robot planning in turn sees the plans of this step.  Before the first solve the controls are zero and every plan stands at
+its start.  closed_loop() parks a robot that has reached its goal (its rows become its final position); in a host-driven
+loop the library does not know who has arrived: park a robot by giving it zero controls (set_u), where vrange admits 0.
+fleet_walls() fetches the rows of the last refresh, refresh_fleet() refreshes alone (for drawing).
 """
 import copy
 import ctypes as C
@@ -151,6 +166,12 @@ def polyline_walls(points, closed=False):
     return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.float32)
 
 
+def fleet_others(count):
+    """(B, B - 1) int: row a holds the other robots of reader a in ascending order -- the order of a fleet's wall slots."""
+    count = int(count)
+    return np.array([[b for b in range(count) if b != a] for a in range(count)], dtype=np.int64).reshape(count, max(count - 1, 0))
+
+
 def _is_track_set(obstacle_set):
     return np.asarray(obstacle_set[0]).ndim == 3
 
@@ -194,6 +215,7 @@ class MPPI_Numba(object):
         self._goal_track_key = None   # the goal track of params['goal_track'] the library holds (None: none)
         self._own_goals = False       # MPPI_Batch: per-problem goal tracks are set (they win over params['goal_track'])
         self._goal_tracks = None      # the goal tracks held, whoever set them: (1 or B, L, 2) float32 (None: static goals)
+        self._fleet = None            # MPPI_Batch.set_fleet: (radii (B,), margin, half-widths (B, B - 1)) (None: off)
         self.reset()
 
     def __del__(self):
@@ -249,6 +271,9 @@ class MPPI_Numba(object):
         """params['wall_segments'] / ['wall_halfwidth']: handed over when they have changed, cleared when the keys have
         gone.  Without crowd mode the library refuses them (MppiError)."""
         if "wall_tracks" in p:
+            if self._fleet is not None:
+                raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
+                                 "itself (set_fleet(None) first; 'wall_segments' stay in force beside it)")
             if "wall_segments" in p:
                 raise ValueError("params hold both 'wall_segments' and 'wall_tracks': walls are static or have tracks, "
                                  "give one of the two")
@@ -759,6 +784,9 @@ class MPPI_Batch(MPPI_Numba):
                 self._own_walls, self._wall_tracks_key = False, None
             self.wall_sets = None
             return
+        if self._fleet is not None:
+            raise ValueError("set_wall_sets while the fleet is on: the fleet makes every problem's wall set itself "
+                             "(set_fleet(None) first)")
         assert len(sets) == self.num_instances, "one wall set per problem"
         kinds = {_is_wall_track_set(s) for s in sets}
         if len(kinds) > 1:
@@ -789,6 +817,52 @@ class MPPI_Batch(MPPI_Numba):
         self._hand_over_goal_tracks(list(tracks))
         self._own_goals, self._goal_track_key = True, None
         self.goal_tracks = held
+
+    # ------------------------------------------------------------------ a fleet
+    def set_fleet(self, radii, margin=0.0):
+        """Fleet mode (crowd mode, B >= 2): the problems are robots of body radius `radii` -- a scalar or (B,) -- that avoid
+        each other's current plans, kept `margin` apart; None turns it off.  From now on every solve(), rollout() and
+        control step of closed_loop() starts by rebuilding, on the device, every robot's walls from the others' plans (the
+        module header says which).  The half-width of reader a against b is float32(r_a + r_b + margin), summed in float64
+        from the float32 radii.  Raises while per-problem wall sets or params['wall_tracks'] are held."""
+        if radii is None:
+            _lib.call("mppi_planner_set_fleet", self._handle, 0, None)
+            self._fleet = None
+            return
+        B = self.num_instances
+        r = np.ascontiguousarray(np.broadcast_to(_f32(radii), (B,)))
+        if not (np.isfinite(r).all() and (r >= 0).all() and np.isfinite(margin)):
+            raise ValueError("fleet radii are finite and >= 0, the margin finite")
+        if self._own_walls or self._wall_tracks_key is not None:
+            raise ValueError("set_fleet while per-problem wall sets or params['wall_tracks'] are held: the fleet makes every "
+                             "problem's wall set itself (set_wall_sets(None) / drop the key first)")
+        r64 = r.astype(np.float64)
+        full = ((r64[:, None] + r64[None, :]) + np.float64(margin)).astype(np.float32)
+        half = np.ascontiguousarray(full[np.arange(B)[:, None], fleet_others(B)], dtype=np.float32).reshape(B, max(B - 1, 0))
+        _lib.call("mppi_planner_set_fleet", self._handle, B, _lib.ptr(half if half.size else np.zeros(1, np.float32), C.c_float))
+        self._fleet = (r.copy(), float(margin), half)
+
+    @property
+    def fleet(self):
+        """None while fleet mode is off, else (radii (B,) float32, margin)."""
+        return None if self._fleet is None else (self._fleet[0].copy(), self._fleet[1])
+
+    def refresh_fleet(self):
+        """The refresh alone, as solve() makes it at its head: every robot's walls from the others' current controls and
+        start states.  For drawing and for tests; fleet_walls() fetches the result."""
+        self.move_mppi_task_vars_to_device()
+        _lib.call("mppi_planner_fleet_refresh", self._handle)
+
+    def fleet_walls(self):
+        """What the last refresh left: (segments (B, B - 1, T, 2, 2) float32, half-widths (B, B - 1) float32, others
+        (B, B - 1) int) -- segments[a, k, j] is the segment robot others[a, k] covers in control interval j from "now",
+        as reader a is given it."""
+        if self._fleet is None:
+            raise ValueError("fleet_walls: the fleet is off (set_fleet)")
+        B, t = self.num_instances, self.num_steps
+        seg = np.empty((B, B - 1, t, 2, 2), dtype=np.float32)
+        _lib.call("mppi_planner_get_fleet_walls", self._handle, _lib.ptr(seg, C.c_float))
+        return seg, self._fleet[2].copy(), fleet_others(B)
 
     def check_solve_conditions(self):
         if self.x0s is None:

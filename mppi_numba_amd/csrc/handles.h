@@ -269,6 +269,23 @@ struct mppi_planner {
   uint64_t wtrk_gen = 0;
   std::vector<int> wtrk_counts_host;
   std::vector<float> wtrk_seg_host, wtrk_hw_host;  // what was handed over ([wall][row])
+  // fleet mode (mppi_planner_set_fleet; a batched handle in crowd mode): every problem's wall set is made of the OTHER
+  // problems' current plans, rebuilt on the device at the head of every call that starts iterations (fleet_kernels.h).
+  // fleet_seg_rows: [T][B * fleet_slots] in the layout of wtrk_seg_rows, problem a's slots at a * fleet_slots -- the B - 1
+  // others in ascending order, then the static walls of mppi_planner_set_walls as they were when the storage was built
+  // (they rest while per-problem sets are held, so they are copied into every row here); fleet_hw: [B * fleet_slots];
+  // fleet_range: {a * fleet_slots, fleet_slots}; fleet_plan: [B][T + 1] positions of the noise-free rollouts.  The rows
+  // are counted from "now" (CrowdWallTracks::relative): BatchInst::track_off is neither read for them nor advanced.
+  // fleet_gen: next_generation() whenever the storage is rebuilt (fleet mode set, static walls changed), 0 while off -- a
+  // refresh writes into the same arrays and changes nothing a captured launch holds
+  bool fleet_on = false;
+  float4* fleet_seg_rows = nullptr;
+  float* fleet_hw = nullptr;
+  int2* fleet_range = nullptr;
+  float2* fleet_plan = nullptr;
+  int fleet_slots = 0;
+  uint64_t fleet_gen = 0;
+  std::vector<float> fleet_hw_host;  // what was handed over: [B][B - 1]
   // a goal that moves (mppi_planner_set_goal_tracks): gtrk_rows positions per track, [track][row]; one track for every
   // problem (gtrk_count == 1) or one per problem (gtrk_count == B).  While gtrk_on the rollouts measure the state after step
   // t against row min(track_off + t + 1, gtrk_rows - 1) and params.xgoal / BatchInst::xg, yg rest; the default family

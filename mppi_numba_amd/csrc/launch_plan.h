@@ -1056,6 +1056,18 @@ static GoalRows goal_rows_arg(const mppi_planner* p) {
   return GoalRows{p->gtrk_xy, p->gtrk_rows, BATCHED && p->gtrk_count > 1 ? p->gtrk_rows : 0};
 }
 
+// The wall tracks as a launch takes them: the user's (rows counted from the problem's track offset), or in fleet mode the
+// sets the library makes of the other problems' plans (fleet_kernels.h; rows counted from "now": relative = 1).
+// (the classic single launch has one problem: the first set, which starts at wall 0)
+template <bool BATCHED>
+static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
+  if (p->fleet_on)
+    return CrowdWallTracks{p->fleet_seg_rows, p->fleet_hw, p->fleet_range, p->fleet_slots, p->cfg.num_steps, p->B * p->fleet_slots, 1};
+  const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
+  return CrowdWallTracks{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
+                         own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size(), 0};
+}
+
 // WALLS: 0 none, 1 static walls shared by the problems (CrowdWalls), 2 wall tracks / per-problem sets (CrowdWallTracks)
 // GOALS: a goal that moves (mppi_planner_set_goal_tracks): one GoalRows argument more, behind the walls'
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, int WALLS, bool GOALS = false>
@@ -1063,6 +1075,7 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
   const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, WALLS != 0);  // the size launched
+  if constexpr (WALLS == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
   if constexpr (WALLS != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
@@ -1075,9 +1088,7 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
       return MPPI_OK;
     };
     if constexpr (WALLS == 2) {
-      const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
-      const CrowdWallTracks walls{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
-                                  own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size()};
+      const CrowdWallTracks walls = wall_tracks_arg<BATCHED>(p);
       TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks, GoalRows>, walls));
     } else if constexpr (WALLS == 1) {
       TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls, GoalRows>,
@@ -1089,10 +1100,7 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
     auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks>;
     if (lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // (the classic single launch has one problem: the first set, which starts at wall 0)
-    const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
-    const CrowdWallTracks walls{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
-                                own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size()};
+    const CrowdWallTracks walls = wall_tracks_arg<BATCHED>(p);
     MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls);
   } else if constexpr (WALLS == 1) {
     auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls>;
@@ -1111,22 +1119,25 @@ static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const floa
                     (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
                     (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
                     (WALLS == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
-                    (WALLS == 2 ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
+                    (WALLS == 2 && !p->fleet_on ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
+                    (WALLS == 2 && p->fleet_on ? " walls=" + std::to_string(p->fleet_slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
+                                                     " fleet=" + std::to_string(p->B) : std::string()) +
                     (GOALS ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
 
 // A handle that holds walls (mppi_planner_set_walls) launches the WALLS form, whatever its discs are; wall tracks and
-// per-problem sets (mppi_planner_set_wall_tracks) come first: while they are held the static walls rest.
+// per-problem sets (mppi_planner_set_wall_tracks) come first: while they are held the static walls rest.  Fleet mode
+// (mppi_planner_set_fleet) takes the same path with the sets it makes itself, the static walls copied into them.
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
 static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
   if (p->gtrk_on) {  // (a goal that moves: the same three wall forms with the goal rows behind)
-    if (p->wtrk_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2, true>(p, d, pos, rad, pitch);
+    if (p->wtrk_on || p->fleet_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2, true>(p, d, pos, rad, pitch);
     if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1, true>(p, d, pos, rad, pitch);
     return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0, true>(p, d, pos, rad, pitch);
   }
-  if (p->wtrk_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2>(p, d, pos, rad, pitch);
+  if (p->wtrk_on || p->fleet_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2>(p, d, pos, rad, pitch);
   if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1>(p, d, pos, rad, pitch);
   return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0>(p, d, pos, rad, pitch);
 }
@@ -1151,7 +1162,7 @@ static int launch_rollout_barebone_crowd(mppi_planner* p, DevParams d, bool rot)
 // Crowd mode: does this launch go to the crowd kernel?  kmax: the largest problem's disc count; default_lds: what the
 // default form would hold in LDS.  Walls are the crowd kernel's alone: a handle that holds any always goes there.
 static bool crowd_launch(const mppi_planner* p, int kmax, size_t default_lds) {
-  return p->crowd && (p->n_walls > 0 || p->wtrk_on || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
+  return p->crowd && (p->n_walls > 0 || p->wtrk_on || p->fleet_on || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
 }
 
 template <bool EXACT, bool BATCHED>
@@ -1696,7 +1707,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1715,6 +1726,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.wall_gen = p->wall_gen;  // (the walls' generation, not their address: a new set may land where the old one was)
   sig.wtrk_gen = p->wtrk_gen;
   sig.gtrk_gen = p->gtrk_gen;  // (the goal track's likewise)
+  sig.fleet_gen = p->fleet_gen;  // (the fleet storage's: renewed when it is rebuilt, not when its rows are refreshed)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

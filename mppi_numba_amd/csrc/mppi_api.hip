@@ -22,6 +22,7 @@
 #include "rng_kernels.h"
 #include "rollout_kernels.h"
 #include "rollout_crowd_kernel.h"
+#include "fleet_kernels.h"
 #include "rollout_scan_kernel.h"
 #include "rollout_scan_exact_kernel.h"
 #include "map_kernels.h"
@@ -520,6 +521,10 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->wtrk_seg_rows);
   dev_free(p->wtrk_hw);
   dev_free(p->wtrk_range);
+  dev_free(p->fleet_seg_rows);
+  dev_free(p->fleet_hw);
+  dev_free(p->fleet_range);
+  dev_free(p->fleet_plan);
   dev_free(p->gtrk_xy);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
@@ -923,6 +928,8 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
             "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
     REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds wall tracks, which only the crowd kernel tests (clear them first)");
+    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle is in fleet mode, whose walls only the crowd kernel tests (mppi_planner_set_fleet(p, 0, NULL) first)");
     REQUIRE(!p->trk_on || barebone_track_lds(T, p->trk_max) <= 64 * 1024, MPPI_ERR_INVALID,
             "crowd mode stays on: the disc tracks held (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
             p->trk_max, T, barebone_track_lds(T, p->trk_max));
@@ -943,6 +950,80 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   p->crowd = on != 0;
   drop_graphs(p);  // (the kernel form is part of the captured launches)
   return MPPI_OK;
+}
+
+// ---- fleet mode (include/mppi_hip.h; fleet_kernels.h) ------------------------------------------------------------------------
+// The device arrays of a fleet: built new-first, so that a failure leaves the handle with what it had.
+struct FleetArrays {
+  float4* seg_rows = nullptr;
+  float* hw = nullptr;
+  int2* range = nullptr;
+  float2* plan = nullptr;
+  int slots = 0;
+};
+
+static void fleet_free(FleetArrays& f) {
+  dev_free(f.seg_rows);
+  dev_free(f.hw);
+  dev_free(f.range);
+  dev_free(f.plan);
+}
+
+// pair_hw: [B][B - 1] half-widths, reader a's others in ascending order; the static walls (W of them) behind the B - 1
+// others in every reader's slots and in every row.  Until the first refresh a fleet slot holds the wall nobody can touch.
+static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_seg, const float* wall_hw, int W, FleetArrays* out) {
+  const int B = p->B, T = p->cfg.num_steps, S = B - 1 + W;
+  const size_t pitch = (size_t)B * (size_t)S;
+  REQUIRE((long)pitch <= (1L << 24) && (long)pitch * (long)T <= (1L << 28), MPPI_ERR_INVALID,
+          "fleet of %d with %d static walls and %d steps: too many wall rows (%zu walls x %d)", B, W, T, pitch, T);
+  std::vector<float4> rows(pitch * (size_t)T);
+  std::vector<float> hw(pitch);
+  std::vector<int2> range((size_t)B);
+  for (int a = 0; a < B; ++a) {
+    range[(size_t)a] = make_int2(a * S, S);
+    for (int k = 0; k < S; ++k) {
+      const bool other = k < B - 1;
+      hw[(size_t)a * S + k] = other ? pair_hw[(size_t)a * (B - 1) + k] : wall_hw[k - (B - 1)];
+      const float* w = other ? nullptr : wall_seg + 4 * (size_t)(k - (B - 1));
+      const float4 sg = other ? make_float4(1e18f, 1e18f, 1e18f, 1e18f) : make_float4(w[0], w[1], w[2], w[3]);
+      for (int j = 0; j < T; ++j) rows[(size_t)j * pitch + (size_t)a * S + k] = sg;
+    }
+  }
+  FleetArrays f;
+  f.slots = S;
+  auto upload = [&]() -> int {
+    TRY(dev_alloc(&f.seg_rows, rows.size()));
+    TRY(dev_alloc(&f.hw, hw.size()));
+    TRY(dev_alloc(&f.range, range.size()));
+    TRY(dev_alloc(&f.plan, (size_t)B * (size_t)(T + 1)));
+    HIP_TRY(hipMemcpy(f.seg_rows, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f.hw, hw.data(), sizeof(float) * hw.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f.range, range.data(), sizeof(int2) * range.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(f.plan, 0, sizeof(float2) * (size_t)B * (size_t)(T + 1)));
+    return MPPI_OK;
+  };
+  const int rc = upload();
+  if (rc != MPPI_OK) {
+    fleet_free(f);
+    return rc;
+  }
+  *out = f;
+  return MPPI_OK;
+}
+
+// (the stream has drained) the handle takes the new arrays and a new generation
+static void fleet_commit(mppi_planner* p, const FleetArrays& f) {
+  dev_free(p->fleet_seg_rows);
+  dev_free(p->fleet_hw);
+  dev_free(p->fleet_range);
+  dev_free(p->fleet_plan);
+  p->fleet_seg_rows = f.seg_rows;
+  p->fleet_hw = f.hw;
+  p->fleet_range = f.range;
+  p->fleet_plan = f.plan;
+  p->fleet_slots = f.slots;
+  p->fleet_on = f.seg_rows != nullptr;
+  p->fleet_gen = p->fleet_on ? next_generation() : 0;
 }
 
 // Walls (include/mppi_hip.h): crowd mode only -- they are one more source of hits for the count waves of
@@ -966,6 +1047,13 @@ extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, co
     return MPPI_OK;
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
+  // fleet mode: these walls lie behind the other robots in every reader's set -- the fleet storage is rebuilt with the
+  // new walls, before anything the handle holds is touched
+  FleetArrays fleet;
+  if (p->fleet_on) {
+    TRY(fleet_build(p, p->fleet_hw_host.data(), segments, halfwidths, count, &fleet));
+    fleet_commit(p, fleet);
+  }
   dev_free(p->wall_seg);
   dev_free(p->wall_hw);
   p->n_walls = 0;
@@ -1002,6 +1090,8 @@ extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const in
   long total = 0;
   int wmax = 0;
   if (count > 0) {
+    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+            "the handle is in fleet mode, which owns the per-problem wall sets: turn it off first (mppi_planner_set_fleet(p, 0, NULL))");
     REQUIRE(p->crowd, MPPI_ERR_INVALID,
             "wall tracks need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a wall track has at least one row", rows);
@@ -1144,6 +1234,53 @@ extern "C" int mppi_planner_get_crowd(mppi_planner* p, int* on) {
   return MPPI_OK;
 }
 
+// Fleet mode (include/mppi_hip.h): the storage is built here and whenever the static walls change, never at a refresh.
+extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* halfwidths) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  if (count == 0) {
+    if (!p->fleet_on) return MPPI_OK;
+    HIP_TRY(hipSetDevice(p->cfg.device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    fleet_commit(p, FleetArrays());
+    p->fleet_hw_host.clear();
+    drop_graphs(p);  // (the arrays and the kernel form are arguments of the captured launches)
+    return MPPI_OK;
+  }
+  REQUIRE(p->B >= 2, MPPI_ERR_INVALID,
+          "fleet mode needs a batched handle of at least two problems, one per robot (num_instances %d)", p->B);
+  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 (off) or num_instances %d", count, p->B);
+  REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "fleet mode drives an unsharded handle");
+  REQUIRE(p->crowd, MPPI_ERR_INVALID,
+          "fleet mode needs crowd mode: only the crowd kernel tests walls (mppi_planner_set_crowd(p, 1) first)");
+  REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+          "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
+          "first (mppi_planner_set_wall_tracks with count 0)");
+  REQUIRE(halfwidths, MPPI_ERR_INVALID, "NULL halfwidths");
+  const size_t pairs = (size_t)p->B * (size_t)(p->B - 1);
+  for (size_t k = 0; k < pairs; ++k) {
+    const float h = halfwidths[k];
+    REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "reader %zu, other slot %zu: half-width %g is negative or not finite",
+            k / (size_t)(p->B - 1), k % (size_t)(p->B - 1), (double)h);
+  }
+  if (p->fleet_on && memcmp(halfwidths, p->fleet_hw_host.data(), sizeof(float) * pairs) == 0) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  FleetArrays fleet;
+  TRY(fleet_build(p, halfwidths, p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, &fleet));
+  fleet_commit(p, fleet);
+  p->fleet_hw_host.assign(halfwidths, halfwidths + pairs);
+  drop_graphs(p);
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_fleet(mppi_planner* p, int* on) {
+  REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  *on = p->fleet_on ? p->B : 0;
+  return MPPI_OK;
+}
+
 // The row of every problem's tracks that is "now".  It travels with the start state: a kernel argument of the classic
 // single launch, the problem's BatchInst otherwise -- no synchronisation, and nothing a captured graph holds.
 extern "C" int mppi_planner_set_track_offsets(mppi_planner* p, int count, const int* offsets) {
@@ -1240,10 +1377,57 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
 // largest traction byte that can be in the TDM's grid right now
 #include "launch_plan.h"
 
+// Fleet mode: every reader's rows from the robots' current controls and start states, on the planner's stream -- at the
+// head of every call that starts iterations (solve, iterate_async, the stage-level rollout, each control step of
+// closed_loop), once per call.  done: closed_loop's per-problem flags (a robot at its goal stands), else nullptr.
+// The arrays stay where they are: nothing a captured graph holds changes.
+static int fleet_refresh(mppi_planner* p, const int* done) {
+  if (!p->fleet_on) return MPPI_OK;
+  REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
+  REQUIRE(p->inst_set, MPPI_ERR_STATE, "num_instances = %d: call mppi_planner_set_instances before solving", p->B);
+  TRY(upload_instances(p));
+  const DevParams d = make_dev_params(p);
+  const int B = p->B, T = p->cfg.num_steps;
+  REQUIRE((size_t)T * sizeof(double2) <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large", T);  // (as launch_rollout)
+  const size_t lds = fleet_plans_lds_bytes(T);  // (28 bytes a step: 112 KiB at the 4096 steps the line above admits)
+  auto plans = p->cfg.math == MPPI_MATH_EXACT ? &k_fleet_plans<true> : &k_fleet_plans<false>;
+  if (lds > 64 * 1024)  // (a horizon of more than ~2300 steps)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(plans), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, p->fleet_plan);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_fleet_walls, dim3(ceil_div((long)B * (B - 1), 256), T), dim3(256), 0, p->stream, p->fleet_plan,
+                     p->fleet_seg_rows, B, T, p->fleet_slots);
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_fleet_refresh(mppi_planner* p) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(fleet_refresh(p, nullptr));
+  return drain_stream(p);
+}
+
+// seg: [B][B - 1][T][4] -- reader a's others in ascending order, row j the segment (ax ay bx by) of control interval j
+extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {
+  REQUIRE(p && seg, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
+  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)p->fleet_slots, pitch = B * S;
+  std::vector<float4> rows(pitch * T);
+  TRY(copy_out(p, rows.data(), p->fleet_seg_rows, sizeof(float4) * rows.size()));
+  for (size_t a = 0; a < B; ++a)
+    for (size_t k = 0; k + 1 < B; ++k)
+      for (size_t j = 0; j < T; ++j)
+        memcpy(seg + 4 * ((a * (B - 1) + k) * T + j), &rows[j * pitch + a * S + k], sizeof(float4));
+  return MPPI_OK;
+}
+
 extern "C" int mppi_planner_iterate_async(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, int iterations) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(iterations >= 0, MPPI_ERR_INVALID, "iterations < 0");
   HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(fleet_refresh(p, nullptr));
   return run_iterations(p, lin, ang, iterations);
 }
 
@@ -1403,6 +1587,7 @@ extern "C" int mppi_planner_solve(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang,
   TRY(check_tdms(p, lin, ang));
   TRY(sample_for_solve(p, lin, ang));
   p->mirror_done = false;
+  TRY(fleet_refresh(p, nullptr));
   TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false, /*mirror_last=*/true));
   const size_t u_bytes = sizeof(float2) * (size_t)p->B * (size_t)p->cfg.num_steps;
   // with at least one iteration the last update kernel has written the host-mapped mirror (a
@@ -1631,6 +1816,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
   for (int step = 0; step < max_steps; ++step) {
     TRY(sample_for_solve(p, lin, ang));
     if (step == 0) TRY(plan_loop());  // (needs the sampled grids packed: after the first draw)
+    TRY(fleet_refresh(p, p->loop_done));  // (fleet mode: the others' plans as the last control step left them)
     TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false));
     hipLaunchKernelGGL(k_world_step, dim3(B), dim3(256), sizeof(float2) * (size_t)T, p->stream, G, L, p->inst_dev, p->u,
                        T, step);
@@ -1720,6 +1906,7 @@ extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* an
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(fleet_refresh(p, nullptr));
   DevParams d;
   TRY(prepare_launch(p, lin, ang, &d));
   TRY(launch_rollout(p, d));

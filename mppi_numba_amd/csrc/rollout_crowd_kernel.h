@@ -59,6 +59,11 @@
 // goal is the count wave's goal distance, once per (step, lane): the counter that owns step c0 + j takes row
 // min(s + c0 + j + 1, rows - 1) of the problem's goal track -- a wave-uniform load -- where it took P.xg / P.yg.  The cost
 // wave, the walker and the wall code do not know.  Without the argument the kernel is what it was.
+//
+// A FLEET (mppi_planner_set_fleet; fleet_kernels.h): the per-problem wall sets are made by the library itself, of the
+// other problems' plans, ahead of every call -- so their row 0 is always "now".  One field of CrowdWallTracks says so
+// (relative): the walls' "now" is then 0 whatever the problem's track offset is, while the disc tracks and the goal track
+// of the same launch keep reading theirs at the offset.  Nothing else of the kernel knows.
 #pragma once
 #include <type_traits>
 
@@ -84,13 +89,16 @@ struct CrowdWalls {
 
 // The walls of a launch that move or differ from problem to problem (mppi_planner_set_wall_tracks): seg[row * pitch + k],
 // `pitch` walls per row (the sets of all problems side by side), halfwidth[k] static per wall.  range[b] = {wall0, count}:
-// problem b's walls within a row; nullptr: every problem has the walls [0, max_count).
+// problem b's walls within a row; nullptr: every problem has the walls [0, max_count).  relative != 0 (fleet mode,
+// mppi_planner_set_fleet): the rows are rebuilt ahead of every call and always counted from "now" -- step t meets row
+// min(t, rows - 1) whatever the problem's track offset is.
 struct CrowdWallTracks {
   const float4* seg;
   const float* halfwidth;
   const int2* range;
   int max_count;  // the largest problem's count
   int rows, pitch;
+  int relative;
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -201,11 +209,11 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   double d2 = 1e9;
   bool done = false, reached = false;
   [[maybe_unused]] const int last = P.track_rows - 1, now = min(max(P.track_off, 0), last);  // (an offset past the end: the last row)
-  // ... and the walls' "now": the same raw offset against the walls' own row count
+  // ... and the walls' "now": the same raw offset against the walls' own row count (fleet rows: always row 0)
   [[maybe_unused]] int wlast = 0, wnow = 0;
   if constexpr (WTRK) {
     wlast = walls.rows - 1;
-    wnow = min(max(P.track_off, 0), wlast);
+    wnow = walls.relative ? 0 : min(max(P.track_off, 0), wlast);
   }
   // ... and the goal track's
   [[maybe_unused]] int glast = 0, gnow = 0;
