@@ -1,0 +1,173 @@
+// barebone_launch.h -- the rollout launches of the barebone mode: barebone_choose (barebone_plan.h) decides, one launcher
+// per kernel family carries the choice out.  Included by launch_plan.h, between its launch helpers and launch_rollout_t.
+//
+// The default family, k_rollout_barebone (rollout_kernels.h): one workgroup per tile of 64 rollouts; on a batched handle one
+// launch over the B problems, one workgroup per tile of one problem.  Every problem's discs are a range of one pair of
+// arrays -- the shared set, the concatenated per-problem sets or the tracks -- named by its BatchInst (note_instance_discs).
+// The KD forms are chosen by the LARGEST problem's count; a smaller problem's slots past its own count hold the far,
+// radius-0 disc (+0.0 added), so every problem keeps the bits of its own single-problem launch.
+// The crowd family, k_rollout_barebone_crowd (rollout_crowd_kernel.h): crowd mode from kCrowdMinDiscs discs on, for sets
+// that do not fit in LDS, and for every launch with walls.
+#pragma once
+
+#include <type_traits>
+
+#include "barebone_plan.h"
+
+// What the choice depends on, from the handle (in the order of BareboneHeld's fields).  rot: (cos, sin) by rotation.
+static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
+  return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, p->crowd, p->n_obstacles, p->inst_obs_on, p->inst_obs_max,
+                      p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on};
+}
+
+// The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
+static const float2* barebone_disc_pos(const mppi_planner* p, const BareboneChoice& c) {
+  if (c.discs == kDiscsTracks) return c.family == kBareboneCrowd ? p->trk_pos_rows : p->trk_pos;
+  return c.discs == kDiscsOwn ? p->inst_obs_pos : p->obs_pos;
+}
+static const float* barebone_disc_rad(const mppi_planner* p, const BareboneChoice& c) {
+  return c.discs == kDiscsTracks ? p->trk_r : (c.discs == kDiscsOwn ? p->inst_obs_r : p->obs_r);
+}
+
+// The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.
+template <bool BATCHED>
+static GoalRows goal_rows_arg(const mppi_planner* p) {
+  return GoalRows{p->gtrk_xy, p->gtrk_rows, BATCHED && p->gtrk_count > 1 ? p->gtrk_rows : 0};
+}
+
+// The default family.  Static discs: <EXACT, ROT, KD, BATCHED>; disc tracks: the TRACKS forms, a row of disc slots per step;
+// a goal that moves (mppi_planner_set_goal_tracks): the TRACKS forms with the goal rows as one more argument -- static discs
+// are tracks of one row there (DevParams::track_rows = 1: every step's row of slots holds the same discs -- DESIGN.md
+// section 8: a static disc to the bit), so the goal track costs one template flag on the track forms and no form of its own.
+template <bool EXACT, bool BATCHED>
+static int launch_barebone_default(mppi_planner* p, DevParams d, const BareboneChoice& c, bool rot) {
+  const float2* pos = barebone_disc_pos(p, c);
+  const float* rad = barebone_disc_rad(p, c);
+  const bool tracks = c.discs == kDiscsTracks;
+  if (c.goal_form && !tracks) d.track_rows = 1;
+  const dim3 grid(ceil_div(p->n_local, 64)), block(64);
+  auto launch = [&](auto rot_c, auto kd_c) {
+    constexpr bool ROT = decltype(rot_c)::value;
+    constexpr int KD = decltype(kd_c)::value;
+    if (c.goal_form)
+      MPPI_KLAUNCH((k_rollout_barebone<EXACT, ROT, KD, BATCHED, true, GoalRows>), grid, block, c.lds, p->stream, d, pos, rad,
+                   p->noise, p->u, p->costs, goal_rows_arg<BATCHED>(p));
+    else if (c.track_form)
+      MPPI_KLAUNCH((k_rollout_barebone<EXACT, ROT, KD, BATCHED, true>), grid, block, c.lds, p->stream, d, pos, rad, p->noise,
+                   p->u, p->costs);
+    else
+      MPPI_KLAUNCH((k_rollout_barebone<EXACT, ROT, KD, BATCHED>), grid, block, c.lds, p->stream, d, pos, rad, p->noise, p->u,
+                   p->costs);
+  };
+  if (c.kd == 2) launch(std::true_type(), std::integral_constant<int, 2>());
+  else if (c.kd == 4) launch(std::true_type(), std::integral_constant<int, 4>());
+  else if (rot) launch(std::true_type(), std::integral_constant<int, -1>());
+  else launch(std::false_type(), std::integral_constant<int, -1>());
+  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot);
+  if (BATCHED || c.track_form)  // (the classic single launch of a static set names no disc form)
+    p->last_rollout += (c.kd > 0 ? " discs<=" + std::to_string(c.kd) : std::string(" discs=loop")) +
+                       (tracks ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                       (!c.track_form && c.discs == kDiscsOwn ? " own_discs=1" : "") +
+                       (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
+                       (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+// W waves per workgroup and C steps per chunk.  One tile is one workgroup whatever W is, so few tiles (N = 1000: 16 on
+// 256 CUs) get the whole 16 waves -- 14 counters -- and a launch that fills the device on its own gets fewer: about 32
+// waves per CU in all.  C: the largest multiple of the counters within kCrowdChunkMax, every counter the same share.
+static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
+  const int tiles = ceil_div(p->n_local, 64);
+  const int W = std::min(kCrowdWavesMax, std::max(4, (32 * p->num_cus) / tiles));
+  *waves = W;
+  *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
+}
+
+// The wall tracks as a launch takes them: the user's (rows counted from the problem's track offset), or in fleet mode the
+// sets the library makes of the other problems' plans (fleet_kernels.h; rows counted from "now": relative = 1).
+// (the classic single launch has one problem: the first set, which starts at wall 0)
+template <bool BATCHED>
+static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
+  if (p->fleet_on)
+    return CrowdWallTracks{p->fleet_seg_rows, p->fleet_hw, p->fleet_range, p->fleet_slots, p->cfg.num_steps, p->B * p->fleet_slots, 1};
+  const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
+  return CrowdWallTracks{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
+                         own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size(), 0};
+}
+
+// The crowd family: k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, wall argument, goal argument>.
+// The disc set: the tracks ([row][disc] copy), a problem's own static set, or the shared one.  The wall form of the
+// choice: 1, static walls shared by the problems (CrowdWalls), whatever the discs are; 2, wall tracks and per-problem sets
+// (CrowdWallTracks) -- they come first: while they are held the static walls rest -- and fleet mode, which takes the same
+// form with the sets it makes itself, the static walls copied into them.  A goal that moves: one GoalRows argument
+// more, behind the walls'.
+template <bool EXACT, bool BATCHED>
+static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const BareboneChoice& c, bool rot) {
+  int W = 0, C = 0;
+  crowd_shape(p, &W, &C);
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0);  // the size launched
+  if (c.walls == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
+  if (c.walls != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
+    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
+  const bool tracks = c.discs == kDiscsTracks;
+  const float2* pos = barebone_disc_pos(p, c);
+  const float* rad = barebone_disc_rad(p, c);
+  const int pitch = tracks ? (int)p->trk_r_host.size() : 0;
+  const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
+  auto launch = [&](auto kern, auto... extra) -> int {
+    if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, extra...);
+    return MPPI_OK;
+  };
+  auto dispatch = [&](auto rot_c, auto tracks_c) -> int {
+    constexpr bool ROT = EXACT && decltype(rot_c)::value, TRACKS = decltype(tracks_c)::value;
+    auto with_walls = [&](auto... walls) -> int {  // (without walls: the kernel and its arguments as they were before there were any)
+      constexpr bool WALLS = sizeof...(walls) > 0;
+      if (c.goal_form)
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, decltype(walls)..., GoalRows>, walls..., goal_rows_arg<BATCHED>(p));
+      return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, decltype(walls)...>, walls...);
+    };
+    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
+    if (c.walls == 1) return with_walls(CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls});
+    return with_walls();
+  };
+  if (rot && tracks) TRY(dispatch(std::true_type(), std::true_type()));
+  else if (rot) TRY(dispatch(std::true_type(), std::false_type()));
+  else if (tracks) TRY(dispatch(std::false_type(), std::true_type()));
+  else TRY(dispatch(std::false_type(), std::false_type()));
+  const bool fleet = c.walls == 2 && p->fleet_on;
+  p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
+                    " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
+                    (tracks ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
+                    (c.walls == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
+                    (c.walls == 2 && !fleet ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
+                    (fleet ? " walls=" + std::to_string(p->fleet_slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
+                                 " fleet=" + std::to_string(p->B) : std::string()) +
+                    (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+// A set that does not fit in 64 KiB of LDS while crowd mode is off.
+static int barebone_refuse(const BareboneChoice& c, int T) {
+  if (c.limit == kLimitGoalTrack)
+    return fail(MPPI_ERR_INVALID, "%d discs, %d steps and a goal track: %zu bytes, more than 64 KiB of LDS", c.kmax, T, c.lds);
+  if (c.limit == kLimitDiscTracks)
+    return fail(MPPI_ERR_INVALID, "%d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", c.kmax, T, c.lds);
+  return fail(MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", c.kmax, T);
+}
+
+// One barebone rollout launch: fill the state, choose, refuse or launch.  rot: (cos, sin) by rotation (launch_rollout_t).
+template <bool EXACT, bool BATCHED>
+static int launch_barebone(mppi_planner* p, DevParams d, bool rot) {
+  if (BATCHED) TRY(upload_instances(p));
+  const BareboneHeld held = barebone_held(p, rot);
+  const BareboneChoice c = barebone_choose(held);
+  if (!BATCHED) d.n_obstacles = c.kmax;  // (the classic single launch: the count is a kernel argument, the set the one chosen)
+  if (c.family == kBareboneRefused) return barebone_refuse(c, held.T);
+  if (c.family == kBareboneCrowd) return launch_barebone_crowd<EXACT, BATCHED>(p, d, c, rot);
+  return launch_barebone_default<EXACT, BATCHED>(p, d, c, rot);
+}

@@ -1,0 +1,98 @@
+// barebone_plan.h -- which kernel a barebone rollout launch runs, as a pure function of what the handle holds.
+// Plain C++ without a HIP type: a host program compiles it on its own (tests/test_barebone_plan.py pins the table).
+// barebone_held(p) (barebone_launch.h) fills the state from a handle; the launchers there carry a choice out.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+
+// Crowd mode (mppi_planner_set_crowd; rollout_crowd_kernel.h): from this many discs on -- the largest problem's count --
+// the rollout runs k_rollout_barebone_crowd.  Every form gives the same bits, so the crossover is a timing decision, to be
+// taken from tools/barebone_crowd_timing.py (solve() at N = 1000, T = 50, crowd off and on side by side; profiles/HISTORY.md,
+// "Barebone crowd mode").  NOT MEASURED YET: 5 is the lowest value the design allows -- up to four discs under rotation the
+// KD forms are a single basic block -- and tests/test_gpu_barebone_crowd.py expects the crowd kernel from five discs on.
+// Below it the default forms run (they fit: a set this small needs 16 * T * (1 + K) bytes at the most -- and where a long
+// horizon's tracks do not, the crowd kernel runs).
+constexpr int kCrowdMinDiscs = 5;
+
+constexpr size_t kBareboneLdsMax = 64 * 1024;  // what a launch of the default family may ask for
+
+// The LDS of k_rollout_barebone in bytes (rollout_kernels.h):
+//   [T] double2 control ratios | [slots] float4 discs                  the static forms
+//   [T] double2 control ratios | [T][slots] float4, a row per step     the track forms
+//   ... | [T] float2 goal positions behind the disc rows               the goal forms (track forms only)
+// A row has one slot at the least.  spare_slots: the classic single launch of a static set has always asked for its KD
+// padding on top of the set's own slots -- more than the kernel touches, but the dynamic LDS size is part of the launch.
+inline size_t barebone_lds(int T, int slots, bool track_form, bool goal_form, int spare_slots = 0) {
+  const size_t row = 16 * (size_t)std::max(1, slots);
+  return 16 * (size_t)T + (track_form ? (size_t)T * row : row) + (goal_form ? 8 * (size_t)T : 0) + 16 * (size_t)spare_slots;
+}
+
+// What the choice depends on.
+struct BareboneHeld {
+  int T = 0;
+  bool batched = false;  // one launch over the problems of mppi_planner_set_instances
+  bool rot = false;      // (cos, sin) by rotation (rotation_ok, exact math)
+  bool crowd = false;
+  int n_obstacles = 0;   // the shared static set
+  bool inst_obs_on = false;
+  int inst_obs_max = 0;  // a static set per problem: the largest
+  bool trk_on = false;
+  int trk_max = 0, trk_rows = 0;  // disc tracks: the largest problem's count
+  int n_walls = 0;
+  bool wtrk_on = false, fleet_on = false, gtrk_on = false;
+};
+
+enum BareboneFamily { kBareboneDefault = 0, kBareboneCrowd = 1, kBareboneRefused = 2 };
+enum BareboneDiscs { kDiscsShared = 0, kDiscsOwn = 1, kDiscsTracks = 2 };
+// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off)
+enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3 };
+
+struct BareboneChoice {
+  BareboneFamily family = kBareboneDefault;
+  BareboneDiscs discs = kDiscsShared;
+  int kmax = 0;             // the largest problem's disc count
+  int kd = -1;              // default family: disc slots fixed at compile time (2, 4), or -1: the run-time loop
+  bool track_form = false;  // default family: a row of disc slots per step (disc tracks, or static discs under a goal track)
+  bool goal_form = false;   // a goal that moves
+  int walls = 0;            // crowd family: 0 none, 1 static walls, 2 wall tracks / per-problem sets / fleet
+  size_t lds = 0;           // default family: the dynamic LDS launched
+  BareboneLimit limit = kLimitNone;
+};
+
+// Crowd mode: does a launch go to the crowd kernel?  own_lds: what the default form holds at the least.  Walls are the
+// crowd kernel's alone: a handle that holds any always goes there.
+inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
+  return h.crowd && (h.n_walls > 0 || h.wtrk_on || h.fleet_on || kmax >= kCrowdMinDiscs || own_lds > kBareboneLdsMax);
+}
+
+// The disc source: tracks take the place of both static sets, a problem's own set that of the shared one.  A goal that
+// moves runs the track forms (static discs as tracks of one row).  The KD forms are chosen by the largest problem's count
+// under rotation; a track form whose padded row does not fit falls back to the loop over the problem's own row.
+inline BareboneChoice barebone_choose(const BareboneHeld& h) {
+  BareboneChoice c;
+  c.discs = h.trk_on ? kDiscsTracks : (h.inst_obs_on ? kDiscsOwn : kDiscsShared);
+  c.kmax = h.trk_on ? h.trk_max : (h.inst_obs_on ? h.inst_obs_max : h.n_obstacles);
+  c.goal_form = h.gtrk_on;
+  c.track_form = h.trk_on || h.gtrk_on;
+  c.walls = (h.wtrk_on || h.fleet_on) ? 2 : (h.n_walls > 0 ? 1 : 0);
+  const size_t own_lds = barebone_lds(h.T, c.kmax, c.track_form, c.goal_form);
+  if (crowd_launch(h, c.kmax, own_lds)) {
+    c.family = kBareboneCrowd;
+    return c;
+  }
+  c.kd = !h.rot ? -1 : (c.kmax <= 2 ? 2 : (c.kmax <= 4 ? 4 : -1));
+  if (c.track_form && c.kd > 0 && barebone_lds(h.T, c.kd, true, c.goal_form) > kBareboneLdsMax) c.kd = -1;  // (a long horizon)
+  size_t checked;  // the size held against the limit
+  if (c.track_form || h.batched) {
+    checked = c.lds = barebone_lds(h.T, c.kd > 0 ? c.kd : c.kmax, c.track_form, c.goal_form);
+  } else {  // the classic single launch of a static set: checked without the padding, launched with it on top
+    checked = own_lds;
+    c.lds = barebone_lds(h.T, c.kmax, false, false, /*spare_slots=*/std::max(0, c.kd));
+  }
+  if (checked > kBareboneLdsMax) {
+    c.family = kBareboneRefused;
+    c.limit = c.goal_form ? kLimitGoalTrack : (c.track_form ? kLimitDiscTracks : kLimitStaticDiscs);
+  }
+  return c;
+}

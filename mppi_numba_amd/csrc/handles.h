@@ -387,14 +387,6 @@ static int count_sink_rings(int rows, int cols, F&& sink) {
   return rings;
 }
 
-// LDS of a barebone launch with disc tracks: [T] double2 control ratios | [T][slots] float4, a row of disc slots per step
-static size_t barebone_track_lds(int T, int slots) {
-  return sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)T * (size_t)std::max(1, slots);
-}
-
-// ... with a goal track behind the disc rows: [T] float2 more
-static size_t barebone_goal_lds(int T, int slots) { return barebone_track_lds(T, slots) + sizeof(float2) * (size_t)T; }
-
 static void drop_graphs(mppi_planner* p) {
   for (int i = 0; i < mppi_planner::kGraphSlots; ++i) {
     if (p->graph_exec[i]) (void)hipGraphExecDestroy(p->graph_exec[i]);

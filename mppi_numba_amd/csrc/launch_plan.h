@@ -1022,244 +1022,8 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   return MPPI_OK;
 }
 
-// The barebone mode on a batched handle: one launch over the B problems, one workgroup per tile of one problem
-// (k_rollout_barebone<..., BATCHED>).  Every problem's discs are a range of one pair of arrays -- the shared set, or the
-// concatenated per-problem sets -- named by its BatchInst (note_instance_discs).  The KD forms are chosen by the LARGEST
-// problem's count; a smaller problem's slots past its own count hold the far, radius-0 disc (+0.0 added), so every
-// problem keeps the bits of its own single-problem launch.
-// Discs that move (mppi_planner_set_disc_tracks): the track forms of k_rollout_barebone, one launch over the problems
-// of an instance handle or the classic single launch.  LDS: [T] double2 control ratios | [T][slots] float4, one row of
-// disc slots per step (barebone_track_lds); the KD forms where they fit, else the run-time loop over the largest
-// problem's count.
-// Crowd mode (mppi_planner_set_crowd; rollout_crowd_kernel.h): from this many discs on -- the largest problem's count --
-// the rollout runs k_rollout_barebone_crowd.  Every form gives the same bits, so the crossover is a timing decision, to be
-// taken from tools/barebone_crowd_timing.py (solve() at N = 1000, T = 50, crowd off and on side by side; profiles/HISTORY.md,
-// "Barebone crowd mode").  NOT MEASURED YET: 5 is the lowest value the design allows -- up to four discs under rotation the
-// KD forms are a single basic block -- and tests/test_gpu_barebone_crowd.py expects the crowd kernel from five discs on.
-// Below it the default forms run (they fit: a set this small needs 16 * T * (1 + K) bytes at the most -- and where a long
-// horizon's tracks do not, the crowd kernel runs).
-constexpr int kCrowdMinDiscs = 5;
-
-// W waves per workgroup and C steps per chunk.  One tile is one workgroup whatever W is, so few tiles (N = 1000: 16 on
-// 256 CUs) get the whole 16 waves -- 14 counters -- and a launch that fills the device on its own gets fewer: about 32
-// waves per CU in all.  C: the largest multiple of the counters within kCrowdChunkMax, every counter the same share.
-static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
-  const int tiles = ceil_div(p->n_local, 64);
-  const int W = std::min(kCrowdWavesMax, std::max(4, (32 * p->num_cus) / tiles));
-  *waves = W;
-  *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
-}
-
-// The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.
-template <bool BATCHED>
-static GoalRows goal_rows_arg(const mppi_planner* p) {
-  return GoalRows{p->gtrk_xy, p->gtrk_rows, BATCHED && p->gtrk_count > 1 ? p->gtrk_rows : 0};
-}
-
-// The wall tracks as a launch takes them: the user's (rows counted from the problem's track offset), or in fleet mode the
-// sets the library makes of the other problems' plans (fleet_kernels.h; rows counted from "now": relative = 1).
-// (the classic single launch has one problem: the first set, which starts at wall 0)
-template <bool BATCHED>
-static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
-  if (p->fleet_on)
-    return CrowdWallTracks{p->fleet_seg_rows, p->fleet_hw, p->fleet_range, p->fleet_slots, p->cfg.num_steps, p->B * p->fleet_slots, 1};
-  const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
-  return CrowdWallTracks{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
-                         own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size(), 0};
-}
-
-// WALLS: 0 none, 1 static walls shared by the problems (CrowdWalls), 2 wall tracks / per-problem sets (CrowdWallTracks)
-// GOALS: a goal that moves (mppi_planner_set_goal_tracks): one GoalRows argument more, behind the walls'
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, int WALLS, bool GOALS = false>
-static int launch_crowd_kernel_w(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
-  int W = 0, C = 0;
-  crowd_shape(p, &W, &C);
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, WALLS != 0);  // the size launched
-  if constexpr (WALLS == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
-  if constexpr (WALLS != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
-    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
-  const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
-  if constexpr (GOALS) {
-    const GoalRows goal = goal_rows_arg<BATCHED>(p);
-    auto launch = [&](auto kern, auto... walls) -> int {
-      if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls..., goal);
-      return MPPI_OK;
-    };
-    if constexpr (WALLS == 2) {
-      const CrowdWallTracks walls = wall_tracks_arg<BATCHED>(p);
-      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks, GoalRows>, walls));
-    } else if constexpr (WALLS == 1) {
-      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls, GoalRows>,
-                 CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls}));
-    } else {
-      TRY(launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, false, GoalRows>));
-    }
-  } else if constexpr (WALLS == 2) {
-    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWallTracks>;
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const CrowdWallTracks walls = wall_tracks_arg<BATCHED>(p);
-    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls);
-  } else if constexpr (WALLS == 1) {
-    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, true, CrowdWalls>;
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const CrowdWalls walls{p->wall_seg, p->wall_hw, p->n_walls};
-    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, walls);
-  } else {  // (the kernel and its arguments as they were before there were walls)
-    auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS>;
-    if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch);
-  }
-  p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)ROT) +
-                    " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
-                    (TRACKS ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
-                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                    (WALLS == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
-                    (WALLS == 2 && !p->fleet_on ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
-                    (WALLS == 2 && p->fleet_on ? " walls=" + std::to_string(p->fleet_slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
-                                                     " fleet=" + std::to_string(p->B) : std::string()) +
-                    (GOALS ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
-
-// A handle that holds walls (mppi_planner_set_walls) launches the WALLS form, whatever its discs are; wall tracks and
-// per-problem sets (mppi_planner_set_wall_tracks) come first: while they are held the static walls rest.  Fleet mode
-// (mppi_planner_set_fleet) takes the same path with the sets it makes itself, the static walls copied into them.
-template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS>
-static int launch_crowd_kernel(mppi_planner* p, const DevParams& d, const float2* pos, const float* rad, int pitch) {
-  if (p->gtrk_on) {  // (a goal that moves: the same three wall forms with the goal rows behind)
-    if (p->wtrk_on || p->fleet_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2, true>(p, d, pos, rad, pitch);
-    if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1, true>(p, d, pos, rad, pitch);
-    return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0, true>(p, d, pos, rad, pitch);
-  }
-  if (p->wtrk_on || p->fleet_on) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 2>(p, d, pos, rad, pitch);
-  if (p->n_walls > 0) return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 1>(p, d, pos, rad, pitch);
-  return launch_crowd_kernel_w<EXACT, ROT, BATCHED, TRACKS, 0>(p, d, pos, rad, pitch);
-}
-
-// The disc set a crowd launch reads: the tracks ([row][disc] copy), a problem's own static set, or the shared one.
-template <bool EXACT, bool BATCHED>
-static int launch_rollout_barebone_crowd(mppi_planner* p, DevParams d, bool rot) {
-  if (p->trk_on) {
-    if (!BATCHED) d.n_obstacles = p->trk_max;
-    const int pitch = (int)p->trk_r_host.size();
-    if (rot) return launch_crowd_kernel<EXACT, EXACT, BATCHED, true>(p, d, p->trk_pos_rows, p->trk_r, pitch);
-    return launch_crowd_kernel<EXACT, false, BATCHED, true>(p, d, p->trk_pos_rows, p->trk_r, pitch);
-  }
-  const bool own = p->inst_obs_on;
-  if (!BATCHED) d.n_obstacles = own ? p->inst_obs_max : p->n_obstacles;
-  const float2* pos = own ? p->inst_obs_pos : p->obs_pos;
-  const float* rad = own ? p->inst_obs_r : p->obs_r;
-  if (rot) return launch_crowd_kernel<EXACT, EXACT, BATCHED, false>(p, d, pos, rad, 0);
-  return launch_crowd_kernel<EXACT, false, BATCHED, false>(p, d, pos, rad, 0);
-}
-
-// Crowd mode: does this launch go to the crowd kernel?  kmax: the largest problem's disc count; default_lds: what the
-// default form would hold in LDS.  Walls are the crowd kernel's alone: a handle that holds any always goes there.
-static bool crowd_launch(const mppi_planner* p, int kmax, size_t default_lds) {
-  return p->crowd && (p->n_walls > 0 || p->wtrk_on || p->fleet_on || kmax >= kCrowdMinDiscs || default_lds > 64 * 1024);
-}
-
-template <bool EXACT, bool BATCHED>
-static int launch_rollout_barebone_tracks(mppi_planner* p, DevParams d, bool rot) {
-  const int N = p->n_local, T = p->cfg.num_steps, kmax = p->trk_max;
-  if (crowd_launch(p, kmax, barebone_track_lds(T, kmax))) return launch_rollout_barebone_crowd<EXACT, BATCHED>(p, d, rot);
-  int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
-  if (kd > 0 && barebone_track_lds(T, kd) > 64 * 1024) kd = -1;  // (a long horizon: the padded row does not fit, the problem's own may)
-  const size_t lds = barebone_track_lds(T, kd > 0 ? kd : kmax);  // the size launched
-  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, T, lds);
-  if (!BATCHED) d.n_obstacles = kmax;
-  const dim3 grid(ceil_div(N, 64)), block(64);
-  if (kd == 2)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
-  else if (kd == 4)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
-  else if (rot)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
-  else
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, BATCHED, true>), grid, block, lds, p->stream, d, p->trk_pos, p->trk_r, p->noise, p->u, p->costs);
-  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
-                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
-                    " tracks=" + std::to_string(p->trk_rows) +
-                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string());
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
-
-// A goal that moves (mppi_planner_set_goal_tracks): the default family launches its track forms only, with the goal rows
-// as one more argument.  Static discs are tracks of one row there (DevParams::track_rows = 1: every step's row of slots
-// holds the same discs -- DESIGN.md section 8: a static disc to the bit), so the goal track costs one template flag on the
-// sixteen track forms and no form of its own for static discs.  LDS: barebone_goal_lds, 8 * T bytes more than the track
-// forms'; a set that no longer fits goes to the crowd kernel in crowd mode and is refused otherwise.
-template <bool EXACT, bool BATCHED>
-static int launch_rollout_barebone_goal(mppi_planner* p, DevParams d, bool rot) {
-  const int N = p->n_local, T = p->cfg.num_steps;
-  const bool own = p->inst_obs_on;
-  const int kmax = p->trk_on ? p->trk_max : (own ? p->inst_obs_max : p->n_obstacles);
-  if (crowd_launch(p, kmax, barebone_goal_lds(T, kmax))) return launch_rollout_barebone_crowd<EXACT, BATCHED>(p, d, rot);
-  const float2* pos = p->trk_on ? p->trk_pos : (own ? p->inst_obs_pos : p->obs_pos);
-  const float* rad = p->trk_on ? p->trk_r : (own ? p->inst_obs_r : p->obs_r);
-  if (!p->trk_on) d.track_rows = 1;
-  int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
-  if (kd > 0 && barebone_goal_lds(T, kd) > 64 * 1024) kd = -1;  // (a long horizon: the padded row does not fit, the problem's own may)
-  const size_t lds = barebone_goal_lds(T, kd > 0 ? kd : kmax);  // the size launched
-  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d discs, %d steps and a goal track: %zu bytes, more than 64 KiB of LDS", kmax, T, lds);
-  if (!BATCHED) d.n_obstacles = kmax;
-  const dim3 grid(ceil_div(N, 64)), block(64);
-  const GoalRows goal = goal_rows_arg<BATCHED>(p);
-  if (kd == 2)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
-  else if (kd == 4)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
-  else if (rot)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
-  else
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, BATCHED, true, GoalRows>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, goal);
-  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
-                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
-                    (p->trk_on ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
-                    (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                    " goal_rows=" + std::to_string(p->gtrk_rows);
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
-
-template <bool EXACT>
-static int launch_rollout_barebone_batch(mppi_planner* p, const DevParams& d, bool rot) {
-  TRY(upload_instances(p));
-  if (p->gtrk_on) return launch_rollout_barebone_goal<EXACT, true>(p, d, rot);
-  if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, true>(p, d, rot);
-  const int N = p->n_local, T = p->cfg.num_steps;
-  const bool own = p->inst_obs_on;
-  const int kmax = own ? p->inst_obs_max : p->n_obstacles;
-  const float2* pos = own ? p->inst_obs_pos : p->obs_pos;
-  const float* rad = own ? p->inst_obs_r : p->obs_r;
-  if (crowd_launch(p, kmax, sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, kmax)))
-    return launch_rollout_barebone_crowd<EXACT, true>(p, d, rot);
-  const int kd = !rot ? -1 : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : -1));
-  // LDS: [T] double2 control ratios | one float4 per disc slot, the size launched
-  const size_t lds = sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, kd > 0 ? kd : kmax);
-  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, T);
-  const dim3 grid(ceil_div(N, 64)), block(64);
-  if (kd == 2)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
-  else if (kd == 4)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
-  else if (rot)
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, -1, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
-  else
-    MPPI_KLAUNCH((k_rollout_barebone<EXACT, false, -1, true>), grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs);
-  p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
-                    (kd > 0 ? " discs<=" + std::to_string(kd) : std::string(" discs=loop")) +
-                    (own ? " own_discs=1" : "") + " problems=" + std::to_string(p->B);
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
+// The barebone mode: the launch choice and one launcher per kernel family
+#include "barebone_launch.h"
 
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_t(mppi_planner* p, DevParams d) {
@@ -1270,35 +1034,10 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
     case MPPI_MODE_SPEED_MAP: return launch_rollout_speed_map<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_TDM: return launch_rollout_tdm<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_BAREBONE: {
-      const int N = p->n_local;
       p->tile_packets_fresh = false;
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
       const bool rot = EXACT && rotation_ok(p, d);
-      if (p->inst_set) return launch_rollout_barebone_batch<EXACT>(p, d, rot);
-      if (p->gtrk_on) return launch_rollout_barebone_goal<EXACT, false>(p, d, rot);
-      if (p->trk_on) return launch_rollout_barebone_tracks<EXACT, false>(p, d, rot);
-      // (one problem given its own set through mppi_planner_set_instance_disc_obstacles: the launch with that set)
-      const int K = p->inst_obs_on ? p->inst_obs_max : p->n_obstacles;
-      const float2* pos = p->inst_obs_on ? p->inst_obs_pos : p->obs_pos;
-      const float* rad = p->inst_obs_on ? p->inst_obs_r : p->obs_r;
-      d.n_obstacles = K;
-      const size_t lds_bb = sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)std::max(1, K);
-      if (crowd_launch(p, K, lds_bb)) return launch_rollout_barebone_crowd<EXACT, false>(p, d, rot);
-      REQUIRE(lds_bb <= 64 * 1024, MPPI_ERR_INVALID, "%d disc obstacles and %d steps: more than 64 KiB of LDS", K, p->cfg.num_steps);
-      if (rot && K <= 2)
-        MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 2>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 2 * sizeof(float4),
-                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
-      else if (rot && K <= 4)
-        MPPI_KLAUNCH((k_rollout_barebone<EXACT, true, 4>), dim3(ceil_div(N, 64)), dim3(64), lds_bb + 4 * sizeof(float4),
-                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
-      else if (rot)
-        MPPI_KLAUNCH((k_rollout_barebone<EXACT, true>), dim3(ceil_div(N, 64)), dim3(64), lds_bb,
-                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
-      else
-        MPPI_KLAUNCH((k_rollout_barebone<EXACT, false>), dim3(ceil_div(N, 64)), dim3(64), lds_bb,
-                     p->stream, d, pos, rad, p->noise, p->u, p->costs);
-      p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot);
-      break;
+      return p->inst_set ? launch_barebone<EXACT, true>(p, d, rot) : launch_barebone<EXACT, false>(p, d, rot);
     }
     default:
       return fail(MPPI_ERR_INVALID, "bad mode");

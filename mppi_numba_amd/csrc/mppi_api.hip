@@ -730,578 +730,8 @@ extern "C" int mppi_planner_set_params(mppi_planner* p, const mppi_params* param
   return MPPI_OK;
 }
 
-// Barebone mode: every problem's range of the disc arrays its launch gets (BatchInst::disc0, n_discs) -- its own set
-// (mppi_planner_set_instance_disc_obstacles) or the shared one.  Uploaded with the start states.
-static void note_instance_discs(mppi_planner* p) {
-  if (p->cfg.mode != MPPI_MODE_BAREBONE) return;
-  int k0 = 0;
-  for (int b = 0; b < p->B; ++b) {
-    BatchInst& I = p->inst_host[(size_t)b];
-    if (p->trk_on) {  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
-      const bool own = p->trk_counts_host.size() > 1;
-      I.disc0 = own ? k0 : 0;
-      I.n_discs = p->trk_counts_host[own ? (size_t)b : 0];
-    } else {
-      I.disc0 = p->inst_obs_on ? k0 : 0;
-      I.n_discs = p->inst_obs_on ? p->inst_obs_counts_host[(size_t)b] : p->n_obstacles;
-    }
-    k0 += I.n_discs;
-  }
-  p->inst_dirty = true;
-}
-
-extern "C" int mppi_planner_set_disc_obstacles(mppi_planner* p, const float* positions, const float* radii,
-                                               int count) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(count >= 0 && (count == 0 || (positions && radii)), MPPI_ERR_INVALID, "bad obstacle arrays");
-  // the barebone mirror hands the obstacles over with every solve() (the notebook uploads them per call,
-  // barebone_mppi_numba.ipynb cell 3): unchanged discs cost a comparison, not a synchronisation and two allocations
-  if (count == p->n_obstacles && (size_t)count * 2 == p->obs_pos_host.size() &&
-      (count == 0 || (memcmp(positions, p->obs_pos_host.data(), sizeof(float) * 2 * (size_t)count) == 0 &&
-                      memcmp(radii, p->obs_r_host.data(), sizeof(float) * (size_t)count) == 0)))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  dev_free(p->obs_pos);
-  dev_free(p->obs_r);
-  p->n_obstacles = 0;
-  p->obs_pos_host.clear();
-  p->obs_r_host.clear();
-  if (count > 0) {
-    TRY(dev_alloc(&p->obs_pos, (size_t)count));
-    TRY(dev_alloc(&p->obs_r, (size_t)count));
-    HIP_TRY(hipMemcpy(p->obs_pos, positions, sizeof(float2) * (size_t)count, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->obs_r, radii, sizeof(float) * (size_t)count, hipMemcpyHostToDevice));
-    p->obs_pos_host.assign(positions, positions + 2 * (size_t)count);
-    p->obs_r_host.assign(radii, radii + (size_t)count);
-  }
-  p->n_obstacles = count;
-  note_instance_discs(p);
-  drop_graphs(p);  // (the count is a by-value argument of the captured launches)
-  return MPPI_OK;
-}
-
-// Barebone batch: one disc set per problem.  Like set_disc_obstacles, unchanged arrays cost a comparison (the Python
-// mirror may hand them over with every solve); a change synchronises, reallocates and drops the captured graphs, whose
-// launches hold the arrays and the largest count.  count == 0: every problem back to the shared set.
-extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int count, const int* disc_counts,
-                                                        const float* positions, const float* radii) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc obstacles belong to the barebone mode (mode %d)",
-          p->cfg.mode);
-  REQUIRE(count == 0 || count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 or num_instances %d", count, p->B);
-  long total = 0;
-  int kmax = 0;
-  if (count > 0) {
-    REQUIRE(disc_counts, MPPI_ERR_INVALID, "NULL disc_counts");
-    for (int b = 0; b < count; ++b) {
-      REQUIRE(disc_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative disc count %d", b, disc_counts[b]);
-      total += disc_counts[b];
-      kmax = std::max(kmax, disc_counts[b]);
-    }
-    REQUIRE(total <= (1L << 30), MPPI_ERR_INVALID, "too many discs (%ld)", total);
-    REQUIRE(total == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
-    // what a launch holds in LDS: the control ratios and the largest problem's discs (launch_rollout_barebone_batch)
-    REQUIRE(p->crowd || sizeof(double2) * (size_t)p->cfg.num_steps + sizeof(float4) * (size_t)kmax <= 64 * 1024, MPPI_ERR_INVALID,
-            "a problem with %d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, p->cfg.num_steps);
-  }
-  if (count == 0 ? !p->inst_obs_on
-                 : (p->inst_obs_on && memcmp(disc_counts, p->inst_obs_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
-                    (total == 0 || (memcmp(positions, p->inst_obs_pos_host.data(), sizeof(float) * 2 * (size_t)total) == 0 &&
-                                    memcmp(radii, p->inst_obs_r_host.data(), sizeof(float) * (size_t)total) == 0))))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  dev_free(p->inst_obs_pos);
-  dev_free(p->inst_obs_r);
-  p->inst_obs_on = false;
-  p->inst_obs_max = 0;
-  p->inst_obs_counts_host.clear();
-  p->inst_obs_pos_host.clear();
-  p->inst_obs_r_host.clear();
-  drop_graphs(p);  // (the arrays and the largest count are arguments of the captured launches)
-  if (count > 0) {
-    TRY(dev_alloc(&p->inst_obs_pos, (size_t)total));
-    TRY(dev_alloc(&p->inst_obs_r, (size_t)total));
-    if (total > 0) {
-      HIP_TRY(hipMemcpy(p->inst_obs_pos, positions, sizeof(float2) * (size_t)total, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(p->inst_obs_r, radii, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
-    }
-    p->inst_obs_on = true;
-    p->inst_obs_max = kmax;
-    p->inst_obs_counts_host.assign(disc_counts, disc_counts + count);
-    p->inst_obs_pos_host.assign(positions, positions + 2 * (size_t)total);
-    p->inst_obs_r_host.assign(radii, radii + (size_t)total);
-  }
-  note_instance_discs(p);
-  return MPPI_OK;
-}
-
-// Crowd mode: the tracks the handle holds ([disc][row], trk_pos_host) once more as [row][disc] on the device.
-static int upload_track_rows(mppi_planner* p) {
-  dev_free(p->trk_pos_rows);
-  const size_t rows = (size_t)p->trk_rows, total = p->trk_r_host.size();
-  TRY(dev_alloc(&p->trk_pos_rows, std::max<size_t>(1, rows * total)));
-  if (rows * total == 0) return MPPI_OK;
-  std::vector<float2> by_row(rows * total);
-  for (size_t k = 0; k < total; ++k)
-    for (size_t r = 0; r < rows; ++r)
-      by_row[r * total + k] = make_float2(p->trk_pos_host[2 * (k * rows + r)], p->trk_pos_host[2 * (k * rows + r) + 1]);
-  HIP_TRY(hipMemcpy(p->trk_pos_rows, by_row.data(), sizeof(float2) * by_row.size(), hipMemcpyHostToDevice));
-  return MPPI_OK;
-}
-
-// Barebone mode: discs that move.  `rows` predicted centres per disc (row j: where it is j * dt from "now"), one set shared
-// by every problem (count == 1) or one per problem (count == B), laid out like the static per-problem sets.  Unchanged
-// arrays cost a comparison; a change synchronises, reallocates, drops the captured graphs and makes row 0 "now" again.
-extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const int* disc_counts, int rows,
-                                            const float* tracks, const float* radii) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
-          p->cfg.mode);
-  if (disc_counts == nullptr) count = 0;
-  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
-          "count %d: must be 0, 1 (one set for every problem) or num_instances %d", count, p->B);
-  long total = 0;
-  int kmax = 0;
-  if (count > 0) {
-    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
-    for (int b = 0; b < count; ++b) {
-      REQUIRE(disc_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative disc count %d", b, disc_counts[b]);
-      total += disc_counts[b];
-      kmax = std::max(kmax, disc_counts[b]);
-    }
-    REQUIRE(total * (long)rows <= (1L << 30), MPPI_ERR_INVALID, "too many track rows (%ld discs x %d)", total, rows);
-    REQUIRE(total == 0 || (tracks && radii), MPPI_ERR_INVALID, "NULL tracks or radii");
-    // what a launch holds in LDS at the least: the control ratios and a row of the largest problem's discs per step
-    const size_t lds = barebone_track_lds(p->cfg.num_steps, kmax);
-    REQUIRE(p->crowd || lds <= 64 * 1024, MPPI_ERR_INVALID,
-            "a problem with %d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, p->cfg.num_steps, lds);
-  }
-  const size_t n_pos = (size_t)total * (size_t)rows;
-  if (count == 0 ? !p->trk_on
-                 : (p->trk_on && rows == p->trk_rows && (size_t)count == p->trk_counts_host.size() &&
-                    memcmp(disc_counts, p->trk_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
-                    (total == 0 || (memcmp(tracks, p->trk_pos_host.data(), sizeof(float) * 2 * n_pos) == 0 &&
-                                    memcmp(radii, p->trk_r_host.data(), sizeof(float) * (size_t)total) == 0))))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  dev_free(p->trk_pos);
-  dev_free(p->trk_pos_rows);
-  dev_free(p->trk_r);
-  p->trk_on = false;
-  p->trk_rows = p->trk_max = 0;
-  p->trk_counts_host.clear();
-  p->trk_pos_host.clear();
-  p->trk_r_host.clear();
-  drop_graphs(p);  // (the arrays, the row count and the kernel form are arguments of the captured launches)
-  if (count > 0) {
-    TRY(dev_alloc(&p->trk_pos, std::max<size_t>(1, n_pos)));
-    TRY(dev_alloc(&p->trk_r, std::max<size_t>(1, (size_t)total)));
-    if (total > 0) {
-      HIP_TRY(hipMemcpy(p->trk_pos, tracks, sizeof(float2) * n_pos, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(p->trk_r, radii, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
-    }
-    p->trk_on = true;
-    p->trk_rows = rows;
-    p->trk_max = kmax;
-    p->trk_counts_host.assign(disc_counts, disc_counts + count);
-    p->trk_pos_host.assign(tracks, tracks + 2 * n_pos);
-    p->trk_r_host.assign(radii, radii + (size_t)total);
-    if (p->crowd) TRY(upload_track_rows(p));
-  }
-  for (BatchInst& I : p->inst_host) I.track_off = 0;
-  note_instance_discs(p);
-  return MPPI_OK;
-}
-
-// Crowd mode (include/mppi_hip.h).  Off -> on: the [row][disc] copy of the tracks the handle holds.  On -> off: only when
-// the default forms can launch every set the handle holds (the checks of the hand-overs and of the launches).
-extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  if ((on != 0) == p->crowd) return MPPI_OK;
-  const int T = p->cfg.num_steps;
-  if (!on) {
-    REQUIRE(p->n_walls == 0, MPPI_ERR_INVALID,
-            "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
-    REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
-            "crowd mode stays on: the handle holds wall tracks, which only the crowd kernel tests (clear them first)");
-    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
-            "crowd mode stays on: the handle is in fleet mode, whose walls only the crowd kernel tests (mppi_planner_set_fleet(p, 0, NULL) first)");
-    REQUIRE(!p->trk_on || barebone_track_lds(T, p->trk_max) <= 64 * 1024, MPPI_ERR_INVALID,
-            "crowd mode stays on: the disc tracks held (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
-            p->trk_max, T, barebone_track_lds(T, p->trk_max));
-    REQUIRE(!p->inst_obs_on || sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)p->inst_obs_max <= 64 * 1024, MPPI_ERR_INVALID,
-            "crowd mode stays on: the per-problem disc obstacles held (%d discs, %d steps) need more than 64 KiB of LDS",
-            p->inst_obs_max, T);
-    REQUIRE(sizeof(double2) * (size_t)T + sizeof(float4) * (size_t)std::max(1, p->n_obstacles) <= 64 * 1024, MPPI_ERR_INVALID,
-            "crowd mode stays on: the disc obstacles held (%d discs, %d steps) need more than 64 KiB of LDS", p->n_obstacles, T);
-    const int held = p->trk_on ? p->trk_max : (p->inst_obs_on ? p->inst_obs_max : p->n_obstacles);
-    REQUIRE(!p->gtrk_on || barebone_goal_lds(T, held) <= 64 * 1024, MPPI_ERR_INVALID,
-            "crowd mode stays on: the discs held with a goal track (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS",
-            held, T, barebone_goal_lds(T, held));
-  }
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if (on && p->trk_on) TRY(upload_track_rows(p));
-  if (!on) dev_free(p->trk_pos_rows);
-  p->crowd = on != 0;
-  drop_graphs(p);  // (the kernel form is part of the captured launches)
-  return MPPI_OK;
-}
-
-// ---- fleet mode (include/mppi_hip.h; fleet_kernels.h) ------------------------------------------------------------------------
-// The device arrays of a fleet: built new-first, so that a failure leaves the handle with what it had.
-struct FleetArrays {
-  float4* seg_rows = nullptr;
-  float* hw = nullptr;
-  int2* range = nullptr;
-  float2* plan = nullptr;
-  int slots = 0;
-};
-
-static void fleet_free(FleetArrays& f) {
-  dev_free(f.seg_rows);
-  dev_free(f.hw);
-  dev_free(f.range);
-  dev_free(f.plan);
-}
-
-// pair_hw: [B][B - 1] half-widths, reader a's others in ascending order; the static walls (W of them) behind the B - 1
-// others in every reader's slots and in every row.  Until the first refresh a fleet slot holds the wall nobody can touch.
-static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_seg, const float* wall_hw, int W, FleetArrays* out) {
-  const int B = p->B, T = p->cfg.num_steps, S = B - 1 + W;
-  const size_t pitch = (size_t)B * (size_t)S;
-  REQUIRE((long)pitch <= (1L << 24) && (long)pitch * (long)T <= (1L << 28), MPPI_ERR_INVALID,
-          "fleet of %d with %d static walls and %d steps: too many wall rows (%zu walls x %d)", B, W, T, pitch, T);
-  std::vector<float4> rows(pitch * (size_t)T);
-  std::vector<float> hw(pitch);
-  std::vector<int2> range((size_t)B);
-  for (int a = 0; a < B; ++a) {
-    range[(size_t)a] = make_int2(a * S, S);
-    for (int k = 0; k < S; ++k) {
-      const bool other = k < B - 1;
-      hw[(size_t)a * S + k] = other ? pair_hw[(size_t)a * (B - 1) + k] : wall_hw[k - (B - 1)];
-      const float* w = other ? nullptr : wall_seg + 4 * (size_t)(k - (B - 1));
-      const float4 sg = other ? make_float4(1e18f, 1e18f, 1e18f, 1e18f) : make_float4(w[0], w[1], w[2], w[3]);
-      for (int j = 0; j < T; ++j) rows[(size_t)j * pitch + (size_t)a * S + k] = sg;
-    }
-  }
-  FleetArrays f;
-  f.slots = S;
-  auto upload = [&]() -> int {
-    TRY(dev_alloc(&f.seg_rows, rows.size()));
-    TRY(dev_alloc(&f.hw, hw.size()));
-    TRY(dev_alloc(&f.range, range.size()));
-    TRY(dev_alloc(&f.plan, (size_t)B * (size_t)(T + 1)));
-    HIP_TRY(hipMemcpy(f.seg_rows, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(f.hw, hw.data(), sizeof(float) * hw.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(f.range, range.data(), sizeof(int2) * range.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(f.plan, 0, sizeof(float2) * (size_t)B * (size_t)(T + 1)));
-    return MPPI_OK;
-  };
-  const int rc = upload();
-  if (rc != MPPI_OK) {
-    fleet_free(f);
-    return rc;
-  }
-  *out = f;
-  return MPPI_OK;
-}
-
-// (the stream has drained) the handle takes the new arrays and a new generation
-static void fleet_commit(mppi_planner* p, const FleetArrays& f) {
-  dev_free(p->fleet_seg_rows);
-  dev_free(p->fleet_hw);
-  dev_free(p->fleet_range);
-  dev_free(p->fleet_plan);
-  p->fleet_seg_rows = f.seg_rows;
-  p->fleet_hw = f.hw;
-  p->fleet_range = f.range;
-  p->fleet_plan = f.plan;
-  p->fleet_slots = f.slots;
-  p->fleet_on = f.seg_rows != nullptr;
-  p->fleet_gen = p->fleet_on ? next_generation() : 0;
-}
-
-// Walls (include/mppi_hip.h): crowd mode only -- they are one more source of hits for the count waves of
-// k_rollout_barebone_crowd<..., WALLS> and nothing the default forms know.  Unchanged arrays cost a comparison; a change
-// synchronises, reallocates, takes a new generation (the graph signature's view of the walls) and drops the captured graphs.
-extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* halfwidths, int count) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "walls belong to the barebone mode (mode %d)", p->cfg.mode);
-  REQUIRE(count >= 0 && count <= (1 << 24) && (count == 0 || (segments && halfwidths)), MPPI_ERR_INVALID, "bad wall arrays (count %d)", count);
-  REQUIRE(count == 0 || p->crowd, MPPI_ERR_INVALID,
-          "walls need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
-  for (int k = 0; k < count; ++k) {
-    const float h = halfwidths[k];
-    REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "wall %d: half-width %g is negative or not finite", k, (double)h);
-    for (int i = 0; i < 4; ++i)
-      REQUIRE(std::isfinite(segments[4 * (size_t)k + i]), MPPI_ERR_INVALID, "wall %d: an endpoint coordinate is not finite", k);
-  }
-  if (count == p->n_walls &&
-      (count == 0 || (memcmp(segments, p->wall_seg_host.data(), sizeof(float) * 4 * (size_t)count) == 0 &&
-                      memcmp(halfwidths, p->wall_hw_host.data(), sizeof(float) * (size_t)count) == 0)))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  // fleet mode: these walls lie behind the other robots in every reader's set -- the fleet storage is rebuilt with the
-  // new walls, before anything the handle holds is touched
-  FleetArrays fleet;
-  if (p->fleet_on) {
-    TRY(fleet_build(p, p->fleet_hw_host.data(), segments, halfwidths, count, &fleet));
-    fleet_commit(p, fleet);
-  }
-  dev_free(p->wall_seg);
-  dev_free(p->wall_hw);
-  p->n_walls = 0;
-  p->wall_gen = 0;
-  p->wall_seg_host.clear();
-  p->wall_hw_host.clear();
-  drop_graphs(p);  // (the arrays, the count and the kernel form are arguments of the captured launches)
-  if (count > 0) {
-    TRY(dev_alloc(&p->wall_seg, (size_t)count));
-    TRY(dev_alloc(&p->wall_hw, (size_t)count));
-    HIP_TRY(hipMemcpy(p->wall_seg, segments, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->wall_hw, halfwidths, sizeof(float) * (size_t)count, hipMemcpyHostToDevice));
-    p->wall_seg_host.assign(segments, segments + 4 * (size_t)count);
-    p->wall_hw_host.assign(halfwidths, halfwidths + (size_t)count);
-    p->n_walls = count;
-    p->wall_gen = next_generation();
-  }
-  return MPPI_OK;
-}
-
-// Walls that move, and a wall set per problem (include/mppi_hip.h): crowd mode only, like the static walls.  `rows`
-// segments per wall, one set shared by every problem (count == 1) or one per problem (count == B), the sets one after the
-// other, each [wall][row].  The device keeps them [row][wall] -- a step's walls are contiguous -- with {wall0, count} per
-// problem beside them.  Unchanged arrays cost a comparison; a change synchronises, reallocates, takes a new generation,
-// drops the captured graphs and, for walls that move (rows > 1), makes row 0 "now" again.  Every argument is checked
-// before anything the handle holds is touched.
-extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_counts, int rows,
-                                            const float* segments, const float* halfwidths) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "wall tracks belong to the barebone mode (mode %d)", p->cfg.mode);
-  if (wall_counts == nullptr) count = 0;
-  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
-          "count %d: must be 0, 1 (one set for every problem) or num_instances %d", count, p->B);
-  long total = 0;
-  int wmax = 0;
-  if (count > 0) {
-    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
-            "the handle is in fleet mode, which owns the per-problem wall sets: turn it off first (mppi_planner_set_fleet(p, 0, NULL))");
-    REQUIRE(p->crowd, MPPI_ERR_INVALID,
-            "wall tracks need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
-    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a wall track has at least one row", rows);
-    for (int b = 0; b < count; ++b) {
-      REQUIRE(wall_counts[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative wall count %d", b, wall_counts[b]);
-      total += wall_counts[b];
-      wmax = std::max(wmax, wall_counts[b]);
-    }
-    REQUIRE(total <= (1L << 24) && total * (long)rows <= (1L << 28), MPPI_ERR_INVALID, "too many wall track rows (%ld walls x %d)", total, rows);
-    REQUIRE(total == 0 || (segments && halfwidths), MPPI_ERR_INVALID, "NULL segments or halfwidths");
-    for (long k = 0; k < total; ++k) {
-      const float h = halfwidths[k];
-      REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "wall %ld: half-width %g is negative or not finite", k, (double)h);
-    }
-    for (size_t i = 0; i < 4 * (size_t)total * (size_t)rows; ++i)
-      REQUIRE(std::isfinite(segments[i]), MPPI_ERR_INVALID, "wall %zu, row %zu: an endpoint coordinate is not finite",
-              i / 4 / (size_t)rows, i / 4 % (size_t)rows);
-  }
-  const size_t n_seg = (size_t)total * (size_t)rows;
-  if (count == 0 ? !p->wtrk_on
-                 : (p->wtrk_on && rows == p->wtrk_rows && (size_t)count == p->wtrk_counts_host.size() &&
-                    memcmp(wall_counts, p->wtrk_counts_host.data(), sizeof(int) * (size_t)count) == 0 &&
-                    (total == 0 || (memcmp(segments, p->wtrk_seg_host.data(), sizeof(float) * 4 * n_seg) == 0 &&
-                                    memcmp(halfwidths, p->wtrk_hw_host.data(), sizeof(float) * (size_t)total) == 0))))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  // the new device arrays first: a failed allocation or copy leaves the handle with what it had
-  float4* seg_rows = nullptr;
-  float* hw = nullptr;
-  int2* range = nullptr;
-  if (count > 0) {
-    std::vector<float4> by_row(std::max<size_t>(1, n_seg));
-    for (size_t k = 0; k < (size_t)total; ++k)
-      for (size_t r = 0; r < (size_t)rows; ++r) {
-        const float* s = segments + 4 * (k * (size_t)rows + r);
-        by_row[r * (size_t)total + k] = make_float4(s[0], s[1], s[2], s[3]);
-      }
-    std::vector<int2> ranges((size_t)count);
-    for (int b = 0, k0 = 0; b < count; k0 += wall_counts[b], ++b) ranges[(size_t)b] = make_int2(k0, wall_counts[b]);
-    auto upload = [&]() -> int {
-      TRY(dev_alloc(&seg_rows, by_row.size()));
-      TRY(dev_alloc(&hw, std::max<size_t>(1, (size_t)total)));
-      TRY(dev_alloc(&range, ranges.size()));
-      HIP_TRY(hipMemcpy(seg_rows, by_row.data(), sizeof(float4) * by_row.size(), hipMemcpyHostToDevice));
-      if (total > 0) HIP_TRY(hipMemcpy(hw, halfwidths, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(range, ranges.data(), sizeof(int2) * ranges.size(), hipMemcpyHostToDevice));
-      return MPPI_OK;
-    };
-    const int rc = upload();
-    if (rc != MPPI_OK) {
-      dev_free(seg_rows);
-      dev_free(hw);
-      dev_free(range);
-      return rc;
-    }
-  }
-  dev_free(p->wtrk_seg_rows);
-  dev_free(p->wtrk_hw);
-  dev_free(p->wtrk_range);
-  p->wtrk_seg_rows = seg_rows;
-  p->wtrk_hw = hw;
-  p->wtrk_range = range;
-  const bool moved = p->wtrk_rows > 1 || (count > 0 && rows > 1);  // (a set of one row is static: it leaves "now" alone)
-  p->wtrk_on = count > 0;
-  p->wtrk_rows = count > 0 ? rows : 0;
-  p->wtrk_max = wmax;
-  p->wtrk_gen = count > 0 ? next_generation() : 0;
-  p->wtrk_counts_host.assign(wall_counts, wall_counts + count);
-  p->wtrk_seg_host.assign(segments, segments + (total > 0 ? 4 * n_seg : 0));
-  p->wtrk_hw_host.assign(halfwidths, halfwidths + (total > 0 ? (size_t)total : 0));
-  drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
-  // new walls that move: row 0 is "now"; cleared: likewise unless disc tracks still count the rows
-  if (moved && (count > 0 || !p->trk_on)) {
-    for (BatchInst& I : p->inst_host) I.track_off = 0;
-    p->inst_dirty = true;
-  }
-  return MPPI_OK;
-}
-
-// A goal that moves (include/mppi_hip.h): `rows` positions per track, one track for every problem (count == 1) or one per
-// problem (count == B), [track][row].  Unchanged arrays cost a comparison; a change synchronises, builds the new device
-// copy before the old one is freed (a failure leaves the handle as it was), takes a new generation, drops the captured
-// graphs and, for a goal that moves (rows > 1), makes row 0 "now" again.
-extern "C" int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows, const float* xy) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "goal tracks belong to the barebone mode (mode %d)", p->cfg.mode);
-  REQUIRE(count == 0 || count == 1 || count == p->B, MPPI_ERR_INVALID,
-          "count %d: must be 0, 1 (one track for every problem) or num_instances %d", count, p->B);
-  size_t n_xy = 0;
-  if (count > 0) {
-    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a goal track has at least one row", rows);
-    REQUIRE((long)count * (long)rows <= (1L << 28), MPPI_ERR_INVALID, "too many goal track rows (%d tracks x %d)", count, rows);
-    REQUIRE(xy, MPPI_ERR_INVALID, "NULL xy");
-    n_xy = (size_t)count * (size_t)rows;
-    for (size_t i = 0; i < 2 * n_xy; ++i)
-      REQUIRE(std::isfinite(xy[i]), MPPI_ERR_INVALID, "goal track %zu, row %zu: a coordinate is not finite", i / 2 / (size_t)rows,
-              i / 2 % (size_t)rows);
-  }
-  if (count == 0 ? !p->gtrk_on
-                 : (p->gtrk_on && rows == p->gtrk_rows && count == p->gtrk_count &&
-                    memcmp(xy, p->gtrk_host.data(), sizeof(float) * 2 * n_xy) == 0))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float2* fresh = nullptr;
-  if (count > 0) {  // the new device array first: a failed allocation or copy leaves the handle with what it had
-    auto upload = [&]() -> int {
-      TRY(dev_alloc(&fresh, n_xy));
-      HIP_TRY(hipMemcpy(fresh, xy, sizeof(float2) * n_xy, hipMemcpyHostToDevice));
-      return MPPI_OK;
-    };
-    const int rc = upload();
-    if (rc != MPPI_OK) {
-      dev_free(fresh);
-      return rc;
-    }
-  }
-  dev_free(p->gtrk_xy);
-  p->gtrk_xy = fresh;
-  const bool moved = p->gtrk_rows > 1 || (count > 0 && rows > 1);  // (a track of one row is a static goal: it leaves "now" alone)
-  p->gtrk_on = count > 0;
-  p->gtrk_rows = count > 0 ? rows : 0;
-  p->gtrk_count = count;
-  p->gtrk_gen = count > 0 ? next_generation() : 0;
-  p->gtrk_host.assign(xy, xy + (count > 0 ? 2 * n_xy : 0));
-  drop_graphs(p);  // (the array, the row count and the kernel form are arguments of the captured launches)
-  // a new goal that moves: row 0 is "now"; cleared: likewise unless disc tracks or wall tracks still count the rows
-  if (moved && (count > 0 || !(p->trk_on || (p->wtrk_on && p->wtrk_rows > 1)))) {
-    for (BatchInst& I : p->inst_host) I.track_off = 0;
-    p->inst_dirty = true;
-  }
-  return MPPI_OK;
-}
-
-extern "C" int mppi_planner_get_crowd(mppi_planner* p, int* on) {
-  REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  *on = p->crowd ? 1 : 0;
-  return MPPI_OK;
-}
-
-// Fleet mode (include/mppi_hip.h): the storage is built here and whenever the static walls change, never at a refresh.
-extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* halfwidths) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  if (count == 0) {
-    if (!p->fleet_on) return MPPI_OK;
-    HIP_TRY(hipSetDevice(p->cfg.device));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    fleet_commit(p, FleetArrays());
-    p->fleet_hw_host.clear();
-    drop_graphs(p);  // (the arrays and the kernel form are arguments of the captured launches)
-    return MPPI_OK;
-  }
-  REQUIRE(p->B >= 2, MPPI_ERR_INVALID,
-          "fleet mode needs a batched handle of at least two problems, one per robot (num_instances %d)", p->B);
-  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 (off) or num_instances %d", count, p->B);
-  REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "fleet mode drives an unsharded handle");
-  REQUIRE(p->crowd, MPPI_ERR_INVALID,
-          "fleet mode needs crowd mode: only the crowd kernel tests walls (mppi_planner_set_crowd(p, 1) first)");
-  REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
-          "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
-          "first (mppi_planner_set_wall_tracks with count 0)");
-  REQUIRE(halfwidths, MPPI_ERR_INVALID, "NULL halfwidths");
-  const size_t pairs = (size_t)p->B * (size_t)(p->B - 1);
-  for (size_t k = 0; k < pairs; ++k) {
-    const float h = halfwidths[k];
-    REQUIRE(std::isfinite(h) && h >= 0.0f, MPPI_ERR_INVALID, "reader %zu, other slot %zu: half-width %g is negative or not finite",
-            k / (size_t)(p->B - 1), k % (size_t)(p->B - 1), (double)h);
-  }
-  if (p->fleet_on && memcmp(halfwidths, p->fleet_hw_host.data(), sizeof(float) * pairs) == 0) return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  FleetArrays fleet;
-  TRY(fleet_build(p, halfwidths, p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, &fleet));
-  fleet_commit(p, fleet);
-  p->fleet_hw_host.assign(halfwidths, halfwidths + pairs);
-  drop_graphs(p);
-  return MPPI_OK;
-}
-
-extern "C" int mppi_planner_get_fleet(mppi_planner* p, int* on) {
-  REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  *on = p->fleet_on ? p->B : 0;
-  return MPPI_OK;
-}
-
-// The row of every problem's tracks that is "now".  It travels with the start state: a kernel argument of the classic
-// single launch, the problem's BatchInst otherwise -- no synchronisation, and nothing a captured graph holds.
-extern "C" int mppi_planner_set_track_offsets(mppi_planner* p, int count, const int* offsets) {
-  REQUIRE(p && offsets, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
-          p->cfg.mode);
-  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d != num_instances %d of this handle", count, p->B);
-  for (int b = 0; b < count; ++b) REQUIRE(offsets[b] >= 0, MPPI_ERR_INVALID, "problem %d: negative track offset %d", b, offsets[b]);
-  for (int b = 0; b < count; ++b) p->inst_host[(size_t)b].track_off = offsets[b];
-  p->inst_dirty = true;
-  return MPPI_OK;
-}
-
-extern "C" int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets) {
-  REQUIRE(p && offsets, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc tracks belong to the barebone mode (mode %d)",
-          p->cfg.mode);
-  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d != num_instances %d of this handle", count, p->B);
-  for (int b = 0; b < count; ++b) offsets[b] = p->inst_host[(size_t)b].track_off;
-  return MPPI_OK;
-}
+// (barebone_api.h, included behind launch_plan.h below)
+static void note_instance_discs(mppi_planner* p);
 
 // Every entry point that waits for the planner's stream does it through this: the wait itself, then the words the
 // kernels of the drained launches may have raised -- a peer whose numbers did not arrive (MPPI_ERR_COMM), a rollout
@@ -1377,37 +807,8 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
 // largest traction byte that can be in the TDM's grid right now
 #include "launch_plan.h"
 
-// Fleet mode: every reader's rows from the robots' current controls and start states, on the planner's stream -- at the
-// head of every call that starts iterations (solve, iterate_async, the stage-level rollout, each control step of
-// closed_loop), once per call.  done: closed_loop's per-problem flags (a robot at its goal stands), else nullptr.
-// The arrays stay where they are: nothing a captured graph holds changes.
-static int fleet_refresh(mppi_planner* p, const int* done) {
-  if (!p->fleet_on) return MPPI_OK;
-  REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
-  REQUIRE(p->inst_set, MPPI_ERR_STATE, "num_instances = %d: call mppi_planner_set_instances before solving", p->B);
-  TRY(upload_instances(p));
-  const DevParams d = make_dev_params(p);
-  const int B = p->B, T = p->cfg.num_steps;
-  REQUIRE((size_t)T * sizeof(double2) <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large", T);  // (as launch_rollout)
-  const size_t lds = fleet_plans_lds_bytes(T);  // (28 bytes a step: 112 KiB at the 4096 steps the line above admits)
-  auto plans = p->cfg.math == MPPI_MATH_EXACT ? &k_fleet_plans<true> : &k_fleet_plans<false>;
-  if (lds > 64 * 1024)  // (a horizon of more than ~2300 steps)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(plans), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, p->fleet_plan);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_fleet_walls, dim3(ceil_div((long)B * (B - 1), 256), T), dim3(256), 0, p->stream, p->fleet_plan,
-                     p->fleet_seg_rows, B, T, p->fleet_slots);
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
-
-extern "C" int mppi_planner_fleet_refresh(mppi_planner* p) {
-  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  TRY(fleet_refresh(p, nullptr));
-  return drain_stream(p);
-}
+// the hand-overs of the barebone mode
+#include "barebone_api.h"
 
 // seg: [B][B - 1][T][4] -- reader a's others in ascending order, row j the segment (ax ay bx by) of control interval j
 extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {

@@ -378,3 +378,49 @@ def test_errors():
     single = MPPI_Numba(cfg)
     single.setup(make_params(cfg.dt, 1.0))
     assert np.isfinite(single.solve()).all()
+
+
+@pytest.mark.parametrize("kind", ["static", "tracks"])
+def test_a_set_handed_back_gives_the_first_result(kind):
+    """A hand-over builds the new device arrays before it frees the old ones (csrc/barebone_api.h, staged upload).  A set
+    of 2 discs per problem, one of 5, the first again: the third result is the first one's bit for bit, nothing of the
+    set in between is left.  tracks: crowd mode, so that the [row][disc] copy goes the same way."""
+    from mppi_numba_amd.barebone import MPPI_Batch
+    B, n, t, L = 2, 64, 8, 3
+    rng = np.random.default_rng(77)
+    cfg = make_cfg(n, t)
+    cfg.crowd = kind == "tracks"
+    x0s, goals = problems(rng, B)
+    params = make_params(cfg.dt, 1.0)
+
+    def sets_of(count):
+        # (within the 1.6 m the 8 steps can cover, so that rollouts hit them)
+        sets = [((x0s[b, :2] + rng.uniform(-1.2, 1.2, (count, 2))).astype(np.float32),
+                 rng.uniform(0.3, 0.7, count).astype(np.float32)) for b in range(B)]
+        if kind == "static":
+            return sets
+        return [((pos[:, None, :] + 0.1 * np.arange(L)[None, :, None]).astype(np.float32), rad) for pos, rad in sets]
+
+    small, large = sets_of(2), sets_of(5)
+    batch = MPPI_Batch(cfg, B)
+    batch.setup(params, x0s, goals, small)
+    u_in = rng.normal(0.5, 0.2, (B, t, 2)).astype(np.float32)
+    noise = rng.normal(0, 1, (B, n, t, 2)).astype(np.float32)
+
+    def result(sets):
+        batch.set_obstacle_sets(sets)
+        batch.set_u(u_in)
+        batch.set_noise(noise)
+        batch.rollout()
+        costs, kernel = batch.costs_d.copy_to_host(), batch.last_rollout_kernel()
+        batch.update()
+        return costs, batch.u_cur_d.copy_to_host(), kernel
+
+    first, between, again = result(small), result(large), result(small)
+    tail = " tracks=%d problems=%d" % (L, B) if kind == "tracks" else " own_discs=1 problems=%d" % B
+    assert first[2] == "k_rollout_barebone exact=1 rotation=1 discs<=2" + tail, first[2]
+    assert between[2].startswith("k_rollout_barebone_crowd" if kind == "tracks" else "k_rollout_barebone exact=1 rotation=1 discs=loop"), between[2]
+    assert again[2] == first[2]
+    assert (between[0] != first[0]).any(), "bad input: the larger sets change no cost"
+    assert_bits(again[0], first[0], "costs with the first sets handed back")
+    assert_bits(again[1], first[1], "controls with the first sets handed back")
