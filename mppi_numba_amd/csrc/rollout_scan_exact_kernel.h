@@ -1002,12 +1002,19 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
   //  measured: 2.2k cycles against 1.3k -- 200 four-byte stores at the very end of the launch)
   if (c == 2 || c == 3) {
     const int t = 64 * (c - 2) + lane;
+    // Costs are thousands of lambda apart: all but one to three of a tile's weights are exactly +0.0f (a weight is
+    // never -0.0f), and fmaf(+0, e, a) = a for finite e and every a but -0.0f -- which a sum that starts at +0.0f
+    // reaches only when a subnormal weight's product underflows, and whose sign combine_step's fma onto +0.0 drops.
+    // The weight is the same for all lanes: the rollouts that count, in order, from one ballot (a NaN weight counts).
+    const float wl = wsh[r];
+    uint32_t todo = (uint32_t)__ballot(lane < R && wl != 0.0f);
     if (t < T) {
       const float2* row = e2 + (size_t)t * R;
       const int sw = t & (R - 1);
       float ax = 0.0f, ay = 0.0f;
-#pragma unroll 8
-      for (int m = 0; m < R; ++m) {
+      while (todo != 0u) {
+        const int m = __builtin_ctz(todo);
+        todo &= todo - 1u;
         const float wm = wsh[m];
         const float2 en = row[m ^ sw];
         ax = fmaf(wm, en.x, ax);
