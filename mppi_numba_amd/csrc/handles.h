@@ -1,6 +1,7 @@
 // handles.h -- what the opaque handles of include/mppi_hip.h hold (included by mppi_api.hip only).
 #pragma once
 #include "host_common.h"
+#include "map_plan.h"
 
 // ---------------------------------------------------------------------------
 // TDM
@@ -45,7 +46,7 @@ struct mppi_tdm {
   // How many concentric rings of border cells carry ZERO traction in every grid a sampler can write (the padding ring of
   // terrain.py:511-583: a rollout that enters it never moves again, so none leaves the map as long as a step is no longer
   // than the ring is wide).  The exact schedule's state role computes its LDS address without a clamp only on maps where
-  // that -- or the reach bound -- proves the clamp idle (launch_plan.h: unclamped_lookup_ok); capped at kSinkRingCap.
+  // that -- or the reach bound -- proves the clamp idle (map_plan.h: map_unclamped_ok); capped at kSinkRingCap.
   static constexpr int kSinkRingCap = 16;
   int maps_sink_ring = 0, injected_sink_ring = 0;
   // samples sharded over GPUs (mppi_tdm_set_sample_shard): this handle's G grids are samples
@@ -71,20 +72,7 @@ struct PackedMaps {
   const int8_t* risk = nullptr;            // lin's risk map (speed-map mode)
 };
 
-// ---- k_rollout_scan / k_rollout_scan_exact: the launch geometry (launch_plan.h: scan_plan) --------
-struct ScanPlan {
-  int waves = 0;       // waves per workgroup: one per 8 steps (+ the three walkers of the exact kernel)
-  int chunk_waves = 0; // ... of which work on 8 steps each
-  int tile = 32;       // rollouts per workgroup: 32 (two lanes per rollout) or 64
-  size_t lds = 0;
-  bool pow2res = false;
-  bool exact = false;  // k_rollout_scan_exact: the three running sums walked with the reference's roundings
-  // k_rollout_scan_exact on a map the planner has stopped speculating on (round 5): every tile runs the exact
-  // three-wave schedule at once (ScanFallback::direct) -- noise, folded update and tile packets as ever, so the
-  // iteration stays one launch and the kernel family does not depend on the map
-  bool direct = false;
-  int fallback_offset = -1, fallback_map_bytes = 0, small_offset = 0;  // where the exact schedule's controls | window | ring and the small arrays live (direct)
-};
+// (struct ScanPlan, the launch geometry of k_rollout_scan / k_rollout_scan_exact: map_plan.h)
 
 // ---------------------------------------------------------------------------
 // planner
@@ -317,10 +305,10 @@ struct mppi_planner {
   // synchronised anyway it compares that with the LAUNCHES it made (a launch lasts as long as its slowest
   // tile: one failing tile stalls it) and, from one failed tile per two launches on, stops speculating
   // until the packed map changes.
-  // scan_plan()'s answer for the state it was derived from (launch_plan.h)
-  std::vector<unsigned char> scan_key;
-  ScanPlan scan_cached;
-  bool scan_cached_ok = false;
+  // map_choice()'s answer and the state it was computed from (launch_plan.h): a cache, no more
+  mutable MapHeld choice_held;
+  mutable MapChoice choice_cached;
+  mutable bool choice_valid = false;
   unsigned int* spec_fail_host = nullptr;  // pinned, device-mapped
   unsigned int* spec_fail_dev = nullptr;   // device view of the same word
   uint64_t spec_launches = 0;

@@ -254,140 +254,50 @@ static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nu
   return MPPI_OK;
 }
 
-// Decide whether the deterministic rollout can keep its map in LDS: the 16-bit cell
-// window must cover every cell reachable from x0 within the horizon and fit next to
-// the staged controls.  Fills the window fields of `d`.
-static bool plan_lds_window(mppi_planner* p, DevParams& d, size_t* lds_bytes) {
-  const int T = p->cfg.num_steps;
-  const size_t head = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);
-  const size_t budget = (size_t)p->lds_per_cu - 1024;  // leave room for the runtime's own use
-  if (!p->cells16_valid) return false;
-  if (p->cfg.mode == MPPI_MODE_SPEED_MAP ? !p->cells16_with_risk : p->cfg.mode != MPPI_MODE_DET) return false;
-  const size_t cell_bytes = p->cells16_with_risk ? sizeof(uint32_t) : sizeof(uint16_t);
+// ---- the map modes: what the launch choice depends on (map_plan.h), read off a handle ----------------------------
+static MapHeld map_held(const mppi_planner* p) {
   const mppi_params& a = p->params;
+  const PackedMaps& m = p->packed;
+  MapHeld h;
+  memset(&h, 0, sizeof(h));  // (padding included: the choice is cached on a memcmp of this)
+  h.mode = p->cfg.mode; h.math = p->cfg.math; h.debug_flags = p->debug_flags; h.speculation_off = p->speculation_off;
+  h.n_local = p->n_local; h.T = p->cfg.num_steps; h.num_cus = p->num_cus; h.lds_per_cu = p->lds_per_cu;
+  h.inst_set = p->inst_set; h.inst_tiles = p->inst_tiles; h.B = p->B;
+  h.cells16_valid = p->cells16_valid; h.cells16_with_risk = p->cells16_with_risk; h.pitch16 = p->pitch16;
+  h.rows = m.rows; h.cols = m.cols; h.lin_max_byte = m.lin_max_byte; h.ang_max_byte = m.ang_max_byte;
+  h.sink_ring = m.sink_ring; h.grid_packed = m.lin_grid != 0;
+  h.theta_bounded = p->theta_bounded;
+  h.lin_lo = m.lin_lo; h.lin_ratio = m.lin_ratio; h.ang_lo = m.ang_lo; h.ang_ratio = m.ang_ratio;
+  h.dt = a.dt; h.res = a.res; h.xlo = a.xlo; h.ylo = a.ylo;
+  h.vrange[0] = a.vrange[0]; h.vrange[1] = a.vrange[1]; h.wrange[0] = a.wrange[0]; h.wrange[1] = a.wrange[1];
+  h.x0 = a.x0[0]; h.y0 = a.x0[1];
+  return h;
+}
+
+// A window plan (map_plan.h: map_window) into the launch parameters, and a batched handle's per-problem window origins
+// into its host mirror -- the only place that writes them.  false: no LDS window.
+static bool apply_window(mppi_planner* p, const MapHeld& h, const WindowPlan& w, DevParams& d, size_t* lds_bytes) {
+  if (!w.cells) return false;
   d.pitch16 = p->pitch16;
-  const size_t whole = (size_t)d.rows * p->pitch16 * cell_bytes;
-  // cells reachable from x0 within the horizon (plus a margin), columns in multiples of 8
-  double vmax = std::fmax(std::fabs((double)a.vrange[0]), std::fabs((double)a.vrange[1]));
-  double trmax = std::fmax(std::fabs(d.lin_lo), std::fabs(d.lin_lo + (double)d.lin_max_byte * d.lin_ratio));
-  double reach_m = (double)T * (double)a.dt * vmax * trmax;
-  size_t bytes = whole + 1;
-  long r0 = 0, r1 = d.rows, c0 = 0, c1 = p->pitch16;
-  if (p->inst_set) {
-    // batched handle: one window SIZE for all problems (the full reach square, clipped to the
-    // map size), one ORIGIN per problem, shifted inwards at the map border
-    for (BatchInst& I : p->inst_host) I.win_r0 = I.win_c0 = 0;
-    d.win_step_cells = std::isfinite(reach_m) ? (float)((double)a.dt * vmax * trmax / (double)a.res) : 0.0f;
-    d.win_progressive = std::isfinite(reach_m) ? 1 : 0;
-    if (std::isfinite(reach_m)) {
-      long reach = (long)std::ceil(reach_m / (double)a.res) + 2;
-      long wr = std::min((long)d.rows, 2 * reach + 1);
-      long wc = std::min((long)p->pitch16, (2 * reach + 1 + 7) / 8 * 8 + 8);
-      size_t wbytes = (size_t)wr * (size_t)wc * cell_bytes;
-      if (wbytes < whole) {
-        if (head + wbytes > budget) return false;
-        for (BatchInst& I : p->inst_host) {
-          long xi0 = (long)std::floor(((double)I.x0 - (double)a.xlo) / (double)a.res);
-          long yi0 = (long)std::floor(((double)I.y0 - (double)a.ylo) / (double)a.res);
-          I.win_r0 = (int)std::min(std::max(0L, yi0 - reach), (long)d.rows - wr);
-          I.win_c0 = (int)std::min(std::max(0L, xi0 - reach) / 8 * 8, (long)p->pitch16 - wc);
-        }
-        d.win_r0 = 0; d.win_c0 = 0; d.win_rows = (int)wr; d.win_cols = (int)wc;
-        *lds_bytes = head + wbytes;
-        return true;
-      }
-    }
-    if (head + whole > budget) return false;
-    d.win_r0 = 0; d.win_c0 = 0; d.win_rows = d.rows; d.win_cols = p->pitch16;
-    *lds_bytes = head + whole;
-    return true;
-  }
-  if (std::isfinite(reach_m)) {
-    long reach = (long)std::ceil(reach_m / (double)a.res) + 2;
-    long xi0 = (long)std::floor(((double)a.x0[0] - (double)a.xlo) / (double)a.res);
-    long yi0 = (long)std::floor(((double)a.x0[1] - (double)a.ylo) / (double)a.res);
-    r0 = std::max(0L, yi0 - reach);
-    r1 = std::min((long)d.rows, yi0 + reach + 1);
-    c0 = std::max(0L, xi0 - reach) / 8 * 8;
-    c1 = std::min((long)p->pitch16, (std::min((long)d.cols, xi0 + reach + 1) + 7) / 8 * 8);
-    if (r1 > r0 && c1 > c0) bytes = (size_t)(r1 - r0) * (size_t)(c1 - c0) * cell_bytes;
-  }
-  // (either way the rollouts spread at most step_cells per step)
-  d.win_step_cells = std::isfinite(reach_m) ? (float)((double)a.dt * vmax * trmax / (double)a.res) : 0.0f;
-  d.win_progressive = std::isfinite(reach_m) ? 1 : 0;
-  if (bytes < whole) {  // the reach window is smaller: less to copy, more LDS left
-    if (head + bytes > budget) return false;
-    d.win_r0 = (int)r0; d.win_c0 = (int)c0; d.win_rows = (int)(r1 - r0); d.win_cols = (int)(c1 - c0);
-    *lds_bytes = head + bytes;
-    return true;
-  }
-  if (head + whole > budget) return false;
-  d.win_r0 = 0; d.win_c0 = 0; d.win_rows = d.rows; d.win_cols = p->pitch16;
-  *lds_bytes = head + whole;
+  d.win_step_cells = w.step_cells;
+  d.win_progressive = w.progressive;
+  if (p->inst_set)
+    for (BatchInst& I : p->inst_host) window_origin(h, w, I.x0, I.y0, &I.win_r0, &I.win_c0);
+  if (!w.ok) return false;
+  d.win_r0 = w.r0; d.win_c0 = w.c0; d.win_rows = w.rows; d.win_cols = w.cols;
+  *lds_bytes = w.lds;
   return true;
 }
 
-// The exact schedule's state role (rollout_kernels.h, PipeWindow<POW2RES = true>) forms its LDS address without the
-// [0, last] clamp -- one instruction per coordinate on the horizon's only dependent chain.  That is sound on a map no
-// rollout can leave: the reference's padded maps (a ring of zero-traction cells at least as wide as one step is long:
-// terrain.py:511-583 -- whoever enters it stays), or a reach square that lies strictly inside the map.  Anything else
-// (an mppi_tdm filled through the C API without such a ring, a window clipped by the border) takes the variant with the
-// exact floor division and the clamp, i.e. the border cell, like k_rollout_map and k_rollout_fused.
-static bool unclamped_lookup_ok(const mppi_planner* p, const DevParams& d) {
-  const mppi_params& a = p->params;
-  const double vmax = std::fmax(std::fabs((double)a.vrange[0]), std::fabs((double)a.vrange[1]));
-  const double trmax = std::fmax(std::fabs(d.lin_lo), std::fabs(d.lin_lo + (double)d.lin_max_byte * d.lin_ratio));
-  const double step_cells = (double)a.dt * vmax * trmax / (double)a.res;
-  if (!std::isfinite(step_cells)) return false;
-  if (p->packed.lin_grid && (double)p->packed.sink_ring >= std::ceil(step_cells + 1e-3)) return true;
-  if (p->inst_set) return false;  // (per-problem windows are shifted inwards at the border)
-  const double reach = std::ceil((double)p->cfg.num_steps * step_cells) + 2.0;
-  const double xi0 = std::floor(((double)a.x0[0] - (double)a.xlo) / (double)a.res);
-  const double yi0 = std::floor(((double)a.x0[1] - (double)a.ylo) / (double)a.res);
-  return yi0 - reach > 0.0 && yi0 + reach + 1.0 < (double)d.rows && xi0 - reach > 0.0 && xi0 + reach + 1.0 < (double)d.cols;
+// Decide whether the rollout can keep its map in LDS; fills the window fields of `d`.
+static bool plan_lds_window(mppi_planner* p, DevParams& d, size_t* lds_bytes) {
+  const MapHeld h = map_held(p);
+  return apply_window(p, h, map_window(h), d, lds_bytes);
 }
 
-// Incremental trig, (cos, sin) advanced by rotation: the host bounds the heading increment |dt * w * traction| by 0.36 rad
-// (barebone mode: traction 1) and the horizon by 2000 steps.
-static bool rotation_ok(const mppi_planner* p, const DevParams& d) {
-  const mppi_params& a = p->params;
-  const double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-  const double trmax = p->cfg.mode == MPPI_MODE_BAREBONE
-                           ? 1.0
-                           : std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-  const double dmax = (double)a.dt * wmax * trmax;
-  return std::isfinite(dmax) && dmax <= 0.36 && p->cfg.num_steps <= 2000;
-}
-
-// res == 2^k exactly: four-instruction cell coordinates
-static bool res_is_pow2(const mppi_planner* p) {
-  int res_exp = 0;
-  return std::frexp((double)p->params.res, &res_exp) == 0.5;
-}
-
-// Waves (tiles of 64 rollouts) per workgroup of the one-wave-per-tile kernels that keep the map
-// window in LDS.  The window makes it one workgroup per CU, so the workgroup is sized to cover
-// the problem in one round: at least 4 waves (one per SIMD, and enough lanes to copy the
-// window), at most 16.  Batched handle: a workgroup stays inside one problem, i.e. the count
-// divides the tiles per problem -- among the divisors the one with the fewest rounds, then the
-// smallest (1536 tiles: 8 waves in 1 round, not 4 waves in 2; measured 130 -> 105 us).
-static int fused_waves_per_workgroup(const mppi_planner* p, int n_rollouts) {
-  const int tiles = ceil_div(n_rollouts, 64);
-  int waves = ceil_div(tiles, p->num_cus);
-  waves = waves < 4 ? 4 : (waves > 16 ? 16 : waves);
-  if (!p->inst_set) return waves;
-  auto pick = [&](int lowest) {
-    int best = 0, best_rounds = 1 << 30;
-    for (int d = lowest; d <= 16; ++d) {
-      if (p->inst_tiles % d != 0) continue;
-      const int rounds = ceil_div(ceil_div(tiles, d), p->num_cus);
-      if (rounds < best_rounds) { best = d; best_rounds = rounds; }  // ascending: ties keep the smallest
-    }
-    return best;
-  };
-  const int at_least_four = pick(4);
-  return at_least_four ? at_least_four : pick(1);
-}
+// (the CVaR and barebone launchers ask these two on their own)
+static bool rotation_ok(const mppi_planner* p, const DevParams&) { return map_rotation_ok(map_held(p)); }
+static bool res_is_pow2(const mppi_planner* p) { return map_res_pow2(map_held(p)); }
 
 // per-problem start / goal / window origin -> device, when they changed
 static int upload_instances(mppi_planner* p) {
@@ -402,7 +312,7 @@ static int upload_instances(mppi_planner* p) {
 // set (mppi_planner_time_kernels) the runtime stamps the dispatch's own begin / end -- what
 // rocprofv3 reads -- into those events; with both null it is an ordinary launch.
 // (A launch whose noise came from the second stream and that does not look at the generator's flag itself is ordered
-//  behind it by the event, here, at the last moment: which kernel runs is decided deep inside the launch paths.)
+//  behind it by the event, here, at the last moment: the launchers know which kernel runs.)
 static void settle_noise_wait(mppi_planner* p) {
   if (!p->noise_wait_pending) return;
   p->noise_wait_pending = false;
@@ -437,118 +347,25 @@ static DevParams noise_flag_params(mppi_planner* p, DevParams d) {
 }
 
 
-// ---- k_rollout_scan (rollout_scan_kernel.h): the time-parallel rollout of MPPI_MATH_FAST --------
-// Eligible: deterministic-dynamics mode, 16-bit cells (the reference's own maps always are), a horizon
-// of at most 16 waves of 8 steps, LDS for the per-step records, and a map the speculation pays on.
-// (struct ScanPlan: handles.h -- the planner caches one)
-
-// Where k_rollout_scan_exact re-executes a tile on the exact schedule: in the LDS of the walks' groups and positions
-// (dead by then; unused in direct mode), or behind everything.  Returns the total LDS of the launch, 0: no room.
-static size_t scan_fallback_place(const mppi_planner* p, const DevParams& d, int W, size_t lds_now, int* offset, int* map_bytes_out) {
-  const size_t map_bytes = (size_t)d.win_rows * (size_t)d.win_cols * sizeof(uint16_t);
-  const size_t need = ScanFallback::bytes(8 * W, (int)map_bytes);
-  const size_t budget = (size_t)p->lds_per_cu - 1024;
-  const size_t total = (ScanExactLds::total(W) + 15) & ~(size_t)15;
-  if (need <= ScanExactLds::grp(W) + ScanExactLds::p2(W)) {
-    *offset = (int)(ScanExactLds::e2(W) + ScanExactLds::ccr(W));
-    *map_bytes_out = (int)map_bytes;
-    return lds_now;
+// ---- the launch choice of the map modes (map_plan.h: map_choose), cached on the state it was computed from ----------
+// It is asked several times per iteration (which kernel runs, whether it generates its noise, whether the next launch
+// can take this one's update, whether the peer exchange is usable).  map_choose is a pure function of MapHeld and the
+// key is the whole MapHeld: a hit cannot be stale.
+static const MapChoice& map_choice(const mppi_planner* p, const MapHeld& h) {
+  if (!p->choice_valid || memcmp(&p->choice_held, &h, sizeof(h)) != 0) {
+    p->choice_cached = map_choose(h);
+    p->choice_held = h;
+    p->choice_valid = true;
   }
-  if (total + need <= budget) {
-    *offset = (int)total;
-    *map_bytes_out = (int)map_bytes;
-    return std::max(lds_now, total + need);
-  }
-  return 0;
+  return p->choice_cached;
 }
 
-static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out);
-
-// scan_plan() is asked several times per iteration (which kernel runs, whether it generates its noise, whether the next
-// launch can take this one's update, whether the peer exchange is usable): the answer is cached on everything it is
-// derived from.  (Batched handles are planned afresh every time: their plan also rewrites the per-problem window origins.)
+// the next rollout launch runs a time-parallel kernel (k_rollout_scan, k_rollout_scan_exact): its geometry
 static bool scan_plan(const mppi_planner* p, ScanPlan* out) {
-  struct Key {
-    mppi_params params;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid;
-    int debug_flags, speculation_off, cells16_valid, cells16_with_risk, params_set, pad;
-  } key;
-  if (p->inst_set) return scan_plan_compute(p, out);
-  memset(&key, 0, sizeof(key));
-  key.params = p->params;
-  key.lin_maps = p->packed.lin_maps; key.lin_grid = p->packed.lin_grid;
-  key.ang_maps = p->packed.ang_maps; key.ang_grid = p->packed.ang_grid;
-  key.debug_flags = p->debug_flags; key.speculation_off = p->speculation_off; key.cells16_valid = p->cells16_valid;
-  key.cells16_with_risk = p->cells16_with_risk; key.params_set = p->params_set;
-  mppi_planner* q = const_cast<mppi_planner*>(p);  // (the cache only)
-  if (q->scan_key.size() != sizeof(key) || memcmp(q->scan_key.data(), &key, sizeof(key)) != 0) {
-    q->scan_cached_ok = scan_plan_compute(p, &q->scan_cached);
-    q->scan_key.assign(reinterpret_cast<const unsigned char*>(&key), reinterpret_cast<const unsigned char*>(&key) + sizeof(key));
-  }
-  if (q->scan_cached_ok && out) *out = q->scan_cached;
-  return q->scan_cached_ok;
-}
-
-static bool scan_plan_compute(const mppi_planner* p, ScanPlan* out) {
-  if (p->debug_flags & MPPI_DEBUG_NO_SCAN_KERNEL) return false;
-  // (round 6) the speed-map mode too: its dynamics run on nominal traction -- the walks' assumption by construction --
-  // and the risk byte comes with the (32-bit) cell; exact arithmetic only, no direct form (rollout_scan_exact_kernel.h)
-  const bool speed = p->cfg.mode == MPPI_MODE_SPEED_MAP;
-  if (p->cfg.mode != MPPI_MODE_DET && !speed) return false;
-  if (!p->cells16_valid || p->cells16_with_risk != speed) return false;
-  if (speed && p->cfg.math != MPPI_MATH_EXACT) return false;
-  // (MPPI_DEBUG_NO_SPECULATION: "the speculative kernels on their exact schedule from the first step" -- for this kernel
-  //  that is the direct launch, whatever the map has shown so far: how the tests reach it on any map)
-  const bool stopped = p->speculation_off && !(p->debug_flags & MPPI_DEBUG_KEEP_SPECULATING);
-  if (stopped && p->cfg.math != MPPI_MATH_EXACT) return false;  // (the tolerance kernel has no exact schedule inside)
-  const bool direct = (stopped || (p->debug_flags & MPPI_DEBUG_NO_SPECULATION)) && p->cfg.math == MPPI_MATH_EXACT;
-  if (direct && ((p->debug_flags & MPPI_DEBUG_NO_SCAN_DIRECT) || p->cfg.math != MPPI_MATH_EXACT ||
-                 !p->packed.lin_grid || speed))
-    return false;
-  const int T = p->cfg.num_steps;
-  ScanPlan plan;
-  plan.direct = direct;
-  plan.exact = p->cfg.math == MPPI_MATH_EXACT;
-  plan.chunk_waves = ceil_div(T, 8);
-  if (plan.exact && plan.chunk_waves > ScanExactLds::kMaxChunkWaves) return false;  // (T <= 104; beyond, k_rollout_pipe)
-  plan.waves = plan.exact ? ScanExactLds::waves(plan.chunk_waves) : plan.chunk_waves;
-  if (plan.waves > 16) return false;
-  plan.tile = (!plan.exact && (p->debug_flags & MPPI_DEBUG_SCAN_FULL_TILES)) ? 64 : 32;
-  // one round of workgroups over the CUs: beyond that the kernels with one wave per tile win (a
-  // 32-rollout workgroup lasts ~10 us whatever N is: N = 16384 would be two rounds against 18 us
-  // of k_rollout_pipe, N = 65536 eight against 78 us of k_rollout_fused)
-  if (ceil_div(p->n_local, plan.tile) > p->num_cus) return false;
-  plan.lds = plan.exact ? ScanExactLds::total(plan.chunk_waves)
-                        : (plan.tile == 64 ? ScanLds<64>::total(plan.waves) : ScanLds<32>::total(plan.waves));
-  // (the accumulating wave reads up to two groups of records past the last one: keep that inside the allocation)
-  plan.lds = std::max(plan.lds, (size_t)40 * 1024);
-  if (plan.lds > (size_t)p->lds_per_cu - 1024) return false;
-  plan.pow2res = res_is_pow2(p);
-  // (the template flag also selects the unclamped address of the exact schedule inside the kernel -- direct launches
-  //  and re-executed tiles: only where no rollout can leave the map)
-  const DevParams d0 = make_dev_params(p);
-  // (the speed-map form has no exact schedule inside: its lookups all clamp)
-  plan.pow2res = plan.pow2res && (speed || (p->packed.lin_grid && unclamped_lookup_ok(p, d0)));
-  if (plan.direct) {
-    // the exact schedule needs the 16-bit window of the cells reachable within the horizon in LDS, next to the noise,
-    // and the exact-increment rotation (|dt * w * traction| <= 0.36 rad): else k_rollout_pipe / the general kernels
-    DevParams d = d0;
-    size_t lds_win = 0;
-    // (a batched handle's per-problem window origins are recomputed into its host mirror: the values launch_rollout_det
-    //  computes from the same start states -- idempotent)
-    if (!plan_lds_window(const_cast<mppi_planner*>(p), d, &lds_win)) return false;
-    // LDS of a direct launch: noise | control-cost terms | {controls, window, ring} | small arrays (the walks' groups
-    // and positions do not exist)
-    const int W = plan.chunk_waves;
-    const size_t map_bytes = (size_t)d.win_rows * (size_t)d.win_cols * sizeof(uint16_t);
-    const size_t need = (ScanFallback::bytes(8 * W, (int)map_bytes) + 15) & ~(size_t)15;
-    plan.fallback_offset = (int)(ScanExactLds::e2(W) + ScanExactLds::ccr(W));
-    plan.fallback_map_bytes = (int)map_bytes;
-    plan.small_offset = plan.fallback_offset + (int)need;
-    plan.lds = std::max((size_t)plan.small_offset + ScanExactLds::small(W), (size_t)40 * 1024);
-    if (plan.lds > (size_t)p->lds_per_cu - 1024) return false;
-  }
-  if (out) *out = plan;
+  if (p->cfg.mode != MPPI_MODE_DET && p->cfg.mode != MPPI_MODE_SPEED_MAP) return false;
+  const MapChoice& c = map_choice(p, map_held(p));
+  if (c.family != kMapScan && c.family != kMapScanExact) return false;
+  if (out) *out = c.scan;
   return true;
 }
 
@@ -599,10 +416,9 @@ static PeerExchange make_peer_exchange(mppi_planner* p) {
 // (update_kernels.h, PendingApply::reduce_tiles): step t in workgroup t, at most two steps per idle walker wave.
 static bool tiles_can_reduce(int tiles, int n_steps) { return 4 * tiles >= n_steps; }
 
-static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan_in, bool have_window) {
-  ScanPlan plan = plan_in;
+static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan) {
   const int N = p->n_local, T = p->cfg.num_steps;
-  const bool speed = p->cfg.mode == MPPI_MODE_SPEED_MAP;
+  const bool speed = plan.speed;
   REQUIRE(!speed || (plan.exact && !plan.direct), MPPI_ERR_STATE, "internal: speed-map mode on a kernel that does not serve it");
   const int tiles = ceil_div(N, plan.tile);
   REQUIRE(p->tile_packets[0] && p->tile_packets[1], MPPI_ERR_STATE, "internal: no tile packet buffers on this handle");
@@ -654,21 +470,9 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
     if (p->p2p_on) pend.peers = make_peer_exchange(p);  // (advances the inbox set)
   }
   if (!plan.direct) p->spec_launches += 1;
-  // Exact kernel: where a tile whose vote fails is re-executed (rollout_scan_exact_kernel.h, scan_exact_reexecute):
-  // controls, 16-bit map window and one chunk ring in the LDS of the walks' groups and positions, dead by then --
-  // or behind everything when the horizon is too short for that region to hold them.
-  ScanFallback fallback = {-1, 0, 0, 0, 0};
-  fallback.rot_ok = rotation_ok(p, d) ? 1 : 0;  // the exact-increment rotation of the state role (as launch_rollout_det's)
-  if (plan.direct) {
-    REQUIRE(have_window && plan.fallback_offset >= 0, MPPI_ERR_STATE, "internal: direct exact schedule without its map window");
-    fallback.offset = plan.fallback_offset;
-    fallback.map_bytes = plan.fallback_map_bytes;
-    fallback.small_offset = plan.small_offset;
-    fallback.direct = 1;
-  } else if (plan.exact && have_window && !speed) {  // (speed-map: 32-bit cells, no exact schedule inside)
-    const size_t lds = scan_fallback_place(p, d, plan.chunk_waves, plan.lds, &fallback.offset, &fallback.map_bytes);
-    if (lds) plan.lds = lds;
-  }
+  // Exact kernel: where a tile whose vote fails is re-executed, or (direct) every tile runs (map_plan.h: map_scan)
+  REQUIRE(!plan.direct || plan.fallback_offset >= 0, MPPI_ERR_STATE, "internal: direct exact schedule without its map window");
+  const ScanFallback fallback = {plan.fallback_offset, plan.fallback_map_bytes, plan.direct ? 1 : 0, plan.rot_ok ? 1 : 0, plan.small_offset};
 #define MPPI_LAUNCH_SCAN_EXACT(P2, GEN)                                                                    \
   do {                                                                                                    \
     auto kern = speed ? k_rollout_scan_exact<P2, GEN, false, true>                                        \
@@ -734,239 +538,94 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
   return MPPI_OK;
 }
 
-// ---- deterministic-dynamics mode: which rollout kernel runs ------------------
-// Decided per launch from measurements (profiles/r06_families.md; history: r01_ablation.md, r02_stamps.md, r03_scan_notes.md):
-//   every tile of 32 rollouts a CU, T <= 104    k_rollout_scan_exact / k_rollout_scan (time-parallel; launch_scan above)
-//   one or two tiles of 64 per CU               k_rollout_pipe   (exact three-wave schedule)
-//   beyond (throughput regime)                  k_rollout_fused  (one wave per tile, 4..16 per CU)
-//   no LDS window / no incremental trig         k_rollout_map    (general)
-// (Rounds 2-5 had two speculative pipelines between the first two, k_rollout_deep and k_rollout_spec; re-measured at the
-//  end of round 6 against the exact pipeline and the throughput kernel on one box neither won by 5 % anywhere it was still
-//  selected -- k_rollout_spec lost by a factor of two at T = 200 -- and both were removed: profiles/r06_families.md.)
-struct DetRegime {
-  bool have_window;       // the 16-bit cell window reachable within the horizon fits in LDS
-  size_t lds_win;         // ... bytes of {staged controls, window}
-  bool rot_ok;            // incremental trig applies (|dt*w*traction| <= 0.36 rad, T <= 2000, exact math)
-  bool pow2res;           // resolution is a power of two: four-instruction cell coordinates
-  bool pow2res_unclamped; // ... and no rollout can leave the map: the exact schedule's address without a clamp (unclamped_lookup_ok)
-  bool rot_ok_fast;       // ... the same bound under MPPI_MATH_FAST (k_rollout_fused<one pass>)
-};
-
-static int try_launch_pipe(mppi_planner* p, DevParams& d, const DetRegime& r, bool* launched) {
-  *launched = false;
+// ---- the map modes: one launcher per kernel family, carrying out a choice (map_plan.h) ----------
+static int launch_pipe(mppi_planner* p, const DevParams& d, const MapChoice& c) {
   const int N = p->n_local, T = p->cfg.num_steps;
-  const bool pow2res = r.pow2res_unclamped;
-  const size_t lds_win = r.lds_win;
-  if (r.have_window && r.rot_ok) {
-    // pipelined kernel: the map window in LDS + the incremental trig
-    const size_t map_bytes = lds_win - sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);
-    int pairs = ceil_div(ceil_div(N, 64), p->num_cus);  // wave triples per workgroup
-    if (pairs < 1) pairs = 1;
-    if (pairs > kPipeMaxTriples) pairs = kPipeMaxTriples + 1;  // (beyond the kernel's launch bounds: the throughput kernel's)
-    // batched handle: the triples of a workgroup share one problem's window and controls
-    if (p->inst_set) while (p->inst_tiles % pairs != 0) --pairs;
-    const size_t budget = (size_t)p->lds_per_cu - 1024;
-    auto ring_bytes = [&](int chunk) {
-      return (size_t)pairs * (2 * (size_t)chunk * 64 * (sizeof(float2) + sizeof(double2)) + 2 * (size_t)chunk * 64 * 2);
-    };
-    int chunk = 0;
-    for (;;) {  // fewer triples per workgroup (more workgroups than CUs) before giving the kernel up
-      // (6: the whole-map window of the long horizons -- 135 KiB at T = 200 -- leaves room for chunks of six steps but
-      //  not of eight; every chunk costs ~340 cycles beside its steps, so six instead of four is 28 cycles per step)
-      for (int cnd : {8, 6, 4, 2})
-        if (lds_win + ring_bytes(cnd) <= budget) { chunk = cnd; break; }
-      if (chunk > 0 || pairs == 1) break;
-      --pairs;
-      if (p->inst_set) while (p->inst_tiles % pairs != 0) --pairs;
-    }
-    // The pipelined kernel is the low-latency choice: it wins while one workgroup per CU covers the problem with one
-    // wave triple, and with two when chunks of four steps at least fit beside the window (measured at the end of round 6,
-    // N x T, us per iteration pipe | fused: 8192 x 200 44 | 79; 16384 x 100 39 | 53; 16384 x 200 63 | 85;
-    // 32768 x 100 55 | 60; 32768 x 200 (chunks of two) 102 | 77; 49152 x 100 (three triples) 74 | 48:
-    // profiles/r06_families.md).  Beyond that the fused kernel, 4..16 waves per CU, has the better throughput.
-    const bool latency_regime = pairs <= kPipeMaxTriples && (pairs == 1 || chunk >= 4) && ceil_div(ceil_div(N, 64), pairs) <= p->num_cus;
-    if (chunk > 0 && latency_regime) {
-      // control-cost products in LDS when there is room, else in a global scratch array
-      const size_t cc_bytes = (size_t)pairs * T * 64 * sizeof(double);
-      const bool cc_lds = lds_win + ring_bytes(chunk) + cc_bytes <= budget && !(p->debug_flags & MPPI_DEBUG_CC_GLOBAL);
-      const size_t lds_total = lds_win + ring_bytes(chunk) + (cc_lds ? cc_bytes : 0);
-      const int block = 192 * pairs;
-      const int grid = ceil_div(N, 64 * pairs);
-      // spare CUs generate the next iteration's noise inside this launch (no spare CU: in line)
-      const int extra = p->next_noise_wanted && grid < p->num_cus ? p->num_cus - grid : 0;
-      const NoiseJob next_job = next_noise_job(p, extra);
-      if (!cc_lds && !p->cc_scratch) TRY(dev_alloc(&p->cc_scratch, (size_t)ceil_div(N, 64) * 64 * T));
-#define MPPI_LAUNCH_PIPE(CH, P2, CL)                                                                  \
-  do {                                                                                                \
-auto kern = k_rollout_pipe<CH, P2, CL>;                                                           \
-if (lds_total > 64 * 1024)                                                                        \
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total));       \
-MPPI_KLAUNCH(kern, dim3(grid + extra), dim3(block), lds_total, p->stream, d, p->cells16,    \
-                   p->noise, p->u, p->costs, p->w_rel, p->tile_beta, p->cc_scratch,                \
-                   (int)map_bytes, grid, next_job);                                                \
-  } while (0)
-#define MPPI_LAUNCH_PIPE_C(P2, CL)            \
-  do {                                        \
-if (chunk == 8) MPPI_LAUNCH_PIPE(8, P2, CL);      \
-else if (chunk == 6) MPPI_LAUNCH_PIPE(6, P2, CL); \
-else if (chunk == 4) MPPI_LAUNCH_PIPE(4, P2, CL); \
-else MPPI_LAUNCH_PIPE(2, P2, CL);                 \
-  } while (0)
-      if (pow2res && cc_lds) MPPI_LAUNCH_PIPE_C(true, true);
-      else if (pow2res) MPPI_LAUNCH_PIPE_C(true, false);
-      else if (cc_lds) MPPI_LAUNCH_PIPE_C(false, true);
-      else MPPI_LAUNCH_PIPE_C(false, false);
-#undef MPPI_LAUNCH_PIPE_C
-      {
-        char buf[256];
-        snprintf(buf, sizeof(buf),
-                 "k_rollout_pipe chunk=%d pow2res=%d cc_lds=%d triples_per_wg=%d window=%dx%d@(%d,%d) lds=%zu "
-                 "noise_blocks=%d problems=%d",
-                 chunk, (int)pow2res, (int)cc_lds, pairs, d.win_rows, d.win_cols, d.win_r0, d.win_c0, lds_total,
-                 extra, p->inst_set ? p->B : 0);
-        p->last_rollout = buf;
-      }
-#undef MPPI_LAUNCH_PIPE
-      p->tile_packets_fresh = true;
-      *launched = true;
-      return MPPI_OK;
-    }
-  }
+  // spare CUs generate the next iteration's noise inside this launch (no spare CU: in line)
+  const int extra = p->next_noise_wanted && c.grid < p->num_cus ? p->num_cus - c.grid : 0;
+  const NoiseJob next_job = next_noise_job(p, extra);
+  if (!c.cc_lds && !p->cc_scratch) TRY(dev_alloc(&p->cc_scratch, (size_t)ceil_div(N, 64) * 64 * T));
+  // the compile-time form: [chunk 8, 6, 4, 2][POW2RES][CC_LDS]
+#define MPPI_PIPE_FORMS(CH) \
+  {{k_rollout_pipe<CH, false, false>, k_rollout_pipe<CH, false, true>}, {k_rollout_pipe<CH, true, false>, k_rollout_pipe<CH, true, true>}}
+  static const decltype(&k_rollout_pipe<8, true, true>) forms[4][2][2] = {MPPI_PIPE_FORMS(8), MPPI_PIPE_FORMS(6), MPPI_PIPE_FORMS(4), MPPI_PIPE_FORMS(2)};
+#undef MPPI_PIPE_FORMS
+  const auto kern = forms[(8 - c.chunk) / 2][c.pow2res][c.cc_lds];
+  if (c.lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+  MPPI_KLAUNCH(kern, dim3(c.grid + extra), dim3(c.block), c.lds, p->stream, d, p->cells16, p->noise, p->u, p->costs, p->w_rel,
+               p->tile_beta, p->cc_scratch, c.map_bytes, c.grid, next_job);
+  char buf[256];
+  snprintf(buf, sizeof(buf),
+           "k_rollout_pipe chunk=%d pow2res=%d cc_lds=%d triples_per_wg=%d window=%dx%d@(%d,%d) lds=%zu "
+           "noise_blocks=%d problems=%d",
+           c.chunk, (int)c.pow2res, (int)c.cc_lds, c.triples, d.win_rows, d.win_cols, d.win_r0, d.win_c0, c.lds, extra,
+           p->inst_set ? p->B : 0);
+  p->last_rollout = buf;
+  p->tile_packets_fresh = true;
   return MPPI_OK;
 }
 
-template <bool EXACT, bool BOUNDED>
-static int launch_windowed_or_general(mppi_planner* p, DevParams& d, const DetRegime& r) {
-  const int N = p->n_local, T = p->cfg.num_steps;
-  const bool pow2res = r.pow2res;
-  const size_t lds_win = r.lds_win;
-  const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
-  if (r.have_window) {
-    // the window makes it one workgroup per CU: size the workgroup so that the grid
-    // is at most one wave of workgroups over the CUs
-    // (at least 4 waves: one per SIMD, and four times the lanes to copy the window)
-    const int waves = fused_waves_per_workgroup(p, N);
-    int block = 64 * waves;
-    if (r.rot_ok || r.rot_ok_fast) {
-      // (MPPI_MATH_FAST: one pass over the noise, the control cost added once)
-      // (round 6: workgroups of at most four waves -- nobody hides a wave's trips to memory: k_rollout_fused, LONE)
-      const bool lone = EXACT && waves <= 4;
-      auto fused = EXACT ? (lone ? (pow2res ? k_rollout_fused<true, false, false, true> : k_rollout_fused<false, false, false, true>)
-                                 : (pow2res ? k_rollout_fused<true> : k_rollout_fused<false>))
-                         : (pow2res ? k_rollout_fused<true, false, true> : k_rollout_fused<false, false, true>);
-      // Round 6 (exact mode reads the noise twice): what the window leaves of the CU's LDS keeps the noise of the first
-      // steps for the second pass -- one workgroup per CU either way (DevParams::stash_steps; N = 65536, T = 100: 56 of
-      // the 100 steps of each of the four waves)
-      size_t lds_fused = lds_win;
-      d.stash_steps = d.stash_offset = 0;
-      if (EXACT) {
-        const size_t off = (lds_win + 15) & ~(size_t)15, limit = (size_t)p->lds_per_cu - 1024;
-        if (limit > off) {
-          const int fit = (int)((limit - off) / ((size_t)waves * 64 * sizeof(float2)));
-          const int steps = std::min(fit, T) & ~7;
-          if (steps >= 8) {
-            d.stash_steps = steps;
-            d.stash_offset = (int)off;
-            lds_fused = off + (size_t)waves * (size_t)steps * 64 * sizeof(float2);
-          }
-        }
-      }
-      if (lds_fused > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fused),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused));
-      MPPI_KLAUNCH_WAITS_ITSELF(fused, dim3(ceil_div(N, block)), dim3(block), lds_fused, p->stream, noise_flag_params(p, d), p->cells16,
-                                p->noise, p->u, p->costs, p->w_rel, p->tile_beta);
-      char buf[200];
-      snprintf(buf, sizeof(buf), "k_rollout_fused%s pow2res=%d waves_per_wg=%d window=%dx%d problems=%d noise_kept=%d",
-               EXACT ? "" : "<one pass>", (int)pow2res, waves, d.win_rows, d.win_cols, p->inst_set ? p->B : 0, d.stash_steps);
-      p->last_rollout = buf;
-      p->tile_packets_fresh = true;
-            return MPPI_OK;
-    }
-    auto kern = k_rollout_map<MAP_DET, EXACT, BOUNDED, true>;
-    if (lds_win > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_win));
-    MPPI_KLAUNCH(kern, dim3(ceil_div(N, block)), dim3(block), lds_win, p->stream, d, p->cells,
-                       p->cells16, (const int8_t*)nullptr, p->noise, p->u, p->costs);
-    {
-      char buf[200];
-      snprintf(buf, sizeof(buf), "k_rollout_map det lds_window exact=%d waves_per_wg=%d window=%dx%d problems=%d",
-               (int)EXACT, waves, d.win_rows, d.win_cols, p->inst_set ? p->B : 0);
-      p->last_rollout = buf;
-    }
-  } else {
-    MPPI_KLAUNCH((k_rollout_map<MAP_DET, EXACT, BOUNDED, false>), dim3(ceil_div(N, 64)), dim3(64),
-                       lds_map, p->stream, d, p->cells, (const uint16_t*)nullptr, (const int8_t*)nullptr,
-                       p->noise, p->u, p->costs);
-    p->last_rollout = "k_rollout_map det global_cells exact=" + std::to_string((int)EXACT);
-  }
+// k_rollout_fused, the deterministic-dynamics and the speed-map forms
+static int launch_fused(mppi_planner* p, DevParams d, const MapChoice& c) {
+  const bool P2 = c.pow2res;
+  auto fused = c.speed ? (c.one_pass ? (P2 ? k_rollout_fused<true, true, true> : k_rollout_fused<false, true, true>)
+                                     : (P2 ? k_rollout_fused<true, true> : k_rollout_fused<false, true>))
+               : c.one_pass ? (P2 ? k_rollout_fused<true, false, true> : k_rollout_fused<false, false, true>)
+               : c.lone ? (P2 ? k_rollout_fused<true, false, false, true> : k_rollout_fused<false, false, false, true>)
+                        : (P2 ? k_rollout_fused<true> : k_rollout_fused<false>);
+  d.stash_steps = c.stash_steps;
+  d.stash_offset = c.stash_offset;
+  if (c.lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+  MPPI_KLAUNCH_WAITS_ITSELF(fused, dim3(c.grid), dim3(c.block), c.lds, p->stream, noise_flag_params(p, d), p->cells16,
+                            p->noise, p->u, p->costs, p->w_rel, p->tile_beta);
+  char buf[200];
+  int len = snprintf(buf, sizeof(buf), "k_rollout_fused%s%s pow2res=%d waves_per_wg=%d window=%dx%d problems=%d",
+                     c.one_pass ? "<one pass>" : "", c.speed ? " speed_map" : "", (int)P2, c.waves, d.win_rows, d.win_cols,
+                     p->inst_set ? p->B : 0);
+  if (!c.speed) snprintf(buf + len, sizeof(buf) - len, " noise_kept=%d", c.stash_steps);
+  p->last_rollout = buf;
+  p->tile_packets_fresh = true;
   return MPPI_OK;
 }
 
+// k_rollout_map: no incremental trig, or no LDS window
 template <bool EXACT, bool BOUNDED>
-static int launch_rollout_det(mppi_planner* p, DevParams d) {
+static int launch_general(mppi_planner* p, const DevParams& d, const MapChoice& c) {
+  const bool speed = p->cfg.mode == MPPI_MODE_SPEED_MAP;
+  const auto kern = c.windowed ? k_rollout_map<MAP_DET, EXACT, BOUNDED, true>
+                               : (speed ? k_rollout_map<MAP_SPEED, EXACT, BOUNDED, false> : k_rollout_map<MAP_DET, EXACT, BOUNDED, false>);
+  if (c.windowed && c.lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+  MPPI_KLAUNCH(kern, dim3(c.grid), dim3(c.block), c.lds, p->stream, d, p->cells,
+               c.windowed ? p->cells16 : (const uint16_t*)nullptr, (const int8_t*)(speed ? p->packed.risk : nullptr), p->noise, p->u, p->costs);
+  char buf[200];
+  if (c.windowed)
+    snprintf(buf, sizeof(buf), "k_rollout_map det lds_window exact=%d waves_per_wg=%d window=%dx%d problems=%d", (int)EXACT, c.waves,
+             d.win_rows, d.win_cols, p->inst_set ? p->B : 0);
+  else
+    snprintf(buf, sizeof(buf), "k_rollout_map %s global_cells exact=%d", speed ? "speed_map" : "det", (int)EXACT);
+  p->last_rollout = buf;
+  return MPPI_OK;
+}
+
+// deterministic-dynamics and speed-map mode: ask the choice, carry it out
+template <bool EXACT, bool BOUNDED>
+static int launch_rollout_map(mppi_planner* p, DevParams d) {
   p->tile_packets_fresh = false;
+  const MapHeld h = map_held(p);
+  const MapChoice c = map_choice(p, h);
   size_t lds_win = 0;
-  bool have_window = plan_lds_window(p, d, &lds_win);
+  (void)apply_window(p, h, c.window, d, &lds_win);
   TRY(upload_instances(p));
-  {
-    ScanPlan plan;
-    if (scan_plan(p, &plan)) return launch_scan(p, d, plan, have_window);
+  switch (c.family) {
+    case kMapScan:
+    case kMapScanExact: return launch_scan(p, d, c.scan);
+    case kMapPipe: TRY(launch_pipe(p, d, c)); break;
+    case kMapFused: TRY(launch_fused(p, d, c)); break;
+    case kMapGeneral: TRY((launch_general<EXACT, BOUNDED>(p, d, c))); break;
   }
-  const bool rot = rotation_ok(p, d);
-  DetRegime r;
-  r.have_window = have_window; r.lds_win = lds_win;
-  r.rot_ok = EXACT && BOUNDED && rot;
-  r.rot_ok_fast = !EXACT && p->theta_bounded && rot;
-  r.pow2res = res_is_pow2(p);
-  r.pow2res_unclamped = r.pow2res && unclamped_lookup_ok(p, d);
-  bool launched = false;
-  TRY(try_launch_pipe(p, d, r, &launched));
-  if (!launched) TRY((launch_windowed_or_general<EXACT, BOUNDED>(p, d, r)));
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
-}
-
-template <bool EXACT, bool BOUNDED>
-static int launch_rollout_speed_map(mppi_planner* p, DevParams d) {
-  const int N = p->n_local, T = p->cfg.num_steps;
-  const size_t lds_map = sizeof(double2) * ((size_t)T + (size_t)(T + 1) / 2);  // + staged u[t]
-  p->tile_packets_fresh = false;
-  size_t lds_win = 0;
-  const bool have_window = plan_lds_window(p, d, &lds_win);  // 32-bit cells: 16 bits + risk byte
-  TRY(upload_instances(p));
-  {
-    // latency regime (every tile of 32 rollouts a CU, T <= 104): the time-parallel kernel, one launch per iteration
-    ScanPlan plan;
-    if (scan_plan(p, &plan)) {
-      d.pitch16 = p->pitch16;
-      return launch_scan(p, d, plan, have_window);
-    }
-  }
-  if (have_window && (BOUNDED || (!EXACT && p->theta_bounded)) && rotation_ok(p, d)) {
-    const int waves = fused_waves_per_workgroup(p, N);
-    const bool pow2res = res_is_pow2(p);
-    auto fused = EXACT ? (pow2res ? k_rollout_fused<true, true> : k_rollout_fused<false, true>)
-                       : (pow2res ? k_rollout_fused<true, true, true> : k_rollout_fused<false, true, true>);
-    if (lds_win > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fused),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_win));
-    MPPI_KLAUNCH_WAITS_ITSELF(fused, dim3(ceil_div(N, 64 * waves)), dim3(64 * waves), lds_win, p->stream, noise_flag_params(p, d), p->cells16,
-                              p->noise, p->u, p->costs, p->w_rel, p->tile_beta);
-    char buf[200];
-    snprintf(buf, sizeof(buf), "k_rollout_fused%s speed_map pow2res=%d waves_per_wg=%d window=%dx%d problems=%d",
-             EXACT ? "" : "<one pass>", (int)pow2res, waves, d.win_rows, d.win_cols, p->inst_set ? p->B : 0);
-    p->last_rollout = buf;
-    p->tile_packets_fresh = true;
-    HIP_TRY(hipGetLastError());
-    return MPPI_OK;
-  }
-  MPPI_KLAUNCH((k_rollout_map<MAP_SPEED, EXACT, BOUNDED, false>), dim3(ceil_div(N, 64)), dim3(64),
-                     lds_map, p->stream, d, p->cells, (const uint16_t*)nullptr, (const int8_t*)p->packed.risk,
-                     p->noise, p->u, p->costs);
-  p->last_rollout = "k_rollout_map speed_map global_cells exact=" + std::to_string((int)EXACT);
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -1030,8 +689,8 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
   p->scan_packets_fresh = false;
   if (p->noise_virtual && !p->scan_gen_now) TRY(materialize_noise(p));  // the coming kernel reads its noise
   switch (p->cfg.mode) {
-    case MPPI_MODE_DET: return launch_rollout_det<EXACT, BOUNDED>(p, d);
-    case MPPI_MODE_SPEED_MAP: return launch_rollout_speed_map<EXACT, BOUNDED>(p, d);
+    case MPPI_MODE_DET:
+    case MPPI_MODE_SPEED_MAP: return launch_rollout_map<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_TDM: return launch_rollout_tdm<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_BAREBONE: {
       p->tile_packets_fresh = false;
@@ -1042,8 +701,6 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
     default:
       return fail(MPPI_ERR_INVALID, "bad mode");
   }
-  HIP_TRY(hipGetLastError());
-  return MPPI_OK;
 }
 
 
@@ -1062,15 +719,13 @@ static int launch_rollout(mppi_planner* p, const DevParams& d) {
   // |theta| can never exceed |theta0| + T*dt*max|w|*max(traction): when that is far
   // inside the range of the two-term pi/2 reduction, the kernels drop the libm branch
   const mppi_params& a = p->params;
-  double wmax = std::fmax(std::fabs((double)a.wrange[0]), std::fabs((double)a.wrange[1]));
-  double trmax = std::fmax(std::fabs(d.ang_lo), std::fabs(d.ang_lo + (double)d.ang_max_byte * d.ang_ratio));
-  if (p->cfg.mode == MPPI_MODE_BAREBONE) trmax = 1.0;
+  const MapReach reach = map_reach(map_held(p));
   double th0_max = std::fabs((double)a.x0[2]);
   if (p->inst_set) {
     th0_max = 0.0;
     for (const BatchInst& I : p->inst_host) th0_max = std::fmax(th0_max, std::fabs((double)I.th0));
   }
-  double theta_bound = th0_max + (double)p->cfg.num_steps * (double)a.dt * wmax * trmax;
+  double theta_bound = th0_max + (double)p->cfg.num_steps * (double)a.dt * reach.wmax * reach.trmax_ang;
   bool bounded = std::isfinite(theta_bound) && theta_bound < 5.0e4;
   p->theta_bounded = bounded;
   // mppi_planner_time_kernels on a two-stream loop: the kernels of the throughput regime stamp their own begin / end
@@ -1081,9 +736,6 @@ static int launch_rollout(mppi_planner* p, const DevParams& d) {
   return bounded ? launch_rollout_t<true, true>(p, dk) : launch_rollout_t<true, false>(p, dk);
 }
 
-// tile-relative weights (unless the rollout kernel just emitted them) + the row kernel:
-// applies the update on a single GPU; with several GPUs leaves this rank's packet in
-// packets[rank] for the exchange
 // ---- CVaR mode, samples sharded over GPUs: all-gather of the (N, M/G) cost slabs, then every
 //      rank reduces all N control samples over all M costs ---------------
 static int cvar_numel(const mppi_planner* p) {
@@ -1118,6 +770,9 @@ static int exchange_sample_costs(mppi_planner* p) {
   return launch_cvar_reduce(p);
 }
 
+// tile-relative weights (unless the rollout kernel just emitted them) + the row kernel:
+// applies the update on a single GPU; with several GPUs leaves this rank's packet in
+// packets[rank] for the exchange
 static int launch_update_local(mppi_planner* p, bool apply_here) {
   const int N = p->n_local, T = p->cfg.num_steps;
   const mppi_params& a = p->params;

@@ -1201,10 +1201,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)
     L.win_active = windowed && (plan.win_rows < plan.rows || plan.win_cols < p->pitch16) ? 1 : 0;
     if (L.win_active) {
-      const mppi_params& a = p->params;
-      double vmax = std::fmax(std::fabs((double)a.vrange[0]), std::fabs((double)a.vrange[1]));
-      double trmax = std::fmax(std::fabs(plan.lin_lo), std::fabs(plan.lin_lo + (double)plan.lin_max_byte * plan.lin_ratio));
-      L.reach = (int)((long)std::ceil((double)T * (double)a.dt * vmax * trmax / (double)a.res) + 2);
+      L.reach = (int)((long)std::ceil(map_reach(map_held(p)).reach_m / (double)p->params.res) + 2);
     }
     return MPPI_OK;
   };

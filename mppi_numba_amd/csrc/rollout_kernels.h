@@ -758,6 +758,7 @@ struct PipeRing {
   static constexpr int kHalf = C * 64;  // entries per buffer
   // xy[2][C][64] float2 + qd[2][C][64] double2 {dt*v, dt*w} + cell[2][C][64] uint16 (the 16-bit cell a step started in)
   static constexpr int kBytesPerPair = 2 * kHalf * (int)sizeof(float2) + 2 * kHalf * (int)sizeof(double2) + 2 * kHalf * 2;
+  static_assert(kBytesPerPair == pipe_ring_bytes(C), "lds_layouts.h sizes the launches by this ring");
 };
 
 // ---- the state role of the exact schedule: one chunk of C steps (round 5) --------------------------------------
@@ -769,7 +770,7 @@ struct PipeRing {
 // (float64 copies of the new state, the rotation of (cos, sin) by the exact heading increment, the ring stores) run in
 // its shadow (sched_barrier keeps the compiler from moving them back in front).  The instruction count per step is
 // cut as well: both cell coordinates in one packed float32 subtract and one packed fma; no clamp where the host has
-// proved it idle (POW2RES variant: a map no rollout can leave -- launch_plan.h, unclamped_lookup_ok; elsewhere the
+// proved it idle (POW2RES variant: a map no rollout can leave -- map_plan.h, map_unclamped_ok; elsewhere the
 // variant with the exact floor division clamps to the border cell); the raw 16-bit cell goes to the cost wave
 // instead of a shifted byte.  Same operations on the same operands as before: the oracle's bits.
 typedef float pipe_f2 __attribute__((ext_vector_type(2)));
@@ -802,7 +803,7 @@ struct PipeWindow {
       const pipe_f2 q = __builtin_elementwise_fma(pipe_f2{x, y} - lo, pipe_f2{inv_res, inv_res}, -origin);
       // (the instruction itself, not a C++ conversion -- which is undefined for a negative value: v_cvt_u32_f32 saturates
       //  at 0.  No upper clamp: the host selects this variant only where no rollout can leave the map, launch_plan.h:
-      //  unclamped_lookup_ok; the steps past the horizon of the last chunk may index beyond the window -- an LDS read of
+      //  map_unclamped_ok; the steps past the horizon of the last chunk may index beyond the window -- an LDS read of
       //  bytes nobody uses, or zero past the allocation)
       asm("v_cvt_u32_f32 %0, %1" : "=v"(xi) : "v"(q.x));
       asm("v_cvt_u32_f32 %0, %1" : "=v"(yi) : "v"(q.y));
@@ -1136,9 +1137,8 @@ __device__ __forceinline__ void pipe_tile_body(DevParams P, const uint16_t* __re
   }
 }
 
-// (at most two wave triples per workgroup -- launch_plan.h: try_launch_pipe --: six waves, so that the three roles' one
-//  register allocation may use 256 registers per lane instead of the 128 a workgroup of 1024 threads would leave)
-constexpr int kPipeMaxTriples = 2;
+// (at most two wave triples per workgroup -- kPipeMaxTriples, lds_layouts.h; map_plan.h: map_pipe --: six waves, so that the
+//  three roles' one register allocation may use 256 registers per lane instead of the 128 a workgroup of 1024 threads would leave)
 template <int C, bool POW2RES, bool CC_LDS>
 __global__ __launch_bounds__(192 * kPipeMaxTriples) void k_rollout_pipe(DevParams P, const uint16_t* __restrict__ cells16,
                                const float2* __restrict__ noise, const float2* __restrict__ u,

@@ -75,23 +75,7 @@ namespace mppi {
 #ifndef MPPI_SCAN_POLL_SLEEP
 #define MPPI_SCAN_POLL_SLEEP 2
 #endif
-struct ScanExactLds {
-  static constexpr int R = 32, CHL = 4, kMaxChunkWaves = 13;
-  // the waves a workgroup needs for W groups (walkers: waves 0, 4, 1; chunk waves: kGroupOfWave in the kernel)
-  __host__ __device__ static constexpr int waves(int W) {
-    constexpr int need[kMaxChunkWaves] = {6, 6, 6, 10, 10, 10, 14, 14, 14, 15, 16, 16, 16};  // 1 + the highest wave among groups 0 .. W-1 and the walkers
-    return need[W - 1];
-  }
-  __host__ __device__ static constexpr size_t plane(int W) { return (size_t)W * 8 * R * 8; }
-  __host__ __device__ static constexpr size_t e2(int W) { return plane(W); }
-  __host__ __device__ static constexpr size_t ccr(int W) { return plane(W); }
-  __host__ __device__ static constexpr size_t grp(int W) { return 2 * plane(W); }
-  __host__ __device__ static constexpr size_t p2(int W) { return (size_t)(W * 8 + 1) * R * 8; }
-  __host__ __device__ static constexpr size_t small(int W) {
-    return (size_t)W * 8 * (16 + 8) + R * 64 + 64 + 8 * (kMaxFoldedRanks + 2) + 8 * 16 * 4 + (size_t)2 * W * R * 16;
-  }
-  __host__ __device__ static constexpr size_t total(int W) { return e2(W) + ccr(W) + grp(W) + p2(W) + small(W); }
-};
+// (struct ScanExactLds, the sizes of these arrays: lds_layouts.h)
 
 // ---- a tile whose vote failed, re-executed on the exact three-wave schedule of k_rollout_pipe ---------------
 // (rollout_kernels.h, pipe_tile_body: the same operations on the same operands, i.e. the bits of k_rollout_map and
@@ -115,7 +99,7 @@ struct ScanFallback {
   // exchange of a multi-GPU run) does not change with the map.  The window copy is requested at kernel entry (LDS
   // nobody else uses in this mode), by the cost wave, straight into LDS.
   int direct;
-  // the host has proved |dt * w * traction| <= 0.36 rad for every step (launch_rollout_det's rot_ok): the state role
+  // the host has proved |dt * w * traction| <= 0.36 rad for every step (map_plan.h: map_rotation_ok): the state role
   // rotates (cos, sin) by the exact heading increment without looking at it.  (With the test inside the loop the
   // compiler lays the full evaluation out in line and the rotation behind a taken branch: 416 instead of 265 cycles
   // per step -- profiles/r05_pipe_notes.md)
@@ -123,9 +107,9 @@ struct ScanFallback {
   // direct mode: the walks' groups and positions do not exist; the region sits right behind the control-cost terms and
   // the small arrays (control ratios, weights, flags, u_sh ...) behind it, at this offset
   int small_offset;
-  static constexpr int kRingBytes = PipeRing<8>::kBytesPerPair;
-  __host__ __device__ static constexpr size_t bytes(int Tp, int map_bytes) { return (size_t)Tp * 8 + (size_t)map_bytes + kRingBytes; }
+  // (the bytes of the region: ScanFallbackLds, lds_layouts.h)
 };
+static_assert(ScanFallbackLds::kRingBytes == PipeRing<8>::kBytesPerPair, "the region holds one chunk ring of 8 steps");
 
 // us_ready (direct mode): the controls of the launch, [Tp] float2 in LDS already (u_sh), the window copied and a
 // workgroup barrier behind both -- nothing is staged and the schedule starts at once.  background(): what the waves

@@ -60,23 +60,7 @@ struct ScanPackets {
   int n_tiles;
 };
 
-template <int R>
-struct ScanLds {
-  static constexpr int S = 64 / R;     // lanes per rollout in a wave
-  static constexpr int CHL = 8 / S;    // steps per lane
-  // per workgroup of W waves (K = W * S chunks of CHL steps, Tp = 8 W steps)
-  __host__ __device__ static constexpr size_t rec(int W) { return (size_t)W * 64 * CHL * 8; }   // {sg, pen}[CHL] per (chunk, rollout)
-  __host__ __device__ static constexpr size_t ccr(int W) { return (size_t)W * 64 * CHL * 4; }   // cc[CHL]
-  __host__ __device__ static constexpr size_t e2(int W) { return (size_t)W * 8 * R * 8; }       // noise [Tp][R] float2
-  // + (a sharded iteration's update applied in this launch: update_kernels.h, PendingApply) the ranks'
-  //   scales and the updated controls [Tp] float2
-  __host__ __device__ static constexpr size_t small(int W) {
-    return (size_t)R * (16 + 8 + 8 + 4) + 64 + 8 * (kMaxFoldedRanks + 2) + (size_t)W * 64;
-  }
-  __host__ __device__ static constexpr size_t total(int W) { return rec(W) + ccr(W) + e2(W) + small(W); }
-  // the three float64 sums of phases A-C, [3][K][R], live where the records of phase D' go
-  static_assert(3 * 8 <= CHL * 8, "sums alias the records");
-};
+// (struct ScanLds<R>, the LDS of a workgroup: lds_layouts.h)
 
 // one Philox block -> the noise of steps (2*tp, 2*tp + 1) of global rollout `n_global`, with the
 // very expressions of noise_row (rng_kernels.h): the standalone generator reproduces it bit for bit

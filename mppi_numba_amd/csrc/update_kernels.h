@@ -21,6 +21,7 @@
 //   sum_n exp(-(c_n-beta)/l) x_n = sum_g exp(-(beta_g-beta)/l) * sum_{n in g} exp(-(c_n-beta_g)/l) x_n
 #pragma once
 #include "device_math.h"
+#include "lds_layouts.h"
 
 namespace mppi {
 
@@ -56,8 +57,7 @@ __device__ __forceinline__ void apply_update(float2* u, float2* u_prev, float2* 
 // (rollout_scan*.h) take the packets instead and form u[t] themselves -- every wave the 8 steps it
 // owns, with k_apply's expressions in k_apply's order (same bits on every rank); the first tile's
 // workgroup also stores the sequence, into the OTHER control buffer (the rest of the grid is still
-// reading the old one).  packets == nullptr: nothing pending, u is read as it is.
-constexpr int kMaxFoldedRanks = 16;
+// reading the old one).  packets == nullptr: nothing pending, u is read as it is.  (kMaxFoldedRanks: lds_layouts.h)
 
 // The peer exchange (no RCCL on the iteration's path).  Every rank owns an INBOX in fine-grained device memory:
 // [2 sets][world][T steps][4 words]; rank g's numbers for step t -- the doubles beta_g, den_g, num_g[t].x, num_g[t].y of
