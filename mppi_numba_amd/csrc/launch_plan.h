@@ -4,6 +4,7 @@
 // mppi_api.hip (which is the only file that includes this one: everything here has internal linkage).
 #pragma once
 #include "handles.h"
+#include "update_plan.h"
 
 static int tdm_max_byte(const mppi_tdm* t) { return t->injected ? (int)t->injected_max : t->table_max; }
 
@@ -374,6 +375,26 @@ static bool scan_generates_noise(const mppi_planner* p) {
   return !(p->debug_flags & MPPI_DEBUG_SCAN_READ_NOISE) && p->cfg.rng == MPPI_RNG_PHILOX && scan_plan(p, nullptr);
 }
 
+// ---- the update: what its choice depends on (update_plan.h), read off a handle -- the only place that does ----------
+// The arguments are launch_iteration's; a stage-level call has none.  launch_iteration adds what only it knows
+// (want_next, have_noise, side_stream_pays).
+static UpdateHeld update_held(const mppi_planner* p, bool prof = false, bool defer_exchange = false, bool may_leave_apply = false) {
+  UpdateHeld h;
+  memset(&h, 0, sizeof(h));
+  h.mode = p->cfg.mode; h.world_size = p->cfg.world_size; h.has_comm = p->comm != nullptr; h.m_count = p->m_count;
+  h.B = p->B; h.inst_set = p->inst_set; h.n_local = p->n_local; h.n_inst = p->n_inst; h.inst_tiles = p->inst_tiles;
+  h.T = p->cfg.num_steps; h.rng = p->cfg.rng;
+  h.debug_flags = p->debug_flags; h.fold_off = p->fold_off; h.p2p_on = p->p2p_on; h.graph_on = p->graph_on;
+  h.stream_flags_off = p->stream_flags_off; h.flags_env_off = noise_flag_disabled();
+  h.flag_words = p->noise_flag_dev && p->progress_dev;
+  h.prof = prof; h.defer_exchange = defer_exchange; h.may_leave_apply = may_leave_apply; h.mirror_now = p->mirror_now;
+  h.scan_packets_fresh = p->scan_packets_fresh; h.tile_packets_fresh = p->tile_packets_fresh; h.scan_tile = p->scan_tile;
+  ScanPlan next;
+  h.next_scan = scan_plan(p, &next);
+  h.next_tile = h.next_scan ? next.tile : 0;
+  return h;
+}
+
 // the noise of the last iteration into noise_buf when it exists as counters only
 static int materialize_noise(mppi_planner* p) {
   if (!p->noise_virtual) return MPPI_OK;
@@ -412,9 +433,7 @@ static PeerExchange make_peer_exchange(mppi_planner* p) {
   return X;
 }
 
-// One GPU: whether a rollout launch over `tiles` workgroups can combine its predecessor's tile packets itself
-// (update_kernels.h, PendingApply::reduce_tiles): step t in workgroup t, at most two steps per idle walker wave.
-static bool tiles_can_reduce(int tiles, int n_steps) { return 4 * tiles >= n_steps; }
+static PendingApply make_pending_apply(mppi_planner* p, int tiles);  // (with the update launches, below)
 
 static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan) {
   const int N = p->n_local, T = p->cfg.num_steps;
@@ -439,36 +458,12 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
     extra = p->num_cus - tiles;
   }
   const NoiseJob next_job = next_noise_job(p, extra);
-  // a sharded iteration whose update has not been applied yet: this launch does it (PendingApply)
-  PendingApply pend;
-  memset(&pend, 0, sizeof(pend));
-  if (p->apply_pending || p->reduce_pending) {
-    const mppi_params& a = p->params;
-    pend.packets = p->packets;
-    pend.u_out = p->u_alt;
-    pend.u_prev = p->u_prev;
-    pend.stats = p->stats;
-    pend.world = p->cfg.world_size;
-    pend.stride = p->B * packet_len(T);
-    pend.lambda = a.lambda_weight;
-    pend.v_lo = a.vrange[0]; pend.v_hi = a.vrange[1];
-    pend.w_lo = a.wrange[0]; pend.w_hi = a.wrange[1];
-  }
   if (p->reduce_pending) {
-    // the previous launch's tile packets, combined and applied by this launch (no update kernel ran); several GPUs:
-    // with the peer exchange in between
     REQUIRE(!p->apply_pending, MPPI_ERR_STATE, "internal: tile packets left to a launch that cannot reduce them");
     REQUIRE(tiles_can_reduce(tiles, T) && plan.tile == p->scan_tile, MPPI_ERR_STATE, "internal: %d workgroups cannot combine the tile packets of %d steps", tiles, T);
-    pend.packets = p->packets;  // (not read in this mode; non-null: "an update is pending")
-    pend.world = 1;
-    pend.reduce_tiles = p->tile_packets[p->tpk_cur];
-    pend.reduce_n_tiles = ceil_div(N, p->scan_tile);
-    pend.published = p->published;
-    pend.flag_set = p->reduce_index & 1;
-    pend.fault = p->fold_fault_dev;
-    pend.max_polls = p->fold_max_polls;
-    if (p->p2p_on) pend.peers = make_peer_exchange(p);  // (advances the inbox set)
   }
+  // an update left to this launch (launch_update): the rank packets, or the previous launch's `tiles` tile packets
+  const PendingApply pend = make_pending_apply(p, tiles);
   if (!plan.direct) p->spec_launches += 1;
   // Exact kernel: where a tile whose vote fails is re-executed, or (direct) every tile runs (map_plan.h: map_scan)
   REQUIRE(!plan.direct || plan.fallback_offset >= 0, MPPI_ERR_STATE, "internal: direct exact schedule without its map window");
@@ -705,7 +700,6 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
 
 
 static int launch_apply(mppi_planner* p);
-static bool next_rollout_reduces_tiles(const mppi_planner* p);
 static int settle_reduce_pending(mppi_planner* p);
 
 static int launch_rollout(mppi_planner* p, const DevParams& d) {
@@ -714,8 +708,11 @@ static int launch_rollout(mppi_planner* p, const DevParams& d) {
   REQUIRE((size_t)p->cfg.num_steps * sizeof(double2) <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large",
           p->cfg.num_steps);
   // an update left to its consumer (launch_update) and a rollout kernel that will not take it
-  if (p->apply_pending && !(p->cfg.mode == MPPI_MODE_DET && scan_plan(p, nullptr))) TRY(launch_apply(p));  // (sharded updates fold in deterministic-dynamics mode only)
-  if (p->reduce_pending && !next_rollout_reduces_tiles(p)) TRY(settle_reduce_pending(p));
+  if (p->apply_pending || p->reduce_pending) {
+    const UpdateHeld held = update_held(p);
+    if (p->apply_pending && !rollout_keeps_pending_packets(held)) TRY(launch_apply(p));  // (sharded updates fold in deterministic-dynamics mode only)
+    if (p->reduce_pending && !next_rollout_takes(held).reduces_tiles) TRY(settle_reduce_pending(p));
+  }
   // |theta| can never exceed |theta0| + T*dt*max|w|*max(traction): when that is far
   // inside the range of the two-term pi/2 reduction, the kernels drop the libm branch
   const mppi_params& a = p->params;
@@ -770,86 +767,68 @@ static int exchange_sample_costs(mppi_planner* p) {
   return launch_cvar_reduce(p);
 }
 
-// tile-relative weights (unless the rollout kernel just emitted them) + the row kernel:
-// applies the update on a single GPU; with several GPUs leaves this rank's packet in
-// packets[rank] for the exchange
-static int launch_update_local(mppi_planner* p, bool apply_here) {
-  const int N = p->n_local, T = p->cfg.num_steps;
+// ---- the update: launch_update carries out a choice (update_plan.h: update_choose), one launcher
+//      per kernel family.  The choice is pure; every side effect on the handle happens here. ---------------------------
+static_assert(kUpdateRowsBlock == kRowThreads, "update_plan.h and update_kernels.h disagree");
+
+// where a local launch leaves this rank's packet for an exchange; the host mirror, written by solve()'s last update only
+static double* update_packet(const mppi_planner* p) { return p->packets + (size_t)p->cfg.rank * p->B * packet_len(p->cfg.num_steps); }
+static float2* update_mirror(const mppi_planner* p) { return p->mirror_now ? p->u_host_dev : (float2*)nullptr; }
+
+// k_combine_tiles: the rollout launch (a time-parallel kernel) has reduced w_rel * noise over every tile
+static int launch_combine_tiles(mppi_planner* p, const UpdateChoice& c) {
   const mppi_params& a = p->params;
-  double* my_packet = p->packets + (size_t)p->cfg.rank * p->B * packet_len(T);
-  if (p->scan_packets_fresh) {
-    // the rollout launch (k_rollout_scan) has reduced w_rel * noise over every tile: combine the tiles
-    p->scan_packets_fresh = false;
-    p->tile_packets_fresh = false;
-    const dim3 grid(T, p->B);
-    unsigned long long* gen = p->graph_on ? p->gen_dev : (unsigned long long*)nullptr;
-    const int per_problem = ceil_div(p->n_inst, p->scan_tile);
-    // (graph replay: this launch also accounts for the iterations whose update ran inside a rollout launch)
-    const unsigned long long bump = 1ull + (unsigned long long)p->bumps_owed;
-    const float* tiles = p->tile_packets[p->tpk_cur];
-    PeerExchange peers;
-    memset(&peers, 0, sizeof(peers));
-    if (apply_here && p->p2p_on && p->cfg.world_size > 1) peers = make_peer_exchange(p);  // (exchanged inside the launch)
-    if (apply_here)
-      MPPI_KLAUNCH((k_combine_tiles<true>), grid, dim3(64), 0, p->stream, tiles, per_problem,
-                   T, a.lambda_weight, my_packet, p->u, p->u_prev, (p->mirror_now ? p->u_host_dev : (float2*)nullptr), a.vrange[0], a.vrange[1],
-                   a.wrange[0], a.wrange[1], p->stats, gen, bump, p->published, peers);
-    else
-      MPPI_KLAUNCH((k_combine_tiles<false>), grid, dim3(64), 0, p->stream, tiles, per_problem,
-                   T, a.lambda_weight, my_packet, p->u, p->u_prev, (p->mirror_now ? p->u_host_dev : (float2*)nullptr), a.vrange[0], a.vrange[1],
-                   a.wrange[0], a.wrange[1], p->stats, gen, bump, p->published, peers);
-    if (p->graph_on) p->bumps_launched += bump;
-    p->bumps_owed = 0;
-    p->reduce_index = 0;  // (the flags are all clear again)
-    HIP_TRY(hipGetLastError());
-    return MPPI_OK;
-  }
-  if (p->noise_virtual) TRY(materialize_noise(p));  // the row kernel streams the noise
-  // rollout kernels without the weight epilogue: the row kernel forms the tile weights itself
-  // from the costs (same bits) unless there are too many tiles for its LDS arrays
-  const bool from_costs = !p->tile_packets_fresh && 2 * sizeof(float) * (size_t)p->inst_tiles <= 60 * 1024;
-  if (!p->tile_packets_fresh && !from_costs)
-    MPPI_KLAUNCH(k_tile_weights, dim3(p->n_tiles), dim3(64), 0, p->stream, p->costs, N, a.lambda_weight,
-                       p->w_rel, p->tile_beta);
+  p->scan_packets_fresh = false;
   p->tile_packets_fresh = false;
-  const size_t lds = sizeof(float) * (size_t)p->inst_tiles * (from_costs ? 2 : 1);
-  REQUIRE(lds <= 60 * 1024, MPPI_ERR_INVALID, "too many rollouts per GPU for the update kernel (%d)", N);
-  // rows per workgroup: see k_update_rows
-  const bool many_rows = (long)T * p->B >= 2048;
-  const dim3 grid(many_rows ? ceil_div(T, 4) : T, p->B);
-// (slim: 256 threads with four times the loads in flight each and at most two workgroups per CU -- 60 KB of LDS each --,
-//  for the launches beside which the next iteration's noise is generated: k_update_rows, THREADS)
-#define MPPI_LAUNCH_ROWS(APPLY, TC, FC)                                                                         \
-  do {                                                                                                          \
-    if (slim)                                                                                                   \
-      MPPI_KLAUNCH((k_update_rows<APPLY, TC, FC, 256>), grid, dim3(256), std::max(lds, (size_t)60 * 1024), p->stream, \
-                   FC ? p->costs : p->w_rel, p->tile_beta, p->n_inst, p->inst_tiles, p->noise, T,               \
-                   a.lambda_weight, my_packet, p->u, p->u_prev, (p->mirror_now ? p->u_host_dev : (float2*)nullptr), a.vrange[0], a.vrange[1], \
-                   a.wrange[0], a.wrange[1], p->stats, p->graph_on ? p->gen_dev : (unsigned long long*)nullptr, \
-                   p->ktime_update_slot, p->ktime_waves, p->progress_dev, p->progress_seq);                     \
-    else                                                                                                        \
-      MPPI_KLAUNCH((k_update_rows<APPLY, TC, FC>), grid, dim3(kRowThreads), lds, p->stream,                     \
-                   FC ? p->costs : p->w_rel, p->tile_beta, p->n_inst, p->inst_tiles, p->noise, T,               \
-                   a.lambda_weight, my_packet, p->u, p->u_prev, (p->mirror_now ? p->u_host_dev : (float2*)nullptr), a.vrange[0], a.vrange[1], \
-                   a.wrange[0], a.wrange[1], p->stats, p->graph_on ? p->gen_dev : (unsigned long long*)nullptr, \
-                   p->ktime_update_slot, p->ktime_waves, (unsigned long long*)nullptr, 0ull);                   \
-  } while (0)
-#define MPPI_LAUNCH_ROWS_TC(APPLY, FC)        \
-  do {                                        \
-    if (many_rows) MPPI_LAUNCH_ROWS(APPLY, 4, FC); \
-    else MPPI_LAUNCH_ROWS(APPLY, 1, FC);           \
-  } while (0)
-  const bool slim = p->update_signals;
-  if (apply_here && from_costs) MPPI_LAUNCH_ROWS_TC(true, true);
-  else if (apply_here) MPPI_LAUNCH_ROWS_TC(true, false);
-  else if (from_costs) MPPI_LAUNCH_ROWS_TC(false, true);
-  else MPPI_LAUNCH_ROWS_TC(false, false);
-#undef MPPI_LAUNCH_ROWS_TC
-#undef MPPI_LAUNCH_ROWS
+  unsigned long long* gen = p->graph_on ? p->gen_dev : (unsigned long long*)nullptr;
+  // (graph replay: this launch also accounts for the iterations whose update ran inside a rollout launch)
+  const unsigned long long bump = 1ull + (unsigned long long)p->bumps_owed;
+  PeerExchange peers;
+  memset(&peers, 0, sizeof(peers));
+  if (c.peers_ride) peers = make_peer_exchange(p);  // (exchanged inside the launch; advances the inbox set)
+  static const decltype(&k_combine_tiles<true>) forms[2] = {k_combine_tiles<false>, k_combine_tiles<true>};  // [APPLY]
+  MPPI_KLAUNCH(forms[c.apply_here], dim3(c.grid_x, c.grid_y), dim3(c.block), 0, p->stream, p->tile_packets[p->tpk_cur],
+               c.per_problem_tiles, p->cfg.num_steps, a.lambda_weight, update_packet(p), p->u, p->u_prev, update_mirror(p),
+               a.vrange[0], a.vrange[1], a.wrange[0], a.wrange[1], p->stats, gen, bump, p->published, peers);
+  if (p->graph_on) p->bumps_launched += bump;
+  p->bumps_owed = 0;
+  p->reduce_index = 0;  // (the flags are all clear again)
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+// k_update_rows, with k_tile_weights in front where the choice says so: applies the update, or leaves this rank's
+// packet for the exchange
+static int launch_update_rows(mppi_planner* p, const UpdateChoice& c) {
+  const mppi_params& a = p->params;
+  if (p->noise_virtual) TRY(materialize_noise(p));  // the row kernel streams the noise
+  if (c.tile_weights_first)
+    MPPI_KLAUNCH(k_tile_weights, dim3(p->n_tiles), dim3(64), 0, p->stream, p->costs, p->n_local, a.lambda_weight,
+                 p->w_rel, p->tile_beta);
+  p->tile_packets_fresh = false;
+  REQUIRE(c.lds <= kUpdateLdsMax, MPPI_ERR_INVALID, "too many rollouts per GPU for the update kernel (%d)", p->n_local);
+  // the compile-time form: [APPLY][TC 1, 4][FROM_COSTS][slim: 256 threads]
+#define MPPI_ROWS_FORMS(APPLY, TC)                                              \
+  {{k_update_rows<APPLY, TC, false>, k_update_rows<APPLY, TC, false, kUpdateRowsSlimBlock>}, \
+   {k_update_rows<APPLY, TC, true>, k_update_rows<APPLY, TC, true, kUpdateRowsSlimBlock>}}
+  static const decltype(&k_update_rows<true, 1, true>) forms[2][2][2][2] = {{MPPI_ROWS_FORMS(false, 1), MPPI_ROWS_FORMS(false, 4)},
+                                                                           {MPPI_ROWS_FORMS(true, 1), MPPI_ROWS_FORMS(true, 4)}};
+#undef MPPI_ROWS_FORMS
+  const auto kern = forms[c.apply_here][c.rows_per_wg == 4][c.from_costs][c.slim];
+  // (slim: the launch signals its start to the gate kernel in front of the noise generator beside it)
+  MPPI_KLAUNCH(kern, dim3(c.grid_x, c.grid_y), dim3(c.block), c.lds_launch, p->stream, c.from_costs ? p->costs : p->w_rel,
+               p->tile_beta, p->n_inst, p->inst_tiles, p->noise, p->cfg.num_steps, a.lambda_weight, update_packet(p), p->u,
+               p->u_prev, update_mirror(p), a.vrange[0], a.vrange[1], a.wrange[0], a.wrange[1], p->stats,
+               p->graph_on ? p->gen_dev : (unsigned long long*)nullptr, p->ktime_update_slot, p->ktime_waves,
+               c.slim ? p->progress_dev : (unsigned long long*)nullptr, c.slim ? p->progress_seq : 0ull);
   if (p->graph_on) ++p->bumps_launched;
   HIP_TRY(hipGetLastError());
   p->update_signalled = p->update_signals;
   return MPPI_OK;
+}
+
+static int launch_update_kernel(mppi_planner* p, const UpdateChoice& c) {
+  return c.kernel == kUpdateCombineTiles ? launch_combine_tiles(p, c) : launch_update_rows(p, c);
 }
 
 // (out of place into the handle's other control buffer, like an update applied by its consumer: every
@@ -857,8 +836,7 @@ static int launch_update_local(mppi_planner* p, bool apply_here) {
 static int launch_apply(mppi_planner* p) {
   const mppi_params& a = p->params;
   hipLaunchKernelGGL(k_apply, dim3(p->B), dim3(kUpdateThreads), 0, p->stream, p->packets, p->cfg.world_size,
-                     p->cfg.rank, p->cfg.num_steps, a.lambda_weight, p->u, p->u_alt, p->u_prev,
-                     (p->mirror_now ? p->u_host_dev : (float2*)nullptr), a.vrange[0],
+                     p->cfg.rank, p->cfg.num_steps, a.lambda_weight, p->u, p->u_alt, p->u_prev, update_mirror(p), a.vrange[0],
                      a.vrange[1], a.wrange[0], a.wrange[1], p->stats);
   HIP_TRY(hipGetLastError());
   std::swap(p->u, p->u_alt);
@@ -867,55 +845,55 @@ static int launch_apply(mppi_planner* p) {
   return MPPI_OK;
 }
 
-// Whether the NEXT rollout launch of this handle can apply a sharded update itself (PendingApply).
-static bool next_rollout_applies_updates(const mppi_planner* p) {
-  return !(p->debug_flags & MPPI_DEBUG_NO_FOLDED_APPLY) && p->B == 1 && !p->inst_set && p->m_count == 1 &&
-         p->cfg.world_size <= kMaxFoldedRanks && p->cfg.mode == MPPI_MODE_DET && !p->mirror_now && scan_plan(p, nullptr);
-}
-
-// Several GPUs without a collective: the peer exchange is connected and the kernels that carry it will run (the
-// time-parallel kernels leave tile packets; one problem per handle).  Decided from things every rank has alike.
-static bool p2p_usable(const mppi_planner* p) {
-  ScanPlan plan;
-  return p->p2p_on && p->cfg.world_size > 1 && p->cfg.world_size <= kMaxFoldedRanks && p->B == 1 && !p->inst_set &&
-         p->m_count == 1 && p->cfg.mode == MPPI_MODE_DET && scan_plan(p, &plan);
-}
-
-// Whether the NEXT rollout launch can combine and apply the tile packets of this one (no update kernel).
-static bool next_rollout_reduces_tiles(const mppi_planner* p) {
-  ScanPlan plan;
-  return !p->fold_off && !(p->debug_flags & (MPPI_DEBUG_NO_FOLDED_APPLY | MPPI_DEBUG_NO_REDUCE_FOLD)) && p->B == 1 && !p->inst_set &&
-         p->m_count == 1 && ((p->cfg.world_size == 1 && !p->comm) || p2p_usable(p)) &&
-         (p->cfg.mode == MPPI_MODE_DET || p->cfg.mode == MPPI_MODE_SPEED_MAP) && !p->mirror_now &&
-         scan_plan(p, &plan) && plan.tile == p->scan_tile &&
-         tiles_can_reduce(ceil_div(p->n_local, plan.tile), p->cfg.num_steps);
+// What a time-parallel rollout launch over `tiles` workgroups needs to take the update left to it (PendingApply): the
+// gathered rank packets (apply_pending), or the previous launch's tile packets -- as many as this launch has tiles:
+// launch_scan has checked -- which it combines and applies itself (reduce_pending; several GPUs: with the peer
+// exchange in between).  Nothing pending: all zero.
+static PendingApply make_pending_apply(mppi_planner* p, int tiles) {
+  PendingApply pend;
+  memset(&pend, 0, sizeof(pend));
+  if (!p->apply_pending && !p->reduce_pending) return pend;
+  const mppi_params& a = p->params;
+  pend.packets = p->packets;  // (not read when the tiles are reduced; non-null: "an update is pending")
+  pend.u_out = p->u_alt;
+  pend.u_prev = p->u_prev;
+  pend.stats = p->stats;
+  pend.world = p->reduce_pending ? 1 : p->cfg.world_size;
+  pend.stride = p->B * packet_len(p->cfg.num_steps);
+  pend.lambda = a.lambda_weight;
+  pend.v_lo = a.vrange[0]; pend.v_hi = a.vrange[1];
+  pend.w_lo = a.wrange[0]; pend.w_hi = a.wrange[1];
+  if (p->reduce_pending) {
+    pend.reduce_tiles = p->tile_packets[p->tpk_cur];
+    pend.reduce_n_tiles = tiles;
+    pend.published = p->published;
+    pend.flag_set = p->reduce_index & 1;
+    pend.fault = p->fold_fault_dev;
+    pend.max_polls = p->fold_max_polls;
+    if (p->p2p_on) pend.peers = make_peer_exchange(p);  // (advances the inbox set)
+  }
+  return pend;
 }
 
 // tile packets left to a rollout launch that will not come (another kernel family, a stage-level call): the
-// ordinary combination
+// ordinary combination, applied here on any number of GPUs
 static int settle_reduce_pending(mppi_planner* p) {
   p->reduce_pending = false;
   p->scan_packets_fresh = true;
-  return launch_update_local(p, true);
+  return launch_update_kernel(p, update_local_launch(update_held(p), kUpdateLocalApply));
 }
 
-// `defer_exchange` (mppi_group_iterate_async): stop after this rank's packet; the caller issues the
-// all-gathers of all its devices inside one RCCL group and then launches k_apply on each
-// `may_leave_apply`: another iteration follows on this stream: the update may be left to its rollout launch
-static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false, bool may_leave_apply = false) {
+static int launch_update(mppi_planner* p, const UpdateChoice& c, bool prof) {
   p->mirror_done = p->mirror_now;
-  if (defer_exchange) return launch_update_local(p, false);
-  // (a communicator on a single rank is honoured too: it exercises the same path as N ranks)
-  // (samples sharded: every rank holds all N costs and all the noise -- the update is local)
-  if ((p->cfg.world_size == 1 && !p->comm) || p->m_count > 1 || (p2p_usable(p) && p->scan_packets_fresh)) {
-    if (may_leave_apply && !prof && p->scan_packets_fresh && next_rollout_reduces_tiles(p)) {
-      // the next rollout launch reduces this one's tile packets and applies the update itself: no launch here
-      p->scan_packets_fresh = false;
-      p->reduce_pending = true;
-      if (p->graph_on) ++p->bumps_owed;
-      return MPPI_OK;
-    }
-    TRY(launch_update_local(p, true));
+  if (c.route == kUpdateLeaveTiles) {  // no launch here
+    p->scan_packets_fresh = false;
+    p->reduce_pending = true;
+    if (p->graph_on) ++p->bumps_owed;
+    return MPPI_OK;
+  }
+  if (c.route == kUpdatePacketOnly) return launch_update_kernel(p, c);
+  if (c.route == kUpdateLocalApply) {
+    TRY(launch_update_kernel(p, c));
     if (prof) {
       HIP_TRY(hipEventRecord(p->ev_stage[3], p->stream));
       HIP_TRY(hipEventRecord(p->ev_stage[4], p->stream));
@@ -925,7 +903,7 @@ static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false
   REQUIRE(p->comm, MPPI_ERR_STATE,
           "world_size %d but no communicator: call mppi_planner_comm_init (or use update_local/update_apply)",
           p->cfg.world_size);
-  TRY(launch_update_local(p, false));
+  TRY(launch_update_kernel(p, c));
   const int len = p->B * packet_len(p->cfg.num_steps);
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[3], p->stream));
   // one all-gather of (2T+2) doubles per problem and iteration, in place
@@ -933,11 +911,17 @@ static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false
   RCCL_TRY(g_rccl.AllGather(p->packets + (size_t)p->cfg.rank * len, p->packets, (size_t)len, ncclDouble, p->comm,
                             p->stream));
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[4], p->stream));
-  if (may_leave_apply && !prof && next_rollout_applies_updates(p)) {
+  if (c.route == kUpdateGatherLeaveApply) {
     p->apply_pending = true;
     return MPPI_OK;
   }
   return launch_apply(p);
+}
+
+// The stage-level calls: mppi_planner_update, and mppi_planner_update_local with `defer_exchange` (stop after this
+// rank's packet: the caller exchanges the packets and applies them)
+static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false) {
+  return launch_update(p, update_choose(update_held(p, prof, defer_exchange)), prof);
 }
 
 // One iteration: {noise unless it was produced ahead, rollout (+ the next iteration's noise when
@@ -950,7 +934,7 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
   // crawls beside the rollout, slows it, and still collides with the update (measured in round 1, profiles/r01_ablation.md,
   // and again in round 6 with a bound of 16: C5 187 us against 178, profiles/r06_ns_notes.md section 3)
   constexpr int kSideStreamMaxWaves = 8;
-  const bool side_stream_pays = (long)p->n_local * p->cfg.num_steps >= 4L * 1000 * 1000 &&
+  const bool side_stream_pays = update_noise_is_long(p->n_local, p->cfg.num_steps) &&
                                 ceil_div(ceil_div(p->n_local, 64), p->num_cus) <= kSideStreamMaxWaves;
   const bool ktime_stamps = p->ktime_index >= 0 && p->ktime_dev && p->ktime_use_stamps;  // (mppi_planner_time_kernels)
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[0], p->stream));
@@ -1042,18 +1026,16 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     }
   }
   p->progress_capable_last = p->progress_signalled;
-  // Where the rollout fills the SIMDs by itself (more than 8 of its waves per CU: the batched handles, C5) a generator
-  // beside it only takes its issue slots; but the update behind it is bound by memory: there the next iteration's noise is
-  // generated beside the UPDATE launch -- which runs slim (k_update_rows<.., 256>: a quarter of the waves, the same bytes
-  // in flight) and signals its start to the generator's gate kernel.  (MPPI_NO_NOISE_FLAG: no flags, no second stream here)
-  const bool beside_update = want_next && !have_noise && !side_stream_pays && !noise_flag_disabled() && !p->graph_on &&
-                             !prof && !defer_exchange && p->noise_flag_dev && p->progress_dev && !p->stream_flags_off &&
-                             p->cfg.rng == MPPI_RNG_PHILOX && (long)p->n_local * p->cfg.num_steps >= 4L * 1000 * 1000 &&
-                             !p->scan_packets_fresh && p->cfg.world_size == 1 && !p->comm && p->m_count == 1 &&
-                             2 * sizeof(float) * (size_t)p->inst_tiles <= 60 * 1024;
-  p->update_signals = beside_update;
+  // How this iteration's weights become the next u (update_plan.h), decided from what the rollout launch has left.
+  // beside_update: the next iteration's noise is generated beside the update launch -- which runs slim
+  // (k_update_rows<.., 256>: a quarter of the waves, the same bytes in flight) and signals its start to the generator's
+  // gate kernel.  (MPPI_NO_NOISE_FLAG: no flags, no second stream here)
+  UpdateHeld held = update_held(p, prof, defer_exchange, may_leave_apply);
+  held.want_next = want_next; held.have_noise = have_noise; held.side_stream_pays = side_stream_pays;
+  const UpdateChoice update = update_choose(held);
+  p->update_signals = update.beside_update;
   p->update_signalled = false;
-  if (beside_update) ++p->progress_seq;
+  if (update.beside_update) ++p->progress_seq;
   p->next_noise_wanted = false;
   p->scan_gen_now = false;
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[2], p->stream));
@@ -1069,7 +1051,7 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     ++p->ktime_index;
   }
   {
-    const int rc = launch_update(p, prof, defer_exchange, may_leave_apply);
+    const int rc = launch_update(p, update, prof);
     p->kev_start = p->kev_stop = nullptr;
     p->ktime_update_slot = nullptr;
     p->update_signals = false;

@@ -1416,7 +1416,7 @@ extern "C" int mppi_planner_update_local(mppi_planner* p, double* packet) {
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   REQUIRE(!p->sample_costs_local_only, MPPI_ERR_STATE, "sample shards: exchange the per-sample costs before the update");
   HIP_TRY(hipSetDevice(p->cfg.device));
-  TRY(launch_update_local(p, false));
+  TRY(launch_update(p, false, /*defer_exchange=*/true));
   const int len = p->B * packet_len(p->cfg.num_steps);
   HIP_TRY(hipMemcpyAsync(packet, p->packets + (size_t)p->cfg.rank * len, sizeof(double) * (size_t)len,
                          hipMemcpyDeviceToHost, p->stream));
@@ -1451,7 +1451,7 @@ extern "C" int mppi_planner_update_apply_and_rollout(mppi_planner* p, const doub
   HIP_TRY(hipMemcpyAsync(p->packets, packets, sizeof(double) * (size_t)len * (size_t)count,
                          hipMemcpyHostToDevice, p->stream));
   // the rollout launch applies the update when it is one that can (launch_rollout settles it otherwise)
-  if (next_rollout_applies_updates(p)) p->apply_pending = true;
+  if (next_rollout_takes(update_held(p)).applies_packets) p->apply_pending = true;
   else TRY(launch_apply(p));
   const int rc = launch_rollout(p, d);
   if (p->apply_pending) {  // (the rollout launch failed before it could take the packets: the update must not be lost)
@@ -1837,7 +1837,7 @@ extern "C" int mppi_group_iterate_async(mppi_planner** ps, mppi_tdm** lins, mppi
       HIP_TRY(hipSetDevice(ps[g]->cfg.device));
       TRY(check_tdms(ps[g], lins[g], angs[g]));
       TRY(ensure_packed(ps[g], lins[g], angs[g]));
-      all_p2p = p2p_usable(ps[g]);
+      all_p2p = update_p2p_usable(update_held(ps[g]));
     }
     if (all_p2p) {
       // Every launch of device g spins inside the kernel until the other devices' numbers for the same iteration have
