@@ -66,7 +66,8 @@ namespace mppi {
 //   grp  [W] x 4 KiB      per group of 8 steps: [8][R] double dt*w, overwritten by (dt*v)*cos once the
 //                         theta walk has passed | [8][R] double (dt*v)*sin; both overwritten, once the
 //                         position walk has passed, by the group's two records
-//                         [R] {double stage[4]; float obstacle[4]; float unknown[4]}
+//                         {double stage[4]; float obstacle[4]; float unknown[4]} per rollout, as four planes
+//                         [R] x 16 bytes (consecutive lanes in consecutive banks)
 //   p2   [Tp + 1][R] float2 positions (row t = before step t); the float32 headings [Tp + 1][R]
 //                         live in its upper half until the positions overwrite them (see th_sh)
 //   small: control ratios, terminal data, event words, weights, flags; per (chunk, rollout) what a rollout
@@ -639,13 +640,15 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
         c_done,
         [&](auto set, int gi) {
           constexpr int S = decltype(set)::value;
-          const char* in = grp + (size_t)gi * 4096 + (size_t)r * 64;
+          // (a record's four 16-byte vectors lie 512 bytes apart, the rollouts of one vector side by side: lanes
+          //  64 bytes apart met in the same LDS banks, and every ds_read_b128 held the LDS several times as long)
+          const char* in = grp + (size_t)gi * 4096 + (size_t)r * 16;
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
-            sg[S][2 * hh] = reinterpret_cast<const double2*>(in + hh * 2048)[0];
-            sg[S][2 * hh + 1] = reinterpret_cast<const double2*>(in + hh * 2048)[1];
-            fo[S][hh] = reinterpret_cast<const float4*>(in + hh * 2048 + 32)[0];
-            fu[S][hh] = reinterpret_cast<const float4*>(in + hh * 2048 + 32)[1];
+            sg[S][2 * hh] = *reinterpret_cast<const double2*>(in + hh * 2048);
+            sg[S][2 * hh + 1] = *reinterpret_cast<const double2*>(in + hh * 2048 + 512);
+            fo[S][hh] = *reinterpret_cast<const float4*>(in + hh * 2048 + 1024);
+            fu[S][hh] = *reinterpret_cast<const float4*>(in + hh * 2048 + 1536);
           }
         },
         [&](auto set, int gi, int flag_value) {
@@ -939,13 +942,12 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       group_pen = __any(pen);
       MPPI_STAMP(stamp_wg && c < 16, stamp_base + 15);
       // the group's records over its (consumed) position increments
-      char* out = grp + (size_t)g * 4096 + (size_t)h * 2048 + (size_t)r * 64;
-      double2* o2 = reinterpret_cast<double2*>(out);
-      o2[0] = make_double2(sg[0], sg[1]);
-      o2[1] = make_double2(sg[2], sg[3]);
-      float4* o4 = reinterpret_cast<float4*>(out + CHL * 8);
-      o4[0] = make_float4(po[0], po[1], po[2], po[3]);
-      o4[1] = make_float4(pu[0], pu[1], pu[2], pu[3]);
+      // (per chunk of 4 steps four planes [R] x 16 bytes: stage 0-1 | stage 2-3 | obstacle | unknown)
+      char* out = grp + (size_t)g * 4096 + (size_t)h * 2048 + (size_t)r * 16;
+      *reinterpret_cast<double2*>(out) = make_double2(sg[0], sg[1]);
+      *reinterpret_cast<double2*>(out + 512) = make_double2(sg[2], sg[3]);
+      *reinterpret_cast<float4*>(out + 1024) = make_float4(po[0], po[1], po[2], po[3]);
+      *reinterpret_cast<float4*>(out + 1536) = make_float4(pu[0], pu[1], pu[2], pu[3]);
     }
     raise(&c_done[g], group_pen ? 3 : 1);
     MPPI_STAMP(stamp_wg && c < 16, stamp_base + 6);

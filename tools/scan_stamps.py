@@ -15,7 +15,11 @@ chunk waves: increments stored (1), sin / cos + position increments (3),
 positions arrived (4), distances done and lookups requested (7), cells there (11), before the wait for the
 earlier groups' events (12), events published (5), own events looked up and terminal cost (13), stopped rollouts
 (14), selects (15), records stored (6); every wave: end (8), first barrier passed
-(9); chunk waves: noise generated (10), control-cost products (2: after the records)."""
+(9); chunk waves: noise generated (10), control-cost products (2: after the records).
+k_rollout_scan_exact as it is launched today: the cost walk is wave 1 (the x | y walk wave 4), and under each
+workgroup's rows a derived table sets the stage-cost walk against its producers, group by group (stage_walk_table).
+A stamp is not free: one more in the cost walker's loop moved its later stamps by 0.2-0.5k cycles
+(profiles/HISTORY.md, "C2 rollout: the stage-cost walk")."""
 import argparse
 import contextlib
 import ctypes as C
@@ -27,6 +31,37 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
+
+
+# k_rollout_scan_exact: which chunk wave owns which group of 8 steps (kGroupOfWave), and the slots of the cost
+# walker's row (wave 1) that hold "the walk left group g"
+GROUP_OF_WAVE = {5: 0, 2: 1, 3: 2, 9: 3, 6: 4, 7: 5, 13: 6, 10: 7, 11: 8, 14: 9, 15: 10, 8: 11, 12: 12}
+WALK_LEFT_SLOT = {0: 5, 6: 6, 9: 7, 10: 10, 11: 11, 12: 12}
+
+
+def stage_walk_table(rows, t0):
+    """The stage-cost walk against its producers: per group, when its records were ready (c_done raised: slot 6 of
+    its chunk wave), when the cost walker left it, how far behind that is, and the walker's cycles per group since
+    the previous group it stamps.  Last line: walk done (slot 1 of wave 1) minus the last c_done."""
+    wave_of = {g: c for c, g in GROUP_OF_WAVE.items()}
+    walker = rows[1]
+    if not walker[0] or not walker[1]:
+        return
+    print(" stage-cost walk: group, records ready, walker left, behind, walker cycles per group")
+    prev_g, prev_left, ready_last = None, None, 0
+    for g in sorted(wave_of):
+        ready = int(rows[wave_of[g]][6] - t0) if rows[wave_of[g]][6] else None
+        ready_last = max(ready_last, ready or 0)
+        left = int(walker[WALK_LEFT_SLOT[g]] - t0) if g in WALK_LEFT_SLOT and walker[WALK_LEFT_SLOT[g]] else None
+        per = ""
+        if left is not None:
+            if prev_left is not None:
+                per = "%.0f" % ((left - prev_left) / (g - prev_g))
+            prev_g, prev_left = g, left
+        print("  %5d %8s %8s %8s %8s" % (g, ready if ready is not None else "-", left if left is not None else "-",
+                                        left - ready if None not in (left, ready) else "-", per))
+    done = int(walker[1] - t0)
+    print("  walk done %d, last records ready %d: %d behind" % (done, ready_last, done - ready_last))
 
 
 def main():
@@ -65,6 +100,8 @@ def main():
         for c, r in enumerate(rows):
             if r[0]:
                 print("%5d  " % c + "".join("%8s" % (int(v - t0) if v else "-") for v in r))
+        if args.math == "exact" and args.workload in ("c2", "c2m"):
+            stage_walk_table(rows, t0)
     rows = [st[64 + 16 * c: 64 + 16 * c + 12] for c in range(16)]
     t0 = min(int(r[0]) for r in rows if r[0])
     # every workgroup's entry / exit (slots 2048 + 2 b, 2049 + 2 b) when the kernel records them
