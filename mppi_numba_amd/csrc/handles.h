@@ -2,6 +2,7 @@
 #pragma once
 #include "host_common.h"
 #include "map_plan.h"
+#include "noise_plan.h"
 
 // ---------------------------------------------------------------------------
 // TDM
@@ -118,10 +119,7 @@ struct mppi_planner {
   // signal their start let a one-wave gate kernel on noise_stream take the place of ev_buf_free
   unsigned long long* progress_dev = nullptr;
   unsigned long long progress_seq = 0;       // launches that signal, so far
-  bool progress_signalled = false;           // the rollout launch of this iteration does
-  bool progress_capable_last = false;        // ... the previous one did: no event is recorded in front of the next
-  bool update_signals = false;               // the coming k_update_rows launch is to signal its start (generator beside the update)
-  bool update_signalled = false;             // ... and it did (that kernel ran)
+  bool progress_capable_last = false;        // the previous iteration's rollout launch did: no event is recorded in front of the next
   unsigned int* flag_fault_host = nullptr;   // pinned, device-mapped: a bounded flag wait gave up (DevParams::flag_fault)
   unsigned int* flag_fault_dev = nullptr;
   bool stream_flags_off = false;             // ... after which this handle orders its two streams with events
@@ -147,8 +145,9 @@ struct mppi_planner {
   long graph_replays = 0, graph_captures = 0;
   std::string last_rollout;        // which rollout kernel variant the last launch used (diagnostic)
   int debug_flags = 0;             // mppi_planner_set_debug_flags (tests pin every kernel variant through it)
-  bool next_noise_wanted = false;  // the coming rollout launch should also generate noise_buf[cur^1]
-  bool next_noise_done = false;    // ... and it did
+  // this iteration's noise choice (noise_plan.h) while launch_iteration makes its rollout launch -- the launchers read
+  // what they are to do from it -- and all zero outside one
+  NoiseChoice noise_now;
   bool noise_on_side_stream = false;  // the noise produced ahead is still in flight on noise_stream
   float2* staging = nullptr;  // (n_local,T) host-layout staging for set/get_noise
   float2* u = nullptr;        // [T]
@@ -187,7 +186,6 @@ struct mppi_planner {
   // the iteration loop of such a handle generates the noise INSIDE the rollout launch (Philox counter
   // blocks, never stored): noise_buf is then stale, and whoever wants the noise of the last iteration
   // (get_noise, get_state_rollout, a stage-level update) has it regenerated from the same counters
-  bool scan_gen_now = false;   // the coming rollout launch is to generate its own noise
   bool noise_virtual = false;  // the noise of the last iteration exists as counters only ...
   int noise_virtual_back = 1;  // ... of Philox epoch noise_epoch - noise_virtual_back
   double* packets = nullptr;  // [world][2+2T]; own packet at [rank]

@@ -217,8 +217,9 @@ static int prepare_launch(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, DevPara
   return MPPI_OK;
 }
 
-// describe one noise generation (advances the Philox epoch)
-static NoiseJob make_noise_job(mppi_planner* p, float2* target) {
+// describe one noise generation (advances the Philox epoch); `back` > 0: the Philox block generated `back` epochs ago,
+// by value (nothing advances)
+static NoiseJob make_noise_job(mppi_planner* p, float2* target, int back = 0) {
   NoiseJob j;
   j.out = target;
   j.states = (p->cfg.rng == MPPI_RNG_XOROSHIRO) ? p->states : nullptr;
@@ -226,14 +227,15 @@ static NoiseJob make_noise_job(mppi_planner* p, float2* target) {
   // graph mode: the epoch is split into a by-value part that stays the same from one replay to
   // the next and the device-side count of executed updates (bumps_launched mirrors it: every
   // earlier update is ahead of this generator in stream order)
-  j.gen_counter = p->graph_on ? (const uint64_t*)p->gen_dev : nullptr;
-  j.epoch = p->graph_on ? p->noise_epoch - p->bumps_launched : p->noise_epoch;
+  const bool by_counter = p->graph_on && !back;
+  j.gen_counter = by_counter ? (const uint64_t*)p->gen_dev : nullptr;
+  j.epoch = by_counter ? p->noise_epoch - p->bumps_launched : p->noise_epoch - (uint64_t)back;
   j.n_local = p->n_local;
   j.n_offset = p->n_offset;
   j.n_steps = p->cfg.num_steps;
   j.std0 = p->params.u_std[0];
   j.std1 = p->params.u_std[1];
-  if (p->cfg.rng == MPPI_RNG_PHILOX) ++p->noise_epoch;
+  if (p->cfg.rng == MPPI_RNG_PHILOX && !back) ++p->noise_epoch;
   return j;
 }
 
@@ -241,15 +243,12 @@ static NoiseJob make_noise_job(mppi_planner* p, float2* target) {
 static NoiseJob next_noise_job(mppi_planner* p, int extra) {
   NoiseJob j;
   memset(&j, 0, sizeof(j));
-  if (extra <= 0) return j;
-  j = make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]);
-  p->next_noise_done = true;
-  return j;
+  return extra > 0 ? make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]) : j;
 }
 
-static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nullptr) {
+static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nullptr, int back = 0) {
   long total = (long)noise_items(p->n_local, p->cfg.num_steps, p->cfg.rng == MPPI_RNG_PHILOX);  // one thread per item
-  NoiseJob job = make_noise_job(p, target);
+  NoiseJob job = make_noise_job(p, target, back);
   hipLaunchKernelGGL(k_noise, dim3(ceil_div(total, 256)), dim3(256), 0, stream ? stream : p->stream, job);
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
@@ -329,20 +328,20 @@ static bool noise_flag_disabled() {
   static const bool disabled = getenv("MPPI_NO_NOISE_FLAG") != nullptr;
   return disabled;
 }
+static bool flag_words(const mppi_planner* p) { return p->noise_flag_dev && p->progress_dev; }
 static DevParams noise_flag_params(mppi_planner* p, DevParams d) {
-  const bool no_flag = noise_flag_disabled();
   d.flag_fault = p->flag_fault_dev;
-  if (p->noise_wait_pending && p->noise_flag_dev && !no_flag && !p->stream_flags_off) {
+  if (p->noise_now.consumer == kOrderFlag && p->noise_wait_pending) {  // (not pending: an update settled in front has waited)
     d.noise_flag = p->noise_flag_dev;
     d.noise_flag_expect = p->noise_flag_expect;
     p->noise_wait_pending = false;
   } else {
     settle_noise_wait(p);
   }
-  if (p->progress_dev && !no_flag && !p->graph_on && !p->stream_flags_off) {  // (a captured launch would signal a stale number)
+  // (a stage-level launch signals too: nobody waits for it)
+  if (noise_launch_signals(flag_words(p), noise_flag_disabled(), p->graph_on, p->stream_flags_off)) {
     d.progress = p->progress_dev;
     d.progress_value = ++p->progress_seq;
-    p->progress_signalled = true;
   }
   return d;
 }
@@ -359,6 +358,20 @@ static const MapChoice& map_choice(const mppi_planner* p, const MapHeld& h) {
     p->choice_valid = true;
   }
   return p->choice_cached;
+}
+
+// the CVaR mode's fast kernel runs: (cos, sin) by rotation, |theta| bounded, its LDS within 64 KiB
+static bool tdm_fast_kernel(const mppi_planner* p, size_t* lds_fast = nullptr) {
+  const size_t lds = (sizeof(double2) + sizeof(double)) * (size_t)p->cfg.num_steps + sizeof(float) * (size_t)next_pow2(p->cfg.num_grid_samples);
+  if (lds_fast) *lds_fast = lds;
+  return p->theta_bounded && map_rotation_ok(map_held(p)) && lds <= 64 * 1024;
+}
+
+// inside an iteration: the rollout launch about to be made is the one the iteration's noise was chosen for
+static int check_chosen_launch(const mppi_planner* p, int launch) {
+  REQUIRE(p->noise_now.launch == kLaunchNone || p->noise_now.launch == launch, MPPI_ERR_STATE,
+          "internal: rollout launch %d behind a noise choice made for launch %d", launch, p->noise_now.launch);
+  return MPPI_OK;
 }
 
 // the next rollout launch runs a time-parallel kernel (k_rollout_scan, k_rollout_scan_exact): its geometry
@@ -386,7 +399,7 @@ static UpdateHeld update_held(const mppi_planner* p, bool prof = false, bool def
   h.T = p->cfg.num_steps; h.rng = p->cfg.rng;
   h.debug_flags = p->debug_flags; h.fold_off = p->fold_off; h.p2p_on = p->p2p_on; h.graph_on = p->graph_on;
   h.stream_flags_off = p->stream_flags_off; h.flags_env_off = noise_flag_disabled();
-  h.flag_words = p->noise_flag_dev && p->progress_dev;
+  h.flag_words = flag_words(p);
   h.prof = prof; h.defer_exchange = defer_exchange; h.may_leave_apply = may_leave_apply; h.mirror_now = p->mirror_now;
   h.scan_packets_fresh = p->scan_packets_fresh; h.tile_packets_fresh = p->tile_packets_fresh; h.scan_tile = p->scan_tile;
   ScanPlan next;
@@ -398,19 +411,7 @@ static UpdateHeld update_held(const mppi_planner* p, bool prof = false, bool def
 // the noise of the last iteration into noise_buf when it exists as counters only
 static int materialize_noise(mppi_planner* p) {
   if (!p->noise_virtual) return MPPI_OK;
-  NoiseJob j;
-  memset(&j, 0, sizeof(j));
-  j.out = p->noise;
-  j.seed = p->cfg.seed;
-  j.epoch = p->noise_epoch - (uint64_t)p->noise_virtual_back;  // the block the last rollout launch consumed
-  j.n_local = p->n_local;
-  j.n_offset = p->n_offset;
-  j.n_steps = p->cfg.num_steps;
-  j.std0 = p->params.u_std[0];
-  j.std1 = p->params.u_std[1];
-  const long total = (long)noise_items(p->n_local, p->cfg.num_steps, true);
-  hipLaunchKernelGGL(k_noise, dim3(ceil_div(total, 256)), dim3(256), 0, p->stream, j);
-  HIP_TRY(hipGetLastError());
+  TRY(launch_noise(p, p->noise, nullptr, p->noise_virtual_back));  // the block the last rollout launch consumed
   p->noise_virtual = false;
   return MPPI_OK;
 }
@@ -441,22 +442,19 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
   REQUIRE(!speed || (plan.exact && !plan.direct), MPPI_ERR_STATE, "internal: speed-map mode on a kernel that does not serve it");
   const int tiles = ceil_div(N, plan.tile);
   REQUIRE(p->tile_packets[0] && p->tile_packets[1], MPPI_ERR_STATE, "internal: no tile packet buffers on this handle");
-  const bool gen = p->scan_gen_now;
+  const bool gen = p->noise_now.source == kNoiseInKernel;
   ScanPackets pk;
   pk.tiles = p->tile_packets[p->tpk_cur ^ 1];  // (the other one may be read by this very launch: reduce_pending)
   pk.n_tiles = tiles;
   NoiseJob gen_job;
   memset(&gen_job, 0, sizeof(gen_job));
-  int extra = 0;
-  if (gen) {
-    gen_job = make_noise_job(p, nullptr);  // (advances the Philox epoch: this iteration's block)
-  } else if (p->next_noise_wanted && tiles < p->num_cus && p->cfg.rng == MPPI_RNG_PHILOX && !plan.exact) {
-    // a loop that stores its noise (debug flag; the stage-level calls): CUs without a workgroup
-    // produce the next iteration's, as in k_rollout_pipe.  (Producing it in the launch's own tail, by
-    // the waves that idle while one wave accumulates the costs, was measured: the stage gained is lost
-    // again to the slower accumulation and the noise reads -- profiles/r03_scan_notes.md.)
-    extra = p->num_cus - tiles;
-  }
+  if (gen) gen_job = make_noise_job(p, nullptr);  // (advances the Philox epoch: this iteration's block)
+  // a loop that stores its noise (debug flag; the stage-level calls): CUs without a workgroup
+  // produce the next iteration's, as in k_rollout_pipe.  (Producing it in the launch's own tail, by
+  // the waves that idle while one wave accumulates the costs, was measured: the stage gained is lost
+  // again to the slower accumulation and the noise reads -- profiles/r03_scan_notes.md.)
+  const int extra = p->noise_now.extra_blocks;
+  REQUIRE(!extra || (!plan.exact && tiles + extra == p->num_cus), MPPI_ERR_STATE, "internal: %d noise blocks chosen for %d tiles", extra, tiles);
   const NoiseJob next_job = next_noise_job(p, extra);
   if (p->reduce_pending) {
     REQUIRE(!p->apply_pending, MPPI_ERR_STATE, "internal: tile packets left to a launch that cannot reduce them");
@@ -537,7 +535,8 @@ static int launch_scan(mppi_planner* p, const DevParams& d, const ScanPlan& plan
 static int launch_pipe(mppi_planner* p, const DevParams& d, const MapChoice& c) {
   const int N = p->n_local, T = p->cfg.num_steps;
   // spare CUs generate the next iteration's noise inside this launch (no spare CU: in line)
-  const int extra = p->next_noise_wanted && c.grid < p->num_cus ? p->num_cus - c.grid : 0;
+  const int extra = p->noise_now.extra_blocks;
+  REQUIRE(!extra || c.grid + extra == p->num_cus, MPPI_ERR_STATE, "internal: %d noise blocks chosen for %d workgroups", extra, c.grid);
   const NoiseJob next_job = next_noise_job(p, extra);
   if (!c.cc_lds && !p->cc_scratch) TRY(dev_alloc(&p->cc_scratch, (size_t)ceil_div(N, 64) * 64 * T));
   // the compile-time form: [chunk 8, 6, 4, 2][POW2RES][CC_LDS]
@@ -611,6 +610,7 @@ static int launch_rollout_map(mppi_planner* p, DevParams d) {
   p->tile_packets_fresh = false;
   const MapHeld h = map_held(p);
   const MapChoice c = map_choice(p, h);
+  TRY(check_chosen_launch(p, c.family + 1));
   size_t lds_win = 0;
   (void)apply_window(p, h, c.window, d, &lds_win);
   TRY(upload_instances(p));
@@ -631,8 +631,7 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   const int M = p->cfg.num_grid_samples;
   size_t lds = sizeof(double2) * (size_t)T;
   int mp2 = next_pow2(M);
-  int threads = ceil_div(M, 64) * 64;
-  if (threads > 1024) threads = 1024;
+  const int threads = noise_cvar_threads(M);
   lds += sizeof(float) * (size_t)mp2;
   REQUIRE(lds <= 160 * 1024, MPPI_ERR_INVALID, "T=%d, M=%d need %zu bytes of LDS (> 160 KiB)", T, M, lds);
   if (lds > 64 * 1024)
@@ -646,16 +645,13 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
   p->tile_packets_fresh = false;
   TRY(upload_instances(p));
   {
-    const size_t lds_fast = (sizeof(double2) + sizeof(double)) * (size_t)T + sizeof(float) * (size_t)mp2;
-    if ((BOUNDED || (!EXACT && p->theta_bounded)) && rotation_ok(p, d) && lds_fast <= 64 * 1024) {
+    size_t lds_fast = 0;
+    if (tdm_fast_kernel(p, &lds_fast)) {  // (p->theta_bounded: launch_rollout hands exact arithmetic BOUNDED with it)
+      TRY(check_chosen_launch(p, kLaunchCvarFast));
       const bool pow2res = res_is_pow2(p);
       float* sc_out = sc_dst;
       // the next iteration's noise by workgroups appended to the grid (they run in the launch's tail)
-      int extra = 0;
-      if (p->next_noise_wanted && p->cfg.rng == MPPI_RNG_PHILOX) {
-        const long rows = (long)(noise_items(p->n_local, T, true) >> 6);
-        extra = (int)std::min<long>(2L * p->num_cus, ceil_div(rows, (long)(threads / 64) * 4));
-      }
+      const int extra = p->noise_now.extra_blocks;
       const NoiseJob next_job = next_noise_job(p, extra);
       if (pow2res)
         MPPI_KLAUNCH((k_rollout_tdm_fast<true, !EXACT>), dim3(N + extra), dim3(threads), lds_fast, p->stream, d, p->cells,
@@ -669,6 +665,7 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
       return MPPI_OK;
     }
   }
+  TRY(check_chosen_launch(p, kLaunchCvar));
   MPPI_KLAUNCH((k_rollout_tdm<EXACT>), dim3(N), dim3(threads), lds, p->stream, d, p->cells, p->noise,
                      p->u, p->costs, sc_dst, mp2);
   p->last_rollout = "k_rollout_tdm exact=" + std::to_string((int)EXACT);
@@ -682,12 +679,13 @@ static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
 template <bool EXACT, bool BOUNDED>
 static int launch_rollout_t(mppi_planner* p, DevParams d) {
   p->scan_packets_fresh = false;
-  if (p->noise_virtual && !p->scan_gen_now) TRY(materialize_noise(p));  // the coming kernel reads its noise
+  if (p->noise_virtual && p->noise_now.source != kNoiseInKernel) TRY(materialize_noise(p));  // the coming kernel reads its noise
   switch (p->cfg.mode) {
     case MPPI_MODE_DET:
     case MPPI_MODE_SPEED_MAP: return launch_rollout_map<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_TDM: return launch_rollout_tdm<EXACT, BOUNDED>(p, d);
     case MPPI_MODE_BAREBONE: {
+      TRY(check_chosen_launch(p, kLaunchBarebone));
       p->tile_packets_fresh = false;
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
       const bool rot = EXACT && rotation_ok(p, d);
@@ -702,6 +700,20 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
 static int launch_apply(mppi_planner* p);
 static int settle_reduce_pending(mppi_planner* p);
 
+// |theta| can never exceed |theta0| + T*dt*max|w|*max(traction): when that is far
+// inside the range of the two-term pi/2 reduction, the kernels drop the libm branch
+static bool refresh_theta_bounded(mppi_planner* p) {
+  const mppi_params& a = p->params;
+  const MapReach reach = map_reach(map_held(p));
+  double th0_max = std::fabs((double)a.x0[2]);
+  if (p->inst_set) {
+    th0_max = 0.0;
+    for (const BatchInst& I : p->inst_host) th0_max = std::fmax(th0_max, std::fabs((double)I.th0));
+  }
+  const double theta_bound = th0_max + (double)p->cfg.num_steps * (double)a.dt * reach.wmax * reach.trmax_ang;
+  return p->theta_bounded = std::isfinite(theta_bound) && theta_bound < 5.0e4;
+}
+
 static int launch_rollout(mppi_planner* p, const DevParams& d) {
   REQUIRE(p->B == 1 || p->inst_set, MPPI_ERR_STATE,
           "num_instances = %d: call mppi_planner_set_instances before solving", p->B);
@@ -713,18 +725,7 @@ static int launch_rollout(mppi_planner* p, const DevParams& d) {
     if (p->apply_pending && !rollout_keeps_pending_packets(held)) TRY(launch_apply(p));  // (sharded updates fold in deterministic-dynamics mode only)
     if (p->reduce_pending && !next_rollout_takes(held).reduces_tiles) TRY(settle_reduce_pending(p));
   }
-  // |theta| can never exceed |theta0| + T*dt*max|w|*max(traction): when that is far
-  // inside the range of the two-term pi/2 reduction, the kernels drop the libm branch
-  const mppi_params& a = p->params;
-  const MapReach reach = map_reach(map_held(p));
-  double th0_max = std::fabs((double)a.x0[2]);
-  if (p->inst_set) {
-    th0_max = 0.0;
-    for (const BatchInst& I : p->inst_host) th0_max = std::fmax(th0_max, std::fabs((double)I.th0));
-  }
-  double theta_bound = th0_max + (double)p->cfg.num_steps * (double)a.dt * reach.wmax * reach.trmax_ang;
-  bool bounded = std::isfinite(theta_bound) && theta_bound < 5.0e4;
-  p->theta_bounded = bounded;
+  const bool bounded = refresh_theta_bounded(p);
   // mppi_planner_time_kernels on a two-stream loop: the kernels of the throughput regime stamp their own begin / end
   DevParams dk = d;
   dk.ktime = p->ktime_rollout_slot;
@@ -823,7 +824,6 @@ static int launch_update_rows(mppi_planner* p, const UpdateChoice& c) {
                c.slim ? p->progress_dev : (unsigned long long*)nullptr, c.slim ? p->progress_seq : 0ull);
   if (p->graph_on) ++p->bumps_launched;
   HIP_TRY(hipGetLastError());
-  p->update_signalled = p->update_signals;
   return MPPI_OK;
 }
 
@@ -924,32 +924,86 @@ static int launch_update(mppi_planner* p, bool prof, bool defer_exchange = false
   return launch_update(p, update_choose(update_held(p, prof, defer_exchange)), prof);
 }
 
+// ---- the noise: what its choice depends on (noise_plan.h), read off a handle -- the only place that does --------------
+// The arguments are launch_iteration's.  The coming rollout launch is asked of the existing choices, behind
+// refresh_theta_bounded: launch_iteration used to ask map_choose in front of it -- which cannot change whether a
+// time-parallel kernel runs or generates its noise (map_scan does not read theta_bounded), while the pipelined, fused and
+// CVaR launchers, which do depend on it, decided their noise blocks and flags behind it, inside launch_rollout.
+static NoiseHeld noise_held(const mppi_planner* p, bool have_noise, bool want_next, bool prof, bool defer_exchange, bool may_leave_apply) {
+  NoiseHeld h;
+  memset(&h, 0, sizeof(h));
+  h.rng = p->cfg.rng; h.n_local = p->n_local; h.T = p->cfg.num_steps; h.num_cus = p->num_cus; h.num_grid_samples = p->cfg.num_grid_samples;
+  h.debug_flags = p->debug_flags; h.graph_on = p->graph_on; h.stream_flags_off = p->stream_flags_off;
+  h.flags_env_off = noise_flag_disabled(); h.flag_words = flag_words(p);
+  h.want_next = want_next; h.have_noise = have_noise;
+  h.noise_on_side_stream = p->noise_on_side_stream; h.prev_signalled = p->progress_capable_last;
+  switch (p->cfg.mode) {
+    case MPPI_MODE_DET:
+    case MPPI_MODE_SPEED_MAP: {
+      const MapChoice& c = map_choice(p, map_held(p));
+      const bool scan = c.family == kMapScan || c.family == kMapScanExact;
+      h.launch = c.family + 1;
+      h.workgroups = scan ? ceil_div(p->n_local, c.scan.tile) : c.grid;
+      h.scan_exact = scan && c.scan.exact;
+      break;
+    }
+    case MPPI_MODE_TDM: h.launch = tdm_fast_kernel(p) ? kLaunchCvarFast : kLaunchCvar; h.workgroups = p->n_local; break;
+    case MPPI_MODE_BAREBONE: h.launch = kLaunchBarebone; break;
+  }
+  UpdateHeld u = update_held(p, prof, defer_exchange, may_leave_apply);
+  u.scan_packets_fresh = h.launch == kLaunchScan || h.launch == kLaunchScanExact;  // (what the coming launch leaves)
+  u.want_next = 1;
+  h.update_can_host = update_noise_beside(u);
+  return h;
+}
+
+// The one generator on noise_stream: into the other noise buffer, held back behind that buffer's last reader as chosen,
+// announced through the flag, ev_noise_ready behind it.
+static int launch_noise_ahead(mppi_planner* p, const NoiseChoice& c) {
+  switch (c.hold) {
+    case kHoldEventBehind:  // (ordered behind the rollout launch itself)
+      HIP_TRY(hipEventRecord(p->ev_buf_free, p->stream));
+      [[fallthrough]];
+    case kHoldEventFront: HIP_TRY(hipStreamWaitEvent(p->noise_stream, p->ev_buf_free, 0)); break;
+    case kHoldGate:  // (on the start of the launch that signalled last: the rollout, or the update beside which this runs)
+      hipLaunchKernelGGL(k_wait_progress, dim3(1), dim3(64), 0, p->noise_stream, p->progress_dev, p->progress_seq, p->flag_fault_dev);
+      HIP_TRY(hipGetLastError());
+      break;
+    default: return fail(MPPI_ERR_STATE, "internal: a generator on the second stream that nothing holds back");
+  }
+  TraceRange tr(c.beside_update ? "mppi:noise_beside_update" : "mppi:noise_ahead");
+  TRY(launch_noise(p, p->noise_buf[p->noise_cur ^ 1], p->noise_stream));
+  p->used_side_stream = true;
+  if (c.announce != kAnnounceNone) {
+    p->noise_flag_expect = ++p->noise_flag_seq;
+    if (c.announce == kAnnounceFlag) {  // (else the test hook: a generator the consumer never hears of)
+      hipLaunchKernelGGL(k_set_noise_flag, dim3(1), dim3(1), 0, p->noise_stream, p->noise_flag_dev, p->noise_flag_expect);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(p->ev_noise_ready, p->noise_stream));
+  p->noise_on_side_stream = true;
+  // graph mode: join before the update, which advances the epoch counter the generator reads
+  // (and a captured iteration must not leave a fork open)
+  return c.join ? join_noise_ahead(p) : MPPI_OK;
+}
+
 // One iteration: {noise unless it was produced ahead, rollout (+ the next iteration's noise when
 // `want_next`), update}.  `have_noise`: noise_buf[noise_cur ^ 1] already holds this iteration's
-// noise; on return it says the same for the following iteration.
+// noise; on return it says the same for the following iteration.  Where the noise comes from, who produces the next
+// iteration's and how the streams are ordered around it: noise_choose (noise_plan.h).
 static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_noise, bool want_next, bool prof,
                             bool defer_exchange = false, bool may_leave_apply = false) {
-  // (below ~4M rollout-steps the generator takes less than the ~12 us a cross-stream dependency costs)
-  // and above 8 rollout waves per CU the register file has room for one generator wave per SIMD only: the generator
-  // crawls beside the rollout, slows it, and still collides with the update (measured in round 1, profiles/r01_ablation.md,
-  // and again in round 6 with a bound of 16: C5 187 us against 178, profiles/r06_ns_notes.md section 3)
-  constexpr int kSideStreamMaxWaves = 8;
-  const bool side_stream_pays = update_noise_is_long(p->n_local, p->cfg.num_steps) &&
-                                ceil_div(ceil_div(p->n_local, 64), p->num_cus) <= kSideStreamMaxWaves;
   const bool ktime_stamps = p->ktime_index >= 0 && p->ktime_dev && p->ktime_use_stamps;  // (mppi_planner_time_kernels)
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[0], p->stream));
-  // MPPI_MATH_FAST over a map the time-parallel kernel takes: the rollout launch computes its noise
-  // from the Philox counters itself; nothing is generated ahead, nothing is stored
-  const bool gen_in_rollout = scan_generates_noise(p);
-  p->scan_gen_now = gen_in_rollout;
-  if (gen_in_rollout) {
-    if (have_noise) discard_noise_ahead(p);  // (produced ahead by an earlier, different kind of launch)
-    have_noise = false;
-    want_next = false;
-  } else if (have_noise) {
+  (void)refresh_theta_bounded(p);
+  const NoiseChoice noise = noise_choose(noise_held(p, have_noise, want_next, prof, defer_exchange, may_leave_apply));
+  if (noise.source == kNoiseInKernel) {
+    if (noise.discard_ahead) discard_noise_ahead(p);
+  } else if (noise.source == kNoiseAhead) {
     p->noise_cur ^= 1;
     // (ordered behind the generator by the rollout launch itself: its flag, or the event -- settle_noise_wait)
-    if (p->noise_on_side_stream) p->noise_wait_pending = true;
+    p->noise_wait_pending = noise.consumer != kOrderNone;
     p->noise_on_side_stream = false;
     p->noise_virtual = false;
   } else {
@@ -958,22 +1012,9 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     TRY(launch_noise(p, p->noise_buf[p->noise_cur]));
   }
   p->noise = p->noise_buf[p->noise_cur];
-  p->next_noise_wanted = want_next;
-  p->next_noise_done = false;
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[1], p->stream));
-  // the other noise buffer was last read by the previous update, which is behind us on this stream
-  // The generator of the next iteration's noise (second stream, below) must not start before the previous update -- the
-  // last reader of the buffer it overwrites -- is complete.  A rollout launch that signals its own start (DevParams::
-  // progress) provides that without anything in front of it on this stream; the event recorded here held the launch back
-  // by ~6 us.  Whether the coming launch signals is known once it has been made (the kernel is chosen deep inside the
-  // launch paths): the event is left out when the previous iteration's launch did, and made up for behind the launch
-  // (one iteration without overlap) should this one not.
-  p->progress_signalled = false;
-  bool buf_free_recorded = false;
-  if (want_next && side_stream_pays && (!p->progress_capable_last || p->graph_on)) {
-    HIP_TRY(hipEventRecord(p->ev_buf_free, p->stream));
-    buf_free_recorded = true;
-  }
+  // (the other noise buffer was last read by the previous update, which is behind us on this stream)
+  if (noise.record_front) HIP_TRY(hipEventRecord(p->ev_buf_free, p->stream));
   {
     TraceRange tr("mppi:rollout");
     // mppi_planner_time_kernels.  A loop with the second stream in it is timed by the kernels themselves (device
@@ -985,7 +1026,9 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
       p->kev_start = p->ktime_events[4 * (size_t)p->ktime_index];
       p->kev_stop = p->ktime_events[4 * (size_t)p->ktime_index + 1];
     }
+    p->noise_now = noise;
     const int rc = launch_rollout(p, d);
+    p->noise_now = NoiseChoice();
     p->kev_start = p->kev_stop = nullptr;
     p->ktime_rollout_slot = nullptr;
     settle_noise_wait(p);  // (a path that launched nothing: whatever follows on the stream still needs the noise)
@@ -995,49 +1038,18 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     TraceRange tr("mppi:exchange_sample_costs");
     TRY(exchange_sample_costs(p));
   }
-  have_noise = p->next_noise_done;
-  if (want_next && !have_noise && side_stream_pays) {
-    if (buf_free_recorded) {
-      HIP_TRY(hipStreamWaitEvent(p->noise_stream, p->ev_buf_free, 0));
-    } else if (p->progress_signalled) {
-      hipLaunchKernelGGL(k_wait_progress, dim3(1), dim3(64), 0, p->noise_stream, p->progress_dev, p->progress_seq, p->flag_fault_dev);
-      HIP_TRY(hipGetLastError());
-    } else {  // (neither: ordered behind the rollout launch itself)
-      HIP_TRY(hipEventRecord(p->ev_buf_free, p->stream));
-      HIP_TRY(hipStreamWaitEvent(p->noise_stream, p->ev_buf_free, 0));
-    }
-    TraceRange tr("mppi:noise_ahead");
-    TRY(launch_noise(p, p->noise_buf[p->noise_cur ^ 1], p->noise_stream));
-    p->used_side_stream = true;
-    if (p->noise_flag_dev && !p->graph_on) {
-      p->noise_flag_expect = ++p->noise_flag_seq;
-      if (!(p->debug_flags & MPPI_DEBUG_DROP_NOISE_FLAG)) {  // (test hook: a generator the consumer never hears of)
-        hipLaunchKernelGGL(k_set_noise_flag, dim3(1), dim3(1), 0, p->noise_stream, p->noise_flag_dev, p->noise_flag_expect);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    HIP_TRY(hipEventRecord(p->ev_noise_ready, p->noise_stream));
-    have_noise = p->noise_on_side_stream = true;
-    if (p->graph_on) {
-      // graph mode: join before the update, which advances the epoch counter the generator reads
-      // (and a captured iteration must not leave a fork open)
-      HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_noise_ready, 0));
-      p->noise_on_side_stream = false;
-    }
-  }
-  p->progress_capable_last = p->progress_signalled;
+  if (noise.beside_rollout) TRY(launch_noise_ahead(p, noise));
+  p->progress_capable_last = noise.signals;
   // How this iteration's weights become the next u (update_plan.h), decided from what the rollout launch has left.
   // beside_update: the next iteration's noise is generated beside the update launch -- which runs slim
   // (k_update_rows<.., 256>: a quarter of the waves, the same bytes in flight) and signals its start to the generator's
   // gate kernel.  (MPPI_NO_NOISE_FLAG: no flags, no second stream here)
   UpdateHeld held = update_held(p, prof, defer_exchange, may_leave_apply);
-  held.want_next = want_next; held.have_noise = have_noise; held.side_stream_pays = side_stream_pays;
+  held.want_next = want_next && noise.source != kNoiseInKernel; held.have_noise = noise.have_after_rollout;
+  held.side_stream_pays = noise.side_stream_pays;
   const UpdateChoice update = update_choose(held);
-  p->update_signals = update.beside_update;
-  p->update_signalled = false;
+  REQUIRE(update.beside_update == (noise.beside_update != 0), MPPI_ERR_STATE, "internal: the update launch and the noise choice disagree on the generator beside the update");
   if (update.beside_update) ++p->progress_seq;
-  p->next_noise_wanted = false;
-  p->scan_gen_now = false;
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[2], p->stream));
   TraceRange tr_update("mppi:update");
   const int ktime_slot = p->ktime_index;
@@ -1054,24 +1066,12 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     const int rc = launch_update(p, update, prof);
     p->kev_start = p->kev_stop = nullptr;
     p->ktime_update_slot = nullptr;
-    p->update_signals = false;
     TRY(rc);
-    if (p->update_signalled) {  // the generator, gated on this update launch's start
-      p->update_signalled = false;
-      hipLaunchKernelGGL(k_wait_progress, dim3(1), dim3(64), 0, p->noise_stream, p->progress_dev, p->progress_seq, p->flag_fault_dev);
-      HIP_TRY(hipGetLastError());
-      TraceRange tr("mppi:noise_beside_update");
-      TRY(launch_noise(p, p->noise_buf[p->noise_cur ^ 1], p->noise_stream));
-      p->used_side_stream = true;
-      p->noise_flag_expect = ++p->noise_flag_seq;
-      hipLaunchKernelGGL(k_set_noise_flag, dim3(1), dim3(1), 0, p->noise_stream, p->noise_flag_dev, p->noise_flag_expect);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(p->ev_noise_ready, p->noise_stream));
-      have_noise = p->noise_on_side_stream = true;
-    }
+    if (noise.beside_update) TRY(launch_noise_ahead(p, noise));  // gated on this update launch's start
     // (an update left to the next rollout launch has no launch of its own to time)
     if (ktime_slot >= 0 && (size_t)ktime_slot < p->ktime_update_ran.size()) p->ktime_update_ran[(size_t)ktime_slot] = !p->reduce_pending;
   }
+  have_noise = noise.have_noise;
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[5], p->stream));
   return MPPI_OK;
 }

@@ -1,8 +1,8 @@
 // map_plan.h -- which kernel a rollout launch of the map modes (deterministic dynamics, speed map) runs and with what
 // geometry, as a pure function of what the handle holds.  Plain C++ without a HIP type: a host program compiles it on
 // its own (tests/test_map_plan.py pins the table).  map_held(p) (launch_plan.h) fills the state from a handle; the
-// launchers there carry a choice out.  What depends on the running loop -- whether the launch generates its noise, the
-// noise blocks of spare CUs, a pending update -- is the launchers' business, not the choice's.
+// launchers there carry a choice out.  What depends on the running loop is not this choice's business: whether the launch
+// generates its noise and the noise blocks of spare CUs are noise_plan.h's, a pending update update_plan.h's.
 #pragma once
 
 #include <algorithm>

@@ -701,6 +701,14 @@ extern "C" int mppi_planner_create(const mppi_planner_cfg* cfg, mppi_planner** o
   return MPPI_OK;
 }
 
+// the main stream waits for the generator in flight on the second stream, which is then forgotten
+static int join_noise_ahead(mppi_planner* p) {
+  const bool in_flight = p->noise_on_side_stream;
+  p->noise_on_side_stream = false;
+  if (in_flight) HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_noise_ready, 0));
+  return MPPI_OK;
+}
+
 // Graph mode keeps the noise of the next iteration ready.  Dropping it gives its Philox epoch
 // back, so that the sequence of noise blocks the iterations consume stays the one of the direct
 // loop (the xoroshiro-compatible generator cannot rewind: it simply moves on).
@@ -709,8 +717,7 @@ static void discard_noise_ahead(mppi_planner* p) {
   p->primed = false;
   // a generator still in flight on the second stream must not overlap the next one on the main
   // stream (they share the xoroshiro states)
-  if (p->noise_on_side_stream) (void)hipStreamWaitEvent(p->stream, p->ev_noise_ready, 0);
-  p->noise_on_side_stream = false;
+  (void)join_noise_ahead(p);
 }
 
 extern "C" int mppi_planner_set_params(mppi_planner* p, const mppi_params* params) {
@@ -1259,8 +1266,7 @@ extern "C" int mppi_planner_sample_noise(mppi_planner* p) {
   if (p->primed) {
     // the next block of the noise sequence has already been generated (by the last iteration of
     // the previous call): hand it out instead of skipping it
-    if (p->noise_on_side_stream) HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_noise_ready, 0));
-    p->noise_on_side_stream = false;
+    TRY(join_noise_ahead(p));
     p->noise_cur ^= 1;
     p->noise = p->noise_buf[p->noise_cur];
     p->primed = false;
