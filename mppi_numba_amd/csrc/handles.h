@@ -3,6 +3,7 @@
 #include "host_common.h"
 #include "map_plan.h"
 #include "noise_plan.h"
+#include "cvar_plan.h"
 
 // ---------------------------------------------------------------------------
 // TDM

@@ -1,6 +1,8 @@
-// launch_plan.h -- which kernels an iteration launches and with what geometry: packing of the map cells,
-// LDS window planning, the regime selection of the rollout kernels, the update / exchange launches, the
-// iteration loop with its hipGraph replay.  Host code only; the C ABI shims that call into it are in
+// launch_plan.h -- the launches of an iteration: packing of the map cells, the rollout kernels of every mode, the
+// update / exchange launches, the iteration loop with its hipGraph replay.  What is launched and with what geometry is
+// decided by the pure functions of map_plan.h, cvar_plan.h, barebone_plan.h, noise_plan.h and update_plan.h; here are the
+// adapters that fill their states from a handle (map_held, cvar_held, cells_held, update_held, noise_held) and the
+// launchers that carry a choice out and keep every side effect.  Host code only; the C ABI shims that call into it are in
 // mppi_api.hip (which is the only file that includes this one: everything here has internal linkage).
 #pragma once
 #include "handles.h"
@@ -47,10 +49,8 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.inv_res = 1.0f / d.res;
   d.xlo = a.xlo; d.ylo = a.ylo;
   d.cvar_alpha = a.cvar_alpha;
-  d.numel = (int)std::ceil((double)p->cfg.num_grid_samples * (double)a.cvar_alpha);
-  if (d.numel < 1) d.numel = 1;
-  if (d.numel > p->cfg.num_grid_samples) d.numel = p->cfg.num_grid_samples;
-  // (samples sharded over GPUs: the local kernel's own reduction is not used; cvar_numel())
+  // (samples sharded over GPUs: the local kernel's own reduction is not used; cvar_reduce_choose)
+  d.numel = cvar_numel(p->cfg.num_grid_samples, a.cvar_alpha);
   d.dist_weight = a.dist_weight;
   d.v_post_den = (double)a.v_post_rollout + 1e-6;
   d.lin_lo = m.lin_lo; d.lin_ratio = m.lin_ratio; d.rows = m.rows; d.cols = m.cols;
@@ -107,38 +107,39 @@ static void note_packed(mppi_planner* p, const mppi_tdm* lin, const mppi_tdm* an
   m.risk = lin->risk;
 }
 
-// solve() of a CVaR planner, Philox generators: both TDMs sampled straight into the cell words
-// the rollout gathers (k_sample_cellsM_philox), no (G, R, C) int8 grids and no transpose; the
-// int8 grids follow on demand from the same counters (tdm_materialize).  Returns false when
-// the ordinary sample + pack path has to run.
-static bool sample_into_cells(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, double alpha_dyn, int* rc) {
-  *rc = MPPI_OK;
-  if (p->cfg.mode != MPPI_MODE_TDM || lin == ang) return false;
-  if (lin->cfg.rng != MPPI_RNG_PHILOX || ang->cfg.rng != MPPI_RNG_PHILOX) return false;
-  if (lin->bins > 64 || ang->bins > 64 || !(alpha_dyn > 0.0)) return false;
-  if (lin->first_sample != ang->first_sample) return false;
+// ---- from the TDMs to the cell words: what the route depends on (cvar_plan.h: cells_choose), read off the handles --
+//      the only place that does.  for_solve: asked by sample_for_solve, with the alpha_dyn it samples at. ----------------
+static CellsHeld cells_held(const mppi_planner* p, const mppi_tdm* lin, const mppi_tdm* ang, bool for_solve, double alpha_dyn) {
+  CellsHeld h;
+  memset(&h, 0, sizeof(h));
+  h.mode = p->cfg.mode; h.M = p->cfg.num_grid_samples; h.for_solve = for_solve;
+  if (h.mode == MPPI_MODE_BAREBONE) return h;  // (no TDMs)
+  h.same_tdm = lin == ang;
+  h.lin_rng = lin->cfg.rng; h.ang_rng = ang->cfg.rng; h.lin_bins = lin->bins; h.ang_bins = ang->bins;
+  h.alpha_positive = alpha_dyn > 0.0;
+  h.lin_first_sample = lin->first_sample; h.ang_first_sample = ang->first_sample;
+  h.rows = lin->rows; h.cols = lin->cols;
+  h.lin_compact_ok = lin->compact_ok; h.ang_compact_ok = ang->compact_ok;
+  h.lin_injected = lin->injected; h.ang_injected = ang->injected;
+  h.lin_injected_nonneg = lin->injected_min >= 0; h.ang_injected_nonneg = ang->injected_min >= 0;
+  h.has_risk = lin->has_risk;
+  const PackedMaps& m = p->packed;
+  h.packed_match = m.lin_maps == lin->maps_version && m.lin_grid == lin->grid_version && m.ang_maps == ang->maps_version &&
+                   m.ang_grid == ang->grid_version;
+  return h;
+}
+
+// solve() of a CVaR planner: both TDMs sampled straight into the cell words the rollout gathers; the int8 grids follow
+// on demand from the same counters (tdm_materialize)
+static int sample_into_cells(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, double alpha_dyn, const CellsChoice& c) {
   const int M = p->cfg.num_grid_samples;
-  // a wave of this kernel sets up the thresholds of its 4 cells for M/64 rounds of draws: measured
-  // against sample + sample + transpose, 65 vs 61 us at M = 128 and 192 vs 363 us at M = 1024
-  if (M < 192) return false;
-  if ((*rc = reserve_cells(p, lin, M)) != MPPI_OK) return true;
-  const long cell_groups = (long)lin->rows * ((lin->cols + 3) / 4);
-  const int bins = std::max(lin->bins, ang->bins);
-  dim3 grid((unsigned)ceil_div(cell_groups, 4));
-#define MPPI_SAMPLE_CELLS(MAXB)                                                                                    \
-  hipLaunchKernelGGL(k_sample_cellsM_philox<MAXB>, grid, dim3(256), 0, p->stream, lin->pmf, lin->bins, lin->table, \
-                     lin->cfg.seed, lin->epoch, ang->pmf, ang->bins, ang->table, ang->cfg.seed, ang->epoch,        \
-                     lin->obs, lin->unk, lin->rows, lin->cols, alpha_dyn, M, p->cells,                            \
-                     (uint64_t)(lin->first_sample >> 1) * (uint64_t)cell_groups)
-  if (bins <= 8) MPPI_SAMPLE_CELLS(8);
-  else if (bins <= 16) MPPI_SAMPLE_CELLS(16);
-  else if (bins <= 32) MPPI_SAMPLE_CELLS(32);
-  else MPPI_SAMPLE_CELLS(64);
-#undef MPPI_SAMPLE_CELLS
-  if (hipGetLastError() != hipSuccess) {
-    *rc = fail(MPPI_ERR_HIP, "k_sample_cellsM_philox launch failed");
-    return true;
-  }
+  TRY(reserve_cells(p, lin, M));
+  static const decltype(&k_sample_cellsM_philox<8>) forms[4] = {k_sample_cellsM_philox<8>, k_sample_cellsM_philox<16>,
+                                                                k_sample_cellsM_philox<32>, k_sample_cellsM_philox<64>};
+  hipLaunchKernelGGL(forms[c.bins], dim3(c.grid_x), dim3(256), 0, p->stream, lin->pmf, lin->bins, lin->table, lin->cfg.seed,
+                     lin->epoch, ang->pmf, ang->bins, ang->table, ang->cfg.seed, ang->epoch, lin->obs, lin->unk, lin->rows,
+                     lin->cols, alpha_dyn, M, p->cells, (uint64_t)(lin->first_sample >> 1) * (uint64_t)c.cell_groups);
+  if (hipGetLastError() != hipSuccess) return fail(MPPI_ERR_HIP, "k_sample_cellsM_philox launch failed");
   for (mppi_tdm* t : {lin, ang}) {
     t->sampled_epoch = t->epoch++;
     t->sampled_alpha = alpha_dyn;
@@ -149,7 +150,7 @@ static bool sample_into_cells(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang, dou
   }
   p->cells16_valid = false;
   note_packed(p, lin, ang);
-  return true;
+  return MPPI_OK;
 }
 
 // (re)build the packed cell words when the sampled grids or the masks changed
@@ -158,51 +159,39 @@ static int ensure_packed(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {
   // solve() samples the traction grids itself; the stage-level entry points use what is there
   REQUIRE(lin->grid_version > 0 && ang->grid_version > 0, MPPI_ERR_STATE,
           "traction grids have never been sampled: call mppi_tdm_sample_grids (or mppi_planner_solve) first");
-  const PackedMaps& m = p->packed;
-  if (m.lin_maps == lin->maps_version && m.lin_grid == lin->grid_version && m.ang_maps == ang->maps_version &&
-      m.ang_grid == ang->grid_version)
-    return MPPI_OK;
+  const CellsChoice c = cells_choose(cells_held(p, lin, ang, false, 0.0));
+  if (c.route == kCellsNothing) return MPPI_OK;
   const int M = p->cfg.num_grid_samples;
   TRY(reserve_cells(p, lin, M));
   // (another planner may have sampled these TDMs straight into ITS cell words)
   TRY(tdm_materialize(lin, p->stream));
   TRY(tdm_materialize(ang, p->stream));
   p->cells16_valid = false;
-  if (M == 1) {
-    hipLaunchKernelGGL(k_pack_cells_single, dim3(ceil_div((long)lin->rows * lin->cols, 256)), dim3(256), 0,
-                       p->stream, lin->grid, ang->grid, lin->cfg.max_cols, lin->obs, lin->unk, lin->rows,
-                       lin->cols, p->cells);
-    auto grid_7bit = [](const mppi_tdm* t) {
-      return t->injected ? (t->injected_min >= 0) : t->compact_ok;
-    };
-    if (lin->compact_ok && grid_7bit(lin) && grid_7bit(ang)) {
-      p->pitch16 = ceil_div(lin->cols, 8) * 8;
-      // speed-map mode: 32-bit cells (16 bits + risk byte) in the same buffer, twice the 16-bit units
-      const bool with_risk = p->cfg.mode == MPPI_MODE_SPEED_MAP && lin->has_risk;
-      size_t need16 = (size_t)lin->rows * p->pitch16 * (with_risk ? 2 : 1);
-      if (need16 > p->cells16_capacity) {
+  if (c.route == kCellsPackMulti) {
+    hipLaunchKernelGGL(k_pack_cells_multi, dim3(c.grid_x, c.grid_y), dim3(256), 0, p->stream, lin->grid, ang->grid,
+                       lin->cfg.max_rows, lin->cfg.max_cols, lin->obs, lin->unk, lin->rows, lin->cols, M, p->cells);
+  } else {
+    hipLaunchKernelGGL(k_pack_cells_single, dim3(c.grid_x), dim3(256), 0, p->stream, lin->grid, ang->grid, lin->cfg.max_cols,
+                       lin->obs, lin->unk, lin->rows, lin->cols, p->cells);
+    if (c.mirror != kMirrorNone) {
+      p->pitch16 = c.pitch16;
+      if (c.mirror_units > p->cells16_capacity) {
         HIP_TRY(hipStreamSynchronize(p->stream));
         dev_free(p->cells16);
         p->cells16_capacity = 0;  // (stays 0 if the allocation below fails)
-        TRY(dev_alloc(&p->cells16, need16));
-        p->cells16_capacity = need16;
+        TRY(dev_alloc(&p->cells16, c.mirror_units));
+        p->cells16_capacity = c.mirror_units;
       }
-      if (with_risk)
-        hipLaunchKernelGGL(k_pack_cells32_risk, dim3(ceil_div((long)lin->rows * p->pitch16, 256)), dim3(256), 0,
-                           p->stream, lin->grid, ang->grid, lin->cfg.max_cols, lin->obs, lin->unk, lin->risk,
-                           lin->rows, lin->cols, p->pitch16, reinterpret_cast<uint32_t*>(p->cells16));
+      if (c.mirror == kMirror32Risk)
+        hipLaunchKernelGGL(k_pack_cells32_risk, dim3(c.mirror_grid), dim3(256), 0, p->stream, lin->grid, ang->grid,
+                           lin->cfg.max_cols, lin->obs, lin->unk, lin->risk, lin->rows, lin->cols, p->pitch16,
+                           reinterpret_cast<uint32_t*>(p->cells16));
       else
-        hipLaunchKernelGGL(k_pack_cells16, dim3(ceil_div((long)need16, 256)), dim3(256), 0, p->stream, lin->grid,
-                           ang->grid, lin->cfg.max_cols, lin->obs, lin->unk, lin->rows, lin->cols, p->pitch16,
-                           p->cells16);
+        hipLaunchKernelGGL(k_pack_cells16, dim3(c.mirror_grid), dim3(256), 0, p->stream, lin->grid, ang->grid,
+                           lin->cfg.max_cols, lin->obs, lin->unk, lin->rows, lin->cols, p->pitch16, p->cells16);
       p->cells16_valid = true;
-      p->cells16_with_risk = with_risk;
+      p->cells16_with_risk = c.mirror == kMirror32Risk;
     }
-  } else {
-    dim3 grid((unsigned)(lin->rows * ceil_div(lin->cols, 64)), (unsigned)ceil_div(M, 64));
-    hipLaunchKernelGGL(k_pack_cells_multi, grid, dim3(256), 0, p->stream, lin->grid, ang->grid,
-                       lin->cfg.max_rows, lin->cfg.max_cols, lin->obs, lin->unk, lin->rows, lin->cols, M,
-                       p->cells);
   }
   HIP_TRY(hipGetLastError());
   note_packed(p, lin, ang);
@@ -295,9 +284,15 @@ static bool plan_lds_window(mppi_planner* p, DevParams& d, size_t* lds_bytes) {
   return apply_window(p, h, map_window(h), d, lds_bytes);
 }
 
-// (the CVaR and barebone launchers ask these two on their own)
-static bool rotation_ok(const mppi_planner* p, const DevParams&) { return map_rotation_ok(map_held(p)); }
-static bool res_is_pow2(const mppi_planner* p) { return map_res_pow2(map_held(p)); }
+// ---- the CVaR mode: what its kernel choice depends on (cvar_plan.h: cvar_choose), read off a handle -- the only place
+//      that does ------------------------------------------------------------------------------------------------------
+static CvarHeld cvar_held(const mppi_planner* p) {
+  CvarHeld h;
+  memset(&h, 0, sizeof(h));
+  h.map = map_held(p);
+  h.num_grid_samples = p->cfg.num_grid_samples; h.m_count = p->m_count; h.want_sample_costs = p->want_sample_costs;
+  return h;
+}
 
 // per-problem start / goal / window origin -> device, when they changed
 static int upload_instances(mppi_planner* p) {
@@ -358,13 +353,6 @@ static const MapChoice& map_choice(const mppi_planner* p, const MapHeld& h) {
     p->choice_valid = true;
   }
   return p->choice_cached;
-}
-
-// the CVaR mode's fast kernel runs: (cos, sin) by rotation, |theta| bounded, its LDS within 64 KiB
-static bool tdm_fast_kernel(const mppi_planner* p, size_t* lds_fast = nullptr) {
-  const size_t lds = (sizeof(double2) + sizeof(double)) * (size_t)p->cfg.num_steps + sizeof(float) * (size_t)next_pow2(p->cfg.num_grid_samples);
-  if (lds_fast) *lds_fast = lds;
-  return p->theta_bounded && map_rotation_ok(map_held(p)) && lds <= 64 * 1024;
 }
 
 // inside an iteration: the rollout launch about to be made is the one the iteration's noise was chosen for
@@ -625,50 +613,36 @@ static int launch_rollout_map(mppi_planner* p, DevParams d) {
   return MPPI_OK;
 }
 
-template <bool EXACT, bool BOUNDED>
-static int launch_rollout_tdm(mppi_planner* p, DevParams d) {
-  const int N = p->n_local, T = p->cfg.num_steps;
-  const int M = p->cfg.num_grid_samples;
-  size_t lds = sizeof(double2) * (size_t)T;
-  int mp2 = next_pow2(M);
-  const int threads = noise_cvar_threads(M);
-  lds += sizeof(float) * (size_t)mp2;
-  REQUIRE(lds <= 160 * 1024, MPPI_ERR_INVALID, "T=%d, M=%d need %zu bytes of LDS (> 160 KiB)", T, M, lds);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rollout_tdm<EXACT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (p->want_sample_costs && !p->sample_costs && p->m_count == 1) TRY(dev_alloc(&p->sample_costs, (size_t)N * M));
-  if (p->m_count > 1 && !p->slabs) TRY(dev_alloc(&p->slabs, (size_t)p->m_count * N * M));
+// CVaR mode: ask the choice (cvar_plan.h: cvar_choose), allocate what it names, launch its form, write the text
+static int launch_rollout_tdm(mppi_planner* p, const DevParams& d) {
+  const int N = p->n_local, T = p->cfg.num_steps, M = p->cfg.num_grid_samples;
+  const CvarChoice c = cvar_choose(cvar_held(p));
+  REQUIRE(!c.refused, MPPI_ERR_INVALID, "T=%d, M=%d need %zu bytes of LDS (> 160 KiB)", T, M, c.lds);
+  static const decltype(&k_rollout_tdm<true>) general[2] = {k_rollout_tdm<false>, k_rollout_tdm<true>};  // [EXACT]
+  static const decltype(&k_rollout_tdm_fast<true, true>) fast[2][2] = {  // [POW2RES][cost f32]
+      {k_rollout_tdm_fast<false, false>, k_rollout_tdm_fast<false, true>}, {k_rollout_tdm_fast<true, false>, k_rollout_tdm_fast<true, true>}};
+  if (c.set_attribute)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(general[c.exact]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+  if (c.costs_to == kCvarCostsSampleCosts && !p->sample_costs) TRY(dev_alloc(&p->sample_costs, (size_t)N * M));
+  if (c.costs_to == kCvarCostsSlab && !p->slabs) TRY(dev_alloc(&p->slabs, (size_t)p->m_count * N * M));
   // sharded samples: the per-sample costs go into this rank's slab of the gather buffer
-  float* const sc_dst = p->m_count > 1 ? p->slabs + (size_t)p->m_rank * N * M
-                                       : (p->want_sample_costs ? p->sample_costs : nullptr);
+  float* const sc_dst = c.costs_to == kCvarCostsSlab ? p->slabs + (size_t)p->m_rank * N * M
+                                                     : (c.costs_to == kCvarCostsSampleCosts ? p->sample_costs : nullptr);
   p->tile_packets_fresh = false;
   TRY(upload_instances(p));
-  {
-    size_t lds_fast = 0;
-    if (tdm_fast_kernel(p, &lds_fast)) {  // (p->theta_bounded: launch_rollout hands exact arithmetic BOUNDED with it)
-      TRY(check_chosen_launch(p, kLaunchCvarFast));
-      const bool pow2res = res_is_pow2(p);
-      float* sc_out = sc_dst;
-      // the next iteration's noise by workgroups appended to the grid (they run in the launch's tail)
-      const int extra = p->noise_now.extra_blocks;
-      const NoiseJob next_job = next_noise_job(p, extra);
-      if (pow2res)
-        MPPI_KLAUNCH((k_rollout_tdm_fast<true, !EXACT>), dim3(N + extra), dim3(threads), lds_fast, p->stream, d, p->cells,
-                           p->noise, p->u, p->costs, sc_out, mp2, N, next_job);
-      else
-        MPPI_KLAUNCH((k_rollout_tdm_fast<false, !EXACT>), dim3(N + extra), dim3(threads), lds_fast, p->stream, d, p->cells,
-                           p->noise, p->u, p->costs, sc_out, mp2, N, next_job);
-      p->last_rollout = std::string(EXACT ? "k_rollout_tdm_fast" : "k_rollout_tdm_fast<cost f32>") + " pow2res=" +
-                        (pow2res ? "1" : "0") + " noise_blocks=" + std::to_string(extra);
-      HIP_TRY(hipGetLastError());
-      return MPPI_OK;
-    }
+  TRY(check_chosen_launch(p, c.launch));
+  if (c.fast) {
+    // the next iteration's noise by workgroups appended to the grid (they run in the launch's tail)
+    const int extra = p->noise_now.extra_blocks;
+    const NoiseJob next_job = next_noise_job(p, extra);
+    MPPI_KLAUNCH(fast[c.pow2res][c.cost_f32], dim3(N + extra), dim3(c.threads), c.lds, p->stream, d, p->cells, p->noise, p->u,
+                 p->costs, sc_dst, c.mp2, N, next_job);
+    p->last_rollout = std::string(c.cost_f32 ? "k_rollout_tdm_fast<cost f32>" : "k_rollout_tdm_fast") + " pow2res=" +
+                      (c.pow2res ? "1" : "0") + " noise_blocks=" + std::to_string(extra);
+  } else {
+    MPPI_KLAUNCH(general[c.exact], dim3(N), dim3(c.threads), c.lds, p->stream, d, p->cells, p->noise, p->u, p->costs, sc_dst, c.mp2);
+    p->last_rollout = "k_rollout_tdm exact=" + std::to_string(c.exact);
   }
-  TRY(check_chosen_launch(p, kLaunchCvar));
-  MPPI_KLAUNCH((k_rollout_tdm<EXACT>), dim3(N), dim3(threads), lds, p->stream, d, p->cells, p->noise,
-                     p->u, p->costs, sc_dst, mp2);
-  p->last_rollout = "k_rollout_tdm exact=" + std::to_string((int)EXACT);
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -683,12 +657,12 @@ static int launch_rollout_t(mppi_planner* p, DevParams d) {
   switch (p->cfg.mode) {
     case MPPI_MODE_DET:
     case MPPI_MODE_SPEED_MAP: return launch_rollout_map<EXACT, BOUNDED>(p, d);
-    case MPPI_MODE_TDM: return launch_rollout_tdm<EXACT, BOUNDED>(p, d);
+    case MPPI_MODE_TDM: return launch_rollout_tdm(p, d);
     case MPPI_MODE_BAREBONE: {
       TRY(check_chosen_launch(p, kLaunchBarebone));
       p->tile_packets_fresh = false;
       // (cos, sin) by rotation where the host can bound the heading increment: |dt * w| <= 0.36 rad, T <= 2000
-      const bool rot = EXACT && rotation_ok(p, d);
+      const bool rot = EXACT && map_rotation_ok(map_held(p));
       return p->inst_set ? launch_barebone<EXACT, true>(p, d, rot) : launch_barebone<EXACT, false>(p, d, rot);
     }
     default:
@@ -736,21 +710,13 @@ static int launch_rollout(mppi_planner* p, const DevParams& d) {
 
 // ---- CVaR mode, samples sharded over GPUs: all-gather of the (N, M/G) cost slabs, then every
 //      rank reduces all N control samples over all M costs ---------------
-static int cvar_numel(const mppi_planner* p) {
-  const int M = p->cfg.num_grid_samples * p->m_count;
-  int numel = (int)std::ceil((double)M * (double)p->params.cvar_alpha);  // mppi.py:716-717 over all M samples
-  return numel < 1 ? 1 : (numel > M ? M : numel);
-}
-
 static int launch_cvar_reduce(mppi_planner* p) {
-  const int N = p->n_local, Ml = p->cfg.num_grid_samples, M = Ml * p->m_count;
-  const int mp2 = next_pow2(M);
-  const int threads = mp2 > 1024 ? 1024 : (mp2 < 64 ? 64 : mp2);  // one element per thread when it fits
-  const size_t lds = sizeof(float) * (size_t)mp2;
-  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "M = %d samples over all shards: too many for the CVaR reduction", M);
-  if (p->want_sample_costs && p->sample_costs == nullptr) TRY(dev_alloc(&p->sample_costs, (size_t)N * M));
-  hipLaunchKernelGGL(k_cvar_reduce, dim3(N), dim3(threads), lds, p->stream, p->slabs, p->m_count, N, Ml, cvar_numel(p),
-                     p->params.cvar_alpha, p->costs, p->want_sample_costs ? p->sample_costs : (float*)nullptr, mp2);
+  const int N = p->n_local, Ml = p->cfg.num_grid_samples;
+  const CvarReduceChoice c = cvar_reduce_choose(Ml, p->m_count, p->params.cvar_alpha);
+  REQUIRE(!c.refused, MPPI_ERR_INVALID, "M = %d samples over all shards: too many for the CVaR reduction", c.m_total);
+  if (p->want_sample_costs && p->sample_costs == nullptr) TRY(dev_alloc(&p->sample_costs, (size_t)N * c.m_total));
+  hipLaunchKernelGGL(k_cvar_reduce, dim3(N), dim3(c.threads), c.lds, p->stream, p->slabs, p->m_count, N, Ml, c.numel,
+                     p->params.cvar_alpha, p->costs, p->want_sample_costs ? p->sample_costs : (float*)nullptr, c.mp2);
   HIP_TRY(hipGetLastError());
   p->tile_packets_fresh = false;
   p->sample_costs_local_only = false;
@@ -947,7 +913,12 @@ static NoiseHeld noise_held(const mppi_planner* p, bool have_noise, bool want_ne
       h.scan_exact = scan && c.scan.exact;
       break;
     }
-    case MPPI_MODE_TDM: h.launch = tdm_fast_kernel(p) ? kLaunchCvarFast : kLaunchCvar; h.workgroups = p->n_local; break;
+    case MPPI_MODE_TDM: {
+      const CvarChoice c = cvar_choose(cvar_held(p));
+      h.launch = c.launch;
+      h.workgroups = c.workgroups;
+      break;
+    }
     case MPPI_MODE_BAREBONE: h.launch = kLaunchBarebone; break;
   }
   UpdateHeld u = update_held(p, prof, defer_exchange, may_leave_apply);
@@ -1277,8 +1248,8 @@ static int sample_for_solve(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {
   if (p->cfg.mode == MPPI_MODE_BAREBONE) return MPPI_OK;
   TraceRange tr("mppi:sample_grids");
   double alpha = (p->cfg.mode == MPPI_MODE_TDM) ? p->params.alpha_dyn : 1.0;
-  int rc = MPPI_OK;
-  if (sample_into_cells(p, lin, ang, alpha, &rc)) return rc;
+  const CellsChoice c = cells_choose(cells_held(p, lin, ang, true, alpha));
+  if (c.route == kCellsSample) return sample_into_cells(p, lin, ang, alpha, c);
   TRY(tdm_sample_on(lin, alpha, p->stream));
   TRY(tdm_sample_on(ang, alpha, p->stream));
   return MPPI_OK;

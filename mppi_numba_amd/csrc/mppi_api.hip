@@ -327,32 +327,26 @@ extern "C" int mppi_tdm_get_maps(mppi_tdm* t, int8_t* pmf, int8_t* obstacle, int
   return MPPI_OK;
 }
 
+// the geometry of a TDM's sampling kernel (cvar_plan.h: sample_choose)
+static SampleChoice tdm_sample_choice(const mppi_tdm* t) {
+  return sample_choose(t->cfg.rng, t->bins, t->rows, t->cols, t->cfg.num_grids, t->cfg.thread_dim_x, t->cfg.thread_dim_y);
+}
+
 // the Philox draws of (epoch, alpha_dyn) into the (G, R, C) int8 grids
 static int tdm_launch_philox(mppi_tdm* t, double alpha_dyn, uint64_t epoch, hipStream_t stream) {
   const int G = t->cfg.num_grids;
-  {
-    const long cell_groups = (long)t->rows * ((t->cols + 3) / 4);
-    if (t->bins <= 64) {
-      // enough workgroups to fill the chip, as many samples per thread as that allows
-      int chunks = ceil_div(256L * 1024, cell_groups);
-      chunks = chunks < 1 ? 1 : (chunks > G ? G : chunks);
-      const int g_chunk = (ceil_div(G, chunks) + 1) & ~1;  // even: a Philox block serves a pair of samples
-      dim3 grid((unsigned)ceil_div(cell_groups, 256), (unsigned)ceil_div(G, g_chunk));
-#define MPPI_SAMPLE(MAXB)                                                                                       \
-  hipLaunchKernelGGL(k_sample_grids_philox_cols<MAXB>, grid, dim3(256), 0, stream, t->pmf, t->bins, t->rows, t->cols, \
-                     t->table, alpha_dyn, t->cfg.seed, epoch, G, g_chunk, t->grid, t->cfg.max_rows, t->cfg.max_cols, \
-                     (uint64_t)(t->first_sample >> 1) * (uint64_t)cell_groups)
-      if (t->bins <= 8) MPPI_SAMPLE(8);
-      else if (t->bins <= 16) MPPI_SAMPLE(16);
-      else if (t->bins <= 32) MPPI_SAMPLE(32);
-      else MPPI_SAMPLE(64);
-#undef MPPI_SAMPLE
-    } else {
-      long total = (long)G * cell_groups;
-      hipLaunchKernelGGL(k_sample_grids_philox, dim3(ceil_div(total, 256)), dim3(256), 0, stream, t->pmf, t->bins,
-                         t->rows, t->cols, t->table, alpha_dyn, t->cfg.seed, epoch, G, t->grid,
-                         t->cfg.max_rows, t->cfg.max_cols, (uint64_t)t->first_sample * (uint64_t)cell_groups);
-    }
+  const SampleChoice c = tdm_sample_choice(t);
+  const dim3 grid(c.grid_x, c.grid_y);
+  if (c.kernel == kSampleColumns) {
+    static const decltype(&k_sample_grids_philox_cols<8>) forms[4] = {k_sample_grids_philox_cols<8>, k_sample_grids_philox_cols<16>,
+                                                                     k_sample_grids_philox_cols<32>, k_sample_grids_philox_cols<64>};
+    hipLaunchKernelGGL(forms[c.bins], grid, dim3(c.block), 0, stream, t->pmf, t->bins, t->rows, t->cols, t->table, alpha_dyn,
+                       t->cfg.seed, epoch, G, c.g_chunk, t->grid, t->cfg.max_rows, t->cfg.max_cols,
+                       (uint64_t)(t->first_sample >> 1) * (uint64_t)c.cell_groups);
+  } else {
+    hipLaunchKernelGGL(k_sample_grids_philox, grid, dim3(c.block), 0, stream, t->pmf, t->bins, t->rows, t->cols, t->table,
+                       alpha_dyn, t->cfg.seed, epoch, G, t->grid, t->cfg.max_rows, t->cfg.max_cols,
+                       (uint64_t)t->first_sample * (uint64_t)c.cell_groups);
   }
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
@@ -377,10 +371,10 @@ static int tdm_sample_on(mppi_tdm* t, double alpha_dyn, hipStream_t stream) {
     t->grid_stale = false;
     ++t->epoch;
   } else {
-    int threads = G * t->cfg.thread_dim_x * t->cfg.thread_dim_y;
-    hipLaunchKernelGGL(k_sample_grids_xoroshiro, dim3(ceil_div(threads, 64)), dim3(64), 0, stream, t->pmf,
-                       t->bins, t->rows, t->cols, t->table, alpha_dyn, t->states, G, t->cfg.thread_dim_x,
-                       t->cfg.thread_dim_y, t->grid, t->cfg.max_rows, t->cfg.max_cols);
+    const SampleChoice c = tdm_sample_choice(t);
+    hipLaunchKernelGGL(k_sample_grids_xoroshiro, dim3(c.grid_x), dim3(c.block), 0, stream, t->pmf, t->bins, t->rows, t->cols,
+                       t->table, alpha_dyn, t->states, G, t->cfg.thread_dim_x, t->cfg.thread_dim_y, t->grid, t->cfg.max_rows,
+                       t->cfg.max_cols);
   }
   HIP_TRY(hipGetLastError());
   t->sampled_maps_version = t->maps_version;
