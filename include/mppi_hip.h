@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPPI_HIP_ABI_VERSION 1
+#define MPPI_HIP_ABI_VERSION 2
 
 typedef enum mppi_status {
   MPPI_OK = 0,
@@ -263,6 +263,30 @@ int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* offsets);
 int mppi_planner_set_crowd(mppi_planner* p, int on);
 int mppi_planner_get_crowd(mppi_planner* p, int* on);
 
+/* MPPI_MODE_BAREBONE in crowd mode only: disc samples -- S sampled futures of K moving discs, as a
+ * predictor of pedestrians hands them out.  positions is (samples, disc_count, rows, 2) float32:
+ * sample s is a track set as for mppi_planner_set_disc_tracks (rows are instants, "now" is the
+ * problem's track offset, the state after step t meets row min(offset + t + 1, rows - 1)); radii
+ * (disc_count) float32, finite and >= 0.  The cost of a rollout under sample s is, bit for bit, the
+ * cost of the crowd launch with that sample as its disc tracks; walls, wall tracks, the fleet's
+ * walls and a goal track stay in force and do not depend on s.  The rollout's cost is the CVaR tail
+ * over its S costs (mppi_params::cvar_alpha, 0 < alpha <= 1; the reference's mppi.py:716-755 with
+ * block_width = S): sorted descending iff alpha < 1, the strided float32 tree over the first
+ * numel = ceil(S * alpha) entries, divided in double.  S = 1 is the plain track set to the bit.
+ * While held the samples are the disc source of every launch (the tracks' place: the shared static
+ * set rests) and every problem of a batched handle sees the same set; they count as disc tracks
+ * wherever rows are counted (mppi_planner_closed_loop advances "now").  samples = 0 clears.
+ * Unchanged input costs a comparison; a change drops the captured graphs and, for a set of more
+ * than one row, sets every offset to 0.  mppi_planner_describe_last_rollout ends in
+ * " samples=<S> numel=<n>".  MPPI_ERR_INVALID for a map mode, crowd mode off, samples outside
+ * [0, 16] (kCrowdSamplesMax), rows < 1, disc_count + walls > 65535 (a step's hits are counted in
+ * 16 bits), a radius that is negative or not finite, or per-problem disc sets / disc tracks held.
+ * While samples are held, mppi_planner_set_disc_tracks and
+ * mppi_planner_set_instance_disc_obstacles with a count, and mppi_planner_set_crowd(p, 0), are
+ * refused (MPPI_ERR_INVALID): one owner of the disc source. */
+int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples, int disc_count, int rows,
+                                        const float* positions, const float* radii);
+
 /* MPPI_MODE_BAREBONE in crowd mode only: wall obstacles.  A wall is a segment A -> B with a
  * half-width h >= 0; segments is (count, 4) float32 -- ax ay bx by -- and halfwidths (count)
  * float32.  Step t of a rollout (t = 0 .. T-1) moves the robot from P (the position before the
@@ -398,7 +422,10 @@ int mppi_planner_get_noise(mppi_planner* p, float* noise);
 int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang);     /* mppi.py:613-1111 */
 int mppi_planner_set_costs(mppi_planner* p, const float* costs);             /* (N_local) */
 int mppi_planner_get_costs(mppi_planner* p, float* costs);
-int mppi_planner_get_sample_costs(mppi_planner* p, float* costs);            /* (N_local,M), TDM mode */
+/* (N_local,M), TDM mode; MPPI_MODE_BAREBONE while disc samples are held: (N_local,S) -- (B*N,S) for
+ * a batched handle --, the per-sample costs before the tail, in sample order.  NULL arms recording
+ * for the rollouts that follow; a pointer fetches. */
+int mppi_planner_get_sample_costs(mppi_planner* p, float* costs);
 int mppi_planner_update(mppi_planner* p);                                    /* mppi.py:1113-1191 */
 int mppi_planner_get_weights(mppi_planner* p, float* weights);               /* normalised, (N_local) */
 

@@ -26,7 +26,7 @@ DEBUG_NO_FOLDED_APPLY = 256
 DEBUG_NO_REDUCE_FOLD = 512
 DEBUG_NO_SCAN_DIRECT = 1024
 DEBUG_DROP_NOISE_FLAG = 2048
-ABI_VERSION = 1
+ABI_VERSION = 2
 P2P_HANDLE_BYTES = 64
 
 
@@ -105,6 +105,7 @@ SIGNATURES = {
     "mppi_planner_set_disc_obstacles": [_vp, _f32p, _f32p, C.c_int],
     "mppi_planner_set_instance_disc_obstacles": [_vp, C.c_int, C.POINTER(C.c_int), _f32p, _f32p],
     "mppi_planner_set_disc_tracks": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p],
+    "mppi_planner_set_disc_track_samples": [_vp, C.c_int, C.c_int, C.c_int, _f32p, _f32p],
     "mppi_planner_set_track_offsets": [_vp, C.c_int, C.POINTER(C.c_int)],
     "mppi_planner_get_track_offsets": [_vp, C.c_int, C.POINTER(C.c_int)],
     "mppi_planner_set_crowd": [_vp, C.c_int],

@@ -52,6 +52,16 @@ robot planning in turn sees the plans of this step.  Before the first solve the 
 its start.  closed_loop() parks a robot that has reached its goal (its rows become its final position); in a host-driven
 loop the library does not know who has arrived: park a robot by giving it zero controls (set_u), where vrange admits 0.
 fleet_walls() fetches the rows of the last refresh, refresh_fleet() refreshes alone (for drawing).
+
+Disc samples (crowd mode only): params['obstacle_track_samples'] (S, K, L, 2), S <= 16, in place of 'obstacle_positions' and
+'obstacle_tracks' gives the K discs S sampled futures, as a predictor hands them out (goes straight, turns left, stops);
+sample s is an ordinary track set, params['obstacle_radius'] (K,) its radii.  The cost of a rollout under sample s is the cost
+the launch gives it with obstacle_tracks = samples[s], bit for bit; walls, wall tracks, a goal track and the fleet stay in
+force and do not depend on s.  The rollout's cost is the conditional value at risk over its S costs: params['cvar_alpha'] in
+(0, 1], default 1.0 -- the mean of the worst ceil(S * alpha) costs as the reference's CVaR mode forms it (sorted descending
+iff alpha < 1, a strided float32 tree, the division in double); alpha = 1 is the mean, alpha <= 1/S the worst case.  Without a
+sample set nothing reads cvar_alpha.  In a batch every problem sees the same samples.  record_sample_costs() /
+sample_costs() give the (N, S) per-sample costs; sampled_tracks() is the simplest predictor to try it with.
 """
 import copy
 import ctypes as C
@@ -119,6 +129,24 @@ def constant_velocity_tracks(positions, velocities, dt, rows):
     assert len(pos) == len(vel), "positions and velocities differ in length"
     times = (np.arange(rows, dtype=np.float64) * float(dt)).reshape(1, rows, 1)
     return np.ascontiguousarray((pos + vel * times).astype(np.float32))
+
+
+def sampled_tracks(positions, velocities, dt, rows, vel_std, samples, seed=0):
+    """(S, K, rows, 2) float32 disc samples for params['obstacle_track_samples']: sample 0 is constant_velocity_tracks of the
+    nominal velocities, samples 1 .. S-1 the same with the velocities perturbed by
+    numpy.random.default_rng(seed).normal(0, vel_std), one (S - 1, K, 2) draw, evaluated in float64 and rounded once to
+    float32.  Host only.  The simplest predictor there is -- every disc keeps a velocity drawn once -- and not a model of
+    anything."""
+    samples = int(samples)
+    assert samples >= 1, "a sample set has at least one sample"
+    vel = np.asarray(velocities, dtype=np.float64).reshape(-1, 2)
+    noise = np.random.default_rng(seed).normal(0.0, float(vel_std), size=(samples - 1,) + vel.shape)
+    sets = [constant_velocity_tracks(positions, vel, dt, rows)]
+    sets += [constant_velocity_tracks(positions, vel + noise[s], dt, rows) for s in range(samples - 1)]
+    return np.ascontiguousarray(np.stack(sets), dtype=np.float32)
+
+
+MAX_DISC_SAMPLES = 16  # (kCrowdSamplesMax of the library)
 
 
 def constant_velocity_walls(segments, velocities, dt, rows, at=0.5):
@@ -207,6 +235,7 @@ class MPPI_Numba(object):
         self.device_var_initialized = False
         self._discs_key = None  # what the device's disc arrays hold (None: nothing handed over yet)
         self._tracks_from_params = False  # ... and whether they are the tracks of params['obstacle_tracks']
+        self._samples_key = None          # the disc samples of params['obstacle_track_samples'] the library holds (None: none)
         self._own_tracks = False          # MPPI_Batch: per-problem tracks are set (they win over params')
         self._walls_key = ()  # what the device's wall arrays hold (): none
         self._wall_tracks_key = None  # the wall tracks of params['wall_tracks'] the library holds (None: none)
@@ -403,7 +432,65 @@ class MPPI_Numba(object):
         return now[0].copy() if self.num_instances == 1 else now.copy()
 
     def _tracks_on(self):
-        return self._tracks_from_params or self._own_tracks
+        return self._tracks_from_params or self._own_tracks or self._samples_key is not None
+
+    # ------------------------------------------------------------------ disc samples
+    def _hand_over_samples(self, p):
+        """params['obstacle_track_samples'] (S, K, L, 2) with params['obstacle_radius'] (K,): handed over when they have
+        changed, cleared when the key has gone (row 0 is "now" again, as for tracks).  True while samples are held."""
+        if "obstacle_track_samples" not in p:
+            if self._samples_key is not None:
+                _lib.call("mppi_planner_set_disc_track_samples", self._handle, 0, 0, 0, None, None)
+                self._samples_key = None
+                self._discs_key = None  # (the static discs below are handed over again)
+                self._fetch_track_offset()
+            return False
+        others = [k for k in ("obstacle_positions", "obstacle_tracks") if k in p]
+        if others:
+            raise ValueError("params hold both 'obstacle_track_samples' and '{}': discs are static, have tracks or have "
+                             "sampled tracks, give one of the three".format(others[0]))
+        if getattr(self, "obstacle_sets", None) is not None:
+            raise ValueError("params hold 'obstacle_track_samples' while obstacle_sets are held: disc samples are shared by "
+                             "every problem (set_obstacle_sets(None) first)")
+        smp, orad = np.asarray(p['obstacle_track_samples']), np.asarray(p['obstacle_radius'])
+        key = (smp.dtype.str, smp.shape, smp.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
+        if key == self._samples_key:
+            return True
+        if smp.ndim != 4 or smp.shape[3] != 2 or smp.shape[0] < 1 or smp.shape[2] < 1:
+            raise ValueError("params['obstacle_track_samples'] has shape (S, K, L, 2) with S, L >= 1, got {}".format(smp.shape))
+        if smp.shape[0] > MAX_DISC_SAMPLES:
+            raise ValueError("params['obstacle_track_samples'] holds {} samples, more than {}".format(smp.shape[0], MAX_DISC_SAMPLES))
+        rad = np.ascontiguousarray(_f32(orad).reshape(-1))
+        if len(rad) != smp.shape[1]:
+            raise ValueError("params['obstacle_track_samples'] holds {} discs, params['obstacle_radius'] {} radii".format(
+                smp.shape[1], len(rad)))
+        if self._tracks_from_params:  # (the params no longer hold plain tracks)
+            self._hand_over_tracks(None)
+            self._tracks_from_params = False
+        pos = np.ascontiguousarray(_f32(smp))
+        _lib.call("mppi_planner_set_disc_track_samples", self._handle, int(smp.shape[0]), int(smp.shape[1]), int(smp.shape[2]),
+                  _lib.ptr(pos if pos.size else np.zeros(2, np.float32), C.c_float),
+                  _lib.ptr(rad if rad.size else np.zeros(1, np.float32), C.c_float))
+        self._samples_key = key
+        self._discs_key = None
+        self._fetch_track_offset()  # (a new set of more than one row: row 0 is "now")
+        return True
+
+    def record_sample_costs(self):
+        """From the next rollout on the per-sample costs are kept (while disc samples are held); sample_costs() fetches."""
+        self.move_mppi_task_vars_to_device()
+        _lib.call("mppi_planner_get_sample_costs", self._handle, None)
+
+    def sample_costs(self):
+        """(N, S) float32 -- (B, N, S) for a batch: every rollout's cost under each disc sample, before the CVaR tail, in
+        sample order."""
+        if self._samples_key is None:
+            raise ValueError("sample_costs: no disc samples are held (params['obstacle_track_samples'])")
+        S = int(np.asarray(self.params['obstacle_track_samples']).shape[0])
+        lead = () if self.num_instances == 1 else (self.num_instances,)
+        out = np.empty(lead + (self.num_control_rollouts, S), dtype=np.float32)
+        _lib.call("mppi_planner_get_sample_costs", self._handle, _lib.ptr(out, C.c_float))
+        return out
 
     def _wall_tracks_on(self):
         return self._wall_rows > 1
@@ -507,6 +594,10 @@ class MPPI_Numba(object):
         c.v_post_rollout = 0.0
         c.lambda_weight = float(p['lambda_weight'])
         c.cvar_alpha = 1.0
+        if 'cvar_alpha' in p:  # (read by the sample forms alone: without disc samples every launch keeps its bits)
+            c.cvar_alpha = float(p['cvar_alpha'])
+            if not 0.0 < c.cvar_alpha <= 1.0:
+                raise ValueError("params['cvar_alpha'] = {}: must lie in (0, 1]".format(p['cvar_alpha']))
         c.obs_cost = float(DEFAULT_OBS_COST if 'obs_penalty' not in p else p['obs_penalty'])
         c.unknown_cost = 0.0
         c.res, c.xlo, c.ylo = 1.0, 0.0, 0.0
@@ -515,6 +606,8 @@ class MPPI_Numba(object):
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
         self._hand_over_walls(p)
+        if ("obstacle_track_samples" in p or self._samples_key is not None) and self._hand_over_samples(p):
+            return
         # the discs: handed over when they have changed (the notebook uploads them with every solve)
         if "obstacle_tracks" in p:
             if "obstacle_positions" in p:
@@ -747,6 +840,9 @@ class MPPI_Batch(MPPI_Numba):
             _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
             self.obstacle_sets = None
             return
+        if self._samples_key is not None or (self.params is not None and "obstacle_track_samples" in self.params):
+            raise ValueError("set_obstacle_sets while params hold 'obstacle_track_samples': disc samples are shared by every "
+                             "problem (drop the key first)")
         assert len(obstacle_sets) == self.num_instances, "one disc set per problem"
         kinds = {_is_track_set(s) for s in obstacle_sets}
         if len(kinds) > 1:

@@ -1,5 +1,5 @@
 // barebone_api.h -- the hand-overs of the barebone mode (include/mppi_hip.h): disc sets, disc tracks, crowd mode, walls,
-// wall tracks, goal tracks, fleet mode, track offsets.  Included by mppi_api.hip behind launch_plan.h.
+// disc samples, wall tracks, goal tracks, fleet mode, track offsets.  Included by mppi_api.hip behind launch_plan.h.
 //
 // Every hand-over goes the same way: check the arguments; return at once when what is handed over is what is held
 // (the Python mirror hands its arrays over with every solve: unchanged arrays cost a comparison, not a synchronisation and
@@ -15,7 +15,10 @@ static void note_instance_discs(mppi_planner* p) {
   int k0 = 0;
   for (int b = 0; b < p->B; ++b) {
     BatchInst& I = p->inst_host[(size_t)b];
-    if (p->trk_on) {  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
+    if (p->smp_on) {  // (disc samples: one set of K discs for every problem, the samples side by side within a row)
+      I.disc0 = 0;
+      I.n_discs = p->smp_discs;
+    } else if (p->trk_on) {  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
       const bool own = p->trk_counts_host.size() > 1;
       I.disc0 = own ? k0 : 0;
       I.n_discs = p->trk_counts_host[own ? (size_t)b : 0];
@@ -81,7 +84,7 @@ static int check_finite(const float* v, size_t n, size_t rows, size_t per_row, c
 //   - never when neither the old nor the new set moves (a set of one row is static: it leaves "now" alone).
 enum TrackKind { kGoalTracks = 0, kWallTracks = 1, kDiscTracks = 2 };
 static void reset_track_offsets(mppi_planner* p, TrackKind kind, bool moved, bool cleared) {
-  const bool above = (kind < kDiscTracks && p->trk_on) || (kind < kWallTracks && p->wtrk_on && p->wtrk_rows > 1);
+  const bool above = (kind < kDiscTracks && (p->trk_on || p->smp_on)) || (kind < kWallTracks && p->wtrk_on && p->wtrk_rows > 1);
   if (!moved || (cleared && above)) return;
   for (BatchInst& I : p->inst_host) I.track_off = 0;
   p->inst_dirty = true;
@@ -156,6 +159,8 @@ extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int cou
   long total = 0;
   int kmax = 0;
   if (count > 0) {
+    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+            "the handle holds disc samples, which every problem shares: clear them first (mppi_planner_set_disc_track_samples with samples 0)");
     REQUIRE(disc_counts, MPPI_ERR_INVALID, "NULL disc_counts");
     TRY(sum_counts(count, disc_counts, "disc", &total, &kmax));
     REQUIRE(total <= (1L << 30), MPPI_ERR_INVALID, "too many discs (%ld)", total);
@@ -204,6 +209,8 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
   long total = 0;
   int kmax = 0;
   if (count > 0) {
+    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+            "the handle holds disc samples, the disc source of its launches: clear them first (mppi_planner_set_disc_track_samples with samples 0)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
     TRY(sum_counts(count, disc_counts, "disc", &total, &kmax));
     REQUIRE(total * (long)rows <= (1L << 30), MPPI_ERR_INVALID, "too many track rows (%ld discs x %d)", total, rows);
@@ -244,6 +251,67 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
   return MPPI_OK;
 }
 
+// Disc samples (include/mppi_hip.h): S sampled futures of K moving discs, `rows` rows each, handed over [sample][disc][row]
+// and shared by every problem; crowd mode only.  The device keeps them [row][sample][disc] -- all that a step tests is
+// contiguous.  While held they are the disc source of every launch (the tracks' place; the shared static set rests) and
+// count as disc tracks wherever the rows are counted.  A change takes a new generation and makes row 0 "now" again.
+extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples, int disc_count, int rows, const float* positions,
+                                                   const float* radii) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc samples belong to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(samples >= 0 && samples <= kCrowdSamplesMax, MPPI_ERR_INVALID, "samples %d: must be 0 (none) to %d", samples, kCrowdSamplesMax);
+  size_t n_pos = 0;
+  if (samples > 0) {
+    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+            "disc samples need crowd mode: only the crowd kernel has sample forms (mppi_planner_set_crowd(p, 1) first)");
+    REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
+    REQUIRE(disc_count >= 0, MPPI_ERR_INVALID, "negative disc count %d", disc_count);
+    const int walls = p->fleet_on ? p->fleet_slots : (p->wtrk_on ? p->wtrk_max : p->n_walls);
+    REQUIRE((long)disc_count + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
+            "%d discs and %d walls: a sample form counts a step's hits in 16 bits, %d at the most", disc_count, walls, kCrowdSampleHitsMax);
+    REQUIRE((long)samples * (long)disc_count * (long)rows <= (1L << 30), MPPI_ERR_INVALID,
+            "too many sample rows (%d samples x %d discs x %d)", samples, disc_count, rows);
+    REQUIRE(disc_count == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
+    for (int k = 0; k < disc_count; ++k)
+      REQUIRE(std::isfinite(radii[k]) && radii[k] >= 0.0f, MPPI_ERR_INVALID, "disc %d: radius %g is negative or not finite", k, (double)radii[k]);
+    REQUIRE(!p->inst_obs_on, MPPI_ERR_INVALID,
+            "the handle holds per-problem disc sets; disc samples are shared by every problem: clear the sets first "
+            "(mppi_planner_set_instance_disc_obstacles with count 0)");
+    REQUIRE(!(p->trk_on && p->trk_counts_host.size() > 1), MPPI_ERR_INVALID,
+            "the handle holds per-problem disc tracks; disc samples are shared by every problem: clear the tracks first "
+            "(mppi_planner_set_disc_tracks with count 0)");
+    n_pos = (size_t)samples * (size_t)disc_count * (size_t)rows;
+  }
+  if (samples == 0 ? !p->smp_on
+                   : (p->smp_on && samples == p->smp_count && disc_count == p->smp_discs && rows == p->smp_rows &&
+                      same_as_held(p->smp_pos_host, positions, 2 * n_pos) && same_as_held(p->smp_r_host, radii, (size_t)disc_count)))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  float2* pos_rows = nullptr;
+  float* r = nullptr;
+  if (samples > 0)  // [sample][disc][row] is [item][row] with S * K items: by_row gives [row][sample][disc]
+    TRY(staged([&]() -> int {
+      TRY(dev_stage(&pos_rows, by_row<float2>(positions, (size_t)samples * (size_t)disc_count, (size_t)rows).data(), n_pos));
+      TRY(dev_stage(&r, radii, (size_t)disc_count));
+      return MPPI_OK;
+    }, pos_rows, r));
+  dev_take(p->smp_pos_rows, pos_rows);
+  dev_take(p->smp_r, r);
+  const bool moved = p->smp_rows > 1 || (samples > 0 && rows > 1);  // (a set of one row is static: it leaves "now" alone)
+  p->smp_on = samples > 0;
+  p->smp_count = samples;
+  p->smp_discs = samples > 0 ? disc_count : 0;
+  p->smp_rows = samples > 0 ? rows : 0;
+  p->smp_gen = samples > 0 ? next_generation() : 0;
+  p->smp_pos_host.assign(positions, positions + 2 * n_pos);
+  p->smp_r_host.assign(radii, radii + (samples > 0 ? (size_t)disc_count : 0));
+  drop_graphs(p);  // (the arrays, the counts and the kernel form are arguments of the captured launches)
+  reset_track_offsets(p, kDiscTracks, moved, samples == 0);
+  note_instance_discs(p);
+  return MPPI_OK;
+}
+
 // Crowd mode (include/mppi_hip.h).  Off -> on: the [row][disc] copy of the tracks the handle holds.  On -> off: only when
 // the default family can launch every set the handle holds -- the tracks, the per-problem sets and the shared set each on
 // their own (clearing one brings the next back), and what is launched now with its goal track: barebone_choose is asked.
@@ -252,6 +320,8 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
   if ((on != 0) == p->crowd) return MPPI_OK;
   if (!on) {
+    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds disc samples, which only the crowd kernel rolls out (clear them first)");
     REQUIRE(p->n_walls == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
     REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,

@@ -15,17 +15,23 @@
 #include "barebone_plan.h"
 
 // What the choice depends on, from the handle (in the order of BareboneHeld's fields).  rot: (cos, sin) by rotation.
+static void crowd_shape(const mppi_planner* p, int* waves, int* chunk);
 static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
+  int W = 0, C = 0;
+  crowd_shape(p, &W, &C);
   return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, p->crowd, p->n_obstacles, p->inst_obs_on, p->inst_obs_max,
-                      p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on};
+                      p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on,
+                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W};
 }
 
 // The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
 static const float2* barebone_disc_pos(const mppi_planner* p, const BareboneChoice& c) {
+  if (c.discs == kDiscsSamples) return p->smp_pos_rows;
   if (c.discs == kDiscsTracks) return c.family == kBareboneCrowd ? p->trk_pos_rows : p->trk_pos;
   return c.discs == kDiscsOwn ? p->inst_obs_pos : p->obs_pos;
 }
 static const float* barebone_disc_rad(const mppi_planner* p, const BareboneChoice& c) {
+  if (c.discs == kDiscsSamples) return p->smp_r;
   return c.discs == kDiscsTracks ? p->trk_r : (c.discs == kDiscsOwn ? p->inst_obs_r : p->obs_r);
 }
 
@@ -83,6 +89,11 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
   *waves = W;
   *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
 }
+// (barebone_plan.h restates the chunk and the LDS formula for the host: a sample form's chunk is chosen there)
+static_assert(kCrowdChunkSteps == kCrowdChunkMax, "barebone_plan.h and rollout_crowd_kernel.h disagree on the chunk");
+static_assert(crowd_lds_bytes(37, 14, true, 3) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 &&
+                  crowd_lds_bytes(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8,
+              "crowd_lds_bytes: the layout crowd_lds (barebone_plan.h) restates");
 
 // The wall tracks as a launch takes them: the user's (rows counted from the problem's track offset), or in fleet mode the
 // sets the library makes of the other problems' plans (fleet_kernels.h; rows counted from "now": relative = 1).
@@ -101,19 +112,31 @@ static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
 // choice: 1, static walls shared by the problems (CrowdWalls), whatever the discs are; 2, wall tracks and per-problem sets
 // (CrowdWallTracks) -- they come first: while they are held the static walls rest -- and fleet mode, which takes the same
 // form with the sets it makes itself, the static walls copied into them.  A goal that moves: one GoalRows argument
-// more, behind the walls'.
+// more, behind the walls'.  Disc samples (mppi_planner_set_disc_track_samples): the sample forms, one CrowdSamples argument
+// at the end -- TRACKS forms over the [row][sample][disc] copy, with the chunk and the LDS of the choice.
 template <bool EXACT, bool BATCHED>
 static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const BareboneChoice& c, bool rot) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0);  // the size launched
+  if (c.samples > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples);  // the size launched
+  if (c.samples > 0) {
+    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples), MPPI_ERR_STATE,
+            "disc samples: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
+    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS",
+            c.samples, p->cfg.num_steps, lds);
+    const int walls = c.walls == 2 ? (p->fleet_on ? p->fleet_slots : p->wtrk_max) : (c.walls == 1 ? p->n_walls : 0);
+    REQUIRE((long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
+            "disc samples: %d discs and %d walls, more than the %d hits a step's 16-bit counter holds", c.kmax, walls, kCrowdSampleHitsMax);
+    if (p->want_sample_costs && !p->sample_costs) TRY(dev_alloc(&p->sample_costs, (size_t)p->n_local * (size_t)kCrowdSamplesMax));
+  }
   if (c.walls == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
   if (c.walls != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
   const bool tracks = c.discs == kDiscsTracks;
   const float2* pos = barebone_disc_pos(p, c);
   const float* rad = barebone_disc_rad(p, c);
-  const int pitch = tracks ? (int)p->trk_r_host.size() : 0;
+  const int pitch = c.samples > 0 ? c.samples * c.kmax : (tracks ? (int)p->trk_r_host.size() : 0);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
   auto launch = [&](auto kern, auto... extra) -> int {
     if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
@@ -133,7 +156,25 @@ static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const Bare
     if (c.walls == 1) return with_walls(CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls});
     return with_walls();
   };
-  if (rot && tracks) TRY(dispatch(std::true_type(), std::true_type()));
+  // disc samples: TRACKS forms with one CrowdSamples behind the other arguments; static shared walls as wall tracks of one
+  // row (their [wall] array IS the [row][wall] array of one row)
+  auto dispatch_samples = [&](auto rot_c) -> int {
+    constexpr bool ROT = EXACT && decltype(rot_c)::value;
+    const CrowdSamples smp{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(c.samples, d.cvar_alpha)};
+    auto with_walls = [&](auto... walls) -> int {
+      constexpr bool WALLS = sizeof...(walls) > 0;
+      if (c.goal_form)
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdSamples>, walls...,
+                      goal_rows_arg<BATCHED>(p), smp);
+      return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdSamples>, walls..., smp);
+    };
+    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
+    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
+    return with_walls();
+  };
+  if (c.samples > 0 && rot) TRY(dispatch_samples(std::true_type()));
+  else if (c.samples > 0) TRY(dispatch_samples(std::false_type()));
+  else if (rot && tracks) TRY(dispatch(std::true_type(), std::true_type()));
   else if (rot) TRY(dispatch(std::true_type(), std::false_type()));
   else if (tracks) TRY(dispatch(std::false_type(), std::true_type()));
   else TRY(dispatch(std::false_type(), std::false_type()));
@@ -141,18 +182,23 @@ static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const Bare
   p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
                     " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
                     (tracks ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                    (c.samples > 0 ? " tracks=" + std::to_string(p->smp_rows) : std::string()) +
                     (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
                     (c.walls == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
                     (c.walls == 2 && !fleet ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
                     (fleet ? " walls=" + std::to_string(p->fleet_slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
                                  " fleet=" + std::to_string(p->B) : std::string()) +
-                    (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
+                    (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string()) +
+                    (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
+                                   : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
 
 // A set that does not fit in 64 KiB of LDS while crowd mode is off.
 static int barebone_refuse(const BareboneChoice& c, int T) {
+  if (c.limit == kLimitSamplesNeedCrowd)
+    return fail(MPPI_ERR_INVALID, "%d disc samples need crowd mode: only the crowd kernel has sample forms", c.samples);
   if (c.limit == kLimitGoalTrack)
     return fail(MPPI_ERR_INVALID, "%d discs, %d steps and a goal track: %zu bytes, more than 64 KiB of LDS", c.kmax, T, c.lds);
   if (c.limit == kLimitDiscTracks)

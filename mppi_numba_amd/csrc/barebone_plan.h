@@ -28,6 +28,31 @@ inline size_t barebone_lds(int T, int slots, bool track_form, bool goal_form, in
   return 16 * (size_t)T + (track_form ? (size_t)T * row : row) + (goal_form ? 8 * (size_t)T : 0) + 16 * (size_t)spare_slots;
 }
 
+// Disc samples (mppi_planner_set_disc_track_samples; rollout_crowd_kernel.h): S sampled futures of the moving discs, the
+// rollout's cost the CVaR tail over its S costs.  Crowd family only.
+constexpr int kCrowdSamplesMax = 16;
+constexpr int kCrowdSampleHitsMax = 65535;  // the sample forms count a step's hits in 16 bits: discs + walls at the most
+constexpr int kCrowdChunkSteps = 16;        // (kCrowdChunkMax of rollout_crowd_kernel.h)
+constexpr size_t kCrowdSampleLdsAim = 64 * 1024;  // the chunk of a sample form shrinks towards this
+
+// The dynamic LDS of k_rollout_barebone_crowd in bytes (crowd_lds_bytes of rollout_crowd_kernel.h, restated for the host):
+//   [T] double2 control ratios | [2][C][64] double goal distance | [2][C (+ 1 with walls)][64] float2 position |
+//   [2][C][64] int hits | two "tile done" words                                        the plain forms (samples = 0)
+//   ... | [2][C][S][64] uint16 hits | two words | [S][64] float running costs          the sample forms
+inline size_t crowd_lds(int T, int C, bool walls, int samples = 0) {
+  const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4 : (size_t)2 * C * 64 * 4;
+  return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8;
+}
+
+// C steps per chunk for a workgroup of W waves: the largest multiple of the W - 2 counters within kCrowdChunkSteps, every
+// counter the same share.  A sample form gives up whole shares while its LDS is above kCrowdSampleLdsAim (one share stays).
+inline int crowd_chunk(int W, int T = 0, bool walls = false, int samples = 0) {
+  const int counters = std::min(std::max(W - 2, 1), kCrowdChunkSteps);
+  int C = (kCrowdChunkSteps / counters) * counters;
+  while (samples > 0 && C > counters && crowd_lds(T, C, walls, samples) > kCrowdSampleLdsAim) C -= counters;
+  return C;
+}
+
 // What the choice depends on.
 struct BareboneHeld {
   int T = 0;
@@ -41,12 +66,15 @@ struct BareboneHeld {
   int trk_max = 0, trk_rows = 0;  // disc tracks: the largest problem's count
   int n_walls = 0;
   bool wtrk_on = false, fleet_on = false, gtrk_on = false;
+  int samples = 0;                   // disc samples: S (0: none held), ...
+  int smp_discs = 0, smp_rows = 0;   // ... K discs of L rows each
+  int crowd_waves = 16;              // crowd family: waves per workgroup (crowd_shape of barebone_launch.h)
 };
 
 enum BareboneFamily { kBareboneDefault = 0, kBareboneCrowd = 1, kBareboneRefused = 2 };
-enum BareboneDiscs { kDiscsShared = 0, kDiscsOwn = 1, kDiscsTracks = 2 };
-// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off)
-enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3 };
+enum BareboneDiscs { kDiscsShared = 0, kDiscsOwn = 1, kDiscsTracks = 2, kDiscsSamples = 3 };
+// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off); disc samples without crowd mode
+enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3, kLimitSamplesNeedCrowd = 4 };
 
 struct BareboneChoice {
   BareboneFamily family = kBareboneDefault;
@@ -56,8 +84,10 @@ struct BareboneChoice {
   bool track_form = false;  // default family: a row of disc slots per step (disc tracks, or static discs under a goal track)
   bool goal_form = false;   // a goal that moves
   int walls = 0;            // crowd family: 0 none, 1 static walls, 2 wall tracks / per-problem sets / fleet
-  size_t lds = 0;           // default family: the dynamic LDS launched
+  size_t lds = 0;           // default family: the dynamic LDS launched; a sample form: likewise
   BareboneLimit limit = kLimitNone;
+  int samples = 0;          // crowd family: 0, or the sample form over this many disc samples
+  int chunk = 0;            // a sample form: steps per chunk
 };
 
 // Crowd mode: does a launch go to the crowd kernel?  own_lds: what the default form holds at the least.  Walls are the
@@ -69,8 +99,27 @@ inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
 // The disc source: tracks take the place of both static sets, a problem's own set that of the shared one.  A goal that
 // moves runs the track forms (static discs as tracks of one row).  The KD forms are chosen by the largest problem's count
 // under rotation; a track form whose padded row does not fit falls back to the loop over the problem's own row.
+// Disc samples are a disc source of the crowd family alone: they take the place of the tracks, run as TRACKS forms, and
+// take static shared walls as wall tracks of one row (walls = 1 stays the choice; the launcher makes the argument).
 inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   BareboneChoice c;
+  if (h.samples > 0) {
+    c.discs = kDiscsSamples;
+    c.kmax = h.smp_discs;
+    c.goal_form = h.gtrk_on;
+    c.track_form = true;
+    c.walls = (h.wtrk_on || h.fleet_on) ? 2 : (h.n_walls > 0 ? 1 : 0);
+    c.samples = h.samples;
+    if (!h.crowd) {
+      c.family = kBareboneRefused;
+      c.limit = kLimitSamplesNeedCrowd;
+      return c;
+    }
+    c.family = kBareboneCrowd;
+    c.chunk = crowd_chunk(h.crowd_waves, h.T, c.walls != 0, c.samples);
+    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, c.samples);
+    return c;
+  }
   c.discs = h.trk_on ? kDiscsTracks : (h.inst_obs_on ? kDiscsOwn : kDiscsShared);
   c.kmax = h.trk_on ? h.trk_max : (h.inst_obs_on ? h.inst_obs_max : h.n_obstacles);
   c.goal_form = h.gtrk_on;

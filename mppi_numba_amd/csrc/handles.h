@@ -233,6 +233,17 @@ struct mppi_planner {
   // that the discs a step tests are contiguous
   bool crowd = false;
   float2* trk_pos_rows = nullptr;
+  // disc samples (mppi_planner_set_disc_track_samples; crowd mode only): smp_count sampled futures of smp_discs discs,
+  // smp_rows rows each, shared by every problem.  While smp_on they are the disc source -- the tracks' place: the shared
+  // static set rests, BatchInst::track_off is "now" -- and every rollout launch is a sample form of the crowd kernel.
+  // smp_pos_rows: [row][sample][disc], so that all a step tests is contiguous.  smp_gen: next_generation() at every change,
+  // 0 while off.  The per-sample costs go to sample_costs ([n_local][smp_count]) while want_sample_costs
+  bool smp_on = false;
+  float2* smp_pos_rows = nullptr;
+  float* smp_r = nullptr;
+  int smp_count = 0, smp_discs = 0, smp_rows = 0;
+  uint64_t smp_gen = 0;
+  std::vector<float> smp_pos_host, smp_r_host;  // what was handed over ([sample][disc][row])
   // walls (mppi_planner_set_walls; crowd mode only): segments (ax, ay, bx, by) and half-widths, static and shared by every
   // problem.  n_walls > 0: every rollout launch is the crowd kernel's WALLS form.  wall_gen: next_generation() at every
   // change, 0 without walls -- what the graph signature holds of them

@@ -67,10 +67,10 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.n_grids = p->cfg.num_grid_samples;
   d.n_obstacles = p->n_obstacles;
   // (discs that move: a batch reads each problem's offset from its BatchInst, as it reads the start state)
-  d.track_rows = p->trk_on ? p->trk_rows : 0;
+  d.track_rows = p->smp_on ? p->smp_rows : (p->trk_on ? p->trk_rows : 0);  // (disc samples stand where the tracks do)
   // (wall tracks share the offset: rollout_crowd_kernel.h clamps it against the walls' own row count)
   // (... and so does a goal track, against its own)
-  d.track_off = (p->trk_on || p->wtrk_on || p->gtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
+  d.track_off = (p->trk_on || p->smp_on || p->wtrk_on || p->gtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
   d.inst = p->inst_set ? p->inst_dev : nullptr;
   d.inst_tiles = p->inst_tiles;
   d.n_inst = p->n_inst;
@@ -1054,7 +1054,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1074,6 +1074,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.wtrk_gen = p->wtrk_gen;
   sig.gtrk_gen = p->gtrk_gen;  // (the goal track's likewise)
   sig.fleet_gen = p->fleet_gen;  // (the fleet storage's: renewed when it is rebuilt, not when its rows are refreshed)
+  sig.smp_gen = p->smp_gen;  // (the disc samples')
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

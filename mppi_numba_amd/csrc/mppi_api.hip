@@ -509,6 +509,8 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->inst_obs_r);
   dev_free(p->trk_pos);
   dev_free(p->trk_pos_rows);
+  dev_free(p->smp_pos_rows);
+  dev_free(p->smp_r);
   dev_free(p->trk_r);
   dev_free(p->wall_seg);
   dev_free(p->wall_hw);
@@ -1193,7 +1195,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.dt = dt > 0.0 ? dt : (double)p->params.dt;
     L.goal_tolerance = goal_tolerance;
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
-    L.advance_tracks = p->trk_on || (p->wtrk_on && p->wtrk_rows > 1) || (p->gtrk_on && p->gtrk_rows > 1) ? 1 : 0;
+    L.advance_tracks = p->trk_on || p->smp_on || (p->wtrk_on && p->wtrk_rows > 1) || (p->gtrk_on && p->gtrk_rows > 1) ? 1 : 0;
     L.goal_xy = p->gtrk_on ? p->gtrk_xy : nullptr;
     L.goal_rows = p->gtrk_rows;
     L.goal_stride = p->gtrk_count > 1 ? p->gtrk_rows : 0;
@@ -1337,12 +1339,15 @@ extern "C" int mppi_planner_get_costs(mppi_planner* p, float* costs) {
 
 extern "C" int mppi_planner_get_sample_costs(mppi_planner* p, float* costs) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->cfg.mode == MPPI_MODE_TDM, MPPI_ERR_STATE, "per-sample costs exist in MPPI_MODE_TDM only");
+  const bool disc_samples = p->cfg.mode == MPPI_MODE_BAREBONE && p->smp_on;
+  REQUIRE(p->cfg.mode == MPPI_MODE_TDM || disc_samples, MPPI_ERR_STATE,
+          "per-sample costs exist in MPPI_MODE_TDM, and in the barebone mode while disc samples are held");
   if (!costs) {  // arm: the next rollout records them
     p->want_sample_costs = true;
     return MPPI_OK;
   }
   REQUIRE(p->sample_costs, MPPI_ERR_STATE, "call once with NULL before the rollout to arm recording");
+  if (disc_samples) return copy_out(p, costs, p->sample_costs, sizeof(float) * (size_t)p->n_local * (size_t)p->smp_count);
   // (samples sharded over GPUs: all M = count * num_grid_samples costs, gathered)
   return copy_out(p, costs, p->sample_costs,
                   sizeof(float) * (size_t)p->n_local * p->cfg.num_grid_samples * (size_t)p->m_count);

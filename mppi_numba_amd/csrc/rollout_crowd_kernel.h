@@ -64,6 +64,23 @@
 // other problems' plans, ahead of every call -- so their row 0 is always "now".  One field of CrowdWallTracks says so
 // (relative): the walls' "now" is then 0 whatever the problem's track offset is, while the disc tracks and the goal track
 // of the same launch keep reading theirs at the offset.  Nothing else of the kernel knows.
+//
+// DISC SAMPLES (mppi_planner_set_disc_track_samples): S sampled futures of the moving discs, one CrowdSamples argument at the
+// end of the pack (TRACKS forms only; walls: the CrowdWallTracks form only, static shared walls as tracks of one row).  A
+// rollout's cost under sample s is the cost of the plain launch with that sample as its tracks, bit for bit; the rollout's
+// cost is the CVaR tail over its S costs (mppi.py:716-755 with block_width = S, as k_rollout_tdm restates it).  The device
+// copy is [row][sample][disc] -- disc_pitch = S * K: all that a step tests is contiguous.
+//   count  the owner of (step, lane) loads the position once and walks the step's S * ceil(K / 64) tiles, sample after
+//          sample, the next tile in flight; the walls are counted once, behind sample 0's last tile, and their number is
+//          added to every sample's count.  S counts of 16 bits (the hand-over refuses K + walls > 65535) -> LDS
+//          [step][sample][lane], one goal distance as before.
+//   cost   S chains that share nd2 and the done / reached / d2 freeze; the running costs live in LDS [S][64], the loop is
+//          sample-outer, steps-of-the-chunk-inner (a register array indexed by a run-time s would go to scratch memory).
+//   tail   the terminal term and the T control-cost terms onto each of the S costs in the existing order; the S values to
+//          the sample-cost array when recording is on; per lane a compare-exchange network over its LDS column (descending,
+//          iff cvar_alpha < 1), the strided float32 tree over the first numel entries walked serially -- the tree's shape
+//          fixes the bits, not who executes it --, the division in double.
+// Without the argument the kernel is what it was.
 #pragma once
 #include <type_traits>
 
@@ -75,8 +92,11 @@ constexpr int kCrowdChunkMax = 16;   // steps per chunk at the most (the walker 
 constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
 // dynamic LDS: [T] double2 control ratios | [2][C][64] double goal distance | [2][C][64] float2 position |
 // [2][C][64] int hits | two "tile done" words.  walls: [2][C + 1][64] positions (slot 0: the chunk's entry position)
-__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false) {
-  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * (sizeof(double) + sizeof(int)) +
+// disc samples (S > 0): [2][C][S][64] uint16 hits in place of the int hits, and [S][64] float running costs at the end
+__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0) {
+  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * sizeof(double) +
+         (samples > 0 ? (size_t)2 * C * samples * 64 * sizeof(unsigned short) + (size_t)samples * 64 * sizeof(float)
+                      : (size_t)2 * C * 64 * sizeof(int)) +
          (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int);
 }
 
@@ -99,6 +119,13 @@ struct CrowdWallTracks {
   int max_count;  // the largest problem's count
   int rows, pitch;
   int relative;
+};
+
+// The disc samples of a launch: `count` samples, obs_pos [row][sample][disc]; the CVaR tail over the first `numel` of a
+// rollout's costs (sorted descending iff DevParams::cvar_alpha < 1); sample_costs: [n][count], or nullptr (not recorded).
+struct CrowdSamples {
+  float* sample_costs;
+  int count, numel;
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -143,20 +170,37 @@ __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks&
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&) { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls, const GoalRows&) { return walls; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&) { return walls; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdSamples&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdSamples&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&) { return walls; }
 template <typename... WallArgs>
 constexpr bool kCrowdWallTracks = (std::is_same_v<WallArgs, CrowdWallTracks> || ...);
+template <typename... WallArgs>
+constexpr bool kCrowdSamples = (std::is_same_v<WallArgs, CrowdSamples> || ...);
+__device__ __forceinline__ CrowdSamples crowd_samples_of() { return CrowdSamples{nullptr, 0, 1}; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<First, CrowdSamples>) return first;
+  else return crowd_samples_of(rest...);
+}
 
 // WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
 // shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets); behind it, with a goal
-// that moves, one GoalRows.
+// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls).
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
     const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch, WallArgs... wall_args) {
   constexpr bool GOALS = kGoalRows<WallArgs...>;
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0),
-                "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; else none");
+  constexpr bool SAMPLES = kCrowdSamples<WallArgs...>;
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0),
+                "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; disc samples: "
+                "one CrowdSamples behind that; else none");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
+  static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
+  [[maybe_unused]] const CrowdSamples smp = crowd_samples_of(wall_args...);
+  [[maybe_unused]] const int S = SAMPLES ? smp.count : 1;
   [[maybe_unused]] GoalRows G = goal_rows_of(wall_args...);
   [[maybe_unused]] const auto walls = crowd_walls_of(wall_args...);
   [[maybe_unused]] int wall0 = 0, wcount = 0;  // WTRK: this problem's walls within a row
@@ -188,6 +232,15 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   float2* poss = reinterpret_cast<float2*>(nd2s + 2 * C * 64);
   int* cnts = reinterpret_cast<int*>(poss + 2 * CP * 64);
   int* tile_done = cnts + 2 * C * 64;  // [2], used in turn: a wave still looks at one while wave 1 writes the other
+  // SAMPLES: [2][C][S][64] 16-bit hits where the int hits are, the two words behind them, then [S][64] running costs
+  [[maybe_unused]] unsigned short* cnts16 = reinterpret_cast<unsigned short*>(cnts);
+  [[maybe_unused]] float* scost = nullptr;
+  if constexpr (SAMPLES) {
+    tile_done = reinterpret_cast<int*>(cnts16 + (size_t)2 * C * S * 64);
+    scost = reinterpret_cast<float*>(tile_done + 2);
+    if (wave == 1)  // (the cost wave's own columns: nobody else touches them)
+      for (int s = 0; s < S; ++s) scost[s * 64 + lane] = 0.0f;
+  }
   if (threadIdx.x < 2) tile_done[threadIdx.x] = 0;
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
   const int n = blockIdx.x * 64 + lane;
@@ -248,17 +301,40 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
       if (ph >= 2) {  // ---- cost of chunk ph - 2
         const int c = ph - 2, c0 = c * C, cl = min(C, T - c0);
         const size_t at = (size_t)((c & 1) * C) * 64 + lane;
-        for (int j = 0; j < cl; ++j) {
-          const double nd2 = nd2s[at + j * 64];
-          const int hits = cnts[at + j * 64];
-          float c1 = (float)((double)cost + P.dist_weight * nd2);
-          for (int h = 0; __any(h < hits); ++h)
-            if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
-          const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
-          cost = act ? c1 : cost;
-          d2 = act ? nd2 : d2;
-          reached = reached || (act && hit_goal);
-          done = done || hit_goal;
+        if constexpr (SAMPLES) {  // S chains, sample-outer; the freeze is the same for every sample: the last one keeps it
+          double d2_s = d2;
+          bool done_s = done, reached_s = reached;
+          for (int s = 0; s < S; ++s) {
+            float cs = scost[s * 64 + lane];
+            d2_s = d2; done_s = done; reached_s = reached;
+            for (int j = 0; j < cl; ++j) {
+              const double nd2 = nd2s[at + j * 64];
+              const int hits = cnts16[(at - lane + (size_t)j * 64) * S + s * 64 + lane];
+              float c1 = (float)((double)cs + P.dist_weight * nd2);
+              for (int h = 0; __any(h < hits); ++h)
+                if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
+              const bool hit_goal = nd2 <= (double)P.gt2, act = !done_s;
+              cs = act ? c1 : cs;
+              d2_s = act ? nd2 : d2_s;
+              reached_s = reached_s || (act && hit_goal);
+              done_s = done_s || hit_goal;
+            }
+            scost[s * 64 + lane] = cs;
+          }
+          d2 = d2_s; done = done_s; reached = reached_s;
+        } else {
+          for (int j = 0; j < cl; ++j) {
+            const double nd2 = nd2s[at + j * 64];
+            const int hits = cnts[at + j * 64];
+            float c1 = (float)((double)cost + P.dist_weight * nd2);
+            for (int h = 0; __any(h < hits); ++h)
+              if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
+            const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
+            cost = act ? c1 : cost;
+            d2 = act ? nd2 : d2;
+            reached = reached || (act && hit_goal);
+            done = done || hit_goal;
+          }
         }
         if (__all(done) && lane == 0) tile_done[ph & 1] = 1;
       }
@@ -319,74 +395,148 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         [[maybe_unused]] double dx0, dy0, LLd0, hh0;
         if constexpr (WTRK) load_wall_row(wave - 2, 0, sg0, dx0, dy0, LLd0, hh0);  // (the first tile of the first step owned)
         else if constexpr (WALLS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
-        int j = wave - 2, base = 0, hits = 0;
-        float2 op;
-        double rr;
-        load_disc(j, base, op, rr);
-        while (j < cl) {
-          int nj = j, nbase = base + 64;
-          if (nbase >= K) { nj = j + NC; nbase = 0; }
-          float2 op_nxt;
-          double rr_nxt;
-          load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
-          const float2 pos = poss[atp + j * 64];
-          const int kt = min(64, K - base);
-          for (int l0 = 0; l0 < kt; l0 += 4) {
-#pragma unroll
-            for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
-              const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
-              const double rrl = crowd_lane_f64(rr, l);
-              const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
-              const double diff = fma(ex, ex, ey * ey) - rrl;
-              hits += (diff > 0.0) ? 0 : 1;
+        if constexpr (SAMPLES) {
+          // sample sm's tile [base, base + 64) as step c0 + j sees it: the row's samples lie side by side, K discs each
+          auto load_sample_disc = [&](int j, int sm, int base, float2& op, double& rr) {
+            const int k = base + lane;
+            op = make_float2(1e18f, 1e18f);
+            float r = 0.0f;
+            if (j < cl && k < K) {
+              op = obs_pos[(size_t)min(now + c0 + j + 1, last) * (size_t)disc_pitch + (size_t)sm * (size_t)K + (size_t)k];
+              r = obs_r[k];
             }
-          }
-          if (nj != j) {  // the step's last tile
-            if constexpr (WALLS) {  // ... then the walls, against the step's segment P -> Q
-              const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
-              const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
-              float4 sg = sg0;
-              double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
-              if constexpr (WTRK) {  // this problem's walls as this step sees them
-                for (int wbase = 0; wbase < wcount; wbase += 64) {
-                  float4 sg_nxt;
-                  double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                  const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
-                  load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
-                  const int wt = min(64, wcount - wbase);
-                  for (int l = 0; l < wt; ++l) {
-                    const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                    const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                    hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                           crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                ? 1 : 0;
-                  }
-                  sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
-                }
-                sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
-              } else {
-                for (int wbase = 0; wbase < walls.count; wbase += 64) {
-                  float4 sg_nxt;
-                  double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                  load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
-                  const int wt = min(64, walls.count - wbase);
-                  for (int l = 0; l < wt; ++l) {
-                    const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                    const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                    hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                           crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                ? 1 : 0;
-                  }
-                  sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
-                }
+            rr = (double)r * (double)r;
+          };
+          int j = wave - 2, sm = 0, base = 0, hits = 0, whits = 0;
+          float2 op;
+          double rr;
+          load_sample_disc(j, sm, base, op, rr);
+          while (j < cl) {
+            int nj = j, nsm = sm, nbase = base + 64;
+            if (nbase >= K) {
+              nbase = 0;
+              if (++nsm == S) { nsm = 0; nj = j + NC; }
+            }
+            float2 op_nxt;
+            double rr_nxt;
+            load_sample_disc(nj, nsm, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
+            const float2 pos = poss[atp + j * 64];
+            const int kt = min(64, K - base);
+            for (int l0 = 0; l0 < kt; l0 += 4) {
+#pragma unroll
+              for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+                const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
+                const double rrl = crowd_lane_f64(rr, l);
+                const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+                const double diff = fma(ex, ex, ey * ey) - rrl;
+                hits += (diff > 0.0) ? 0 : 1;
               }
             }
-            cnts[at + j * 64] = hits;
-            if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
-            else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
-            hits = 0;
+            if (nbase == 0) {  // the sample's last tile
+              if constexpr (WALLS) {
+                if (sm == 0) {  // the step's walls, once: this problem's walls as this step sees them, against P -> Q
+                  const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
+                  const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                  float4 sg = sg0;
+                  double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
+                  whits = 0;
+                  for (int wbase = 0; wbase < wcount; wbase += 64) {
+                    float4 sg_nxt;
+                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                    const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
+                    load_wall_row(more ? j : j + NC, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);
+                    const int wt = min(64, wcount - wbase);
+                    for (int l = 0; l < wt; ++l) {
+                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                      whits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                              crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                   ? 1 : 0;
+                    }
+                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+                  }
+                  sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
+                }
+              }
+              cnts16[(at - lane + (size_t)j * 64) * S + sm * 64 + lane] = (unsigned short)(hits + whits);
+              if (sm == 0) {
+                if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
+                else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+              }
+              hits = 0;
+            }
+            j = nj; sm = nsm; base = nbase; op = op_nxt; rr = rr_nxt;
           }
-          j = nj; base = nbase; op = op_nxt; rr = rr_nxt;
+        } else {
+          int j = wave - 2, base = 0, hits = 0;
+          float2 op;
+          double rr;
+          load_disc(j, base, op, rr);
+          while (j < cl) {
+            int nj = j, nbase = base + 64;
+            if (nbase >= K) { nj = j + NC; nbase = 0; }
+            float2 op_nxt;
+            double rr_nxt;
+            load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
+            const float2 pos = poss[atp + j * 64];
+            const int kt = min(64, K - base);
+            for (int l0 = 0; l0 < kt; l0 += 4) {
+#pragma unroll
+              for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+                const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
+                const double rrl = crowd_lane_f64(rr, l);
+                const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+                const double diff = fma(ex, ex, ey * ey) - rrl;
+                hits += (diff > 0.0) ? 0 : 1;
+              }
+            }
+            if (nj != j) {  // the step's last tile
+              if constexpr (WALLS) {  // ... then the walls, against the step's segment P -> Q
+                const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
+                const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                float4 sg = sg0;
+                double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
+                if constexpr (WTRK) {  // this problem's walls as this step sees them
+                  for (int wbase = 0; wbase < wcount; wbase += 64) {
+                    float4 sg_nxt;
+                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                    const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
+                    load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                    const int wt = min(64, wcount - wbase);
+                    for (int l = 0; l < wt; ++l) {
+                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                      hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                             crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                  ? 1 : 0;
+                    }
+                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+                  }
+                  sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
+                } else {
+                  for (int wbase = 0; wbase < walls.count; wbase += 64) {
+                    float4 sg_nxt;
+                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                    load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                    const int wt = min(64, walls.count - wbase);
+                    for (int l = 0; l < wt; ++l) {
+                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                      hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                             crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                  ? 1 : 0;
+                    }
+                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
+                  }
+                }
+              }
+              cnts[at + j * 64] = hits;
+              if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
+              else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+              hits = 0;
+            }
+            j = nj; base = nbase; op = op_nxt; rr = rr_nxt;
+          }
         }
       }
     }
@@ -394,6 +544,41 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     if (tile_done[ph & 1]) break;  // (uniform: every rollout of the tile is at its goal)
   }
   if (wave != 1) return;
+  if constexpr (SAMPLES) {  // the tail onto each of the S costs, then the CVaR over the lane's column (wave 1 alone: no barrier)
+    for (int s = 0; s < S; ++s) scost[s * 64 + lane] = (float)((double)scost[s * 64 + lane] + (reached ? 0.0 : 1.0) * d2);
+    int t0 = 0;
+    for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {  // loads and products once, the rounded additions per sample in order
+      double cc[kNoiseBatch];
+#pragma unroll
+      for (int j = 0; j < kNoiseBatch; ++j) cc[j] = control_cost(P, uos[t0 + j], col[(size_t)(t0 + j) * 64]);
+      for (int s = 0; s < S; ++s) {
+        float cs = scost[s * 64 + lane];
+#pragma unroll
+        for (int j = 0; j < kNoiseBatch; ++j) cs = (float)((double)cs + cc[j]);
+        scost[s * 64 + lane] = cs;
+      }
+    }
+    for (int t = t0; t < T; ++t) {
+      const double cc = control_cost(P, uos[t], col[(size_t)t * 64]);
+      for (int s = 0; s < S; ++s) scost[s * 64 + lane] = (float)((double)scost[s * 64 + lane] + cc);
+    }
+    if (smp.sample_costs && live)
+      for (int s = 0; s < S; ++s) smp.sample_costs[(size_t)n * (size_t)S + s] = scost[s * 64 + lane];
+    if (P.cvar_alpha < 1.0f) {  // descending: odd-even transposition, S rounds of compare-exchange
+      for (int r = 0; r < S; ++r)
+        for (int i = r & 1; i + 1 < S; i += 2) {
+          const float a = scost[i * 64 + lane], b = scost[(i + 1) * 64 + lane];
+          scost[i * 64 + lane] = a < b ? b : a;
+          scost[(i + 1) * 64 + lane] = a < b ? a : b;
+        }
+    }
+    const int numel = smp.numel;  // the strided float32 tree over the first numel entries (mppi.py:744-751)
+    for (int st = 1; st < numel; st <<= 1)
+      for (int i = 0; i + st < numel; i += 2 * st) scost[i * 64 + lane] = scost[i * 64 + lane] + scost[(i + st) * 64 + lane];
+    if (live) costs[n] = (float)((double)scost[lane] / (double)numel);
+    if (P.ktime && lane == 0) P.ktime[P.ktime_waves + blockIdx.x] = (unsigned long long)wall_clock64();
+    return;
+  }
   cost = (float)((double)cost + (reached ? 0.0 : 1.0) * d2);
   int t0 = 0;
   for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {  // loads and products batched, the float32-rounded additions in order
