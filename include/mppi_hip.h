@@ -397,6 +397,38 @@ int mppi_planner_fleet_refresh(mppi_planner* p);
  * fleet mode is on. */
 int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg);
 
+/* MPPI_MODE_BAREBONE, crowd mode: a body footprint -- the robot as `count` discs (1 .. 8) rigidly
+ * attached to its pose, so that the heading counts in the hit tests.  discs (count, 3) float32,
+ * rows (ox, oy, rho): a body disc's centre in the robot frame (x along the heading, y to the left)
+ * and its radius, rho >= 0, everything finite; count = 0 clears (discs ignored), and the robot is
+ * its reference point again: every launch then has the kernel form, the arguments and the bits it
+ * had before.  One footprint for every problem of a batch.  At a float32 state (x, y, th), with
+ * s, c the float64 sine and cosine of (double)th, body disc i has its centre at
+ *     cx = (float)((double)x + ((double)ox * c - (double)oy * s))
+ *     cy = (float)((double)y + ((double)ox * s + (double)oy * c))
+ * (products and sums in double in the order written, no fma, one rounding).  Discs: body disc i
+ * touches disc k at step t iff the disc test of the launches says so with the centre at the
+ * post-step state in place of the position and (r_k + rho_i)^2, the sum in double, in place of
+ * r_k^2; the body touches disc k iff any of its discs does, and the step's disc hits are the
+ * number of discs touched -- one hit per obstacle, however many body discs reach it.  Walls:
+ * during step t body disc i moves from its centre at the pre-step state (step 0: the start state,
+ * heading included) to its centre at the post-step state; the wall test of mppi_planner_set_walls
+ * is applied to that segment with the half-width h_k + rho_i (the sum in double), and the body hits
+ * wall k iff any of its discs does.  (A point of a turning body moves on an arc; its chord is what
+ * is tested: the arc leaves it by at most |o| * (1 - cos(dt * w / 2)).)  The disc rows, the wall
+ * rows, per-problem sets and disc samples are chosen as without a footprint; the goal distance,
+ * the goal test, the freeze and the terminal term are the reference point's; a hit adds obs_cost
+ * once, as before.  While a footprint is held every rollout launch is k_rollout_barebone_crowd,
+ * whatever else the handle holds, and mppi_planner_describe_last_rollout ends in
+ * " footprint=<count>".  A change drops the captured graphs.  MPPI_ERR_INVALID, the handle keeping
+ * what it had: count > 8 or negative, a negative radius or a value that is not finite, a handle
+ * that is not barebone or not in crowd mode (and mppi_planner_set_crowd(p, 0) while a footprint is
+ * held), fleet mode on (and mppi_planner_set_fleet with a count while a footprint is held: the
+ * fleet's half-widths already contain the reader's body). */
+int mppi_planner_set_footprint(mppi_planner* p, const float* discs, int count);
+/* discs (8, 3) float32: the first *count rows are the footprint held (*count = 0: none) */
+int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* count);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

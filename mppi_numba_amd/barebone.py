@@ -62,6 +62,22 @@ force and do not depend on s.  The rollout's cost is the conditional value at ri
 iff alpha < 1, a strided float32 tree, the division in double); alpha = 1 is the mean, alpha <= 1/S the worst case.  Without a
 sample set nothing reads cvar_alpha.  In a batch every problem sees the same samples.  record_sample_costs() /
 sample_costs() give the (N, S) per-sample costs; sampled_tracks() is the simplest predictor to try it with.
+
+A body footprint (crowd mode only): params['footprint'] (F, 3), 1 <= F <= 8, rows (ox, oy, rho) -- a body disc's centre in the
+robot frame (x along the heading, y to the left) and its radius -- makes the robot F discs rigidly attached to its pose, so
+that the heading counts in the hit tests: a cart 1.0 m long and 0.4 m wide passes a 0.7 m doorway lengthwise, which its
+circumscribed disc cannot.  At a state (x, y, th) body disc i has its centre at x + (ox cos th - oy sin th),
+y + (ox sin th + oy cos th), in float64 and rounded once to float32 (body_discs()).  The body touches a disc iff any body disc
+does, with the radii added, at the post-step state; it hits a wall iff any body disc's chord, from its centre before the
+step to its centre after it, does, with rho added to the half-width.  A step's hits are counted per obstacle, however many
+body discs reach one, so a finer cover of the same body does not multiply the penalty; every hit adds obs_penalty once.
+Tracks, wall tracks, per-problem sets and disc samples work as before; goal distance, goal test, freeze and terminal
+cost are measured at the reference point (x, y).  rectangle_footprint() covers a rectangle with discs on the body axis.
+Without the key the robot is the point it always was, to the bit.  Limits: one footprint for every problem of a batch
+(per-problem footprints are not provided); the footprint and the fleet exclude each other (the fleet's half-widths already
+contain the reader's body; a fleet of elongated robots is what comes after); a point of a turning body moves on an arc and
+its chord is what is tested -- the arc leaves the chord by at most |o| (1 - cos(dt w / 2)), 2.5 mm for |o| = 0.5 m at
+dt w = 0.2 rad.
 """
 import copy
 import ctypes as C
@@ -147,6 +163,52 @@ def sampled_tracks(positions, velocities, dt, rows, vel_std, samples, seed=0):
 
 
 MAX_DISC_SAMPLES = 16  # (kCrowdSamplesMax of the library)
+MAX_FOOTPRINT_DISCS = 8  # (kCrowdFootprintMax of the library)
+
+
+def rectangle_footprint(front, rear, width, count=None):
+    """(count, 3) float32 footprint rows (ox, oy, rho) for params['footprint']: discs on the body axis that cover the
+    rectangle [-rear, front] x [-width/2, width/2] of the robot frame.  The rectangle is cut into `count` equal pieces
+    along the axis; disc j has its centre in the middle of piece j, at -rear + (j + 1/2) * len / count, and the radius of
+    the piece's circumscribed circle, sqrt((len / (2 count))^2 + (width / 2)^2).  count defaults to ceil(len / width),
+    clipped to 1 .. 8.  Evaluated in float64 and rounded once."""
+    front, rear, width = float(front), float(rear), float(width)
+    length = front + rear
+    if not (np.isfinite([front, rear, width]).all() and length > 0.0 and width >= 0.0):
+        raise ValueError("rectangle_footprint: front + rear > 0 and width >= 0, all finite")
+    if count is None:
+        count = int(np.ceil(length / width)) if width > 0.0 else MAX_FOOTPRINT_DISCS
+        count = min(max(count, 1), MAX_FOOTPRINT_DISCS)
+    count = int(count)
+    if not 1 <= count <= MAX_FOOTPRINT_DISCS:
+        raise ValueError("rectangle_footprint: count {} is not in 1 .. {}".format(count, MAX_FOOTPRINT_DISCS))
+    out = np.zeros((count, 3), dtype=np.float64)
+    out[:, 0] = -rear + (np.arange(count, dtype=np.float64) + 0.5) * length / count
+    out[:, 2] = np.sqrt((length / (2.0 * count)) ** 2 + (width / 2.0) ** 2)
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
+def _footprint_rows(footprint):
+    """params['footprint'] as the library takes it: (F, 3) float32, 1 <= F <= 8 (ValueError otherwise)."""
+    fp = np.asarray(footprint)
+    if fp.ndim != 2 or fp.shape[1] != 3 or not 1 <= fp.shape[0] <= MAX_FOOTPRINT_DISCS:
+        raise ValueError("params['footprint'] has shape (F, 3) with 1 <= F <= {}, got {}".format(MAX_FOOTPRINT_DISCS, fp.shape))
+    return np.ascontiguousarray(_f32(fp))
+
+
+def body_discs(states, footprint):
+    """(..., F, 2) float32: the centres of the body's discs at states (..., 3) = (x, y, th), as the rollouts form them --
+    the states rounded to float32 first, s, c the float64 sine and cosine of the float32 heading,
+    cx = x + (ox * c - oy * s), cy = y + (ox * s + oy * c) in float64 in this order, rounded once.  For drawing."""
+    st = _f32(states)
+    if st.shape[-1] < 3:
+        raise ValueError("states have shape (..., 3), got {}".format(st.shape))
+    fp = _footprint_rows(footprint).astype(np.float64)
+    x, y, th = (st[..., i, None].astype(np.float64) for i in range(3))
+    s, c = np.sin(th), np.cos(th)
+    cx = x + (fp[:, 0] * c - fp[:, 1] * s)
+    cy = y + (fp[:, 0] * s + fp[:, 1] * c)
+    return np.ascontiguousarray(np.stack([cx, cy], axis=-1).astype(np.float32))
 
 
 def constant_velocity_walls(segments, velocities, dt, rows, at=0.5):
@@ -245,6 +307,7 @@ class MPPI_Numba(object):
         self._own_goals = False       # MPPI_Batch: per-problem goal tracks are set (they win over params['goal_track'])
         self._goal_tracks = None      # the goal tracks held, whoever set them: (1 or B, L, 2) float32 (None: static goals)
         self._fleet = None            # MPPI_Batch.set_fleet: (radii (B,), margin, half-widths (B, B - 1)) (None: off)
+        self._footprint_key = None    # the footprint of params['footprint'] the library holds (None: none)
         self.reset()
 
     def __del__(self):
@@ -367,6 +430,33 @@ class MPPI_Numba(object):
                   _lib.ptr(seg_all, C.c_float), _lib.ptr(half_all, C.c_float))
         self._wall_rows = int(rows)
         self._fetch_track_offset()  # (new walls that move: row 0 is "now"; a set of one row is static and leaves it alone)
+
+    # ------------------------------------------------------------------ a body footprint
+    def _hand_over_footprint(self, p):
+        """params['footprint'] (F, 3): handed over when its bytes have changed, cleared when the key has gone.  Without
+        crowd mode the library refuses it (MppiError); beside the fleet it is refused here (ValueError)."""
+        if "footprint" not in p:
+            if self._footprint_key is not None:
+                _lib.call("mppi_planner_set_footprint", self._handle, None, 0)
+                self._footprint_key = None
+            return
+        if self._fleet is not None:
+            raise ValueError("params hold 'footprint' while the fleet is on: the fleet's half-widths already contain the "
+                             "reader's body (set_fleet(None) first, or drop the key)")
+        fp = np.asarray(p['footprint'])
+        key = (fp.dtype.str, fp.shape, fp.tobytes())
+        if key == self._footprint_key:
+            return
+        rows = _footprint_rows(fp)
+        _lib.call("mppi_planner_set_footprint", self._handle, _lib.ptr(rows, C.c_float), len(rows))
+        self._footprint_key = key
+
+    @property
+    def footprint(self):
+        """The footprint the library holds: (F, 3) float32, or None (the robot is its reference point)."""
+        rows, count = np.zeros((MAX_FOOTPRINT_DISCS, 3), dtype=np.float32), C.c_int(0)
+        _lib.call("mppi_planner_get_footprint", self._handle, _lib.ptr(rows, C.c_float), C.byref(count))
+        return rows[:count.value].copy() if count.value else None
 
     # ------------------------------------------------------------------ a goal that moves
     def _hand_over_goal_tracks(self, tracks, what="goal track"):
@@ -606,6 +696,8 @@ class MPPI_Numba(object):
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
         self._hand_over_walls(p)
+        if "footprint" in p or self._footprint_key is not None:  # (the point robot's path pays one lookup for this)
+            self._hand_over_footprint(p)
         if ("obstacle_track_samples" in p or self._samples_key is not None) and self._hand_over_samples(p):
             return
         # the discs: handed over when they have changed (the notebook uploads them with every solve)
@@ -929,6 +1021,11 @@ class MPPI_Batch(MPPI_Numba):
         r = np.ascontiguousarray(np.broadcast_to(_f32(radii), (B,)))
         if not (np.isfinite(r).all() and (r >= 0).all() and np.isfinite(margin)):
             raise ValueError("fleet radii are finite and >= 0, the margin finite")
+        if self.params is not None and "footprint" in self.params:
+            raise ValueError("set_fleet while params hold 'footprint': the fleet's half-widths already contain the reader's "
+                             "body (drop the key first)")
+        if self._footprint_key is not None:  # (the key has gone and the library has not heard yet)
+            self._hand_over_footprint(self.params if self.params is not None else {})
         if self._own_walls or self._wall_tracks_key is not None:
             raise ValueError("set_fleet while per-problem wall sets or params['wall_tracks'] are held: the fleet makes every "
                              "problem's wall set itself (set_wall_sets(None) / drop the key first)")

@@ -328,6 +328,9 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
             "crowd mode stays on: the handle holds wall tracks, which only the crowd kernel tests (clear them first)");
     REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle is in fleet mode, whose walls only the crowd kernel tests (mppi_planner_set_fleet(p, 0, NULL) first)");
+    REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds a footprint of %d discs, which only the crowd kernel tests (mppi_planner_set_footprint(p, NULL, 0) first)",
+            p->fp_count);
     BareboneHeld now = barebone_held(p);  // (without rotation: every set at its own size, the least a launch can ask for)
     now.crowd = false;
     BareboneHeld own = now, shared = now, tracks = now;
@@ -574,6 +577,9 @@ extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* h
   REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
           "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
           "first (mppi_planner_set_wall_tracks with count 0)");
+  REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
+          "the handle holds a footprint; the fleet's half-widths already contain the reader's body: clear it first "
+          "(mppi_planner_set_footprint(p, NULL, 0))");
   REQUIRE(halfwidths, MPPI_ERR_INVALID, "NULL halfwidths");
   const size_t pairs = (size_t)p->B * (size_t)(p->B - 1);
   TRY(check_halfwidths(halfwidths, pairs, "fleet pair"));
@@ -592,6 +598,46 @@ extern "C" int mppi_planner_get_fleet(mppi_planner* p, int* on) {
   REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
   *on = p->fleet_on ? p->B : 0;
+  return MPPI_OK;
+}
+
+// ---- a body footprint ----------------------------------------------------------------------------------------------------
+// A body footprint (include/mppi_hip.h): crowd mode only, and not beside the fleet.  The rows are a by-value argument of the
+// launches: there is no device array, so nothing to stage -- but the stream is drained like everywhere else, and a change
+// takes a new generation (the graph signature's view of the footprint) and drops the captured graphs.
+extern "C" int mppi_planner_set_footprint(mppi_planner* p, const float* discs, int count) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(count >= 0 && count <= kCrowdFootprintMax, MPPI_ERR_INVALID, "footprint of %d discs: must be 0 (none) to %d", count, kCrowdFootprintMax);
+  if (count > 0) {
+    REQUIRE(discs, MPPI_ERR_INVALID, "NULL discs");
+    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+            "a footprint needs crowd mode: only the crowd kernel has footprint forms (mppi_planner_set_crowd(p, 1) first)");
+    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+            "the handle is in fleet mode, whose half-widths already contain the reader's body: turn it off first "
+            "(mppi_planner_set_fleet(p, 0, NULL))");
+    for (int i = 0; i < count; ++i) {
+      REQUIRE(std::isfinite(discs[3 * i]) && std::isfinite(discs[3 * i + 1]) && std::isfinite(discs[3 * i + 2]), MPPI_ERR_INVALID,
+              "footprint disc %d: a value is not finite", i);
+      REQUIRE(discs[3 * i + 2] >= 0.0f, MPPI_ERR_INVALID, "footprint disc %d: radius %g is negative", i, (double)discs[3 * i + 2]);
+    }
+  }
+  if (count == p->fp_count && (count == 0 || memcmp(discs, p->fp_host, sizeof(float) * 3 * (size_t)count) == 0)) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  memset(p->fp_host, 0, sizeof(p->fp_host));
+  if (count > 0) memcpy(p->fp_host, discs, sizeof(float) * 3 * (size_t)count);
+  p->fp_count = count;
+  p->fp_gen = count > 0 ? next_generation() : 0;
+  drop_graphs(p);  // (the rows, the count and the kernel form are arguments of the captured launches)
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* count) {
+  REQUIRE(p && discs && count, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
+  memcpy(discs, p->fp_host, sizeof(p->fp_host));
+  *count = p->fp_count;
   return MPPI_OK;
 }
 

@@ -21,7 +21,7 @@ static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
   crowd_shape(p, &W, &C);
   return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, p->crowd, p->n_obstacles, p->inst_obs_on, p->inst_obs_max,
                       p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on,
-                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W};
+                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W, p->fp_count};
 }
 
 // The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
@@ -91,6 +91,10 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
 }
 // (barebone_plan.h restates the chunk and the LDS formula for the host: a sample form's chunk is chosen there)
 static_assert(kCrowdChunkSteps == kCrowdChunkMax, "barebone_plan.h and rollout_crowd_kernel.h disagree on the chunk");
+static_assert(kCrowdFootprintMax * 3 == sizeof(mppi_planner::fp_host) / sizeof(float), "handles.h and rollout_crowd_kernel.h disagree on the footprint");
+static_assert(crowd_lds_bytes(37, 14, true, 3, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 &&
+                  crowd_lds_bytes(100, 16, false, 0, true) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 + 2 * 16 * 64 * 4 + 192,
+              "crowd_lds_bytes: the footprint forms' layout crowd_lds (barebone_plan.h) restates");
 static_assert(crowd_lds_bytes(37, 14, true, 3) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 &&
                   crowd_lds_bytes(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8,
               "crowd_lds_bytes: the layout crowd_lds (barebone_plan.h) restates");
@@ -113,15 +117,36 @@ static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
 // (CrowdWallTracks) -- they come first: while they are held the static walls rest -- and fleet mode, which takes the same
 // form with the sets it makes itself, the static walls copied into them.  A goal that moves: one GoalRows argument
 // more, behind the walls'.  Disc samples (mppi_planner_set_disc_track_samples): the sample forms, one CrowdSamples argument
-// at the end -- TRACKS forms over the [row][sample][disc] copy, with the chunk and the LDS of the choice.
+// at the end -- TRACKS forms over the [row][sample][disc] copy, with the chunk and the LDS of the choice.  A body footprint
+// (mppi_planner_set_footprint): the footprint forms, one CrowdFootprint argument behind everything else -- TRACKS forms
+// whatever the discs are (static discs: tracks of one row, DevParams::track_rows = 1, as the default family's goal forms
+// take them), static shared walls as wall tracks of one row, with or without a CrowdSamples argument.
+static CrowdFootprint footprint_arg(const mppi_planner* p) {
+  CrowdFootprint fp{};
+  fp.count = p->fp_count;
+  for (int i = 0; i < p->fp_count; ++i) {  // (the float32 rows widened here: exact, and the kernel's scalar operands as they are)
+    fp.ox[i] = (double)p->fp_host[3 * i];
+    fp.oy[i] = (double)p->fp_host[3 * i + 1];
+    fp.rho[i] = (double)p->fp_host[3 * i + 2];
+  }
+  return fp;
+}
+
 template <bool EXACT, bool BATCHED>
-static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const BareboneChoice& c, bool rot) {
+static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneChoice& c, bool rot) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  if (c.samples > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples);  // the size launched
+  if (c.samples > 0 || c.footprint > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0);  // the size launched
+  if (c.footprint > 0) {
+    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, true), MPPI_ERR_STATE,
+            "footprint: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
+    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "a footprint and %d steps: the crowd kernel needs %zu bytes of LDS",
+            p->cfg.num_steps, lds);
+    if (c.discs != kDiscsTracks && c.discs != kDiscsSamples) d.track_rows = 1;  // (static discs: tracks of one row)
+  }
   if (c.samples > 0) {
-    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples), MPPI_ERR_STATE,
+    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0), MPPI_ERR_STATE,
             "disc samples: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS",
             c.samples, p->cfg.num_steps, lds);
@@ -172,7 +197,34 @@ static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const Bare
     if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
     return with_walls();
   };
-  if (c.samples > 0 && rot) TRY(dispatch_samples(std::true_type()));
+  // a body footprint: TRACKS forms with one CrowdFootprint at the very end; the walls as the sample forms take them
+  auto dispatch_footprint = [&](auto rot_c, auto samples_c) -> int {
+    constexpr bool ROT = EXACT && decltype(rot_c)::value, SMP = decltype(samples_c)::value;
+    const CrowdFootprint fp = footprint_arg(p);
+    const CrowdSamples smp{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(std::max(c.samples, 1), d.cvar_alpha)};
+    auto with_walls = [&](auto... walls) -> int {
+      constexpr bool WALLS = sizeof...(walls) > 0;
+      if constexpr (SMP) {
+        if (c.goal_form)
+          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdSamples, CrowdFootprint>,
+                        walls..., goal_rows_arg<BATCHED>(p), smp, fp);
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdSamples, CrowdFootprint>, walls..., smp, fp);
+      } else {
+        if (c.goal_form)
+          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdFootprint>, walls...,
+                        goal_rows_arg<BATCHED>(p), fp);
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdFootprint>, walls..., fp);
+      }
+    };
+    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
+    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
+    return with_walls();
+  };
+  if (c.footprint > 0 && c.samples > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::true_type()));
+  else if (c.footprint > 0 && c.samples > 0) TRY(dispatch_footprint(std::false_type(), std::true_type()));
+  else if (c.footprint > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::false_type()));
+  else if (c.footprint > 0) TRY(dispatch_footprint(std::false_type(), std::false_type()));
+  else if (c.samples > 0 && rot) TRY(dispatch_samples(std::true_type()));
   else if (c.samples > 0) TRY(dispatch_samples(std::false_type()));
   else if (rot && tracks) TRY(dispatch(std::true_type(), std::true_type()));
   else if (rot) TRY(dispatch(std::true_type(), std::false_type()));
@@ -190,13 +242,16 @@ static int launch_barebone_crowd(mppi_planner* p, const DevParams& d, const Bare
                                  " fleet=" + std::to_string(p->B) : std::string()) +
                     (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string()) +
                     (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
-                                   : std::string());
+                                   : std::string()) +
+                    (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
 
 // A set that does not fit in 64 KiB of LDS while crowd mode is off.
 static int barebone_refuse(const BareboneChoice& c, int T) {
+  if (c.limit == kLimitFootprintNeedsCrowd)
+    return fail(MPPI_ERR_INVALID, "a footprint of %d discs needs crowd mode: only the crowd kernel has footprint forms", c.footprint);
   if (c.limit == kLimitSamplesNeedCrowd)
     return fail(MPPI_ERR_INVALID, "%d disc samples need crowd mode: only the crowd kernel has sample forms", c.samples);
   if (c.limit == kLimitGoalTrack)

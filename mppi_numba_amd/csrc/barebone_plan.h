@@ -39,17 +39,19 @@ constexpr size_t kCrowdSampleLdsAim = 64 * 1024;  // the chunk of a sample form 
 //   [T] double2 control ratios | [2][C][64] double goal distance | [2][C (+ 1 with walls)][64] float2 position |
 //   [2][C][64] int hits | two "tile done" words                                        the plain forms (samples = 0)
 //   ... | [2][C][S][64] uint16 hits | two words | [S][64] float running costs          the sample forms
-inline size_t crowd_lds(int T, int C, bool walls, int samples = 0) {
+//   ... | [2][C (+ 1 with walls)][64] float heading | [3][8] double footprint rows     the footprint forms (behind all of that)
+inline size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false) {
   const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4 : (size_t)2 * C * 64 * 4;
-  return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8;
+  const size_t heading = footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 4 + 3 * 8 * 8 : 0;
+  return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8 + heading;
 }
 
 // C steps per chunk for a workgroup of W waves: the largest multiple of the W - 2 counters within kCrowdChunkSteps, every
 // counter the same share.  A sample form gives up whole shares while its LDS is above kCrowdSampleLdsAim (one share stays).
-inline int crowd_chunk(int W, int T = 0, bool walls = false, int samples = 0) {
+inline int crowd_chunk(int W, int T = 0, bool walls = false, int samples = 0, bool footprint = false) {
   const int counters = std::min(std::max(W - 2, 1), kCrowdChunkSteps);
   int C = (kCrowdChunkSteps / counters) * counters;
-  while (samples > 0 && C > counters && crowd_lds(T, C, walls, samples) > kCrowdSampleLdsAim) C -= counters;
+  while (samples > 0 && C > counters && crowd_lds(T, C, walls, samples, footprint) > kCrowdSampleLdsAim) C -= counters;
   return C;
 }
 
@@ -69,12 +71,15 @@ struct BareboneHeld {
   int samples = 0;                   // disc samples: S (0: none held), ...
   int smp_discs = 0, smp_rows = 0;   // ... K discs of L rows each
   int crowd_waves = 16;              // crowd family: waves per workgroup (crowd_shape of barebone_launch.h)
+  int footprint = 0;                 // body footprint: F discs (0: the robot is its reference point)
 };
 
 enum BareboneFamily { kBareboneDefault = 0, kBareboneCrowd = 1, kBareboneRefused = 2 };
 enum BareboneDiscs { kDiscsShared = 0, kDiscsOwn = 1, kDiscsTracks = 2, kDiscsSamples = 3 };
-// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off); disc samples without crowd mode
-enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3, kLimitSamplesNeedCrowd = 4 };
+// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off); disc samples, or a body footprint, without
+// crowd mode
+enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3, kLimitSamplesNeedCrowd = 4,
+                     kLimitFootprintNeedsCrowd = 5 };
 
 struct BareboneChoice {
   BareboneFamily family = kBareboneDefault;
@@ -84,10 +89,11 @@ struct BareboneChoice {
   bool track_form = false;  // default family: a row of disc slots per step (disc tracks, or static discs under a goal track)
   bool goal_form = false;   // a goal that moves
   int walls = 0;            // crowd family: 0 none, 1 static walls, 2 wall tracks / per-problem sets / fleet
-  size_t lds = 0;           // default family: the dynamic LDS launched; a sample form: likewise
+  size_t lds = 0;           // default family: the dynamic LDS launched; a sample form, a footprint form: likewise
   BareboneLimit limit = kLimitNone;
   int samples = 0;          // crowd family: 0, or the sample form over this many disc samples
-  int chunk = 0;            // a sample form: steps per chunk
+  int chunk = 0;            // a sample form: steps per chunk; a footprint form: likewise
+  int footprint = 0;        // crowd family: 0, or the footprint form over this many body discs
 };
 
 // Crowd mode: does a launch go to the crowd kernel?  own_lds: what the default form holds at the least.  Walls are the
@@ -101,8 +107,17 @@ inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
 // under rotation; a track form whose padded row does not fit falls back to the loop over the problem's own row.
 // Disc samples are a disc source of the crowd family alone: they take the place of the tracks, run as TRACKS forms, and
 // take static shared walls as wall tracks of one row (walls = 1 stays the choice; the launcher makes the argument).
+// A body footprint (mppi_planner_set_footprint) is the crowd family's alone as well: a handle that holds one always goes
+// there, whatever it holds otherwise -- no discs and no walls included --, and launches a footprint form: a TRACKS form, static
+// discs as tracks of one row, static shared walls as wall tracks of one row, with the chunk and the LDS of the choice.
 inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   BareboneChoice c;
+  c.footprint = h.footprint;
+  if (h.footprint > 0 && !h.crowd) {
+    c.family = kBareboneRefused;
+    c.limit = kLimitFootprintNeedsCrowd;
+    return c;
+  }
   if (h.samples > 0) {
     c.discs = kDiscsSamples;
     c.kmax = h.smp_discs;
@@ -116,8 +131,8 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
       return c;
     }
     c.family = kBareboneCrowd;
-    c.chunk = crowd_chunk(h.crowd_waves, h.T, c.walls != 0, c.samples);
-    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, c.samples);
+    c.chunk = crowd_chunk(h.crowd_waves, h.T, c.walls != 0, c.samples, c.footprint > 0);
+    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, c.samples, c.footprint > 0);
     return c;
   }
   c.discs = h.trk_on ? kDiscsTracks : (h.inst_obs_on ? kDiscsOwn : kDiscsShared);
@@ -126,6 +141,13 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   c.track_form = h.trk_on || h.gtrk_on;
   c.walls = (h.wtrk_on || h.fleet_on) ? 2 : (h.n_walls > 0 ? 1 : 0);
   const size_t own_lds = barebone_lds(h.T, c.kmax, c.track_form, c.goal_form);
+  if (h.footprint > 0) {
+    c.family = kBareboneCrowd;
+    c.track_form = true;
+    c.chunk = crowd_chunk(h.crowd_waves);
+    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, 0, true);
+    return c;
+  }
   if (crowd_launch(h, c.kmax, own_lds)) {
     c.family = kBareboneCrowd;
     return c;

@@ -294,6 +294,13 @@ struct mppi_planner {
   int gtrk_rows = 0, gtrk_count = 0;
   uint64_t gtrk_gen = 0;
   std::vector<float> gtrk_host;  // what was handed over
+  // a body footprint (mppi_planner_set_footprint; crowd mode only, and not beside the fleet): fp_count discs (ox, oy, rho)
+  // in the robot frame, one footprint for every problem.  While fp_count > 0 every rollout launch is a footprint form of
+  // the crowd kernel, which takes the rows by value (CrowdFootprint).  fp_gen: next_generation() at every change, 0 while
+  // none is held -- what the graph signature holds of it
+  int fp_count = 0;
+  float fp_host[8 * 3] = {};  // what was handed over: [disc][3]
+  uint64_t fp_gen = 0;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

@@ -81,6 +81,32 @@
 //          iff cvar_alpha < 1), the strided float32 tree over the first numel entries walked serially -- the tree's shape
 //          fixes the bits, not who executes it --, the division in double.
 // Without the argument the kernel is what it was.
+//
+// A BODY FOOTPRINT (mppi_planner_set_footprint): the robot as up to kCrowdFootprintMax discs rigidly attached to its pose, one
+// CrowdFootprint argument at the very end of the pack -- by value, so its rows are wave-uniform (TRACKS forms only; walls:
+// the CrowdWallTracks form only, static discs and static shared walls as tracks of one row).  Body disc i = (ox, oy, rho) has
+// its centre at (float)(x + (ox * c - oy * s)), (float)(y + (ox * s + oy * c)): s, c the full sincos_f64<false> of the state's
+// float32 heading, products and sums in double, one rounding (crowd_body_centres).
+//   walk   beside each position the walker publishes the float32 heading: one more LDS plane, [2][C (+ 1)][64] float behind
+//          everything else, entry slot included -- one store, nothing on the walker's dependent chain.  The count waves set
+//          the pace of these forms and need the registers: the walker loads a chunk's noise at the chunk's head and carries
+//          none across the barrier (the other forms keep the next chunk's in flight: 32 registers live in every wave)
+//   count  the owner of (step, lane) forms the centres of the post-step state once per step, at the step's first disc tile,
+//          and keeps them in registers to its last -- loops unrolled to 8, predicated on the uniform count: a register array
+//          indexed at run time would go to scratch memory.  A disc is touched iff ANY body disc touches it, the existing
+//          test with pos := the centre and rr := (r + rho)^2 in double.  A wall is hit iff ANY body disc's chord, pre-step
+//          centre -> post-step centre, hits it: crowd_wall_hit unchanged with hh := (h + rho)^2.  Eight unrolled copies of
+//          that test cost some 900 bytes of scratch a lane, so the walls go the other way round (crowd_body_wall_hits): a
+//          run-time loop over the body's discs around ONE copy of the test, the rows read from LDS ([3][8] double behind
+//          the headings, written once), both centres formed on the spot from the two states and their sines and cosines
+//          (the second sincos_f64 of a step), one bit per wall OR-ed over the body.  One hit per obstacle, however many body
+//          discs reach it.  (An offset point of a turning body moves on an arc; the chord is what is tested: the arc
+//          leaves it by at most |o| * (1 - cos(dt * w / 2)).)  The compiler's report, gfx950, scratch bytes a lane: the 24
+//          forms without walls 0 .. 36 (the forms without a footprint and without walls: 0 .. 132), the 24 with walls
+//          232 .. 344 (theirs: 88 .. 248) -- one wall test and what the other waves keep do not fit 128 registers
+//          together in either; zero was not reached.
+//   cost   the cost wave, the tail and the CVaR tail do not know; the goal distance is the reference point's.
+// Without the argument the kernel is what it was.
 #pragma once
 #include <type_traits>
 
@@ -93,12 +119,20 @@ constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
 // dynamic LDS: [T] double2 control ratios | [2][C][64] double goal distance | [2][C][64] float2 position |
 // [2][C][64] int hits | two "tile done" words.  walls: [2][C + 1][64] positions (slot 0: the chunk's entry position)
 // disc samples (S > 0): [2][C][S][64] uint16 hits in place of the int hits, and [S][64] float running costs at the end
-__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0) {
+// a body footprint: [2][C (+ 1 with walls)][64] float headings behind all of that, slot for slot beside the positions, and
+// [3][8] double, the footprint's rows (ox | oy | rho), behind them
+__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0, bool footprint = false) {
   return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * sizeof(double) +
          (samples > 0 ? (size_t)2 * C * samples * 64 * sizeof(unsigned short) + (size_t)samples * 64 * sizeof(float)
                       : (size_t)2 * C * 64 * sizeof(int)) +
-         (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int);
+         (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int) +
+         (footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float) + 3 * 8 * sizeof(double) : 0);
 }
+static_assert(crowd_lds_bytes(50, 14, true, 0) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 14 * 64 * 4 + 2 * 15 * 64 * 8 + 8 &&
+                  crowd_lds_bytes(50, 14, true, 2) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 14 * 2 * 64 * 2 + 2 * 64 * 4 + 2 * 15 * 64 * 8 + 8 &&
+                  crowd_lds_bytes(50, 16, false, 0, true) == crowd_lds_bytes(50, 16, false) + 2 * 16 * 64 * 4 + 192 &&
+                  crowd_lds_bytes(50, 14, true, 2, true) == crowd_lds_bytes(50, 14, true, 2) + 2 * 15 * 64 * 4 + 192,
+              "crowd_lds_bytes: without a footprint the layout as it was; with one, the heading plane and the rows on top of it");
 
 // The walls of a launch (WALLS): seg[k] = (ax, ay, bx, by), halfwidth[k]; shared by every problem of a batch.
 struct CrowdWalls {
@@ -126,6 +160,13 @@ struct CrowdWallTracks {
 struct CrowdSamples {
   float* sample_costs;
   int count, numel;
+};
+
+// The body footprint of a launch: `count` discs (ox, oy, rho) in the robot frame, x along the heading, y to the left.
+constexpr int kCrowdFootprintMax = 8;
+struct CrowdFootprint {
+  double ox[kCrowdFootprintMax], oy[kCrowdFootprintMax], rho[kCrowdFootprintMax];  // (the float32 rows, widened on the host)
+  int count;
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -163,6 +204,65 @@ __device__ __forceinline__ bool crowd_wall_hit(double px, double py, double qx, 
          crowd_near(apx, apy, ex, ey, LLe, hh) || crowd_near(bpx, bpy, ex, ey, LLe, hh);
 }
 
+// The centres of the body's discs at the state (x, y, th): s, c from the full sincos_f64 (never the rotation form: the
+// centres are defined on the state's rounded heading alone), products and sums in double in this order, no fma (the build
+// contracts nothing), one rounding to float32.  Entries past fp.count are not touched.  s, c: kept for the walls.
+__device__ __forceinline__ void crowd_body_centres(const CrowdFootprint& fp, float x, float y, float th,
+                                                   float (&cx)[kCrowdFootprintMax], float (&cy)[kCrowdFootprintMax], double& s,
+                                                   double& c) {
+  sincos_f64<false>((double)th, s, c);
+#pragma unroll
+  for (int i = 0; i < kCrowdFootprintMax; ++i) {
+    if (i < fp.count) {
+      const double ox = fp.ox[i], oy = fp.oy[i];
+      cx[i] = (float)((double)x + (ox * c - oy * s));
+      cy[i] = (float)((double)y + (ox * s + oy * c));
+    }
+  }
+}
+
+// Does any body disc touch the disc at (ox, oy) of radius r?  The disc test of the count waves with pos := the centre and
+// rr := (r + rho)^2.
+__device__ __forceinline__ bool crowd_body_touches(const CrowdFootprint& fp, const float (&cx)[kCrowdFootprintMax],
+                                                   const float (&cy)[kCrowdFootprintMax], float ox, float oy, double r) {
+  bool any = false;
+#pragma unroll
+  for (int i = 0; i < kCrowdFootprintMax; ++i) {
+    if (i < fp.count) {
+      const double ex = (double)(cx[i] - ox), ey = (double)(cy[i] - oy);
+      const double R = r + fp.rho[i];
+      const double diff = fma(ex, ex, ey * ey) - R * R;
+      any = any || !(diff > 0.0);
+    }
+  }
+  return any;
+}
+
+// How many of a tile's wt walls does the body hit during a step?  Lane l of sg, dx, dy, LLd, h holds wall l (h: the
+// half-width itself, the body disc's radius is added before the square).  A wall is hit iff ANY body disc's chord, its
+// centre before the step -> its centre after it, hits it: one bit per wall, OR-ed over the body's discs.  The loop over
+// the discs is a run-time loop around ONE copy of the wall test, so nothing here may live in a register array: the rows
+// come from LDS (rows: [3][8] double, ox | oy | rho -- uniform reads) and both centres are formed on the spot from the
+// two states and their sines and cosines, in crowd_body_centres' arithmetic: the same bits.
+__device__ __forceinline__ int crowd_body_wall_hits(const double* rows, int count, float px, float py, double sp, double cp,
+                                                    float qx, float qy, double sq, double cq, const float4& sg, double dx,
+                                                    double dy, double LLd, double h, int wt) {
+  unsigned long long mask = 0ull;
+  for (int i = 0; i < count; ++i) {
+    const double ox = rows[i], oy = rows[kCrowdFootprintMax + i], rho = rows[2 * kCrowdFootprintMax + i];
+    const double pcx = (double)(float)((double)px + (ox * cp - oy * sp)), pcy = (double)(float)((double)py + (ox * sp + oy * cp));
+    const double qcx = (double)(float)((double)qx + (ox * cq - oy * sq)), qcy = (double)(float)((double)qy + (ox * sq + oy * cq));
+    for (int l = 0; l < wt; ++l) {
+      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+      const double H = crowd_lane_f64(h, l) + rho;
+      if (crowd_wall_hit(pcx, pcy, qcx, qcy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l), crowd_lane_f64(LLd, l), H * H))
+        mask |= 1ull << l;
+    }
+  }
+  return __popcll(mask);
+}
+
 // obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
 __device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
@@ -174,10 +274,26 @@ __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdSamples&) { retu
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdSamples&) { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&) { return walls; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&) { return walls; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdSamples&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdSamples&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdFootprint&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdFootprint&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&, const CrowdFootprint&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&, const CrowdFootprint&) { return walls; }
 template <typename... WallArgs>
 constexpr bool kCrowdWallTracks = (std::is_same_v<WallArgs, CrowdWallTracks> || ...);
 template <typename... WallArgs>
 constexpr bool kCrowdSamples = (std::is_same_v<WallArgs, CrowdSamples> || ...);
+template <typename... WallArgs>
+constexpr bool kCrowdFootprint = (std::is_same_v<WallArgs, CrowdFootprint> || ...);
+__device__ __forceinline__ CrowdFootprint crowd_footprint_of() { return CrowdFootprint{{}, {}, {}, 0}; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ CrowdFootprint crowd_footprint_of(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<First, CrowdFootprint>) return first;
+  else return crowd_footprint_of(rest...);
+}
 __device__ __forceinline__ CrowdSamples crowd_samples_of() { return CrowdSamples{nullptr, 0, 1}; }
 template <typename First, typename... Rest>
 __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, const Rest&... rest) {
@@ -187,18 +303,22 @@ __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, con
 
 // WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
 // shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets); behind it, with a goal
-// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls).
+// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls); at the very end,
+// with a body footprint, one CrowdFootprint (TRACKS, and no CrowdWalls).
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
     const float2* __restrict__ u, float* __restrict__ costs, int C, int disc_pitch, WallArgs... wall_args) {
   constexpr bool GOALS = kGoalRows<WallArgs...>;
   constexpr bool SAMPLES = kCrowdSamples<WallArgs...>;
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0),
+  constexpr bool FOOT = kCrowdFootprint<WallArgs...>;
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0) + (FOOT ? 1 : 0),
                 "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; disc samples: "
-                "one CrowdSamples behind that; else none");
+                "one CrowdSamples behind that; a body footprint: one CrowdFootprint behind that; else none");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
   static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
+  static_assert(!FOOT || (TRACKS && WTRK == WALLS), "a body footprint: TRACKS forms, walls as CrowdWallTracks");
+  [[maybe_unused]] const CrowdFootprint fp = crowd_footprint_of(wall_args...);
   [[maybe_unused]] const CrowdSamples smp = crowd_samples_of(wall_args...);
   [[maybe_unused]] const int S = SAMPLES ? smp.count : 1;
   [[maybe_unused]] GoalRows G = goal_rows_of(wall_args...);
@@ -241,6 +361,23 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     if (wave == 1)  // (the cost wave's own columns: nobody else touches them)
       for (int s = 0; s < S; ++s) scost[s * 64 + lane] = 0.0f;
   }
+  // FOOT: [2][CP][64] float headings behind everything else, slot for slot beside the positions
+  [[maybe_unused]] float* heads = nullptr;
+  if constexpr (FOOT && SAMPLES) heads = scost + (size_t)S * 64;
+  else if constexpr (FOOT) heads = reinterpret_cast<float*>(tile_done + 2);
+  // ... and behind them the footprint's rows once more, [3][8] double: what the walls' run-time loop over the body reads
+  [[maybe_unused]] double* fprows = nullptr;
+  if constexpr (FOOT) {
+    fprows = reinterpret_cast<double*>(heads + (size_t)2 * CP * 64);
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 0; i < kCrowdFootprintMax; ++i) {
+        fprows[i] = fp.ox[i];
+        fprows[kCrowdFootprintMax + i] = fp.oy[i];
+        fprows[2 * kCrowdFootprintMax + i] = fp.rho[i];
+      }
+    }
+  }
   if (threadIdx.x < 2) tile_done[threadIdx.x] = 0;
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
   const int n = blockIdx.x * 64 + lane;
@@ -254,8 +391,10 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   float2 e_cur[kCrowdChunkMax];
   if (wave == 0) {
     if (ROT) sincos_f64<false>((double)th, rs, rc);
+    if constexpr (!FOOT) {
 #pragma unroll
-    for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = col[(size_t)min(j, T - 1) * 64];
+      for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = col[(size_t)min(j, T - 1) * 64];
+    }
   }
   // the cost wave's
   float cost = 0.0f;
@@ -279,11 +418,21 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     if (wave == 0) {
       if (ph < n_chunks) {  // ---- walk chunk ph
         const int c0 = ph * C, cl = min(C, T - c0);
-        float2 e_nxt[kCrowdChunkMax];
+        // the next chunk's noise is in flight during this chunk's steps.  FOOT: the count waves set the pace and need the
+        // registers -- the walker loads a chunk's noise at its head and carries nothing across the barrier
+        [[maybe_unused]] float2 e_nxt[kCrowdChunkMax];
+        if constexpr (FOOT) {
 #pragma unroll
-        for (int j = 0; j < kCrowdChunkMax; ++j) e_nxt[j] = col[(size_t)min(c0 + C + j, T - 1) * 64];
+          for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = col[(size_t)min(c0 + j, T - 1) * 64];
+        } else {
+#pragma unroll
+          for (int j = 0; j < kCrowdChunkMax; ++j) e_nxt[j] = col[(size_t)min(c0 + C + j, T - 1) * 64];
+        }
         float2* out = poss + (size_t)((ph & 1) * CP + kEntry) * 64 + lane;
         if constexpr (WALLS) out[-64] = make_float2(x, y);  // where the chunk's first step starts
+        [[maybe_unused]] float* hout = nullptr;
+        if constexpr (FOOT) hout = heads + (size_t)((ph & 1) * CP + kEntry) * 64 + lane;
+        if constexpr (FOOT && WALLS) hout[-64] = th;  // ... and how the body lies there
 #pragma unroll
         for (int j = 0; j < kCrowdChunkMax; ++j) {
           if (j < cl) {
@@ -292,10 +441,13 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             if (ROT) rotate_sincos_f64((double)nth - (double)th, rs, rc);  // exact increment of the ROUNDED heading
             x = nx; y = ny; th = nth;  // (past the goal the state goes on -- nobody looks at it: the cost wave freezes)
             out[j * 64] = make_float2(nx, ny);
+            if constexpr (FOOT) hout[j * 64] = nth;
           }
         }
+        if constexpr (!FOOT) {
 #pragma unroll
-        for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = e_nxt[j];
+          for (int j = 0; j < kCrowdChunkMax; ++j) e_cur[j] = e_nxt[j];
+        }
       }
     } else if (wave == 1) {
       if (ph >= 2) {  // ---- cost of chunk ph - 2
@@ -355,7 +507,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             op = row[k];
             r = obs_r[k];
           }
-          rr = (double)r * (double)r;
+          if constexpr (FOOT) rr = (double)r;  // (the body discs' radii are added before the square)
+          else rr = (double)r * (double)r;
         };
         // this lane's wall of the tile [wbase, wbase + 64) with its constants; past the last wall: a wall nobody can touch.
         // The walls do not change with the step: the first tile is loaded once per chunk
@@ -389,8 +542,14 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
           dx = (double)sg.z - (double)sg.x;
           dy = (double)sg.w - (double)sg.y;
           LLd = dx * dx + dy * dy;
-          hh = (double)h * (double)h;
+          if constexpr (FOOT) hh = (double)h;  // (the body discs' radii are added before the square)
+          else hh = (double)h * (double)h;
         };
+        // FOOT: the body's centres at the post-step state of the step in hand (formed at the step's first tile, kept to its
+        // last) and, for the walls, at its pre-step state
+        constexpr int kLanes = FOOT ? 1 : 4;  // discs tested per trip of the test loop (a body: up to 8 tests a disc as it is)
+        [[maybe_unused]] float qcx[kCrowdFootprintMax] = {}, qcy[kCrowdFootprintMax] = {};
+        [[maybe_unused]] double sq = 0.0, cq = 1.0;  // (sine and cosine of the post-step heading)
         [[maybe_unused]] float4 sg0;
         [[maybe_unused]] double dx0, dy0, LLd0, hh0;
         if constexpr (WTRK) load_wall_row(wave - 2, 0, sg0, dx0, dy0, LLd0, hh0);  // (the first tile of the first step owned)
@@ -405,7 +564,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
               op = obs_pos[(size_t)min(now + c0 + j + 1, last) * (size_t)disc_pitch + (size_t)sm * (size_t)K + (size_t)k];
               r = obs_r[k];
             }
-            rr = (double)r * (double)r;
+            if constexpr (FOOT) rr = (double)r;
+            else rr = (double)r * (double)r;
           };
           int j = wave - 2, sm = 0, base = 0, hits = 0, whits = 0;
           float2 op;
@@ -421,22 +581,31 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             double rr_nxt;
             load_sample_disc(nj, nsm, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
             const float2 pos = poss[atp + j * 64];
+            if constexpr (FOOT) {
+              if (sm == 0 && base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
+            }
             const int kt = min(64, K - base);
-            for (int l0 = 0; l0 < kt; l0 += 4) {
+            for (int l0 = 0; l0 < kt; l0 += kLanes) {
 #pragma unroll
-              for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+              for (int l = l0; l < l0 + kLanes; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
                 const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
                 const double rrl = crowd_lane_f64(rr, l);
-                const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
-                const double diff = fma(ex, ex, ey * ey) - rrl;
-                hits += (diff > 0.0) ? 0 : 1;
+                if constexpr (FOOT) {
+                  hits += crowd_body_touches(fp, qcx, qcy, ox, oy, rrl) ? 1 : 0;
+                } else {
+                  const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+                  const double diff = fma(ex, ex, ey * ey) - rrl;
+                  hits += (diff > 0.0) ? 0 : 1;
+                }
               }
             }
             if (nbase == 0) {  // the sample's last tile
               if constexpr (WALLS) {
                 if (sm == 0) {  // the step's walls, once: this problem's walls as this step sees them, against P -> Q
                   const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
-                  const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                  [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                  [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
+                  if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
                   float4 sg = sg0;
                   double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
                   whits = 0;
@@ -446,12 +615,16 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                     const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
                     load_wall_row(more ? j : j + NC, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);
                     const int wt = min(64, wcount - wbase);
-                    for (int l = 0; l < wt; ++l) {
-                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                      whits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                              crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                   ? 1 : 0;
+                    if constexpr (FOOT) {
+                      whits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt);
+                    } else {
+                      for (int l = 0; l < wt; ++l) {
+                        const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                        const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                        whits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                                crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                     ? 1 : 0;
+                      }
                     }
                     sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                   }
@@ -479,21 +652,30 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             double rr_nxt;
             load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
             const float2 pos = poss[atp + j * 64];
+            if constexpr (FOOT) {
+              if (base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
+            }
             const int kt = min(64, K - base);
-            for (int l0 = 0; l0 < kt; l0 += 4) {
+            for (int l0 = 0; l0 < kt; l0 += kLanes) {
 #pragma unroll
-              for (int l = l0; l < l0 + 4; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+              for (int l = l0; l < l0 + kLanes; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
                 const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
                 const double rrl = crowd_lane_f64(rr, l);
-                const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
-                const double diff = fma(ex, ex, ey * ey) - rrl;
-                hits += (diff > 0.0) ? 0 : 1;
+                if constexpr (FOOT) {
+                  hits += crowd_body_touches(fp, qcx, qcy, ox, oy, rrl) ? 1 : 0;
+                } else {
+                  const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+                  const double diff = fma(ex, ex, ey * ey) - rrl;
+                  hits += (diff > 0.0) ? 0 : 1;
+                }
               }
             }
             if (nj != j) {  // the step's last tile
               if constexpr (WALLS) {  // ... then the walls, against the step's segment P -> Q
                 const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
-                const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
+                if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
                 float4 sg = sg0;
                 double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
                 if constexpr (WTRK) {  // this problem's walls as this step sees them
@@ -503,12 +685,16 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                     const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
                     load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
                     const int wt = min(64, wcount - wbase);
-                    for (int l = 0; l < wt; ++l) {
-                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                      hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                             crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                  ? 1 : 0;
+                    if constexpr (FOOT) {
+                      hits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt);
+                    } else {
+                      for (int l = 0; l < wt; ++l) {
+                        const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                        const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                        hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                               crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                    ? 1 : 0;
+                      }
                     }
                     sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                   }
