@@ -318,6 +318,11 @@ CELLS_ROWS = [
     (cells(lin_bins=17, ang_bins=17), sampled(2)), (cells(lin_bins=32, ang_bins=32), sampled(2)),
     (cells(lin_bins=33, ang_bins=33), sampled(3)), (cells(lin_bins=64, ang_bins=64), sampled(3)),
     (cells(lin_bins=8, ang_bins=33), sampled(3)), (cells(lin_bins=17, ang_bins=2), sampled(2)),
+    # the solves tests/test_gpu_philox_exact.py::test_cell_word_sampler relies on: 5 and 12 bins on a padded map of 34 x 45
+    # cells, an odd M among them -- this route, the 16-bin form (the library has no text that names the route)
+    (cells(lin_bins=5, ang_bins=12, rows=34, cols=45, M=192), dict(route=SAMPLE, bins=1, cell_groups=34 * 12, grid_x=102)),
+    (cells(lin_bins=5, ang_bins=12, rows=34, cols=45, M=193), dict(route=SAMPLE, bins=1, cell_groups=34 * 12, grid_x=102)),
+    (cells(lin_bins=5, ang_bins=12, rows=34, cols=45, M=256), dict(route=SAMPLE, bins=1, cell_groups=34 * 12, grid_x=102)),
     # one sample: the 16-bit mirror where both grids are 7-bit; speed-map mode: 32-bit cells with the risk byte
     (staged(mode=DET, M=1), single(MIRROR16)),
     (staged(mode=TDM, M=1), single(MIRROR16)),
@@ -391,6 +396,11 @@ SAMPLE_ROWS = [
     ((PHILOX, 8, 260, 260, 1024, 16, 16), dict(kernel=COLUMNS, chunks=16, g_chunk=64, grid_y=16)),
     # a map larger than 256 Ki cell groups: one chunk
     ((PHILOX, 8, 1024, 1028, 10, 16, 16), dict(kernel=COLUMNS, cell_groups=1024 * 257, chunks=1, g_chunk=10, grid_x=1028, grid_y=1)),
+    # the chunked launches tests/test_gpu_philox_exact.py draws byte for byte: 16 chunks asked for, 6 samples each, so 11
+    # workgroups cover 65 samples and the last holds half a pair; and 750 chunks of 2
+    ((PHILOX, 8, 128, 512, 65, 16, 16), dict(kernel=COLUMNS, cell_groups=16384, chunks=16, g_chunk=6, grid_x=64, grid_y=11)),
+    ((PHILOX, 8, 16, 48, 1500, 16, 16), dict(kernel=COLUMNS, cell_groups=192, chunks=1366, g_chunk=2, grid_x=1, grid_y=750)),
+    ((PHILOX, 8, 5, 7, 65, 16, 16), dict(kernel=COLUMNS, cell_groups=10, chunks=65, g_chunk=2, grid_x=1, grid_y=33)),
     # beyond 64 bins: the generic kernel, a thread per (sample, cell group)
     ((PHILOX, 65, 70, 90, 256, 16, 16), dict(kernel=GENERIC, cell_groups=1610, grid_x=1610, grid_y=1, block=256, chunks=0)),
     ((PHILOX, 200, 70, 90, 3, 16, 16), dict(kernel=GENERIC, grid_x=19, grid_y=1)),
