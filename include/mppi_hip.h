@@ -429,6 +429,47 @@ int mppi_planner_set_footprint(mppi_planner* p, const float* discs, int count);
 /* discs (8, 3) float32: the first *count rows are the footprint held (*count = 0: none) */
 int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* count);
 
+/* MPPI_MODE_BAREBONE, a batched handle (B >= 2) in crowd mode: a body fleet -- fleet mode for
+ * robots that are not discs.  Every robot of the batch is the same body of n_discs discs (1 .. 8),
+ * discs (n_discs, 3) float32 with the rows and the rules of mppi_planner_set_footprint; count = B
+ * turns it on, count = 0 turns it off (as mppi_planner_set_fleet(p, 0, NULL) does, for either kind
+ * of fleet; the body goes with it).  Everything mppi_planner_set_fleet says about the refresh, the
+ * rows counted from "now", the static walls, parking, the Jacobi lag of the plans and graph replay
+ * holds.  What differs:
+ *   plans   the noise-free rollout with its heading kept: states s_0 .. s_T = (x, y, th) float32; a
+ *           parked robot stands at its start pose, heading included.
+ *   walls   body disc k of robot b has its centre c_j^k at state s_j as mppi_planner_set_footprint
+ *           forms it, to the bit, and sweeps the segment [c_j^k, c_{j+1}^k] in control interval j
+ *           (the chord for the arc, as for any footprint).  Reader a is given that segment as a wall
+ *           of half-width (float)((double)rho_k + (double)margin); margin finite, rho_k + margin >= 0.
+ *   reader  the reader's own body enters as for any wall: body disc i's chord against the wall
+ *           with the half-width h + rho_i, the sum in double.
+ *   hits    a step of a rollout hits robot b iff ANY body disc of the reader hits ANY wall of b:
+ *           one hit, obs_cost once, however many pairs touch.  The static walls behind the fleet
+ *           slots count one hit per wall, as with any footprint.
+ *   slots   reader a's set: (B - 1) * Fp fleet slots, Fp = n_discs rounded up to a power of two,
+ *           robot `other` (ascending, a skipped) disc k at other * Fp + k; the padding slots
+ *           k >= n_discs repeat the last disc.  Then the W static walls.  Work per (step, rollout):
+ *           n_discs * ((B - 1) * Fp + W) wall tests -- a body of 3, 5, 6 or 7 discs pays for its
+ *           padding.  The size limits of the fleet apply to this slot count.
+ * One body for the whole fleet (per-robot bodies are not provided).  The body is held as the handle's
+ * footprint: mppi_planner_get_footprint gives its rows, every launch is a footprint form with wall
+ * tracks, and mppi_planner_describe_last_rollout holds
+ * " walls=<(B-1)*Fp+W> wall_rows=<T> fleet=<B>" and ends in " footprint=<n_discs>".  The same
+ * arguments again are a no-op; a change drains the stream and drops the captured graphs.
+ * MPPI_ERR_INVALID, the handle keeping what it had: the refusals of mppi_planner_set_fleet (a map
+ * mode, B < 2, count not 0 / B, a sharded handle, no crowd mode, wall tracks held), a footprint held
+ * through mppi_planner_set_footprint, a disc fleet on (and mppi_planner_set_fleet with half-widths
+ * while a body fleet is on: the kinds change through "off"), bad rows or a bad margin.  While any
+ * fleet is on mppi_planner_set_footprint is refused; in a body fleet its clear as well. */
+int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const float* discs, int n_discs, double margin);
+/* *n_discs: the body discs of the body fleet that is on, else 0; *margin: its margin */
+int mppi_planner_get_fleet_bodies(mppi_planner* p, int* n_discs, double* margin);
+/* seg (B, B-1, F, T, 4) float32 -- ax ay bx by --: reader a's others in ascending order, body disc
+ * k of each, as the last refresh left them, the padding slots left out.  MPPI_ERR_STATE unless a
+ * body fleet is on; there mppi_planner_get_fleet_walls is refused (MPPI_ERR_INVALID). */
+int mppi_planner_get_fleet_body_walls(mppi_planner* p, float* seg);
+
 /* mppi.py:539-542 shift_optimal_control_sequence / mppi.py:305,375 copy_to_host */
 int mppi_planner_set_u(mppi_planner* p, const float* u);
 int mppi_planner_get_u(mppi_planner* p, float* u);

@@ -117,6 +117,9 @@ SIGNATURES = {
     "mppi_planner_get_fleet": [_vp, C.POINTER(C.c_int)],
     "mppi_planner_fleet_refresh": [_vp],
     "mppi_planner_get_fleet_walls": [_vp, _f32p],
+    "mppi_planner_set_fleet_bodies": [_vp, C.c_int, _f32p, C.c_int, C.c_double],
+    "mppi_planner_get_fleet_bodies": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    "mppi_planner_get_fleet_body_walls": [_vp, _f32p],
     "mppi_planner_set_footprint": [_vp, _f32p, C.c_int],
     "mppi_planner_get_footprint": [_vp, _f32p, C.POINTER(C.c_int)],
     "mppi_planner_set_u": [_vp, _f32p],

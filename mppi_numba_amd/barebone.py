@@ -74,10 +74,25 @@ body discs reach one, so a finer cover of the same body does not multiply the pe
 Tracks, wall tracks, per-problem sets and disc samples work as before; goal distance, goal test, freeze and terminal
 cost are measured at the reference point (x, y).  rectangle_footprint() covers a rectangle with discs on the body axis.
 Without the key the robot is the point it always was, to the bit.  Limits: one footprint for every problem of a batch
-(per-problem footprints are not provided); the footprint and the fleet exclude each other (the fleet's half-widths already
-contain the reader's body; a fleet of elongated robots is what comes after); a point of a turning body moves on an arc and
-its chord is what is tested -- the arc leaves the chord by at most |o| (1 - cos(dt w / 2)), 2.5 mm for |o| = 0.5 m at
-dt w = 0.2 rad.
+(per-problem footprints are not provided); params['footprint'] and set_fleet() exclude each other (the disc fleet's
+half-widths already contain the reader's body; a fleet of elongated robots is set_fleet_bodies(), below); a point of a
+turning body moves on an arc and its chord is what is tested -- the arc leaves the chord by at most
+|o| (1 - cos(dt w / 2)), 2.5 mm for |o| = 0.5 m at dt w = 0.2 rad.
+
+A fleet of bodies: MPPI_Batch.set_fleet_bodies(footprint, margin) is the fleet for robots that are not discs -- carts that
+pass each other lengthwise in a corridor their circumscribed discs would block.  Every robot of the batch has the body
+`footprint` (F, 3), rows as for params['footprint'].  The refresh is the fleet's, with the heading kept: the plan of b is
+its noise-free states s_0 .. s_T = (x, y, th); body disc k of b has its centre at body_discs(s_j)[k] and sweeps the segment
+from there to body_discs(s_{j+1})[k] in control interval j; reader a is given that segment as a wall of half-width
+float32(rho_k + margin), the sum in float64.  The reader's own body meets these walls as a footprint meets any wall (its
+discs' chords, rho_i added to the half-width), and a step hits robot b iff ANY body disc of the reader hits ANY wall of b:
+one hit, obs_penalty once, however many pairs touch.  params['wall_segments'] stay in force behind the fleet's walls, one
+hit per wall.  Discs, disc tracks, disc samples, goal tracks and the goal distance at the reference point are untouched.
+A reader's walls lie in (B - 1) * Fp slots, Fp = F rounded up to a power of two (the padding repeats the last disc), so a
+step of a rollout costs F * ((B - 1) * Fp + W) wall tests: a body of 3, 5, 6 or 7 discs pays for its padding.  Limits: one
+body for the whole fleet; the chord for the arc, as above; the plans are those of the previous control step (the Jacobi
+sweep of the disc fleet).  set_fleet_bodies carries its own body: it is refused while params hold 'footprint', and the two
+kinds of fleet change into each other through set_fleet(None).  fleet_body_walls() fetches the rows of the last refresh.
 """
 import copy
 import ctypes as C
@@ -307,6 +322,7 @@ class MPPI_Numba(object):
         self._own_goals = False       # MPPI_Batch: per-problem goal tracks are set (they win over params['goal_track'])
         self._goal_tracks = None      # the goal tracks held, whoever set them: (1 or B, L, 2) float32 (None: static goals)
         self._fleet = None            # MPPI_Batch.set_fleet: (radii (B,), margin, half-widths (B, B - 1)) (None: off)
+        self._fleet_bodies = None     # MPPI_Batch.set_fleet_bodies: (rows (F, 3), margin) (None: off)
         self._footprint_key = None    # the footprint of params['footprint'] the library holds (None: none)
         self.reset()
 
@@ -363,7 +379,7 @@ class MPPI_Numba(object):
         """params['wall_segments'] / ['wall_halfwidth']: handed over when they have changed, cleared when the keys have
         gone.  Without crowd mode the library refuses them (MppiError)."""
         if "wall_tracks" in p:
-            if self._fleet is not None:
+            if self._fleet is not None or self._fleet_bodies is not None:
                 raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
                                  "itself (set_fleet(None) first; 'wall_segments' stay in force beside it)")
             if "wall_segments" in p:
@@ -443,6 +459,9 @@ class MPPI_Numba(object):
         if self._fleet is not None:
             raise ValueError("params hold 'footprint' while the fleet is on: the fleet's half-widths already contain the "
                              "reader's body (set_fleet(None) first, or drop the key)")
+        if self._fleet_bodies is not None:
+            raise ValueError("params hold 'footprint' while the fleet of bodies is on: that fleet carries its own body "
+                             "(set_fleet(None) first, or drop the key)")
         fp = np.asarray(p['footprint'])
         key = (fp.dtype.str, fp.shape, fp.tobytes())
         if key == self._footprint_key:
@@ -453,7 +472,8 @@ class MPPI_Numba(object):
 
     @property
     def footprint(self):
-        """The footprint the library holds: (F, 3) float32, or None (the robot is its reference point)."""
+        """The footprint the library holds: (F, 3) float32, or None (the robot is its reference point).  While a fleet of
+        bodies is on: the rows of its body."""
         rows, count = np.zeros((MAX_FOOTPRINT_DISCS, 3), dtype=np.float32), C.c_int(0)
         _lib.call("mppi_planner_get_footprint", self._handle, _lib.ptr(rows, C.c_float), C.byref(count))
         return rows[:count.value].copy() if count.value else None
@@ -972,7 +992,7 @@ class MPPI_Batch(MPPI_Numba):
                 self._own_walls, self._wall_tracks_key = False, None
             self.wall_sets = None
             return
-        if self._fleet is not None:
+        if self._fleet is not None or self._fleet_bodies is not None:
             raise ValueError("set_wall_sets while the fleet is on: the fleet makes every problem's wall set itself "
                              "(set_fleet(None) first)")
         assert len(sets) == self.num_instances, "one wall set per problem"
@@ -1013,10 +1033,12 @@ class MPPI_Batch(MPPI_Numba):
         control step of closed_loop() starts by rebuilding, on the device, every robot's walls from the others' plans (the
         module header says which).  The half-width of reader a against b is float32(r_a + r_b + margin), summed in float64
         from the float32 radii.  Raises while per-problem wall sets or params['wall_tracks'] are held."""
-        if radii is None:
+        if radii is None:  # (either kind of fleet)
             _lib.call("mppi_planner_set_fleet", self._handle, 0, None)
-            self._fleet = None
+            self._fleet = self._fleet_bodies = None
             return
+        if self._fleet_bodies is not None:
+            raise ValueError("set_fleet while the fleet of bodies is on: the two kinds change through off (set_fleet(None) first)")
         B = self.num_instances
         r = np.ascontiguousarray(np.broadcast_to(_f32(radii), (B,)))
         if not (np.isfinite(r).all() and (r >= 0).all() and np.isfinite(margin)):
@@ -1040,9 +1062,55 @@ class MPPI_Batch(MPPI_Numba):
         """None while fleet mode is off, else (radii (B,) float32, margin)."""
         return None if self._fleet is None else (self._fleet[0].copy(), self._fleet[1])
 
+    def set_fleet_bodies(self, footprint, margin=0.0):
+        """A fleet of bodies (crowd mode, B >= 2): the fleet of set_fleet() for robots that are the discs of `footprint`
+        (F, 3), 1 <= F <= 8, rows (ox, oy, rho) as for params['footprint'] -- one body for every robot --, kept `margin`
+        apart; None turns it off.  The module header says what the refresh builds and how hits are counted.  It carries
+        its own body: raises while params hold 'footprint', while the disc fleet is on, and while per-problem wall sets
+        or params['wall_tracks'] are held."""
+        if footprint is None:
+            self.set_fleet(None)
+            return
+        rows = _footprint_rows(footprint)
+        margin = float(margin)
+        if not (np.isfinite(rows).all() and (rows[:, 2] >= 0).all() and np.isfinite(margin)
+                and (rows[:, 2].astype(np.float64) + margin >= 0).all()):
+            raise ValueError("a fleet's body has finite rows with rho >= 0, and a finite margin with rho + margin >= 0")
+        if self._fleet is not None:
+            raise ValueError("set_fleet_bodies while the disc fleet is on: the two kinds change through off (set_fleet(None) first)")
+        if self.params is not None and "footprint" in self.params:
+            raise ValueError("set_fleet_bodies while params hold 'footprint': the fleet of bodies carries its own body "
+                             "(drop the key first)")
+        if self._footprint_key is not None:  # (the key has gone and the library has not heard yet)
+            self._hand_over_footprint(self.params if self.params is not None else {})
+        if self._own_walls or self._wall_tracks_key is not None:
+            raise ValueError("set_fleet_bodies while per-problem wall sets or params['wall_tracks'] are held: the fleet makes "
+                             "every problem's wall set itself (set_wall_sets(None) / drop the key first)")
+        _lib.call("mppi_planner_set_fleet_bodies", self._handle, self.num_instances, _lib.ptr(rows, C.c_float), len(rows),
+                  C.c_double(margin))
+        self._fleet_bodies = (rows.copy(), margin)
+
+    @property
+    def fleet_bodies(self):
+        """None while no fleet of bodies is on, else (rows (F, 3) float32, margin)."""
+        return None if self._fleet_bodies is None else (self._fleet_bodies[0].copy(), self._fleet_bodies[1])
+
+    def fleet_body_walls(self):
+        """What the last refresh of a fleet of bodies left: (segments (B, B - 1, F, T, 2, 2) float32, half-widths (F,)
+        float32, others (B, B - 1) int) -- segments[a, o, k, j] is the segment body disc k of robot others[a, o] covers
+        in control interval j from "now", halfwidths[k] = float32(rho_k + margin) the half-width every reader is given it
+        with.  The padding slots are left out."""
+        if self._fleet_bodies is None:
+            raise ValueError("fleet_body_walls: no fleet of bodies is on (set_fleet_bodies)")
+        B, t = self.num_instances, self.num_steps
+        rows, margin = self._fleet_bodies
+        seg = np.empty((B, B - 1, len(rows), t, 2, 2), dtype=np.float32)
+        _lib.call("mppi_planner_get_fleet_body_walls", self._handle, _lib.ptr(seg, C.c_float))
+        return seg, (rows[:, 2].astype(np.float64) + np.float64(margin)).astype(np.float32), fleet_others(B)
+
     def refresh_fleet(self):
         """The refresh alone, as solve() makes it at its head: every robot's walls from the others' current controls and
-        start states.  For drawing and for tests; fleet_walls() fetches the result."""
+        start states.  For drawing and for tests; fleet_walls() / fleet_body_walls() fetch the result."""
         self.move_mppi_task_vars_to_device()
         _lib.call("mppi_planner_fleet_refresh", self._handle)
 
@@ -1050,6 +1118,8 @@ class MPPI_Batch(MPPI_Numba):
         """What the last refresh left: (segments (B, B - 1, T, 2, 2) float32, half-widths (B, B - 1) float32, others
         (B, B - 1) int) -- segments[a, k, j] is the segment robot others[a, k] covers in control interval j from "now",
         as reader a is given it."""
+        if self._fleet_bodies is not None:
+            raise ValueError("fleet_walls: a fleet of bodies is on, whose walls have one more axis (fleet_body_walls)")
         if self._fleet is None:
             raise ValueError("fleet_walls: the fleet is off (set_fleet)")
         B, t = self.num_instances, self.num_steps

@@ -373,13 +373,18 @@ struct FleetArrays {
   float* hw = nullptr;
   int2* range = nullptr;
   float2* plan = nullptr;
+  float* heads = nullptr;      // a body fleet: [B][T + 1] headings ...
+  float2* centres = nullptr;   // ... and [B][T + 1][body] body disc centres
   int slots = 0;
+  int group = 1, body = 0;     // slots per other robot; body discs per robot (0: a disc fleet)
 };
 
-// pair_hw: [B][B - 1] half-widths, reader a's others in ascending order; the static walls (W of them) behind the B - 1
-// others in every reader's slots and in every row.  Until the first refresh a fleet slot holds the wall nobody can touch.
-static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_seg, const float* wall_hw, int W, FleetArrays* out) {
-  const int B = p->B, T = p->cfg.num_steps, S = B - 1 + W;
+// pair_hw: [B][(B - 1) * group] half-widths, reader a's others in ascending order, `group` slots each (a disc fleet: 1; a
+// body fleet of `body` discs: that count rounded up to a power of two); the static walls (W of them) behind the others'
+// slots in every reader's range and in every row.  Until the first refresh a fleet slot holds the wall nobody can touch.
+static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_seg, const float* wall_hw, int W, int group, int body,
+                       FleetArrays* out) {
+  const int B = p->B, T = p->cfg.num_steps, O = (B - 1) * group, S = O + W;
   const size_t pitch = (size_t)B * (size_t)S;
   REQUIRE((long)pitch <= (1L << 24) && (long)pitch * (long)T <= (1L << 28), MPPI_ERR_INVALID,
           "fleet of %d with %d static walls and %d steps: too many wall rows (%zu walls x %d)", B, W, T, pitch, T);
@@ -389,23 +394,32 @@ static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_
   for (int a = 0; a < B; ++a) {
     range[(size_t)a] = make_int2(a * S, S);
     for (int k = 0; k < S; ++k) {
-      const bool other = k < B - 1;
-      hw[(size_t)a * S + k] = other ? pair_hw[(size_t)a * (B - 1) + k] : wall_hw[k - (B - 1)];
-      const float* w = other ? nullptr : wall_seg + 4 * (size_t)(k - (B - 1));
+      const bool other = k < O;
+      hw[(size_t)a * S + k] = other ? pair_hw[(size_t)a * O + k] : wall_hw[k - O];
+      const float* w = other ? nullptr : wall_seg + 4 * (size_t)(k - O);
       const float4 sg = other ? make_float4(1e18f, 1e18f, 1e18f, 1e18f) : make_float4(w[0], w[1], w[2], w[3]);
       for (int j = 0; j < T; ++j) rows[(size_t)j * pitch + (size_t)a * S + k] = sg;
     }
   }
   FleetArrays f;
   f.slots = S;
+  f.group = group;
+  f.body = body;
+  const size_t states = (size_t)B * (size_t)(T + 1);
   TRY(staged([&]() -> int {
     TRY(dev_stage(&f.seg_rows, rows.data(), rows.size()));
     TRY(dev_stage(&f.hw, hw.data(), hw.size()));
     TRY(dev_stage(&f.range, range.data(), range.size()));
     TRY(dev_alloc(&f.plan, (size_t)B * (size_t)(T + 1)));
-    HIP_TRY(hipMemset(f.plan, 0, sizeof(float2) * (size_t)B * (size_t)(T + 1)));
+    HIP_TRY(hipMemset(f.plan, 0, sizeof(float2) * states));
+    if (body > 0) {
+      TRY(dev_alloc(&f.heads, states));
+      TRY(dev_alloc(&f.centres, states * (size_t)body));
+      HIP_TRY(hipMemset(f.heads, 0, sizeof(float) * states));
+      HIP_TRY(hipMemset(f.centres, 0, sizeof(float2) * states * (size_t)body));
+    }
     return MPPI_OK;
-  }, f.seg_rows, f.hw, f.range, f.plan));
+  }, f.seg_rows, f.hw, f.range, f.plan, f.heads, f.centres));
   *out = f;
   return MPPI_OK;
 }
@@ -416,7 +430,11 @@ static void fleet_commit(mppi_planner* p, const FleetArrays& f) {
   dev_take(p->fleet_hw, f.hw);
   dev_take(p->fleet_range, f.range);
   dev_take(p->fleet_plan, f.plan);
+  dev_take(p->fleet_heads, f.heads);
+  dev_take(p->fleet_centres, f.centres);
   p->fleet_slots = f.slots;
+  p->fleet_group = f.group;
+  p->fleet_body = f.body;
   p->fleet_on = f.seg_rows != nullptr;
   p->fleet_gen = p->fleet_on ? next_generation() : 0;
 }
@@ -446,7 +464,7 @@ extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, co
   TRY(staged([&]() -> int {
     if (count > 0) TRY(dev_stage(&seg, segments, (size_t)count));
     if (count > 0) TRY(dev_stage(&hw, halfwidths, (size_t)count));
-    if (p->fleet_on) TRY(fleet_build(p, p->fleet_hw_host.data(), segments, halfwidths, count, &fleet));
+    if (p->fleet_on) TRY(fleet_build(p, p->fleet_hw_host.data(), segments, halfwidths, count, p->fleet_group, p->fleet_body, &fleet));
     return MPPI_OK;
   }, seg, hw));
   if (p->fleet_on) fleet_commit(p, fleet);
@@ -555,6 +573,11 @@ extern "C" int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows
   return MPPI_OK;
 }
 
+// The two kinds of fleet go through "off": one message for both directions.
+static const char* const kFleetKinds =
+    "the handle is in a fleet of the other kind (mppi_planner_set_fleet: discs with half-widths per pair; "
+    "mppi_planner_set_fleet_bodies: one body of discs for every robot): turn it off first (mppi_planner_set_fleet(p, 0, NULL))";
+
 // Fleet mode (include/mppi_hip.h): the storage is built here and whenever the static walls change, never at a refresh.
 extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* halfwidths) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
@@ -563,6 +586,12 @@ extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* h
     if (!p->fleet_on) return MPPI_OK;
     HIP_TRY(hipSetDevice(p->cfg.device));
     HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->fleet_body > 0) {  // (a body fleet holds its body as the handle's footprint: it goes with the fleet)
+      memset(p->fp_host, 0, sizeof(p->fp_host));
+      p->fp_count = 0;
+      p->fp_gen = 0;
+      p->fleet_margin = 0.0;
+    }
     fleet_commit(p, FleetArrays());
     p->fleet_hw_host.clear();
     drop_graphs(p);  // (the arrays and the kernel form are arguments of the captured launches)
@@ -577,6 +606,7 @@ extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* h
   REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
           "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
           "first (mppi_planner_set_wall_tracks with count 0)");
+  REQUIRE(!(p->fleet_on && p->fleet_body > 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
   REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
           "the handle holds a footprint; the fleet's half-widths already contain the reader's body: clear it first "
           "(mppi_planner_set_footprint(p, NULL, 0))");
@@ -587,10 +617,83 @@ extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* h
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   FleetArrays fleet;
-  TRY(fleet_build(p, halfwidths, p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, &fleet));
+  TRY(fleet_build(p, halfwidths, p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, 1, 0, &fleet));
   fleet_commit(p, fleet);
   p->fleet_hw_host.assign(halfwidths, halfwidths + pairs);
   drop_graphs(p);
+  return MPPI_OK;
+}
+
+// n footprint rows (ox, oy, rho): all finite, no negative radius.
+static int check_footprint_rows(const float* discs, int n) {
+  for (int i = 0; i < n; ++i) {
+    REQUIRE(std::isfinite(discs[3 * i]) && std::isfinite(discs[3 * i + 1]) && std::isfinite(discs[3 * i + 2]), MPPI_ERR_INVALID,
+            "footprint disc %d: a value is not finite", i);
+    REQUIRE(discs[3 * i + 2] >= 0.0f, MPPI_ERR_INVALID, "footprint disc %d: radius %g is negative", i, (double)discs[3 * i + 2]);
+  }
+  return MPPI_OK;
+}
+
+// A body fleet (include/mppi_hip.h): the fleet of robots that are n_discs discs each.  The storage as in the disc fleet,
+// with Fp slots a robot; the body is held as the handle's footprint as well, so barebone_choose sees fleet_on with
+// footprint = n_discs and picks the footprint form with wall tracks.
+extern "C" int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const float* discs, int n_discs, double margin) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  if (count == 0) return mppi_planner_set_fleet(p, 0, nullptr);
+  REQUIRE(p->B >= 2, MPPI_ERR_INVALID,
+          "fleet mode needs a batched handle of at least two problems, one per robot (num_instances %d)", p->B);
+  REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 (off) or num_instances %d", count, p->B);
+  REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "fleet mode drives an unsharded handle");
+  REQUIRE(p->crowd, MPPI_ERR_INVALID,
+          "fleet mode needs crowd mode: only the crowd kernel tests walls (mppi_planner_set_crowd(p, 1) first)");
+  REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+          "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
+          "first (mppi_planner_set_wall_tracks with count 0)");
+  REQUIRE(!(p->fleet_on && p->fleet_body == 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
+  REQUIRE(p->fleet_body > 0 || p->fp_count == 0, MPPI_ERR_INVALID,
+          "the handle holds a footprint; a body fleet carries its own body: clear it first (mppi_planner_set_footprint(p, NULL, 0))");
+  REQUIRE(n_discs >= 1 && n_discs <= kCrowdFootprintMax, MPPI_ERR_INVALID, "body of %d discs: must be 1 to %d", n_discs, kCrowdFootprintMax);
+  REQUIRE(discs, MPPI_ERR_INVALID, "NULL discs");
+  TRY(check_footprint_rows(discs, n_discs));
+  REQUIRE(std::isfinite(margin), MPPI_ERR_INVALID, "margin %g is not finite", margin);
+  for (int k = 0; k < n_discs; ++k)
+    REQUIRE((double)discs[3 * k + 2] + margin >= 0.0, MPPI_ERR_INVALID,
+            "body disc %d: radius %g and margin %g give a negative half-width", k, (double)discs[3 * k + 2], margin);
+  if (p->fleet_on && p->fleet_body == n_discs && margin == p->fleet_margin &&
+      memcmp(discs, p->fp_host, sizeof(float) * 3 * (size_t)n_discs) == 0)
+    return MPPI_OK;
+  int group = 1;
+  while (group < n_discs) group *= 2;
+  // every reader sees the same body: slot k of every other robot has half-width float32(rho_k + margin), the sum in
+  // double; the padding slots repeat the last disc
+  const size_t per = (size_t)(p->B - 1) * (size_t)group;
+  std::vector<float> hw((size_t)p->B * per);
+  for (size_t i = 0; i < hw.size(); ++i) {
+    const int k = std::min((int)(i % (size_t)group), n_discs - 1);
+    hw[i] = (float)((double)discs[3 * k + 2] + margin);
+  }
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  FleetArrays fleet;
+  TRY(fleet_build(p, hw.data(), p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, group, n_discs, &fleet));
+  fleet_commit(p, fleet);
+  p->fleet_hw_host = hw;
+  p->fleet_margin = margin;
+  memset(p->fp_host, 0, sizeof(p->fp_host));
+  memcpy(p->fp_host, discs, sizeof(float) * 3 * (size_t)n_discs);
+  p->fp_count = n_discs;
+  p->fp_gen = next_generation();
+  drop_graphs(p);  // (the arrays, the rows, the counts and the kernel form are arguments of the captured launches)
+  return MPPI_OK;
+}
+
+// *n_discs: the body discs of the body fleet that is on, else 0; *margin: its margin
+extern "C" int mppi_planner_get_fleet_bodies(mppi_planner* p, int* n_discs, double* margin) {
+  REQUIRE(p && n_discs && margin, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  *n_discs = p->fleet_on ? p->fleet_body : 0;
+  *margin = p->fleet_on ? p->fleet_margin : 0.0;
   return MPPI_OK;
 }
 
@@ -609,6 +712,8 @@ extern "C" int mppi_planner_set_footprint(mppi_planner* p, const float* discs, i
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
   REQUIRE(count >= 0 && count <= kCrowdFootprintMax, MPPI_ERR_INVALID, "footprint of %d discs: must be 0 (none) to %d", count, kCrowdFootprintMax);
+  REQUIRE(!(p->fleet_on && p->fleet_body > 0), MPPI_ERR_INVALID,
+          "the handle is in a body fleet, which carries its own body: turn the fleet off first (mppi_planner_set_fleet(p, 0, NULL))");
   if (count > 0) {
     REQUIRE(discs, MPPI_ERR_INVALID, "NULL discs");
     REQUIRE(p->crowd, MPPI_ERR_INVALID,
@@ -616,11 +721,7 @@ extern "C" int mppi_planner_set_footprint(mppi_planner* p, const float* discs, i
     REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
             "the handle is in fleet mode, whose half-widths already contain the reader's body: turn it off first "
             "(mppi_planner_set_fleet(p, 0, NULL))");
-    for (int i = 0; i < count; ++i) {
-      REQUIRE(std::isfinite(discs[3 * i]) && std::isfinite(discs[3 * i + 1]) && std::isfinite(discs[3 * i + 2]), MPPI_ERR_INVALID,
-              "footprint disc %d: a value is not finite", i);
-      REQUIRE(discs[3 * i + 2] >= 0.0f, MPPI_ERR_INVALID, "footprint disc %d: radius %g is negative", i, (double)discs[3 * i + 2]);
-    }
+    TRY(check_footprint_rows(discs, count));
   }
   if (count == p->fp_count && (count == 0 || memcmp(discs, p->fp_host, sizeof(float) * 3 * (size_t)count) == 0)) return MPPI_OK;
   HIP_TRY(hipSetDevice(p->cfg.device));
@@ -676,11 +777,23 @@ static int fleet_refresh(mppi_planner* p, const int* done) {
   const int B = p->B, T = p->cfg.num_steps;
   REQUIRE((size_t)T * sizeof(double2) <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large", T);  // (as launch_rollout)
   const size_t lds = fleet_plans_lds_bytes(T);  // (28 bytes a step: 112 KiB at the 4096 steps the line above admits)
-  auto plans = p->cfg.math == MPPI_MATH_EXACT ? &k_fleet_plans<true> : &k_fleet_plans<false>;
+  const bool exact = p->cfg.math == MPPI_MATH_EXACT, body = p->fleet_body > 0;
+  auto plans = body ? (exact ? &k_fleet_plans<true, true> : &k_fleet_plans<false, true>)
+                    : (exact ? &k_fleet_plans<true, false> : &k_fleet_plans<false, false>);
   if (lds > 64 * 1024)  // (a horizon of more than ~2300 steps)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(plans), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, p->fleet_plan);
+  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, p->fleet_plan, body ? p->fleet_heads : nullptr);
   HIP_TRY(hipGetLastError());
+  if (body) {  // the body discs' centres once per (robot, state), then the scatter into every reader's slots
+    const int states = B * (T + 1), F = p->fleet_body, Fp = p->fleet_group;
+    hipLaunchKernelGGL(k_fleet_body_centres, dim3(ceil_div(states, 256)), dim3(256), 0, p->stream, p->fleet_plan, p->fleet_heads,
+                       p->fleet_centres, states, footprint_arg(p));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fleet_body_walls, dim3(ceil_div((long)B * (B - 1) * Fp, 256), T), dim3(256), 0, p->stream, p->fleet_centres,
+                       p->fleet_seg_rows, B, T, p->fleet_slots, F, Fp);
+    HIP_TRY(hipGetLastError());
+    return MPPI_OK;
+  }
   hipLaunchKernelGGL(k_fleet_walls, dim3(ceil_div((long)B * (B - 1), 256), T), dim3(256), 0, p->stream, p->fleet_plan,
                      p->fleet_seg_rows, B, T, p->fleet_slots);
   HIP_TRY(hipGetLastError());

@@ -124,6 +124,9 @@ static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
 static CrowdFootprint footprint_arg(const mppi_planner* p) {
   CrowdFootprint fp{};
   fp.count = p->fp_count;
+  const bool bodies = p->fleet_on && p->fleet_body > 0;  // a body fleet: the others' slots count once per robot
+  fp.group = bodies ? p->fleet_group : 1;
+  fp.grouped = bodies ? (p->B - 1) * p->fleet_group : 0;
   for (int i = 0; i < p->fp_count; ++i) {  // (the float32 rows widened here: exact, and the kernel's scalar operands as they are)
     fp.ox[i] = (double)p->fp_host[3 * i];
     fp.oy[i] = (double)p->fp_host[3 * i + 1];

@@ -30,6 +30,13 @@
 // [B][T + 1] scratch (B * (T + 1) * 8 bytes: cache resident).  Two launches rather than one: the scatter needs every
 // robot's plan, and a single launch would either store 16 bytes at a stride of a whole reader (one robot per workgroup)
 // or need a wait between workgroups.
+//
+// A FLEET OF BODIES (mppi_planner_set_fleet_bodies): every robot is the same F discs attached to its pose, and reader a is
+// given, for every other robot b and body disc k, the segment the disc's centre covers in control interval j.
+// k_fleet_plans<., true> stores the T + 1 headings it walks anyway beside the positions; k_fleet_body_centres forms the
+// centres once per (robot, state) -- B * (T + 1) sine / cosine pairs, never one per reader -- in crowd_body_centres'
+// arithmetic; k_fleet_body_walls scatters them into the CrowdWallTracks layout, Fp slots a robot (F rounded up to a power of
+// two, the padding slots repeating the last disc).  Three plain launches; the disc fleet's two are what they were.
 #pragma once
 #include "rollout_crowd_kernel.h"
 
@@ -42,9 +49,11 @@ __host__ __device__ constexpr size_t fleet_plans_lds_bytes(int T) {
 
 constexpr int kFleetBatch = 8;  // steps whose operands lanes 0 and 1 load ahead of the dependent walk
 
-template <bool EXACT>
+// HEADS (a body fleet): the T + 1 float32 headings of the plan, the final one included, to heads[b][0 .. T] -- the
+// heading before step t is what lane t of its block of 64 holds anyway.  Without it nothing is stored there.
+template <bool EXACT, bool HEADS = false>
 __global__ __launch_bounds__(64) void k_fleet_plans(DevParams P, const float2* __restrict__ u, const int* __restrict__ done,
-                                                    float2* __restrict__ plans) {
+                                                    float2* __restrict__ plans, float* __restrict__ heads = nullptr) {
   extern __shared__ double2 fleet_trig[];
   const int b = (int)blockIdx.x, lane = (int)threadIdx.x, T = P.n_steps;
   const int Tp = (T + 63) & ~63;
@@ -52,6 +61,8 @@ __global__ __launch_bounds__(64) void k_fleet_plans(DevParams P, const float2* _
   float2* out = plans + (size_t)b * (size_t)(T + 1);
   if (done != nullptr && done[b] != 0) {  // (uniform over the workgroup) parked: it stands where it arrived
     for (int t = lane; t <= T; t += 64) out[t] = make_float2(P.x0, P.y0);
+    if constexpr (HEADS)  // ... as it stood: its start state holds the float32 of its final heading
+      for (int t = lane; t <= T; t += 64) heads[(size_t)b * (size_t)(T + 1) + t] = P.th0;
     return;
   }
   float* dtvs = reinterpret_cast<float*>(fleet_trig + Tp);
@@ -83,7 +94,11 @@ __global__ __launch_bounds__(64) void k_fleet_plans(DevParams P, const float2* _
       fleet_trig[t] = make_double2((double)sn, (double)cs);  // (exact both ways)
     }
     dtvs[t] = dtv;
+    if constexpr (HEADS)
+      if (t < T) heads[(size_t)b * (size_t)(T + 1) + t] = mine;
   }
+  if constexpr (HEADS)  // (steps past the horizon added 0: th is the heading after step T - 1)
+    if (lane == 0) heads[(size_t)b * (size_t)(T + 1) + T] = th;
   __syncthreads();
   if (lane < 2) {  // lane 0: x with the cosines, lane 1: y with the sines
     const double* tr = reinterpret_cast<const double*>(fleet_trig) + (1 - lane);
@@ -124,6 +139,43 @@ __global__ __launch_bounds__(256) void k_fleet_walls(const float2* __restrict__ 
   const int b = slot + (slot >= a ? 1 : 0);  // the others in ascending order, skipping the reader
   const float2* c = plans + (size_t)b * (size_t)(T + 1) + j;
   const float2 c0 = c[0], c1 = c[1];
+  seg[(size_t)j * ((size_t)B * (size_t)slots) + (size_t)a * (size_t)slots + (size_t)slot] = make_float4(c0.x, c0.y, c1.x, c1.y);
+}
+
+// ---- a body fleet (mppi_planner_set_fleet_bodies): every robot is F discs attached to its pose -------------------------
+// k_fleet_body_centres: one thread per (robot, state) -- B * (T + 1) sine / cosine pairs, never one per reader.  The centres
+// of the F body discs at state j of robot b's plan, in crowd_body_centres' arithmetic (the full sincos_f64<false> of the
+// float32 heading whatever the math mode is, products and sums in double in its order, one rounding): the bits the crowd
+// kernel forms for a rollout in that state.  centres: [B][T + 1][F] float2.  The rows come by value (CrowdFootprint).
+__global__ __launch_bounds__(256) void k_fleet_body_centres(const float2* __restrict__ plans, const float* __restrict__ heads,
+                                                            float2* __restrict__ centres, int states, CrowdFootprint fp) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;  // robot * (T + 1) + state
+  if (i >= states) return;
+  const float2 c = plans[i];
+  float cx[kCrowdFootprintMax], cy[kCrowdFootprintMax];
+  double sn, cs;
+  crowd_body_centres(fp, c.x, c.y, heads[i], cx, cy, sn, cs);
+  float2* out = centres + (size_t)i * (size_t)fp.count;
+#pragma unroll
+  for (int k = 0; k < kCrowdFootprintMax; ++k)
+    if (k < fp.count) out[k] = make_float2(cx[k], cy[k]);
+}
+
+// k_fleet_body_walls: one thread per (row, reader, slot), numbered like k_fleet_walls' so that a row's stores stay
+// contiguous.  A reader's fleet slots: (B - 1) * Fp, the other robot `o` (ascending, the reader skipped) at o * Fp, its
+// body disc k at o * Fp + k; Fp is F rounded up to a power of two, and the padding slots F <= k < Fp repeat disc F - 1
+// (a duplicate cannot change the OR over a robot's slots).  grid (ceil(B * (B - 1) * Fp / 256), T), block 256.
+__global__ __launch_bounds__(256) void k_fleet_body_walls(const float2* __restrict__ centres, float4* __restrict__ seg, int B, int T,
+                                                          int slots, int F, int Fp) {
+  const int j = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;  // reader * (B - 1) * Fp + slot
+  const int per = (B - 1) * Fp;
+  if (i >= B * per || j >= T) return;
+  const int a = i / per, slot = i - a * per;
+  const int o = slot / Fp, k = min(slot - o * Fp, F - 1);
+  const int b = o + (o >= a ? 1 : 0);
+  const float2* c = centres + ((size_t)b * (size_t)(T + 1) + (size_t)j) * (size_t)F + k;
+  const float2 c0 = c[0], c1 = c[F];
   seg[(size_t)j * ((size_t)B * (size_t)slots) + (size_t)a * (size_t)slots + (size_t)slot] = make_float4(c0.x, c0.y, c1.x, c1.y);
 }
 

@@ -283,7 +283,17 @@ struct mppi_planner {
   float2* fleet_plan = nullptr;
   int fleet_slots = 0;
   uint64_t fleet_gen = 0;
-  std::vector<float> fleet_hw_host;  // what was handed over: [B][B - 1]
+  std::vector<float> fleet_hw_host;  // what was handed over: [B][B - 1]; a body fleet: what was made of it, [B][(B - 1) * Fp]
+  // a body fleet (mppi_planner_set_fleet_bodies): every robot is the same fleet_body discs (0: a disc fleet, or none), and
+  // reader a's fleet slots are the others' body discs, fleet_group = Fp slots a robot (the count rounded up to a power of
+  // two; the padding slots repeat the last disc) -- (B - 1) * Fp slots, then the static walls.  The rows are held in
+  // fp_host / fp_count as well, so that every launch is a footprint form with wall tracks (the reader's own body), which
+  // counts a robot once (CrowdFootprint::group, grouped).  fleet_heads: [B][T + 1] headings beside fleet_plan;
+  // fleet_centres: [B][T + 1][fleet_body] body disc centres (fleet_kernels.h)
+  int fleet_body = 0, fleet_group = 1;
+  double fleet_margin = 0.0;
+  float* fleet_heads = nullptr;
+  float2* fleet_centres = nullptr;
   // a goal that moves (mppi_planner_set_goal_tracks): gtrk_rows positions per track, [track][row]; one track for every
   // problem (gtrk_count == 1) or one per problem (gtrk_count == B).  While gtrk_on the rollouts measure the state after step
   // t against row min(track_off + t + 1, gtrk_rows - 1) and params.xgoal / BatchInst::xg, yg rest; the default family

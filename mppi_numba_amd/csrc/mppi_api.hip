@@ -521,6 +521,8 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->fleet_hw);
   dev_free(p->fleet_range);
   dev_free(p->fleet_plan);
+  dev_free(p->fleet_heads);
+  dev_free(p->fleet_centres);
   dev_free(p->gtrk_xy);
   dev_free(p->state_rollout);
   dev_free(p->slabs);
@@ -817,6 +819,8 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
 extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {
   REQUIRE(p && seg, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
+  REQUIRE(p->fleet_body == 0, MPPI_ERR_INVALID,
+          "the handle is in a body fleet, whose walls have one more axis: mppi_planner_get_fleet_body_walls gives them");
   const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)p->fleet_slots, pitch = B * S;
   std::vector<float4> rows(pitch * T);
   TRY(copy_out(p, rows.data(), p->fleet_seg_rows, sizeof(float4) * rows.size()));
@@ -824,6 +828,23 @@ extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {
     for (size_t k = 0; k + 1 < B; ++k)
       for (size_t j = 0; j < T; ++j)
         memcpy(seg + 4 * ((a * (B - 1) + k) * T + j), &rows[j * pitch + a * S + k], sizeof(float4));
+  return MPPI_OK;
+}
+
+// seg: [B][B - 1][F][T][4] -- reader a's others in ascending order, body disc k of each, row j the segment its centre
+// covers in control interval j; the padding slots are left out
+extern "C" int mppi_planner_get_fleet_body_walls(mppi_planner* p, float* seg) {
+  REQUIRE(p && seg, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->fleet_on && p->fleet_body > 0, MPPI_ERR_STATE, "the handle is not in a body fleet (mppi_planner_set_fleet_bodies)");
+  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)p->fleet_slots, pitch = B * S;
+  const size_t F = (size_t)p->fleet_body, Fp = (size_t)p->fleet_group;
+  std::vector<float4> rows(pitch * T);
+  TRY(copy_out(p, rows.data(), p->fleet_seg_rows, sizeof(float4) * rows.size()));
+  for (size_t a = 0; a < B; ++a)
+    for (size_t o = 0; o + 1 < B; ++o)
+      for (size_t k = 0; k < F; ++k)
+        for (size_t j = 0; j < T; ++j)
+          memcpy(seg + 4 * ((((a * (B - 1) + o) * F) + k) * T + j), &rows[j * pitch + a * S + o * Fp + k], sizeof(float4));
   return MPPI_OK;
 }
 

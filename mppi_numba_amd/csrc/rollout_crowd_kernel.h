@@ -102,14 +102,23 @@
 //          (the second sincos_f64 of a step), one bit per wall OR-ed over the body.  One hit per obstacle, however many body
 //          discs reach it.  (An offset point of a turning body moves on an arc; the chord is what is tested: the arc
 //          leaves it by at most |o| * (1 - cos(dt * w / 2)).)  The compiler's report, gfx950, scratch bytes a lane: the 24
-//          forms without walls 0 .. 36 (the forms without a footprint and without walls: 0 .. 132), the 24 with walls
-//          232 .. 344 (theirs: 88 .. 248) -- one wall test and what the other waves keep do not fit 128 registers
-//          together in either; zero was not reached.
+//          forms without walls 0 .. 40 (the forms without a footprint and without walls: 0 .. 132), the 24 with walls
+//          248 .. 348 (theirs: 88 .. 248; before the grouped count below: 0 .. 36 and 232 .. 344) -- one wall test and
+//          what the other waves keep do not fit 128 registers together in either; zero was not reached.
 //   cost   the cost wave, the tail and the CVaR tail do not know; the goal distance is the reference point's.
 // Without the argument the kernel is what it was.
+//
+// A FLEET OF BODIES (mppi_planner_set_fleet_bodies; fleet_kernels.h): a footprint form with fleet wall tracks in which the
+// first `grouped` walls of every problem's set are the other robots' body discs, `group` slots a robot -- a power of two, so
+// a robot's slots never straddle a tile of 64.  A robot is hit iff ANY body disc of the reader hits ANY of its slots, and
+// that is ONE hit: crowd_body_wall_hits folds the tile's hit mask group by group (crowd_fold.h: log2(group) shift-ORs and a
+// leader mask below g = clamp(grouped - wbase, 0, 64), a population count of the rest).  Two integers by value in
+// CrowdFootprint -- wave-uniform; group = 1, grouped = 0 is the plain population count.  The forms without a CrowdFootprint
+// hold the empty CrowdFootprintRows and compile to what they compiled to (compared in the gfx950 assembly, all 96).
 #pragma once
 #include <type_traits>
 
+#include "crowd_fold.h"
 #include "rollout_kernels.h"
 
 namespace mppi {
@@ -163,10 +172,18 @@ struct CrowdSamples {
 };
 
 // The body footprint of a launch: `count` discs (ox, oy, rho) in the robot frame, x along the heading, y to the left.
+// A body fleet (mppi_planner_set_fleet_bodies): the first `grouped` walls of every problem's set are the other robots' body
+// discs, `group` slots a robot (1, 2, 4 or 8); a robot is hit once, however many of its slots are (crowd_fold.h).  Else
+// group = 1, grouped = 0: every wall counts for itself.
+// (The rows are a struct of their own: a form without a footprint holds an empty CrowdFootprintRows where it always did,
+// and compiles to the code it compiled to before the two integers were there.)
 constexpr int kCrowdFootprintMax = 8;
-struct CrowdFootprint {
+struct CrowdFootprintRows {
   double ox[kCrowdFootprintMax], oy[kCrowdFootprintMax], rho[kCrowdFootprintMax];  // (the float32 rows, widened on the host)
   int count;
+};
+struct CrowdFootprint : CrowdFootprintRows {
+  int group, grouped;
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -244,9 +261,11 @@ __device__ __forceinline__ bool crowd_body_touches(const CrowdFootprint& fp, con
 // the discs is a run-time loop around ONE copy of the wall test, so nothing here may live in a register array: the rows
 // come from LDS (rows: [3][8] double, ox | oy | rho -- uniform reads) and both centres are formed on the spot from the
 // two states and their sines and cosines, in crowd_body_centres' arithmetic: the same bits.
+// wbase: the tile's first wall within the problem's set; the walls below `grouped` count once per aligned group of `group`
+// (a body fleet: the slots of one other robot), the rest one each (crowd_fold_count; wave-uniform integers).
 __device__ __forceinline__ int crowd_body_wall_hits(const double* rows, int count, float px, float py, double sp, double cp,
                                                     float qx, float qy, double sq, double cq, const float4& sg, double dx,
-                                                    double dy, double LLd, double h, int wt) {
+                                                    double dy, double LLd, double h, int wt, int wbase, int group, int grouped) {
   unsigned long long mask = 0ull;
   for (int i = 0; i < count; ++i) {
     const double ox = rows[i], oy = rows[kCrowdFootprintMax + i], rho = rows[2 * kCrowdFootprintMax + i];
@@ -260,7 +279,7 @@ __device__ __forceinline__ int crowd_body_wall_hits(const double* rows, int coun
         mask |= 1ull << l;
     }
   }
-  return __popcll(mask);
+  return crowd_fold_count(mask, group, crowd_fold_span(grouped, wbase));
 }
 
 // obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
@@ -288,9 +307,9 @@ template <typename... WallArgs>
 constexpr bool kCrowdSamples = (std::is_same_v<WallArgs, CrowdSamples> || ...);
 template <typename... WallArgs>
 constexpr bool kCrowdFootprint = (std::is_same_v<WallArgs, CrowdFootprint> || ...);
-__device__ __forceinline__ CrowdFootprint crowd_footprint_of() { return CrowdFootprint{{}, {}, {}, 0}; }
+__device__ __forceinline__ CrowdFootprintRows crowd_footprint_of() { return CrowdFootprintRows{{}, {}, {}, 0}; }
 template <typename First, typename... Rest>
-__device__ __forceinline__ CrowdFootprint crowd_footprint_of(const First& first, const Rest&... rest) {
+__device__ __forceinline__ auto crowd_footprint_of(const First& first, const Rest&... rest) {
   if constexpr (std::is_same_v<First, CrowdFootprint>) return first;
   else return crowd_footprint_of(rest...);
 }
@@ -318,7 +337,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
   static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
   static_assert(!FOOT || (TRACKS && WTRK == WALLS), "a body footprint: TRACKS forms, walls as CrowdWallTracks");
-  [[maybe_unused]] const CrowdFootprint fp = crowd_footprint_of(wall_args...);
+  [[maybe_unused]] const auto fp = crowd_footprint_of(wall_args...);  // (CrowdFootprint, or the empty rows)
   [[maybe_unused]] const CrowdSamples smp = crowd_samples_of(wall_args...);
   [[maybe_unused]] const int S = SAMPLES ? smp.count : 1;
   [[maybe_unused]] GoalRows G = goal_rows_of(wall_args...);
@@ -616,7 +635,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                     load_wall_row(more ? j : j + NC, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);
                     const int wt = min(64, wcount - wbase);
                     if constexpr (FOOT) {
-                      whits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt);
+                      whits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt, wbase, fp.group, fp.grouped);
                     } else {
                       for (int l = 0; l < wt; ++l) {
                         const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
@@ -686,7 +705,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                     load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
                     const int wt = min(64, wcount - wbase);
                     if constexpr (FOOT) {
-                      hits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt);
+                      hits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt, wbase, fp.group, fp.grouped);
                     } else {
                       for (int l = 0; l < wt; ++l) {
                         const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
