@@ -44,6 +44,9 @@
 //   (a rollout stopped in a zero-traction cell keeps paying where it stands: ordinary records)
 //   ... then, by the cost wave: terminal cost, the T control-cost terms
 //   (mppi.py:1005-1009), cost, tile weights; barrier; F: per-tile update sums, lane = step.
+//   (What that tail starts with -- the vote flags[0], the rollout's event words and terminal cost, cc_done and group
+//    0's terms -- the cost wave requests with the last group's records, when every c_done has been seen, and finds in
+//    registers behind the stage walk: no flag of its own, cc_done looked at early and polled only if it was not up.)
 //
 // Workgroup = 3 walkers + ceil(T / 8) chunk waves: T <= 104.  Waves go to the four SIMDs of a CU
 // round robin (wave & 3).  A walk keeps a SIMD's float64 pipe busy for about half of its ~55 cycles
@@ -305,7 +308,6 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
   const int T = Q.n_steps, N = Q.n_local;
   const int Tp = 8 * W;
   const int n = tile * R + r;
-  const bool live = n < N;
   const int t0 = k * CHL;
   const int nvalid = min(max(T - t0, 0), CHL);
   // One GPU, an update left to this launch (update_kernels.h, PendingApply::reduce_tiles): step tt of it is combined
@@ -503,23 +505,34 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
 
   // what every tile ends with, by its cost wave (wave 1): the control cost of all T steps after the terminal cost, the
   // cost, the weights relative to the tile's minimum and the header of the tile's packet
-  auto finish_tile = [&](float cost) {
+  // ahead_tag 1 (the cost walk of a vote that held): the caller has looked at cc_done (ah_cc, one flag per lane) and
+  // requested group 0's terms (ah_c0 .. ah_c3) BEHIND that look, both while it still walked -- the LDS serves a wave's
+  // reads in the order they were issued, so terms requested behind a flag that was up are the stored ones.  A flag
+  // that was not up (never seen in practice): poll with acquire loads, then load, as a caller without the look ahead.
+  // (The terms by value, not through a pointer or a captured array: either form kept them in scratch memory.)
+  const double* const cc_at = ccr + (size_t)r * CHL;
+  const double2 no_terms = make_double2(0.0, 0.0);
+  auto finish_tile = [&](float cost, auto ahead_tag, [[maybe_unused]] int ah_cc, [[maybe_unused]] double2 ah_c0,
+                         [[maybe_unused]] double2 ah_c1, [[maybe_unused]] double2 ah_c2, [[maybe_unused]] double2 ah_c3) {
     // the control cost of all T steps, also after an early goal break (mppi.py:1007-1009); steps past
     // the horizon hold zero noise: their terms are +0.0
-    for ([[maybe_unused]] int polls = 0;
-         !__all(lane >= W || __hip_atomic_load(&cc_done[lane & 15], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 0);) {
-      __builtin_amdgcn_s_sleep(MPPI_SCAN_POLL_SLEEP);
+    bool ahead = false;
+    if constexpr (decltype(ahead_tag)::value != 0) ahead = __all(lane >= W || ah_cc != 0);
+    if (!ahead) {
+      for ([[maybe_unused]] int polls = 0;
+           !__all(lane >= W || __hip_atomic_load(&cc_done[lane & 15], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 0);) {
+        __builtin_amdgcn_s_sleep(MPPI_SCAN_POLL_SLEEP);
 #ifdef MPPI_POLL_BOUND
-      if (++polls > kMaxPolls) __builtin_trap();
+        if (++polls > kMaxPolls) __builtin_trap();
 #endif
+      }
     }
     {
-      const double* at = ccr + (size_t)r * CHL;
       double2 ca[2][4];
       auto load = [&](auto set, int gi) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
-          const double* in = at + (size_t)(2 * gi + hh) * R * CHL;
+          const double* in = cc_at + (size_t)(2 * gi + hh) * R * CHL;
           ca[decltype(set)::value][2 * hh] = reinterpret_cast<const double2*>(in)[0];
           ca[decltype(set)::value][2 * hh + 1] = reinterpret_cast<const double2*>(in)[1];
         }
@@ -531,7 +544,18 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
           cost = (float)((double)cost + ca[decltype(set)::value][i].y);
         }
       };
-      load(PhaseTag<0>(), 0);
+      if constexpr (decltype(ahead_tag)::value != 0) {
+        if (ahead) {
+          ca[0][0] = ah_c0;
+          ca[0][1] = ah_c1;
+          ca[0][2] = ah_c2;
+          ca[0][3] = ah_c3;
+        } else {
+          load(PhaseTag<0>(), 0);
+        }
+      } else {
+        load(PhaseTag<0>(), 0);
+      }
       for (int gi = 0; gi < W; gi += 2) {
         if (gi + 1 < W) load(PhaseTag<1>(), gi + 1);
         add(PhaseTag<0>());
@@ -541,20 +565,26 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       }
     }
     MPPI_STAMP(stamp_wg, stamp_base + 3);
-    const bool mine = live && lane < R;
-    if (mine) costs[n] = cost;
+    // (the rollout of this lane, formed again from the lane: a value kept from the kernel's entry to here is what the
+    //  compiler spills when this wave's tail grows, and its reload from scratch then sits in the serial tail)
+    int lane_here = lane;
+    asm volatile("" : "+v"(lane_here));
+    const int n_here = tile * R + (lane_here & (R - 1));
+    const bool live_here = n_here < N;
+    const bool mine = live_here && lane < R;
+    if (mine) costs[n_here] = cost;
     // first half of the control update (update_kernels.h): weights relative to the tile's minimum.
     // exp(-(c - beta)/lambda) = 2^(n + f): the fraction through v_exp_f32 (relative error ~1e-7 whatever
     // the argument), the integer through the exponent (as k_rollout_scan; a float64 exp is ~1k cycles of
     // this wave's serial tail, and u is held to 1e-5 of the range, not to bits)
-    const float beta = wave_min_f32(live ? cost : __builtin_inff());
+    const float beta = wave_min_f32(live_here ? cost : __builtin_inff());
     float wr = 0.0f;
     if (mine) {
       const double a2 = (double)(cost - beta) * Q.neg_log2e_over_lambda;  // <= 0
       const double nf = floor(a2);
       wr = ldexpf(__builtin_amdgcn_exp2f((float)(a2 - nf)), (int)fmax(nf, -200.0));
     }
-    if (mine) w_rel[n] = wr;
+    if (mine) w_rel[n_here] = wr;
     if (lane < R) wsh[lane] = wr;
     const float den = wave_sum_to_lane63_f32(wr);
     if (lane == 63) {
@@ -636,6 +666,12 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       term_plain = sqrt(fma(dx, dx, dy * dy)) / Q.v_post_den;  // mppi.py:26-28, 1005
       term_ready = true;
     };
+    // requested with the last group's records (fetch below): the vote, this rollout's event words and terminal cost, the
+    // control-cost flags (one per lane) and group 0's terms
+    uint32_t ah_failed = 0u, ah_ev = 0u;
+    double ah_term = 0.0;
+    int ah_cc = 0;
+    double2 ah_c0 = no_terms, ah_c1 = no_terms, ah_c2 = no_terms, ah_c3 = no_terms;
     walk_groups(
         c_done,
         [&](auto set, int gi) {
@@ -649,6 +685,23 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
             sg[S][2 * hh + 1] = *reinterpret_cast<const double2*>(in + hh * 2048 + 512);
             fo[S][hh] = *reinterpret_cast<const float4*>(in + hh * 2048 + 1024);
             fu[S][hh] = *reinterpret_cast<const float4*>(in + hh * 2048 + 1536);
+          }
+          if (gi == W - 1) {
+            // The last group's records are on their way and every c_done has been seen: every vote, event and terminal
+            // cost is in LDS.  What the tail starts with is requested here, behind the records, and arrives while the
+            // group is walked: one LDS round trip instead of three in a row (the vote and the events; the poll of
+            // cc_done; group 0's terms) between the last stage-cost addition and the first control-cost addition.
+            pin_memory_order();
+            ah_failed = flags[0];
+            ah_ev = evw[2 * r] | evw[2 * r + 1];
+            ah_term = term_sh[r];
+            ah_cc = lane < W ? glance(&cc_done[lane & 15]) : 1;
+            pin_memory_order();  // (the terms behind the look at their flags)
+            ah_c0 = reinterpret_cast<const double2*>(cc_at)[0];
+            ah_c1 = reinterpret_cast<const double2*>(cc_at)[1];
+            ah_c2 = reinterpret_cast<const double2*>(cc_at + (size_t)R * CHL)[0];
+            ah_c3 = reinterpret_cast<const double2*>(cc_at + (size_t)R * CHL)[1];
+            pin_memory_order();
           }
         },
         [&](auto set, int gi, int flag_value) {
@@ -686,12 +739,12 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       plain_terminal();
     }
     MPPI_STAMP(stamp_wg, stamp_base + 1);
-    const bool failed = flags[0] != 0u;  // (every chunk wave has published its vote before its c_done)
+    const bool failed = ah_failed != 0u;  // (every chunk wave has published its vote before its c_done)
     if (!failed) {
       MPPI_STAMP(stamp_wg, stamp_base + 2);
-      const bool had_event = (evw[2 * r] | evw[2 * r + 1]) != 0u;
-      cost = (float)((double)cost + (had_event ? term_sh[r] : term_plain));
-      finish_tile(cost);
+      const bool had_event = ah_ev != 0u;
+      cost = (float)((double)cost + (had_event ? ah_term : term_plain));
+      finish_tile(cost, PhaseTag<1>(), ah_cc, ah_c0, ah_c1, ah_c2, ah_c3);
     } else if (fallback.offset < 0) {
       // ---- no room for the map window: the tile step by step, with the tractions of the visited cells, by this
       //      wave alone (k_rollout_map's arithmetic; slow, and counted: the host stops launching this kernel on a
@@ -707,7 +760,7 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
         if (__all(st.done)) break;
       }
       cost = (float)((double)st.cost + (st.reached ? 0.0 : 1.0) * sqrt(st.d2) / Q.v_post_den);
-      finish_tile(cost);
+      finish_tile(cost, PhaseTag<0>(), 0, no_terms, no_terms, no_terms, no_terms);
     }
     // (a failed vote with room for the window: all waves re-execute the tile behind the barrier below)
   } else if (g >= 0) {
@@ -965,7 +1018,7 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
                                                      [&]() { if (g >= 0) chunk_ccr(); }, /*leave_when_idle=*/true);
     if (c == 1) {
       __builtin_amdgcn_s_setprio(3);
-      finish_tile(cost);
+      finish_tile(cost, PhaseTag<0>(), 0, no_terms, no_terms, no_terms, no_terms);
     }
     lds_barrier();
   } else {
@@ -977,7 +1030,7 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
                                                      folded ? u_sh : uq, T, c, lane, (const float2*)nullptr, fallback.rot_ok != 0, []() {});
     if (c == 1) {
       __builtin_amdgcn_s_setprio(3);
-      finish_tile(cost);
+      finish_tile(cost, PhaseTag<0>(), 0, no_terms, no_terms, no_terms, no_terms);
     }
     lds_barrier();
   }
