@@ -429,6 +429,40 @@ int mppi_planner_set_footprint(mppi_planner* p, const float* discs, int count);
 /* discs (8, 3) float32: the first *count rows are the footprint held (*count = 0: none) */
 int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* count);
 
+/* MPPI_MODE_BAREBONE, crowd mode: clearance rings -- a soft cost for passing close, as a staircase.
+ * rings (count, 2) float32, 1 <= count <= 4, rows (margin, penalty): margins finite, > 0 and
+ * strictly increasing, penalties finite and >= 0; count = 0 clears (rings ignored), and every
+ * launch then has the kernel form, the arguments and the bits it had before.  One set for every
+ * problem of a batch.  With m = (double)margin_l, obstacle k of a step is NEAR at ring l iff the
+ * step would touch it were it m larger:
+ *   disc k, point robot    the disc test of the launches -- the float32 difference widened, then
+ *                          fma(ex, ex, ey * ey) - rr, near iff !(diff > 0) -- with rr = R * R,
+ *                          R = (double)r_k + m
+ *   disc k, a footprint    the footprint's disc test with R = ((double)r_k + rho_i) + m; near iff
+ *                          any body disc is
+ *   wall k, point robot    the wall test of mppi_planner_set_walls with hh = H * H,
+ *                          H = (double)h_k + m
+ *   wall k, a footprint    H = ((double)h_k + rho_i) + m per body disc chord; near iff any chord is
+ * A step that crosses a wall is inside every ring.  The walls of fleet mode and of a body fleet are
+ * walls like any other; in a body fleet a robot is near at ring l once, however many of its slots
+ * are.  n_l(t): the obstacles near at ring l in step t, the hit ones included (n_l >= hits, and
+ * n_1 <= n_2 <= ...).  The step's cost chain: the distance term; `hits` float32-rounded additions
+ * of (double)obs_cost, as before; for l = 1 .. count, n_l additions
+ * c1 = (float)((double)c1 + (double)penalty_l); the freeze, as before.  (Additions and not a
+ * product: a ring whose penalty is obs_cost costs what a second copy of the obstacles, m larger,
+ * costs, to the bit.)  The goal distance, the goal test, the freeze, the terminal term and the
+ * control cost do not know about rings.  While rings are held every rollout launch is
+ * k_rollout_barebone_crowd, whatever else the handle holds, and
+ * mppi_planner_describe_last_rollout ends in " rings=<count>" (behind " footprint=<F>" if there is
+ * one).  A change drops the captured graphs.  MPPI_ERR_INVALID, the handle keeping what it had:
+ * count > 4 or negative, a bad row, a handle that is not barebone or not in crowd mode (and
+ * mppi_planner_set_crowd(p, 0) while rings are held), disc samples held (and
+ * mppi_planner_set_disc_track_samples with samples while rings are held: the sample forms count no
+ * rings), more than 65535 discs and walls in a step at a launch. */
+int mppi_planner_set_clearance_rings(mppi_planner* p, const float* rings, int count);
+/* rings (4, 2) float32: the first *count rows are the rings held (*count = 0: none) */
+int mppi_planner_get_clearance_rings(mppi_planner* p, float* rings, int* count);
+
 /* MPPI_MODE_BAREBONE, a batched handle (B >= 2) in crowd mode: a body fleet -- fleet mode for
  * robots that are not discs.  Every robot of the batch is the same body of n_discs discs (1 .. 8),
  * discs (n_discs, 3) float32 with the rows and the rules of mppi_planner_set_footprint; count = B

@@ -122,6 +122,8 @@ SIGNATURES = {
     "mppi_planner_get_fleet_body_walls": [_vp, _f32p],
     "mppi_planner_set_footprint": [_vp, _f32p, C.c_int],
     "mppi_planner_get_footprint": [_vp, _f32p, C.POINTER(C.c_int)],
+    "mppi_planner_set_clearance_rings": [_vp, _f32p, C.c_int],
+    "mppi_planner_get_clearance_rings": [_vp, _f32p, C.POINTER(C.c_int)],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

@@ -93,6 +93,26 @@ step of a rollout costs F * ((B - 1) * Fp + W) wall tests: a body of 3, 5, 6 or 
 body for the whole fleet; the chord for the arc, as above; the plans are those of the previous control step (the Jacobi
 sweep of the disc fleet).  set_fleet_bodies carries its own body: it is refused while params hold 'footprint', and the two
 kinds of fleet change into each other through set_fleet(None).  fleet_body_walls() fetches the rows of the last refresh.
+
+Clearance rings (crowd mode only): params['clearance_rings'] (R, 2), 1 <= R <= 4, rows (margin, penalty) rounded once to
+float32 -- margins finite, > 0 and strictly increasing, penalties finite and >= 0 -- give a cost that rises on the way in, as
+a staircase: an obstacle that a step misses by less than margin_l costs penalty_l, for every ring l it is inside of.  With
+m = float64(margin_l), an obstacle of the step is NEAR at ring l iff the step would touch it were it m larger:
+  disc k, point robot   the disc test -- the float32 difference widened, fma(ex, ex, ey*ey) - rr, near iff not diff > 0 --
+                        with rr = R*R, R = float64(r_k) + m
+  disc k, a footprint   the footprint's disc test with R = (float64(r_k) + rho_i) + m; near iff any body disc is
+  wall k, point robot   the wall test with hh = H*H, H = float64(h_k) + m
+  wall k, a footprint   H = (float64(h_k) + rho_i) + m per body disc chord; near iff any chord is
+A step that crosses a wall is inside every ring.  The fleet's walls and the fleet of bodies' walls are walls like any other;
+in a fleet of bodies a robot is near at ring l once, however many of its slots are.  n_l(t) counts the obstacles near at
+ring l in step t, the hit ones included, so n_l >= hits and n_1 <= n_2 <= ...  The step's cost chain is: the distance term;
+`hits` float32-rounded additions of float64(obs_penalty), as ever; for l = 1 .. R, n_l additions
+c = float32(float64(c) + float64(penalty_l)); the freeze at the goal, as ever.  Additions and not a product: a ring whose
+penalty is obs_penalty costs what a second copy of the obstacles, m larger, costs, to the bit.  Goal distance, goal test,
+freeze, terminal cost and control cost do not know about rings.  clearance_staircase() makes the rows that sit on top of
+peak * (1 - gap/reach)^2.  Without the key nothing changes anywhere.  Limits: refused together with
+'obstacle_track_samples'; one ring set for every problem of a batch; the default kernel family has no rings (a handle that
+holds rings always launches the crowd kernel).
 """
 import copy
 import ctypes as C
@@ -211,6 +231,38 @@ def _footprint_rows(footprint):
     return np.ascontiguousarray(_f32(fp))
 
 
+MAX_CLEARANCE_RINGS = 4  # (kCrowdRingsMax of the library)
+
+
+def clearance_staircase(reach, peak, count):
+    """(count, 2) float32 rows (margin, penalty) for params['clearance_rings']: margins reach * l / count, l = 1 .. count,
+    and penalties c_l = F_l - F_{l+1} with F_l = peak * (1 - (l - 1) / count)**2 and F_{count+1} = 0, evaluated in float64
+    and rounded once.  An obstacle at gap g pays F_l for g in (margin_{l-1}, margin_l] -- every ring from l outwards --: the
+    staircase on top of peak * (1 - g / reach)**2.  ValueError for reach <= 0, peak < 0 or a count outside 1 .. 4."""
+    reach, peak = float(reach), float(peak)
+    if not (np.isfinite(reach) and reach > 0.0):
+        raise ValueError("clearance_staircase: reach {} is not finite and positive".format(reach))
+    if not (np.isfinite(peak) and peak >= 0.0):
+        raise ValueError("clearance_staircase: peak {} is negative or not finite".format(peak))
+    if isinstance(count, bool) or int(count) != count or not 1 <= int(count) <= MAX_CLEARANCE_RINGS:
+        raise ValueError("clearance_staircase: count {} is not in 1 .. {}".format(count, MAX_CLEARANCE_RINGS))
+    count = int(count)
+    level = np.arange(1, count + 2, dtype=np.float64)
+    steps = peak * (1.0 - (level - 1.0) / count) ** 2  # F_1 .. F_{count+1}; the last is 0
+    out = np.zeros((count, 2), dtype=np.float64)
+    out[:, 0] = reach * level[:count] / count
+    out[:, 1] = steps[:count] - steps[1:]
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
+def _ring_rows(rings):
+    """params['clearance_rings'] as the library takes it: (R, 2) float32, 1 <= R <= 4 (ValueError otherwise)."""
+    rg = np.asarray(rings)
+    if rg.ndim != 2 or rg.shape[1] != 2 or not 1 <= rg.shape[0] <= MAX_CLEARANCE_RINGS:
+        raise ValueError("params['clearance_rings'] has shape (R, 2) with 1 <= R <= {}, got {}".format(MAX_CLEARANCE_RINGS, rg.shape))
+    return np.ascontiguousarray(_f32(rg))
+
+
 def body_discs(states, footprint):
     """(..., F, 2) float32: the centres of the body's discs at states (..., 3) = (x, y, th), as the rollouts form them --
     the states rounded to float32 first, s, c the float64 sine and cosine of the float32 heading,
@@ -324,6 +376,7 @@ class MPPI_Numba(object):
         self._fleet = None            # MPPI_Batch.set_fleet: (radii (B,), margin, half-widths (B, B - 1)) (None: off)
         self._fleet_bodies = None     # MPPI_Batch.set_fleet_bodies: (rows (F, 3), margin) (None: off)
         self._footprint_key = None    # the footprint of params['footprint'] the library holds (None: none)
+        self._rings_key = None        # the rings of params['clearance_rings'] the library holds (None: none)
         self.reset()
 
     def __del__(self):
@@ -476,6 +529,30 @@ class MPPI_Numba(object):
         bodies is on: the rows of its body."""
         rows, count = np.zeros((MAX_FOOTPRINT_DISCS, 3), dtype=np.float32), C.c_int(0)
         _lib.call("mppi_planner_get_footprint", self._handle, _lib.ptr(rows, C.c_float), C.byref(count))
+        return rows[:count.value].copy() if count.value else None
+
+    # ------------------------------------------------------------------ clearance rings
+    def _hand_over_rings(self, p):
+        """params['clearance_rings'] (R, 2): handed over when its bytes have changed, cleared when the key has gone.
+        Without crowd mode, beside disc samples, or with a bad row the library refuses it (MppiError)."""
+        if "clearance_rings" not in p:
+            if self._rings_key is not None:
+                _lib.call("mppi_planner_set_clearance_rings", self._handle, None, 0)
+                self._rings_key = None
+            return
+        rg = np.asarray(p['clearance_rings'])
+        key = (rg.dtype.str, rg.shape, rg.tobytes())
+        if key == self._rings_key:
+            return
+        rows = _ring_rows(rg)
+        _lib.call("mppi_planner_set_clearance_rings", self._handle, _lib.ptr(rows, C.c_float), len(rows))
+        self._rings_key = key
+
+    @property
+    def clearance_rings(self):
+        """The clearance rings the library holds: (R, 2) float32 rows (margin, penalty), or None."""
+        rows, count = np.zeros((MAX_CLEARANCE_RINGS, 2), dtype=np.float32), C.c_int(0)
+        _lib.call("mppi_planner_get_clearance_rings", self._handle, _lib.ptr(rows, C.c_float), C.byref(count))
         return rows[:count.value].copy() if count.value else None
 
     # ------------------------------------------------------------------ a goal that moves
@@ -718,7 +795,15 @@ class MPPI_Numba(object):
         self._hand_over_walls(p)
         if "footprint" in p or self._footprint_key is not None:  # (the point robot's path pays one lookup for this)
             self._hand_over_footprint(p)
-        if ("obstacle_track_samples" in p or self._samples_key is not None) and self._hand_over_samples(p):
+        # rings and disc samples exclude each other: a key that has gone is cleared ahead of the samples' hand-over, a key
+        # that is there is handed over behind it (the path without the key pays one lookup for this)
+        rings = "clearance_rings" in p
+        if not rings and self._rings_key is not None:
+            self._hand_over_rings(p)
+        sampled = ("obstacle_track_samples" in p or self._samples_key is not None) and self._hand_over_samples(p)
+        if rings:
+            self._hand_over_rings(p)
+        if sampled:
             return
         # the discs: handed over when they have changed (the notebook uploads them with every solve)
         if "obstacle_tracks" in p:

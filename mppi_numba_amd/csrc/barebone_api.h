@@ -264,6 +264,9 @@ extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples,
   if (samples > 0) {
     REQUIRE(p->crowd, MPPI_ERR_INVALID,
             "disc samples need crowd mode: only the crowd kernel has sample forms (mppi_planner_set_crowd(p, 1) first)");
+    REQUIRE(p->ring_count == 0, MPPI_ERR_INVALID,
+            "the handle holds %d clearance rings, and the sample forms count no rings: clear them first "
+            "(mppi_planner_set_clearance_rings(p, NULL, 0))", p->ring_count);
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
     REQUIRE(disc_count >= 0, MPPI_ERR_INVALID, "negative disc count %d", disc_count);
     const int walls = p->fleet_on ? p->fleet_slots : (p->wtrk_on ? p->wtrk_max : p->n_walls);
@@ -331,6 +334,9 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
     REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds a footprint of %d discs, which only the crowd kernel tests (mppi_planner_set_footprint(p, NULL, 0) first)",
             p->fp_count);
+    REQUIRE(p->ring_count == 0, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds %d clearance rings, which only the crowd kernel counts (mppi_planner_set_clearance_rings(p, NULL, 0) first)",
+            p->ring_count);
     BareboneHeld now = barebone_held(p);  // (without rotation: every set at its own size, the least a launch can ask for)
     now.crowd = false;
     BareboneHeld own = now, shared = now, tracks = now;
@@ -739,6 +745,47 @@ extern "C" int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* co
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
   memcpy(discs, p->fp_host, sizeof(p->fp_host));
   *count = p->fp_count;
+  return MPPI_OK;
+}
+
+// ---- clearance rings -----------------------------------------------------------------------------------------------------
+// Clearance rings (include/mppi_hip.h): crowd mode only, and not beside disc samples.  Like the footprint's, the rows are a
+// by-value argument of the launches: nothing to stage, a new generation and no captured graphs at every change.
+extern "C" int mppi_planner_set_clearance_rings(mppi_planner* p, const float* rings, int count) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "clearance rings belong to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(count >= 0 && count <= kCrowdRingsMax, MPPI_ERR_INVALID, "%d clearance rings: must be 0 (none) to %d", count, kCrowdRingsMax);
+  if (count > 0) {
+    REQUIRE(rings, MPPI_ERR_INVALID, "NULL rings");
+    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+            "clearance rings need crowd mode: only the crowd kernel has ring forms (mppi_planner_set_crowd(p, 1) first)");
+    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+            "the handle holds disc samples, and the sample forms count no rings: clear them first "
+            "(mppi_planner_set_disc_track_samples with samples 0)");
+    for (int l = 0; l < count; ++l) {
+      const float m = rings[2 * l], c = rings[2 * l + 1];
+      REQUIRE(std::isfinite(m) && m > 0.0f, MPPI_ERR_INVALID, "ring %d: margin %g is not finite and positive", l, (double)m);
+      REQUIRE(l == 0 || m > rings[2 * l - 2], MPPI_ERR_INVALID, "ring %d: margin %g does not exceed ring %d's %g", l, (double)m, l - 1,
+              (double)rings[2 * l - 2]);
+      REQUIRE(std::isfinite(c) && c >= 0.0f, MPPI_ERR_INVALID, "ring %d: penalty %g is negative or not finite", l, (double)c);
+    }
+  }
+  if (count == p->ring_count && (count == 0 || memcmp(rings, p->ring_host, sizeof(float) * 2 * (size_t)count) == 0)) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  memset(p->ring_host, 0, sizeof(p->ring_host));
+  if (count > 0) memcpy(p->ring_host, rings, sizeof(float) * 2 * (size_t)count);
+  p->ring_count = count;
+  p->ring_gen = count > 0 ? next_generation() : 0;
+  drop_graphs(p);  // (the rows, the count and the kernel form are arguments of the captured launches)
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_clearance_rings(mppi_planner* p, float* rings, int* count) {
+  REQUIRE(p && rings && count, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "clearance rings belong to the barebone mode (mode %d)", p->cfg.mode);
+  memcpy(rings, p->ring_host, sizeof(p->ring_host));
+  *count = p->ring_count;
   return MPPI_OK;
 }
 

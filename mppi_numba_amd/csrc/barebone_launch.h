@@ -21,7 +21,7 @@ static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
   crowd_shape(p, &W, &C);
   return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, p->crowd, p->n_obstacles, p->inst_obs_on, p->inst_obs_max,
                       p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on,
-                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W, p->fp_count};
+                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W, p->fp_count, p->ring_count};
 }
 
 // The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
@@ -95,6 +95,10 @@ static_assert(kCrowdFootprintMax * 3 == sizeof(mppi_planner::fp_host) / sizeof(f
 static_assert(crowd_lds_bytes(37, 14, true, 3, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 &&
                   crowd_lds_bytes(100, 16, false, 0, true) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 + 2 * 16 * 64 * 4 + 192,
               "crowd_lds_bytes: the footprint forms' layout crowd_lds (barebone_plan.h) restates");
+static_assert(kCrowdRingsMax * 2 == sizeof(mppi_planner::ring_host) / sizeof(float), "handles.h and rollout_crowd_kernel.h disagree on the rings");
+static_assert(crowd_lds_bytes(37, 14, true, 0, true, 4) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192 &&
+                  crowd_lds_bytes(100, 16, false, 0, false, 1) == 16 * 100 + 2 * 16 * 64 * (8 + 8) + 2 * 16 * 2 * 64 * 2 + 8,
+              "crowd_lds_bytes: the ring forms' layout crowd_lds (barebone_plan.h) restates");
 static_assert(crowd_lds_bytes(37, 14, true, 3) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 &&
                   crowd_lds_bytes(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8,
               "crowd_lds_bytes: the layout crowd_lds (barebone_plan.h) restates");
@@ -135,14 +139,36 @@ static CrowdFootprint footprint_arg(const mppi_planner* p) {
   return fp;
 }
 
+// The clearance rings as a launch takes them: the float32 rows widened (exact).
+static CrowdRings rings_arg(const mppi_planner* p) {
+  CrowdRings rg{};
+  rg.count = p->ring_count;
+  for (int l = 0; l < p->ring_count; ++l) {
+    rg.margin[l] = (double)p->ring_host[2 * l];
+    rg.penalty[l] = (double)p->ring_host[2 * l + 1];
+  }
+  return rg;
+}
+
 template <bool EXACT, bool BATCHED>
 static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneChoice& c, bool rot) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  if (c.samples > 0 || c.footprint > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0);  // the size launched
+  if (c.samples > 0 || c.footprint > 0 || c.rings > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
+  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0, c.rings);  // the size launched
+  if (c.rings > 0) {
+    REQUIRE(c.samples == 0, MPPI_ERR_STATE, "clearance rings beside disc samples: the hand-over keeps them apart");
+    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, 0, c.footprint > 0, c.rings), MPPI_ERR_STATE,
+            "clearance rings: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
+    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d clearance rings and %d steps: the crowd kernel needs %zu bytes of LDS",
+            c.rings, p->cfg.num_steps, lds);
+    const int walls = c.walls == 2 ? (p->fleet_on ? p->fleet_slots : p->wtrk_max) : (c.walls == 1 ? p->n_walls : 0);
+    REQUIRE((long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
+            "clearance rings: %d discs and %d walls, more than the %d a step's 16-bit counter holds", c.kmax, walls, kCrowdSampleHitsMax);
+    if (c.discs != kDiscsTracks) d.track_rows = 1;  // (static discs: tracks of one row)
+  }
   if (c.footprint > 0) {
-    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, true), MPPI_ERR_STATE,
+    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, true, c.rings), MPPI_ERR_STATE,
             "footprint: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
     REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "a footprint and %d steps: the crowd kernel needs %zu bytes of LDS",
             p->cfg.num_steps, lds);
@@ -223,7 +249,35 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
     if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
     return with_walls();
   };
-  if (c.footprint > 0 && c.samples > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::true_type()));
+  // clearance rings: TRACKS forms with one CrowdRings behind the goal rows and, with a body footprint, one CrowdFootprint
+  // behind that; the walls as the sample forms take them
+  auto dispatch_rings = [&](auto rot_c, auto foot_c) -> int {
+    constexpr bool ROT = EXACT && decltype(rot_c)::value, FOOT = decltype(foot_c)::value;
+    const CrowdRings rg = rings_arg(p);
+    auto with_walls = [&](auto... walls) -> int {
+      constexpr bool WALLS = sizeof...(walls) > 0;
+      if constexpr (FOOT) {
+        const CrowdFootprint fp = footprint_arg(p);
+        if (c.goal_form)
+          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdRings, CrowdFootprint>,
+                        walls..., goal_rows_arg<BATCHED>(p), rg, fp);
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdRings, CrowdFootprint>, walls..., rg, fp);
+      } else {
+        if (c.goal_form)
+          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdRings>, walls...,
+                        goal_rows_arg<BATCHED>(p), rg);
+        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdRings>, walls..., rg);
+      }
+    };
+    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
+    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
+    return with_walls();
+  };
+  if (c.rings > 0 && c.footprint > 0 && rot) TRY(dispatch_rings(std::true_type(), std::true_type()));
+  else if (c.rings > 0 && c.footprint > 0) TRY(dispatch_rings(std::false_type(), std::true_type()));
+  else if (c.rings > 0 && rot) TRY(dispatch_rings(std::true_type(), std::false_type()));
+  else if (c.rings > 0) TRY(dispatch_rings(std::false_type(), std::false_type()));
+  else if (c.footprint > 0 && c.samples > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::true_type()));
   else if (c.footprint > 0 && c.samples > 0) TRY(dispatch_footprint(std::false_type(), std::true_type()));
   else if (c.footprint > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::false_type()));
   else if (c.footprint > 0) TRY(dispatch_footprint(std::false_type(), std::false_type()));
@@ -246,7 +300,8 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
                     (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string()) +
                     (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
                                    : std::string()) +
-                    (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string());
+                    (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string()) +
+                    (c.rings > 0 ? " rings=" + std::to_string(c.rings) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -255,6 +310,8 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
 static int barebone_refuse(const BareboneChoice& c, int T) {
   if (c.limit == kLimitFootprintNeedsCrowd)
     return fail(MPPI_ERR_INVALID, "a footprint of %d discs needs crowd mode: only the crowd kernel has footprint forms", c.footprint);
+  if (c.limit == kLimitRingsNeedCrowd)
+    return fail(MPPI_ERR_INVALID, "%d clearance rings need crowd mode: only the crowd kernel has ring forms", c.rings);
   if (c.limit == kLimitSamplesNeedCrowd)
     return fail(MPPI_ERR_INVALID, "%d disc samples need crowd mode: only the crowd kernel has sample forms", c.samples);
   if (c.limit == kLimitGoalTrack)

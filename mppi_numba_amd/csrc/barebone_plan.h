@@ -40,8 +40,10 @@ constexpr size_t kCrowdSampleLdsAim = 64 * 1024;  // the chunk of a sample form 
 //   [2][C][64] int hits | two "tile done" words                                        the plain forms (samples = 0)
 //   ... | [2][C][S][64] uint16 hits | two words | [S][64] float running costs          the sample forms
 //   ... | [2][C (+ 1 with walls)][64] float heading | [3][8] double footprint rows     the footprint forms (behind all of that)
-inline size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false) {
-  const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4 : (size_t)2 * C * 64 * 4;
+//   ... | [2][C][1 + R][64] uint16 counts in place of the int hits                     the ring forms (R clearance rings)
+inline size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false, int rings = 0) {
+  const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4
+                      : rings > 0 ? (size_t)2 * C * (1 + rings) * 64 * 2 : (size_t)2 * C * 64 * 4;
   const size_t heading = footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 4 + 3 * 8 * 8 : 0;
   return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8 + heading;
 }
@@ -72,14 +74,15 @@ struct BareboneHeld {
   int smp_discs = 0, smp_rows = 0;   // ... K discs of L rows each
   int crowd_waves = 16;              // crowd family: waves per workgroup (crowd_shape of barebone_launch.h)
   int footprint = 0;                 // body footprint: F discs (0: the robot is its reference point)
+  int rings = 0;                     // clearance rings: R rows (0: none held)
 };
 
 enum BareboneFamily { kBareboneDefault = 0, kBareboneCrowd = 1, kBareboneRefused = 2 };
 enum BareboneDiscs { kDiscsShared = 0, kDiscsOwn = 1, kDiscsTracks = 2, kDiscsSamples = 3 };
-// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off); disc samples, or a body footprint, without
-// crowd mode
+// a refusal: the set that does not fit in 64 KiB of LDS (and crowd mode is off); disc samples, a body footprint, or clearance
+// rings, without crowd mode
 enum BareboneLimit { kLimitNone = 0, kLimitStaticDiscs = 1, kLimitDiscTracks = 2, kLimitGoalTrack = 3, kLimitSamplesNeedCrowd = 4,
-                     kLimitFootprintNeedsCrowd = 5 };
+                     kLimitFootprintNeedsCrowd = 5, kLimitRingsNeedCrowd = 6 };
 
 struct BareboneChoice {
   BareboneFamily family = kBareboneDefault;
@@ -89,11 +92,12 @@ struct BareboneChoice {
   bool track_form = false;  // default family: a row of disc slots per step (disc tracks, or static discs under a goal track)
   bool goal_form = false;   // a goal that moves
   int walls = 0;            // crowd family: 0 none, 1 static walls, 2 wall tracks / per-problem sets / fleet
-  size_t lds = 0;           // default family: the dynamic LDS launched; a sample form, a footprint form: likewise
+  size_t lds = 0;           // default family: the dynamic LDS launched; a sample form, a footprint form, a ring form: likewise
   BareboneLimit limit = kLimitNone;
   int samples = 0;          // crowd family: 0, or the sample form over this many disc samples
-  int chunk = 0;            // a sample form: steps per chunk; a footprint form: likewise
+  int chunk = 0;            // a sample form: steps per chunk; a footprint form, a ring form: likewise
   int footprint = 0;        // crowd family: 0, or the footprint form over this many body discs
+  int rings = 0;            // crowd family: 0, or the ring form over this many clearance rings
 };
 
 // Crowd mode: does a launch go to the crowd kernel?  own_lds: what the default form holds at the least.  Walls are the
@@ -110,9 +114,17 @@ inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
 // A body footprint (mppi_planner_set_footprint) is the crowd family's alone as well: a handle that holds one always goes
 // there, whatever it holds otherwise -- no discs and no walls included --, and launches a footprint form: a TRACKS form, static
 // discs as tracks of one row, static shared walls as wall tracks of one row, with the chunk and the LDS of the choice.
+// Clearance rings (mppi_planner_set_clearance_rings) likewise: the crowd family always, a TRACKS form with the chunk and the
+// LDS of the choice, with or without a footprint.  (The hand-over keeps rings and disc samples apart.)
 inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   BareboneChoice c;
   c.footprint = h.footprint;
+  c.rings = h.rings;
+  if (h.rings > 0 && !h.crowd) {
+    c.family = kBareboneRefused;
+    c.limit = kLimitRingsNeedCrowd;
+    return c;
+  }
   if (h.footprint > 0 && !h.crowd) {
     c.family = kBareboneRefused;
     c.limit = kLimitFootprintNeedsCrowd;
@@ -141,11 +153,11 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   c.track_form = h.trk_on || h.gtrk_on;
   c.walls = (h.wtrk_on || h.fleet_on) ? 2 : (h.n_walls > 0 ? 1 : 0);
   const size_t own_lds = barebone_lds(h.T, c.kmax, c.track_form, c.goal_form);
-  if (h.footprint > 0) {
+  if (h.footprint > 0 || h.rings > 0) {
     c.family = kBareboneCrowd;
     c.track_form = true;
     c.chunk = crowd_chunk(h.crowd_waves);
-    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, 0, true);
+    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, 0, h.footprint > 0, h.rings);
     return c;
   }
   if (crowd_launch(h, c.kmax, own_lds)) {

@@ -1054,7 +1054,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
   } sig;
   memset(&sig, 0, sizeof(sig));
@@ -1076,6 +1076,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.fleet_gen = p->fleet_gen;  // (the fleet storage's: renewed when it is rebuilt, not when its rows are refreshed)
   sig.smp_gen = p->smp_gen;  // (the disc samples')
   sig.fp_gen = p->fp_gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
+  sig.ring_gen = p->ring_gen;  // (the clearance rings' likewise)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

@@ -115,6 +115,27 @@
 // leader mask below g = clamp(grouped - wbase, 0, 64), a population count of the rest).  Two integers by value in
 // CrowdFootprint -- wave-uniform; group = 1, grouped = 0 is the plain population count.  The forms without a CrowdFootprint
 // hold the empty CrowdFootprintRows and compile to what they compiled to (compared in the gfx950 assembly, all 96).
+//
+// CLEARANCE RINGS (mppi_planner_set_clearance_rings): a cost that rises on the way in, as a staircase -- so it stays a matter
+// of counting.  One CrowdRings argument behind the GoalRows (if any) and in front of the CrowdFootprint (if any): R <= 4 rows
+// (margin m_l, penalty c_l), by value, widened on the host (TRACKS forms only; walls: the CrowdWallTracks form only; no disc
+// samples).  Obstacle k is NEAR at ring l iff the step would touch it were it m_l larger: the disc test with
+// rr := ((double)r + m_l)^2 (a body: ((r + rho) + m_l)^2), the wall test with hh := ((double)h + m_l)^2 (a body:
+// ((h + rho) + m_l)^2); a step that crosses a wall is inside every ring.
+//   count  the owner of (step, lane) forms 1 + R counts: the hits as ever and n_l, the obstacles near at ring l (the hit
+//          ones among them).  A disc's d2 is formed once and held against 1 + R squares, which every lane forms for its
+//          disc when the tile is loaded.  A wall's test runs once as well: crowd_wall_parts gives the crossing bit and,
+//          of each of the four crowd_near calls, the pair (num, den) of the branch taken -- near(hh) is num <= hh * den,
+//          den = 1.0 in the two end branches (the product is exact) --, and level l's verdict is
+//          crossing || any(num_i <= hh_l * den_i): at level 0 crowd_wall_hit's on every input.  A body fleet folds each
+//          level's own mask (crowd_fold_count): a robot is near once, however many of its slots are.
+//          1 + R counts of 16 bits -> LDS [step][level][lane] (the hand-over refuses K + walls > 65535).
+//   cost   behind the `hits` additions of obs_cost, for l = 1 .. R, n_l rounded additions of c_l -- the same wave-uniform,
+//          per-lane-predicated loop.  Repeated additions and not a product: a ring with c_l = obs_cost is a second copy of
+//          the obstacles, m_l larger, to the bit.  A ring with c_l = 0 adds +0.0: the identity (see above).
+// The compiler's report, gfx950, scratch bytes a lane of the 48 ring forms: without a footprint 0 .. 144 (no walls) and
+// 156 .. 284 (walls), with one 20 .. 52 and 308 .. 392.  Without the argument the kernel is what it was: the report's
+// figures of all 313 other kernels of the library are the parent's.
 #pragma once
 #include <type_traits>
 
@@ -130,9 +151,12 @@ constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
 // disc samples (S > 0): [2][C][S][64] uint16 hits in place of the int hits, and [S][64] float running costs at the end
 // a body footprint: [2][C (+ 1 with walls)][64] float headings behind all of that, slot for slot beside the positions, and
 // [3][8] double, the footprint's rows (ox | oy | rho), behind them
-__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0, bool footprint = false) {
+// clearance rings (R > 0, no samples): [2][C][1 + R][64] uint16 counts in place of the int hits
+__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0, bool footprint = false,
+                                                     int rings = 0) {
   return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * sizeof(double) +
          (samples > 0 ? (size_t)2 * C * samples * 64 * sizeof(unsigned short) + (size_t)samples * 64 * sizeof(float)
+          : rings > 0 ? (size_t)2 * C * (1 + rings) * 64 * sizeof(unsigned short)
                       : (size_t)2 * C * 64 * sizeof(int)) +
          (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int) +
          (footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float) + 3 * 8 * sizeof(double) : 0);
@@ -142,6 +166,10 @@ static_assert(crowd_lds_bytes(50, 14, true, 0) == 16 * 50 + 2 * 14 * 64 * 8 + 2 
                   crowd_lds_bytes(50, 16, false, 0, true) == crowd_lds_bytes(50, 16, false) + 2 * 16 * 64 * 4 + 192 &&
                   crowd_lds_bytes(50, 14, true, 2, true) == crowd_lds_bytes(50, 14, true, 2) + 2 * 15 * 64 * 4 + 192,
               "crowd_lds_bytes: without a footprint the layout as it was; with one, the heading plane and the rows on top of it");
+static_assert(crowd_lds_bytes(50, 14, true, 0, false, 0) == crowd_lds_bytes(50, 14, true) &&
+                  crowd_lds_bytes(50, 14, true, 0, false, 1) == crowd_lds_bytes(50, 14, true) &&
+                  crowd_lds_bytes(50, 14, true, 0, true, 4) == crowd_lds_bytes(50, 14, true, 0, true) + 2 * 14 * 64 * (5 * 2 - 4),
+              "crowd_lds_bytes: without rings the layout as it was; with R of them, 1 + R counts of 16 bits where the int hits were");
 
 // The walls of a launch (WALLS): seg[k] = (ax, ay, bx, by), halfwidth[k]; shared by every problem of a batch.
 struct CrowdWalls {
@@ -186,6 +214,13 @@ struct CrowdFootprint : CrowdFootprintRows {
   int group, grouped;
 };
 
+// The clearance rings of a launch: `count` rows (margin, penalty), the float32 rows widened on the host; margins ascending.
+constexpr int kCrowdRingsMax = 4;
+struct CrowdRings {
+  int count;
+  double margin[kCrowdRingsMax], penalty[kCrowdRingsMax];
+};
+
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
@@ -219,6 +254,49 @@ __device__ __forceinline__ bool crowd_wall_hit(double px, double py, double qx, 
   const bool crossing = ((o1 > 0.0 && o2 < 0.0) || (o1 < 0.0 && o2 > 0.0)) && ((o3 > 0.0 && o4 < 0.0) || (o3 < 0.0 && o4 > 0.0));
   return crossing || crowd_near(pax, pay, dx, dy, LLd, hh) || crowd_near(qax, qay, dx, dy, LLd, hh) ||
          crowd_near(apx, apy, ex, ey, LLe, hh) || crowd_near(bpx, bpy, ex, ey, LLe, hh);
+}
+
+// crowd_near with the half-width left open: the branch taken gives (num, den), and near(hh) is num <= hh * den -- the end
+// branches have den = 1.0, where the product is hh itself; the third is crowd_near's c * c <= hh * LL as it stands.
+__device__ __forceinline__ void crowd_near_parts(double wx, double wy, double ux, double uy, double LL, double& num, double& den) {
+  const double s = wx * ux + wy * uy;
+  if (s <= 0.0) {
+    num = wx * wx + wy * wy;
+    den = 1.0;
+  } else if (s >= LL) {
+    const double vx = wx - ux, vy = wy - uy;
+    num = vx * vx + vy * vy;
+    den = 1.0;
+  } else {
+    const double c = wx * uy - wy * ux;
+    num = c * c;
+    den = LL;
+  }
+}
+
+// crowd_wall_hit with the half-width left open (clearance rings: one test, 1 + R verdicts): the crossing bit and the
+// (num, den) pairs of its four crowd_near calls, in their order.  crowd_wall_verdict(parts, h * h) is crowd_wall_hit.
+struct CrowdWallParts {
+  bool crossing;
+  double num[4], den[4];
+};
+__device__ __forceinline__ CrowdWallParts crowd_wall_parts(double px, double py, double qx, double qy, double ax, double ay,
+                                                           double bx, double by, double dx, double dy, double LLd) {
+  const double ex = qx - px, ey = qy - py, LLe = ex * ex + ey * ey;
+  const double pax = px - ax, pay = py - ay, qax = qx - ax, qay = qy - ay;  // P - A, Q - A
+  const double apx = ax - px, apy = ay - py, bpx = bx - px, bpy = by - py;  // A - P, B - P
+  const double o1 = dx * pay - dy * pax, o2 = dx * qay - dy * qax;
+  const double o3 = ex * apy - ey * apx, o4 = ex * bpy - ey * bpx;
+  CrowdWallParts w;
+  w.crossing = ((o1 > 0.0 && o2 < 0.0) || (o1 < 0.0 && o2 > 0.0)) && ((o3 > 0.0 && o4 < 0.0) || (o3 < 0.0 && o4 > 0.0));
+  crowd_near_parts(pax, pay, dx, dy, LLd, w.num[0], w.den[0]);
+  crowd_near_parts(qax, qay, dx, dy, LLd, w.num[1], w.den[1]);
+  crowd_near_parts(apx, apy, ex, ey, LLe, w.num[2], w.den[2]);
+  crowd_near_parts(bpx, bpy, ex, ey, LLe, w.num[3], w.den[3]);
+  return w;
+}
+__device__ __forceinline__ bool crowd_wall_verdict(const CrowdWallParts& w, double hh) {
+  return w.crossing || w.num[0] <= hh * w.den[0] || w.num[1] <= hh * w.den[1] || w.num[2] <= hh * w.den[2] || w.num[3] <= hh * w.den[3];
 }
 
 // The centres of the body's discs at the state (x, y, th): s, c from the full sincos_f64 (never the rotation form: the
@@ -282,6 +360,63 @@ __device__ __forceinline__ int crowd_body_wall_hits(const double* rows, int coun
   return crowd_fold_count(mask, group, crowd_fold_span(grouped, wbase));
 }
 
+// Clearance rings: crowd_body_touches at 1 + R sizes -- n[0] takes the touch, n[l] whether any body disc is within
+// ((r + rho) + m_l) of the disc.  One d2 per body disc, held against every level's square.
+__device__ __forceinline__ void crowd_body_ring_touches(const CrowdFootprint& fp, const CrowdRings& rg, const float (&cx)[kCrowdFootprintMax],
+                                                        const float (&cy)[kCrowdFootprintMax], float ox, float oy, double r,
+                                                        int (&n)[1 + kCrowdRingsMax]) {
+  bool any[1 + kCrowdRingsMax] = {};
+#pragma unroll
+  for (int i = 0; i < kCrowdFootprintMax; ++i) {
+    if (i < fp.count) {
+      const double ex = (double)(cx[i] - ox), ey = (double)(cy[i] - oy);
+      const double d2 = fma(ex, ex, ey * ey), R0 = r + fp.rho[i];
+      any[0] = any[0] || !(d2 - R0 * R0 > 0.0);
+#pragma unroll
+      for (int q = 0; q < kCrowdRingsMax; ++q) {
+        if (q < rg.count) {
+          const double R = R0 + rg.margin[q];
+          any[q + 1] = any[q + 1] || !(d2 - R * R > 0.0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q <= kCrowdRingsMax; ++q) n[q] += any[q] ? 1 : 0;
+}
+
+// Clearance rings: crowd_body_wall_hits at 1 + R sizes, H := ((h + rho) + m_l) per body disc chord.  Still a run-time loop
+// over the body around ONE copy of the wall test (crowd_wall_parts); a mask per level, each folded on its own.
+__device__ __forceinline__ void crowd_body_wall_ring_hits(const double* rows, int count, const CrowdRings& rg, float px, float py,
+                                                          double sp, double cp, float qx, float qy, double sq, double cq,
+                                                          const float4& sg, double dx, double dy, double LLd, double h, int wt,
+                                                          int wbase, int group, int grouped, int (&n)[1 + kCrowdRingsMax]) {
+  unsigned long long mask[1 + kCrowdRingsMax] = {};
+  for (int i = 0; i < count; ++i) {
+    const double ox = rows[i], oy = rows[kCrowdFootprintMax + i], rho = rows[2 * kCrowdFootprintMax + i];
+    const double pcx = (double)(float)((double)px + (ox * cp - oy * sp)), pcy = (double)(float)((double)py + (ox * sp + oy * cp));
+    const double qcx = (double)(float)((double)qx + (ox * cq - oy * sq)), qcy = (double)(float)((double)qy + (ox * sq + oy * cq));
+    for (int l = 0; l < wt; ++l) {
+      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+      const CrowdWallParts w = crowd_wall_parts(pcx, pcy, qcx, qcy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                                crowd_lane_f64(LLd, l));
+      const double H0 = crowd_lane_f64(h, l) + rho;
+      if (crowd_wall_verdict(w, H0 * H0)) mask[0] |= 1ull << l;
+#pragma unroll
+      for (int q = 0; q < kCrowdRingsMax; ++q) {
+        if (q < rg.count) {
+          const double H = H0 + rg.margin[q];
+          if (crowd_wall_verdict(w, H * H)) mask[q + 1] |= 1ull << l;
+        }
+      }
+    }
+  }
+  const int span = crowd_fold_span(grouped, wbase);
+#pragma unroll
+  for (int q = 0; q <= kCrowdRingsMax; ++q) n[q] += crowd_fold_count(mask[q], group, span);  // (a level past the last: an empty mask)
+}
+
 // obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
 __device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
 __device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
@@ -301,6 +436,22 @@ __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks&
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdFootprint&) { return walls; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&, const CrowdFootprint&) { return walls; }
 __device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&, const CrowdFootprint&) { return walls; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdRings&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdRings&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdRings&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdRings&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdRings&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdRings&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdRings&, const CrowdFootprint&) { return walls; }
+__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdRings&, const CrowdFootprint&) { return walls; }
+template <typename... WallArgs>
+constexpr bool kCrowdRings = (std::is_same_v<WallArgs, CrowdRings> || ...);
+__device__ __forceinline__ CrowdRings crowd_rings_of() { return CrowdRings{0, {}, {}}; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ CrowdRings crowd_rings_of(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<First, CrowdRings>) return first;
+  else return crowd_rings_of(rest...);
+}
 template <typename... WallArgs>
 constexpr bool kCrowdWallTracks = (std::is_same_v<WallArgs, CrowdWallTracks> || ...);
 template <typename... WallArgs>
@@ -322,8 +473,9 @@ __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, con
 
 // WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
 // shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets); behind it, with a goal
-// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls); at the very end,
-// with a body footprint, one CrowdFootprint (TRACKS, and no CrowdWalls).
+// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls) or, with clearance
+// rings, one CrowdRings (TRACKS, no CrowdWalls, no CrowdSamples); at the very end, with a body footprint, one CrowdFootprint
+// (TRACKS, and no CrowdWalls).
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
@@ -331,12 +483,17 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   constexpr bool GOALS = kGoalRows<WallArgs...>;
   constexpr bool SAMPLES = kCrowdSamples<WallArgs...>;
   constexpr bool FOOT = kCrowdFootprint<WallArgs...>;
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0) + (FOOT ? 1 : 0),
+  constexpr bool RINGS = kCrowdRings<WallArgs...>;
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0) + (RINGS ? 1 : 0) + (FOOT ? 1 : 0),
                 "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; disc samples: "
-                "one CrowdSamples behind that; a body footprint: one CrowdFootprint behind that; else none");
+                "one CrowdSamples behind that, or clearance rings: one CrowdRings; a body footprint: one CrowdFootprint "
+                "behind that; else none");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
   static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
   static_assert(!FOOT || (TRACKS && WTRK == WALLS), "a body footprint: TRACKS forms, walls as CrowdWallTracks");
+  static_assert(!RINGS || (TRACKS && WTRK == WALLS && !SAMPLES), "clearance rings: TRACKS forms, walls as CrowdWallTracks, no disc samples");
+  [[maybe_unused]] const CrowdRings rg = crowd_rings_of(wall_args...);
+  [[maybe_unused]] const int NL = 1 + rg.count;  // RINGS: counts per (step, lane)
   [[maybe_unused]] const auto fp = crowd_footprint_of(wall_args...);  // (CrowdFootprint, or the empty rows)
   [[maybe_unused]] const CrowdSamples smp = crowd_samples_of(wall_args...);
   [[maybe_unused]] const int S = SAMPLES ? smp.count : 1;
@@ -380,6 +537,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     if (wave == 1)  // (the cost wave's own columns: nobody else touches them)
       for (int s = 0; s < S; ++s) scost[s * 64 + lane] = 0.0f;
   }
+  // RINGS: [2][C][NL][64] 16-bit counts where the int hits are, the two words behind them
+  if constexpr (RINGS) tile_done = reinterpret_cast<int*>(cnts16 + (size_t)2 * C * NL * 64);
   // FOOT: [2][CP][64] float headings behind everything else, slot for slot beside the positions
   [[maybe_unused]] float* heads = nullptr;
   if constexpr (FOOT && SAMPLES) heads = scost + (size_t)S * 64;
@@ -493,6 +652,29 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             scost[s * 64 + lane] = cs;
           }
           d2 = d2_s; done = done_s; reached = reached_s;
+        } else if constexpr (RINGS) {  // the chain with the rings' additions behind the hits'
+          for (int j = 0; j < cl; ++j) {
+            const double nd2 = nd2s[at + j * 64];
+            const unsigned short* cn = cnts16 + ((size_t)((c & 1) * C + j) * NL) * 64 + lane;
+            const int hits = cn[0];
+            float c1 = (float)((double)cost + P.dist_weight * nd2);
+            for (int h = 0; __any(h < hits); ++h)
+              if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
+#pragma unroll
+            for (int q = 0; q < kCrowdRingsMax; ++q) {
+              if (q < rg.count) {  // (uniform)
+                const int near = cn[(q + 1) * 64];
+                const double pen = rg.penalty[q];
+                for (int h = 0; __any(h < near); ++h)
+                  if (h < near) c1 = (float)((double)c1 + pen);
+              }
+            }
+            const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
+            cost = act ? c1 : cost;
+            d2 = act ? nd2 : d2;
+            reached = reached || (act && hit_goal);
+            done = done || hit_goal;
+          }
         } else {
           for (int j = 0; j < cl; ++j) {
             const double nd2 = nd2s[at + j * 64];
@@ -571,9 +753,146 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         [[maybe_unused]] double sq = 0.0, cq = 1.0;  // (sine and cosine of the post-step heading)
         [[maybe_unused]] float4 sg0;
         [[maybe_unused]] double dx0, dy0, LLd0, hh0;
-        if constexpr (WTRK) load_wall_row(wave - 2, 0, sg0, dx0, dy0, LLd0, hh0);  // (the first tile of the first step owned)
-        else if constexpr (WALLS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
-        if constexpr (SAMPLES) {
+        // (RINGS: its own loaders, below -- a tile's lane holds 1 + R squares)
+        if constexpr (WTRK && !RINGS) load_wall_row(wave - 2, 0, sg0, dx0, dy0, LLd0, hh0);  // (the first tile of the first step owned)
+        else if constexpr (WALLS && !RINGS) load_wall(0, sg0, dx0, dy0, LLd0, hh0);
+        if constexpr (RINGS) {
+          // The plain walk below with 1 + R counts.  A lane holds of its disc (wall) the squares of every level, formed when
+          // the tile is loaded: (r)^2 | ((double)r + m_l)^2.  A body: the size itself, the sums are formed per body disc.
+          constexpr int kSq = FOOT ? 1 : 1 + kCrowdRingsMax;
+          auto load_ring_disc = [&](int dj, int dbase, float2& op, double (&rr)[kSq]) {
+            const int k = dbase + lane;
+            op = make_float2(1e18f, 1e18f);
+            float r = 0.0f;
+            if (dj < cl && k < K) {
+              op = obs_pos[(size_t)min(now + c0 + dj + 1, last) * (size_t)disc_pitch + (size_t)k];
+              r = obs_r[k];
+            }
+            if constexpr (FOOT) {
+              rr[0] = (double)r;
+            } else {
+              rr[0] = (double)r * (double)r;
+#pragma unroll
+              for (int q = 0; q < kCrowdRingsMax; ++q) {
+                const double R = (double)r + rg.margin[q];
+                rr[q + 1] = q < rg.count ? R * R : 0.0;
+              }
+            }
+          };
+          [[maybe_unused]] auto load_ring_wall = [&](int wj, int wbase, float4& sg, double& dx, double& dy, double& LLd, double (&hh)[kSq]) {
+            const int k = wbase + lane;
+            sg = make_float4(1e18f, 1e18f, 1e18f, 1e18f);
+            float h = 0.0f;
+            if constexpr (WTRK) {
+              if (wj < cl && k < wcount) {
+                sg = walls.seg[(size_t)min(wnow + c0 + wj, wlast) * (size_t)walls.pitch + (size_t)(wall0 + k)];
+                h = walls.halfwidth[wall0 + k];
+              }
+            }
+            dx = (double)sg.z - (double)sg.x;
+            dy = (double)sg.w - (double)sg.y;
+            LLd = dx * dx + dy * dy;
+            if constexpr (FOOT) {
+              hh[0] = (double)h;
+            } else {
+              hh[0] = (double)h * (double)h;
+#pragma unroll
+              for (int q = 0; q < kCrowdRingsMax; ++q) {
+                const double H = (double)h + rg.margin[q];
+                hh[q + 1] = q < rg.count ? H * H : 0.0;
+              }
+            }
+          };
+          int j = wave - 2, base = 0;
+          int n[1 + kCrowdRingsMax] = {};
+          float2 op;
+          double rr[kSq];
+          load_ring_disc(j, base, op, rr);
+          [[maybe_unused]] double hq0[kSq];
+          if constexpr (WALLS) load_ring_wall(wave - 2, 0, sg0, dx0, dy0, LLd0, hq0);  // (the first tile of the first step owned)
+          while (j < cl) {
+            int nj = j, nbase = base + 64;
+            if (nbase >= K) { nj = j + NC; nbase = 0; }
+            float2 op_nxt;
+            double rr_nxt[kSq];
+            load_ring_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
+            const float2 pos = poss[atp + j * 64];
+            if constexpr (FOOT) {
+              if (base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
+            }
+            const int kt = min(64, K - base);
+            for (int l0 = 0; l0 < kt; l0 += kLanes) {
+#pragma unroll
+              for (int l = l0; l < l0 + kLanes; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
+                const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
+                if constexpr (FOOT) {
+                  crowd_body_ring_touches(fp, rg, qcx, qcy, ox, oy, crowd_lane_f64(rr[0], l), n);
+                } else {
+                  const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
+                  const double dd = fma(ex, ex, ey * ey);
+#pragma unroll
+                  for (int q = 0; q < kSq; ++q) {
+                    if (q < NL) {
+                      const double diff = dd - crowd_lane_f64(rr[q], l);
+                      n[q] += (diff > 0.0) ? 0 : 1;
+                    }
+                  }
+                }
+              }
+            }
+            if (nj != j) {  // the step's last tile
+              if constexpr (WALLS) {  // ... then this problem's walls as this step sees them, against P -> Q
+                const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
+                [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
+                [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
+                if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
+                float4 sg = sg0;
+                double dx = dx0, dy = dy0, LLd = LLd0, hq[kSq];
+#pragma unroll
+                for (int q = 0; q < kSq; ++q) hq[q] = hq0[q];
+                for (int wbase = 0; wbase < wcount; wbase += 64) {
+                  float4 sg_nxt;
+                  double dx_nxt, dy_nxt, LLd_nxt, hq_nxt[kSq];
+                  const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
+                  load_ring_wall(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hq_nxt);
+                  const int wt = min(64, wcount - wbase);
+                  if constexpr (FOOT) {
+                    crowd_body_wall_ring_hits(fprows, fp.count, rg, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hq[0], wt,
+                                              wbase, fp.group, fp.grouped, n);
+                  } else {
+                    for (int l = 0; l < wt; ++l) {
+                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                      const CrowdWallParts w = crowd_wall_parts(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l),
+                                                                crowd_lane_f64(dy, l), crowd_lane_f64(LLd, l));
+#pragma unroll
+                      for (int q = 0; q < kSq; ++q) {
+                        if (q < NL) n[q] += crowd_wall_verdict(w, crowd_lane_f64(hq[q], l)) ? 1 : 0;
+                      }
+                    }
+                  }
+                  sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt;
+#pragma unroll
+                  for (int q = 0; q < kSq; ++q) hq[q] = hq_nxt[q];
+                }
+                sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd;
+#pragma unroll
+                for (int q = 0; q < kSq; ++q) hq0[q] = hq[q];
+              }
+              unsigned short* cn = cnts16 + ((size_t)((c & 1) * C + j) * NL) * 64 + lane;
+#pragma unroll
+              for (int q = 0; q <= kCrowdRingsMax; ++q) {
+                if (q < NL) cn[q * 64] = (unsigned short)n[q];
+                n[q] = 0;
+              }
+              if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
+              else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+            }
+            j = nj; base = nbase; op = op_nxt;
+#pragma unroll
+            for (int q = 0; q < kSq; ++q) rr[q] = rr_nxt[q];
+          }
+        } else if constexpr (SAMPLES) {
           // sample sm's tile [base, base + 64) as step c0 + j sees it: the row's samples lie side by side, K discs each
           auto load_sample_disc = [&](int j, int sm, int base, float2& op, double& rr) {
             const int k = base + lane;
