@@ -260,6 +260,10 @@ static MapHeld map_held(const mppi_planner* p) {
   h.dt = a.dt; h.res = a.res; h.xlo = a.xlo; h.ylo = a.ylo;
   h.vrange[0] = a.vrange[0]; h.vrange[1] = a.vrange[1]; h.wrange[0] = a.wrange[0]; h.wrange[1] = a.wrange[1];
   h.x0 = a.x0[0]; h.y0 = a.x0[1];
+  const MapStartBounds inside = map_start_bounds(h);
+  h.starts_inside = map_start_inside(inside, h.x0, h.y0);
+  if (p->inst_set)  // (the host mirror of the per-problem starts: what the window origins are planned from, apply_window)
+    for (const BatchInst& I : p->inst_host) h.starts_inside = h.starts_inside && map_start_inside(inside, I.x0, I.y0);
   return h;
 }
 

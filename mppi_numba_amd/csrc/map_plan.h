@@ -22,7 +22,7 @@ struct MapHeld {
   int cells16_valid, cells16_with_risk, pitch16;  // the 16-bit (speed map: 32-bit) cells the LDS window is copied from
   int rows, cols, lin_max_byte, ang_max_byte, sink_ring, grid_packed;  // PackedMaps (handles.h)
   int theta_bounded;  // |theta| stays inside the two-term pi/2 reduction over the horizon (launch_rollout)
-  int pad_;
+  int starts_inside;  // every start cell is a cell of the map (map_start_inside): x0, and each problem's of a batched handle
   double lin_lo, lin_ratio, ang_lo, ang_ratio;
   float dt, res, xlo, ylo, vrange[2], wrange[2], x0, y0;
 };
@@ -71,11 +71,35 @@ inline bool map_res_pow2(const MapHeld& h) {
 // terrain.py:511-583 -- whoever enters it stays), or a reach square that lies strictly inside the map.  Anything else
 // (an mppi_tdm filled through the C API without such a ring, a window clipped by the border) takes the variant with the
 // exact floor division and the clamp, i.e. the border cell, like k_rollout_map and k_rollout_fused.
-// (a wide enough sink ring says yes even for a start cell outside the map -- tests/test_map_plan.py keeps a
-//  row for that state.)
+// Either argument holds only for a rollout that STARTS on the map: the ring stops who enters it, not who begins beyond
+// it, and the float-to-unsigned conversion of the unclamped address saturates at 0 only, so a start cell beyond a high
+// border would index past the window.  MapHeld::starts_inside says so for x0 and for every problem of a batched handle
+// (tests/test_map_plan.py, tests/test_gpu_border.py).
+// The test is the kernels' own arithmetic: d = x0 - lo in float32, and 0 <= d / res < cols (the quotient is exact where
+// the answer matters, a power of two).  d / res grows with d, so the bound on the quotient is a bound on d, found once
+// per state: a batched handle asks for every problem, several times an iteration.
+struct MapStartBounds {
+  float xlo, ylo, dx_end, dy_end;  // inside: 0 <= x0 - xlo < dx_end and 0 <= y0 - ylo < dy_end
+};
+inline float map_start_end(float res, int n) {  // the smallest d with d / res >= n; a resolution that is not positive: 0
+  if (!(res > 0.0f) || !std::isfinite(res) || n <= 0) return 0.0f;
+  float d = (float)n * res;
+  while (d / res >= (float)n && d > 0.0f) d = std::nextafter(d, 0.0f);
+  while (d / res < (float)n) d = std::nextafter(d, INFINITY);
+  return d;
+}
+inline MapStartBounds map_start_bounds(const MapHeld& h) {
+  return MapStartBounds{h.xlo, h.ylo, map_start_end(h.res, h.cols), map_start_end(h.res, h.rows)};
+}
+inline bool map_start_inside(const MapStartBounds& b, float x0, float y0) {
+  const float dx = x0 - b.xlo, dy = y0 - b.ylo;
+  return dx >= 0.0f && dx < b.dx_end && dy >= 0.0f && dy < b.dy_end;  // (a NaN start: no)
+}
+
 inline bool map_unclamped_ok(const MapHeld& h) {
   const MapReach r = map_reach(h);
   if (!std::isfinite(r.step_cells)) return false;
+  if (!h.starts_inside) return false;
   if (h.grid_packed && (double)h.sink_ring >= std::ceil(r.step_cells + 1e-3)) return true;
   if (h.inst_set) return false;  // (per-problem windows are shifted inwards at the border)
   const double reach = std::ceil((double)h.T * r.step_cells) + 2.0;

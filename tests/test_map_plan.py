@@ -43,6 +43,24 @@ int main() {
                    &h.ang_ratio, &h.dt, &h.res, &h.xlo, &h.ylo, &h.vrange[0], &h.vrange[1], &h.wrange[0], &h.wrange[1], &h.x0,
                    &h.y0, &px, &py) != 37)
       break;
+    // (launch_plan.h: map_held fills this from the handle's start and from every problem's of a batched handle)
+    const MapStartBounds inside = map_start_bounds(h);
+    h.starts_inside = map_start_inside(inside, h.x0, h.y0) && (!h.inst_set || map_start_inside(inside, px, py));
+    {  // the bounds on x0 - lo say what the quotient says: around both ends, ulp by ulp, and for this state's start
+      const float ends[2] = {inside.dx_end, inside.dy_end};
+      const int counts[2] = {h.cols, h.rows};
+      for (int a = 0; a < 2 && h.res > 0.0f; ++a) {
+        float d = ends[a];
+        for (int k = 0; k < 4; ++k) d = std::nextafter(d, 0.0f);
+        for (int k = 0; k < 8; ++k, d = std::nextafter(d, INFINITY))
+          if ((d / h.res < (float)counts[a]) != (d < ends[a])) { std::printf("bounds_disagree\n"); return 1; }
+      }
+      const float qx = (h.x0 - h.xlo) / h.res, qy = (h.y0 - h.ylo) / h.res;
+      if (h.res > 0.0f && map_start_inside(inside, h.x0, h.y0) != (qx >= 0.0f && qx < (float)h.cols && qy >= 0.0f && qy < (float)h.rows)) {
+        std::printf("bounds_disagree\n");
+        return 1;
+      }
+    }
     const MapChoice c = map_choose(h);
     const MapReach r = map_reach(h);
     const WindowPlan& w = c.window;
@@ -271,9 +289,27 @@ OTHER_ROWS = [
     (held(T=40, x0=32.0, y0=32.0, sink_ring=0), dict(unclamped=1, **scan(SCAN_EXACT, 32, 10, 5, 110320, offset=60304, map_bytes=103 * 112 * 2))),
     (held(sink_ring=0), dict(unclamped=0, **scan(SCAN_EXACT, 32, 16, 13, 151952, pow2res=0, offset=53248, map_bytes=40896))),
     (held(sink_ring=0, debug_flags=NO_SCAN_KERNEL), dict(unclamped=0, **pipe(1, 8, 1, 121120, 40896, 1, pow2res=0))),
-    # a start cell OUTSIDE the map passes as long as the sink ring is as wide as a step -- today's answer (1),
-    # kept here so that the fix is this row flipped
-    (held(x0=-5.0, y0=-5.0), dict(unclamped=1)),
+    # a start cell OUTSIDE the map: the ring stops who enters it, not who begins beyond it, and the unclamped address
+    # saturates at 0 only -- the clamped address, whatever the ring (this row said 1 until the start cell was looked at;
+    # on the GPU: tests/test_gpu_border.py)
+    # (its window: the 123 cells of reach around cell -18, clipped at row 0 / column 0)
+    (held(x0=-5.0, y0=-5.0), dict(window(106, 112), unclamped=0, **scan(SCAN_EXACT, 32, 16, 13, 151952, pow2res=0, offset=53248, map_bytes=106 * 112 * 2))),
+    (held(x0=-5.0, y0=-5.0, debug_flags=NO_SCAN_KERNEL), dict(window(106, 112), unclamped=0, **pipe(1, 8, 1, pipe_lds(100, 106, 112, 1, 8, 1), 106 * 112 * 2, 1, pow2res=0))),
+    # ... the map is 260 x 260 cells of 0.25 m from -0.5 m: the last cell inside begins at 64.25 m, the first one outside
+    # at 64.5 m on the high sides and just below -0.5 m on the low sides
+    (held(x0=64.49, y0=64.49), dict(unclamped=1, **{"s.pow2res": 1})),
+    (held(x0=-0.5, y0=-0.5), dict(unclamped=1, **{"s.pow2res": 1})),
+    (held(x0=64.5), dict(unclamped=0, **{"s.pow2res": 0})),
+    (held(y0=64.5), dict(unclamped=0, **{"s.pow2res": 0})),
+    (held(x0=-0.51), dict(unclamped=0, **{"s.pow2res": 0})),
+    (held(y0=-0.51), dict(unclamped=0, **{"s.pow2res": 0})),
+    # ... a batched handle: every problem's start counts (px, py), beside the handle's own
+    (batch(64, px=63.0, py=63.0), dict(unclamped=1, **{"s.pow2res": 1})),
+    (batch(64, px=64.5, py=10.0), dict(unclamped=0, **{"s.pow2res": 0})),
+    (batch(64, px=10.0, py=-0.75), dict(unclamped=0, **{"s.pow2res": 0})),
+    (batch(256, px=70.0, py=70.0), dict(window(247, 256, origins=1, pr0=13, pc0=8), unclamped=0, **pipe(1, 8, 0, 155488, 126464, 256, pow2res=0))),
+    # ... the speed-map form of the time-parallel kernel has no unclamped address: the flag is its cell arithmetic alone
+    (held(mode=SPEED, x0=70.0, y0=70.0), dict(unclamped=0, **{"s.pow2res": 1, "s.speed": 1})),
     # a reach that is not finite: the whole map, no progressive copy, the clamped address; a failed tile by one wave
     (held(v_hi=INF), dict(window(260, 264, progressive=0, step_milli=0), finite=0, unclamped=0, **scan(SCAN_EXACT, 32, 16, 13, 151952, pow2res=0))),
     # a resolution that is no power of two (same cells: the origin and the speed scaled with it)
