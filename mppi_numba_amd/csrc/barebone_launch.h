@@ -7,7 +7,9 @@
 // The KD forms are chosen by the LARGEST problem's count; a smaller problem's slots past its own count hold the far,
 // radius-0 disc (+0.0 added), so every problem keeps the bits of its own single-problem launch.
 // The crowd family, k_rollout_barebone_crowd (rollout_crowd_kernel.h): crowd mode from kCrowdMinDiscs discs on, for sets
-// that do not fit in LDS, and for every launch with walls.
+// that do not fit in LDS, and for every launch with walls, disc samples, a body footprint or clearance rings.  Which of its
+// forms runs is crowd_form's answer (barebone_plan.h: the table of forms and the rules); launch_barebone_crowd builds the
+// kernel's argument pack from it once, one crowd_append step per optional argument.
 #pragma once
 
 #include <type_traits>
@@ -82,26 +84,13 @@ static int launch_barebone_default(mppi_planner* p, DevParams d, const BareboneC
 
 // W waves per workgroup and C steps per chunk.  One tile is one workgroup whatever W is, so few tiles (N = 1000: 16 on
 // 256 CUs) get the whole 16 waves -- 14 counters -- and a launch that fills the device on its own gets fewer: about 32
-// waves per CU in all.  C: the largest multiple of the counters within kCrowdChunkMax, every counter the same share.
+// waves per CU in all.  C: crowd_chunk (barebone_plan.h).
 static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
   const int tiles = ceil_div(p->n_local, 64);
   const int W = std::min(kCrowdWavesMax, std::max(4, (32 * p->num_cus) / tiles));
   *waves = W;
-  *chunk = (kCrowdChunkMax / std::min(W - 2, kCrowdChunkMax)) * std::min(W - 2, kCrowdChunkMax);
+  *chunk = crowd_chunk(W);
 }
-// (barebone_plan.h restates the chunk and the LDS formula for the host: a sample form's chunk is chosen there)
-static_assert(kCrowdChunkSteps == kCrowdChunkMax, "barebone_plan.h and rollout_crowd_kernel.h disagree on the chunk");
-static_assert(kCrowdFootprintMax * 3 == sizeof(mppi_planner::fp_host) / sizeof(float), "handles.h and rollout_crowd_kernel.h disagree on the footprint");
-static_assert(crowd_lds_bytes(37, 14, true, 3, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 &&
-                  crowd_lds_bytes(100, 16, false, 0, true) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 + 2 * 16 * 64 * 4 + 192,
-              "crowd_lds_bytes: the footprint forms' layout crowd_lds (barebone_plan.h) restates");
-static_assert(kCrowdRingsMax * 2 == sizeof(mppi_planner::ring_host) / sizeof(float), "handles.h and rollout_crowd_kernel.h disagree on the rings");
-static_assert(crowd_lds_bytes(37, 14, true, 0, true, 4) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192 &&
-                  crowd_lds_bytes(100, 16, false, 0, false, 1) == 16 * 100 + 2 * 16 * 64 * (8 + 8) + 2 * 16 * 2 * 64 * 2 + 8,
-              "crowd_lds_bytes: the ring forms' layout crowd_lds (barebone_plan.h) restates");
-static_assert(crowd_lds_bytes(37, 14, true, 3) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 &&
-                  crowd_lds_bytes(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8,
-              "crowd_lds_bytes: the layout crowd_lds (barebone_plan.h) restates");
 
 // The wall tracks as a launch takes them: the user's (rows counted from the problem's track offset), or in fleet mode the
 // sets the library makes of the other problems' plans (fleet_kernels.h; rows counted from "now": relative = 1).
@@ -115,16 +104,18 @@ static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
                          own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size(), 0};
 }
 
-// The crowd family: k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, wall argument, goal argument>.
-// The disc set: the tracks ([row][disc] copy), a problem's own static set, or the shared one.  The wall form of the
-// choice: 1, static walls shared by the problems (CrowdWalls), whatever the discs are; 2, wall tracks and per-problem sets
-// (CrowdWallTracks) -- they come first: while they are held the static walls rest -- and fleet mode, which takes the same
-// form with the sets it makes itself, the static walls copied into them.  A goal that moves: one GoalRows argument
-// more, behind the walls'.  Disc samples (mppi_planner_set_disc_track_samples): the sample forms, one CrowdSamples argument
-// at the end -- TRACKS forms over the [row][sample][disc] copy, with the chunk and the LDS of the choice.  A body footprint
-// (mppi_planner_set_footprint): the footprint forms, one CrowdFootprint argument behind everything else -- TRACKS forms
-// whatever the discs are (static discs: tracks of one row, DevParams::track_rows = 1, as the default family's goal forms
-// take them), static shared walls as wall tracks of one row, with or without a CrowdSamples argument.
+// Static shared walls as wall tracks of one row (the sample, footprint and ring forms): their [wall] array IS the
+// [row][wall] array of one row.
+static CrowdWallTracks wall_row_arg(const mppi_planner* p) {
+  return CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0};
+}
+
+// The disc samples as a launch takes them: the CVaR tail's length, and where the per-sample costs go while they are wanted.
+static CrowdSamples samples_arg(const mppi_planner* p, const BareboneChoice& c, const DevParams& d) {
+  return CrowdSamples{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(c.samples, d.cvar_alpha)};
+}
+
+// The body footprint as a launch takes it.
 static CrowdFootprint footprint_arg(const mppi_planner* p) {
   CrowdFootprint fp{};
   fp.count = p->fp_count;
@@ -150,143 +141,91 @@ static CrowdRings rings_arg(const mppi_planner* p) {
   return rg;
 }
 
+// The form a TRACKS flag and a pack of argument types name, and one optional argument of the pack: if the form has it, go on
+// with it appended, else go on without.  An argument that the table (crowd_form_legal) has no form for behind the pack so
+// far is never appended, so no kernel outside the table is ever named.
+template <bool TRACKS, typename... Pack>
+constexpr CrowdForm crowd_form_of() {
+  CrowdForm f;
+  f.tracks = TRACKS;
+  f.walls = kCrowdWallTracks<Pack...> ? kCrowdWallsTracks : ((std::is_same_v<Pack, CrowdWalls> || ...) ? kCrowdWallsStatic : kCrowdWallsNone);
+  f.goal = kGoalRows<Pack...>;
+  f.samples = kCrowdSamples<Pack...>;
+  f.rings = kCrowdRings<Pack...>;
+  f.footprint = kCrowdFootprint<Pack...>;
+  return f;
+}
+template <bool TRACKS, typename Make, typename Next, typename... Pack>
+static int crowd_append(bool has, Make make, Next next, Pack... pack) {
+  if constexpr (crowd_form_legal(crowd_form_of<TRACKS, Pack..., decltype(make())>())) {
+    if (has) return next(pack..., make());
+  }
+  return has ? fail(MPPI_ERR_STATE, "crowd launch: a form outside the table of forms") : next(pack...);
+}
+
+// The crowd family: k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, pack...>.  crowd_form (barebone_plan.h) turns
+// the choice into the form -- the table of forms and every normalisation rule are there -- and the pack is built here once, in
+// its one order: walls, goal, samples or rings, footprint.  The disc set: the tracks ([row][disc] copy), the samples
+// ([row][sample][disc]), a problem's own static set, or the shared one.  The walls: CrowdWalls, static walls shared by the
+// problems; CrowdWallTracks, wall tracks and per-problem sets -- they come first: while they are held the static walls rest --,
+// fleet mode, which takes the same form with the sets it makes itself, the static walls copied into them, and static walls as
+// one row under samples, a footprint or rings.  Those three run with the chunk and the LDS of the choice.
 template <bool EXACT, bool BATCHED>
 static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneChoice& c, bool rot) {
+  const CrowdForm f = crowd_form(c, rot);
+  REQUIRE(!(f.rings && f.samples), MPPI_ERR_STATE, "clearance rings beside disc samples: the hand-over keeps them apart");
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  if (c.samples > 0 || c.footprint > 0 || c.rings > 0) C = c.chunk;  // (a sample form: the chunk of the choice, shrunk to its LDS)
-  const size_t lds = crowd_lds_bytes(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0, c.rings);  // the size launched
-  if (c.rings > 0) {
-    REQUIRE(c.samples == 0, MPPI_ERR_STATE, "clearance rings beside disc samples: the hand-over keeps them apart");
-    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, 0, c.footprint > 0, c.rings), MPPI_ERR_STATE,
-            "clearance rings: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
-    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d clearance rings and %d steps: the crowd kernel needs %zu bytes of LDS",
-            c.rings, p->cfg.num_steps, lds);
+  if (f.samples || f.footprint || f.rings) C = c.chunk;  // (the chunk of the choice: a sample form's shrinks to its LDS)
+  const size_t lds = crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0, c.rings);
+  const bool fits = lds <= (size_t)p->lds_per_cu;
+  if (f.rings)
+    REQUIRE(fits, MPPI_ERR_INVALID, "%d clearance rings and %d steps: the crowd kernel needs %zu bytes of LDS", c.rings, p->cfg.num_steps, lds);
+  else if (f.footprint)
+    REQUIRE(fits, MPPI_ERR_INVALID, "a footprint and %d steps: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
+  else if (f.samples)
+    REQUIRE(fits, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS", c.samples, p->cfg.num_steps, lds);
+  if (f.rings || f.samples) {  // (their counts of a step are 16 bits wide)
     const int walls = c.walls == 2 ? (p->fleet_on ? p->fleet_slots : p->wtrk_max) : (c.walls == 1 ? p->n_walls : 0);
-    REQUIRE((long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
-            "clearance rings: %d discs and %d walls, more than the %d a step's 16-bit counter holds", c.kmax, walls, kCrowdSampleHitsMax);
-    if (c.discs != kDiscsTracks) d.track_rows = 1;  // (static discs: tracks of one row)
+    const bool counted = (long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax;
+    if (f.rings)
+      REQUIRE(counted, MPPI_ERR_INVALID, "clearance rings: %d discs and %d walls, more than the %d a step's 16-bit counter holds", c.kmax,
+              walls, kCrowdSampleHitsMax);
+    else
+      REQUIRE(counted, MPPI_ERR_INVALID, "disc samples: %d discs and %d walls, more than the %d hits a step's 16-bit counter holds",
+              c.kmax, walls, kCrowdSampleHitsMax);
   }
-  if (c.footprint > 0) {
-    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, true, c.rings), MPPI_ERR_STATE,
-            "footprint: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
-    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "a footprint and %d steps: the crowd kernel needs %zu bytes of LDS",
-            p->cfg.num_steps, lds);
-    if (c.discs != kDiscsTracks && c.discs != kDiscsSamples) d.track_rows = 1;  // (static discs: tracks of one row)
-  }
-  if (c.samples > 0) {
-    REQUIRE(lds == c.lds && lds == crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0), MPPI_ERR_STATE,
-            "disc samples: the choice and the kernel disagree on the LDS (%zu, %zu bytes)", c.lds, lds);
-    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS",
-            c.samples, p->cfg.num_steps, lds);
-    const int walls = c.walls == 2 ? (p->fleet_on ? p->fleet_slots : p->wtrk_max) : (c.walls == 1 ? p->n_walls : 0);
-    REQUIRE((long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
-            "disc samples: %d discs and %d walls, more than the %d hits a step's 16-bit counter holds", c.kmax, walls, kCrowdSampleHitsMax);
-    if (p->want_sample_costs && !p->sample_costs) TRY(dev_alloc(&p->sample_costs, (size_t)p->n_local * (size_t)kCrowdSamplesMax));
-  }
+  if (f.samples && p->want_sample_costs && !p->sample_costs) TRY(dev_alloc(&p->sample_costs, (size_t)p->n_local * (size_t)kCrowdSamplesMax));
   if (c.walls == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
   if (c.walls != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
-    REQUIRE(lds <= (size_t)p->lds_per_cu, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
+    REQUIRE(fits, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
+  if (f.disc_row) d.track_rows = 1;
   const bool tracks = c.discs == kDiscsTracks;
   const float2* pos = barebone_disc_pos(p, c);
   const float* rad = barebone_disc_rad(p, c);
   const int pitch = c.samples > 0 ? c.samples * c.kmax : (tracks ? (int)p->trk_r_host.size() : 0);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
-  auto launch = [&](auto kern, auto... extra) -> int {
-    if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, extra...);
-    return MPPI_OK;
-  };
   auto dispatch = [&](auto rot_c, auto tracks_c) -> int {
-    constexpr bool ROT = EXACT && decltype(rot_c)::value, TRACKS = decltype(tracks_c)::value;
-    auto with_walls = [&](auto... walls) -> int {  // (without walls: the kernel and its arguments as they were before there were any)
-      constexpr bool WALLS = sizeof...(walls) > 0;
-      if (c.goal_form)
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, decltype(walls)..., GoalRows>, walls..., goal_rows_arg<BATCHED>(p));
-      return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, decltype(walls)...>, walls...);
+    constexpr bool ROT = decltype(rot_c)::value, TRACKS = decltype(tracks_c)::value;
+    auto launch = [&](auto... pack) -> int {  // (without walls: the kernel and its arguments as they were before there were any)
+      constexpr bool WALLS = crowd_form_of<TRACKS, decltype(pack)...>().walls != kCrowdWallsNone;
+      const auto kern = &k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, decltype(pack)...>;
+      if (lds > 64 * 1024)  // (a horizon of more than ~1500 steps)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, pack...);
+      return MPPI_OK;
     };
-    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
-    if (c.walls == 1) return with_walls(CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls});
-    return with_walls();
+    auto footprint = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.footprint, [&] { return footprint_arg(p); }, launch, pack...); };
+    auto rings = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.rings, [&] { return rings_arg(p); }, footprint, pack...); };
+    auto samples = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.samples, [&] { return samples_arg(p, c, d); }, rings, pack...); };
+    auto goal = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.goal, [&] { return goal_rows_arg<BATCHED>(p); }, samples, pack...); };
+    if (f.walls == kCrowdWallsTracks) return goal(f.wall_row ? wall_row_arg(p) : wall_tracks_arg<BATCHED>(p));
+    if (f.walls == kCrowdWallsStatic) return goal(CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls});
+    return goal();
   };
-  // disc samples: TRACKS forms with one CrowdSamples behind the other arguments; static shared walls as wall tracks of one
-  // row (their [wall] array IS the [row][wall] array of one row)
-  auto dispatch_samples = [&](auto rot_c) -> int {
-    constexpr bool ROT = EXACT && decltype(rot_c)::value;
-    const CrowdSamples smp{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(c.samples, d.cvar_alpha)};
-    auto with_walls = [&](auto... walls) -> int {
-      constexpr bool WALLS = sizeof...(walls) > 0;
-      if (c.goal_form)
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdSamples>, walls...,
-                      goal_rows_arg<BATCHED>(p), smp);
-      return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdSamples>, walls..., smp);
-    };
-    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
-    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
-    return with_walls();
-  };
-  // a body footprint: TRACKS forms with one CrowdFootprint at the very end; the walls as the sample forms take them
-  auto dispatch_footprint = [&](auto rot_c, auto samples_c) -> int {
-    constexpr bool ROT = EXACT && decltype(rot_c)::value, SMP = decltype(samples_c)::value;
-    const CrowdFootprint fp = footprint_arg(p);
-    const CrowdSamples smp{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(std::max(c.samples, 1), d.cvar_alpha)};
-    auto with_walls = [&](auto... walls) -> int {
-      constexpr bool WALLS = sizeof...(walls) > 0;
-      if constexpr (SMP) {
-        if (c.goal_form)
-          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdSamples, CrowdFootprint>,
-                        walls..., goal_rows_arg<BATCHED>(p), smp, fp);
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdSamples, CrowdFootprint>, walls..., smp, fp);
-      } else {
-        if (c.goal_form)
-          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdFootprint>, walls...,
-                        goal_rows_arg<BATCHED>(p), fp);
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdFootprint>, walls..., fp);
-      }
-    };
-    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
-    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
-    return with_walls();
-  };
-  // clearance rings: TRACKS forms with one CrowdRings behind the goal rows and, with a body footprint, one CrowdFootprint
-  // behind that; the walls as the sample forms take them
-  auto dispatch_rings = [&](auto rot_c, auto foot_c) -> int {
-    constexpr bool ROT = EXACT && decltype(rot_c)::value, FOOT = decltype(foot_c)::value;
-    const CrowdRings rg = rings_arg(p);
-    auto with_walls = [&](auto... walls) -> int {
-      constexpr bool WALLS = sizeof...(walls) > 0;
-      if constexpr (FOOT) {
-        const CrowdFootprint fp = footprint_arg(p);
-        if (c.goal_form)
-          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdRings, CrowdFootprint>,
-                        walls..., goal_rows_arg<BATCHED>(p), rg, fp);
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdRings, CrowdFootprint>, walls..., rg, fp);
-      } else {
-        if (c.goal_form)
-          return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., GoalRows, CrowdRings>, walls...,
-                        goal_rows_arg<BATCHED>(p), rg);
-        return launch(&k_rollout_barebone_crowd<EXACT, ROT, BATCHED, true, WALLS, decltype(walls)..., CrowdRings>, walls..., rg);
-      }
-    };
-    if (c.walls == 2) return with_walls(wall_tracks_arg<BATCHED>(p));
-    if (c.walls == 1) return with_walls(CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0});
-    return with_walls();
-  };
-  if (c.rings > 0 && c.footprint > 0 && rot) TRY(dispatch_rings(std::true_type(), std::true_type()));
-  else if (c.rings > 0 && c.footprint > 0) TRY(dispatch_rings(std::false_type(), std::true_type()));
-  else if (c.rings > 0 && rot) TRY(dispatch_rings(std::true_type(), std::false_type()));
-  else if (c.rings > 0) TRY(dispatch_rings(std::false_type(), std::false_type()));
-  else if (c.footprint > 0 && c.samples > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::true_type()));
-  else if (c.footprint > 0 && c.samples > 0) TRY(dispatch_footprint(std::false_type(), std::true_type()));
-  else if (c.footprint > 0 && rot) TRY(dispatch_footprint(std::true_type(), std::false_type()));
-  else if (c.footprint > 0) TRY(dispatch_footprint(std::false_type(), std::false_type()));
-  else if (c.samples > 0 && rot) TRY(dispatch_samples(std::true_type()));
-  else if (c.samples > 0) TRY(dispatch_samples(std::false_type()));
-  else if (rot && tracks) TRY(dispatch(std::true_type(), std::true_type()));
-  else if (rot) TRY(dispatch(std::true_type(), std::false_type()));
-  else if (tracks) TRY(dispatch(std::false_type(), std::true_type()));
-  else TRY(dispatch(std::false_type(), std::false_type()));
+  auto with_tracks = [&](auto rot_c) -> int { return f.tracks ? dispatch(rot_c, std::true_type()) : dispatch(rot_c, std::false_type()); };
+  if constexpr (EXACT) TRY(f.rot ? with_tracks(std::true_type()) : with_tracks(std::false_type()));
+  else TRY(with_tracks(std::false_type()));  // (ROT is exact math's alone: launch_rollout_t grants rot under it only)
   const bool fleet = c.walls == 2 && p->fleet_on;
   p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
                     " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +

@@ -28,31 +28,46 @@ inline size_t barebone_lds(int T, int slots, bool track_form, bool goal_form, in
   return 16 * (size_t)T + (track_form ? (size_t)T * row : row) + (goal_form ? 8 * (size_t)T : 0) + 16 * (size_t)spare_slots;
 }
 
-// Disc samples (mppi_planner_set_disc_track_samples; rollout_crowd_kernel.h): S sampled futures of the moving discs, the
-// rollout's cost the CVaR tail over its S costs.  Crowd family only.
+// The limits of the crowd family, k_rollout_barebone_crowd (rollout_crowd_kernel.h): defined here, once, for the kernel, the
+// handle (handles.h) and the host code alike.
+constexpr int kCrowdChunkMax = 16;          // steps per chunk at the most (the walker keeps a chunk's noise in registers)
+// Disc samples (mppi_planner_set_disc_track_samples): S sampled futures of the moving discs, the rollout's cost the CVaR tail
+// over its S costs.  Crowd family only.
 constexpr int kCrowdSamplesMax = 16;
-constexpr int kCrowdSampleHitsMax = 65535;  // the sample forms count a step's hits in 16 bits: discs + walls at the most
-constexpr int kCrowdChunkSteps = 16;        // (kCrowdChunkMax of rollout_crowd_kernel.h)
+constexpr int kCrowdSampleHitsMax = 65535;  // the sample and ring forms count a step's hits in 16 bits: discs + walls at the most
 constexpr size_t kCrowdSampleLdsAim = 64 * 1024;  // the chunk of a sample form shrinks towards this
+constexpr int kCrowdFootprintMax = 8;       // body footprint (mppi_planner_set_footprint): discs at the most
+constexpr int kCrowdRingsMax = 4;           // clearance rings (mppi_planner_set_clearance_rings): rows at the most
 
-// The dynamic LDS of k_rollout_barebone_crowd in bytes (crowd_lds_bytes of rollout_crowd_kernel.h, restated for the host):
-//   [T] double2 control ratios | [2][C][64] double goal distance | [2][C (+ 1 with walls)][64] float2 position |
-//   [2][C][64] int hits | two "tile done" words                                        the plain forms (samples = 0)
-//   ... | [2][C][S][64] uint16 hits | two words | [S][64] float running costs          the sample forms
-//   ... | [2][C (+ 1 with walls)][64] float heading | [3][8] double footprint rows     the footprint forms (behind all of that)
+// The dynamic LDS of k_rollout_barebone_crowd in bytes -- the one definition: the choice, the launcher and the kernel's
+// pointer arithmetic (rollout_crowd_kernel.h) all follow this layout:
+//   [T] double2 control ratios | [2][C][64] double goal distance | [2][C (+ 1 with walls)][64] float2 position (with walls,
+//   slot 0: the chunk's entry position) | [2][C][64] int hits | two "tile done" words    the plain forms (samples = 0)
+//   ... | [2][C][S][64] uint16 hits in place of the int hits | two words | [S][64] float running costs    the sample forms
 //   ... | [2][C][1 + R][64] uint16 counts in place of the int hits                     the ring forms (R clearance rings)
-inline size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false, int rings = 0) {
+//   ... | [2][C (+ 1 with walls)][64] float heading, slot for slot beside the positions | [3][8] double, the footprint's
+//   rows (ox | oy | rho)                                                               the footprint forms (behind all of that)
+constexpr size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false, int rings = 0) {
   const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4
                       : rings > 0 ? (size_t)2 * C * (1 + rings) * 64 * 2 : (size_t)2 * C * 64 * 4;
   const size_t heading = footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 4 + 3 * 8 * 8 : 0;
   return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8 + heading;
 }
+static_assert(crowd_lds(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 &&
+                  crowd_lds(50, 14, true) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 64 * 4 + 8 &&
+                  crowd_lds(50, 14, true, 2) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 2 * 64 * 2 + 2 * 64 * 4 + 8 &&
+                  crowd_lds(37, 14, true, 3) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 &&
+                  crowd_lds(100, 16, false, 0, true) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 + 2 * 16 * 64 * 4 + 192 &&
+                  crowd_lds(37, 14, true, 3, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 &&
+                  crowd_lds(100, 16, false, 0, false, 1) == 16 * 100 + 2 * 16 * 64 * (8 + 8) + 2 * 16 * 2 * 64 * 2 + 8 &&
+                  crowd_lds(37, 14, true, 0, true, 4) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192,
+              "crowd_lds: the layout above, byte for byte -- plain, sample, footprint and ring forms");
 
-// C steps per chunk for a workgroup of W waves: the largest multiple of the W - 2 counters within kCrowdChunkSteps, every
+// C steps per chunk for a workgroup of W waves: the largest multiple of the W - 2 counters within kCrowdChunkMax, every
 // counter the same share.  A sample form gives up whole shares while its LDS is above kCrowdSampleLdsAim (one share stays).
 inline int crowd_chunk(int W, int T = 0, bool walls = false, int samples = 0, bool footprint = false) {
-  const int counters = std::min(std::max(W - 2, 1), kCrowdChunkSteps);
-  int C = (kCrowdChunkSteps / counters) * counters;
+  const int counters = std::min(std::max(W - 2, 1), kCrowdChunkMax);
+  int C = (kCrowdChunkMax / counters) * counters;
   while (samples > 0 && C > counters && crowd_lds(T, C, walls, samples, footprint) > kCrowdSampleLdsAim) C -= counters;
   return C;
 }
@@ -110,7 +125,7 @@ inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
 // moves runs the track forms (static discs as tracks of one row).  The KD forms are chosen by the largest problem's count
 // under rotation; a track form whose padded row does not fit falls back to the loop over the problem's own row.
 // Disc samples are a disc source of the crowd family alone: they take the place of the tracks, run as TRACKS forms, and
-// take static shared walls as wall tracks of one row (walls = 1 stays the choice; the launcher makes the argument).
+// take static shared walls as wall tracks of one row (walls = 1 stays the choice; crowd_form, below, names the argument).
 // A body footprint (mppi_planner_set_footprint) is the crowd family's alone as well: a handle that holds one always goes
 // there, whatever it holds otherwise -- no discs and no walls included --, and launches a footprint form: a TRACKS form, static
 // discs as tracks of one row, static shared walls as wall tracks of one row, with the chunk and the LDS of the choice.
@@ -178,4 +193,48 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
     c.limit = c.goal_form ? kLimitGoalTrack : (c.track_form ? kLimitDiscTracks : kLimitStaticDiscs);
   }
   return c;
+}
+
+// The form of a crowd launch: which instantiation of k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, pack...>
+// a choice of the crowd family runs, and what the launcher (launch_barebone_crowd of barebone_launch.h) does to the
+// arguments on the way.  The pack is in one order -- walls, goal, samples or rings, footprint:
+//   walls      kCrowdWallsStatic: one CrowdWalls; kCrowdWallsTracks: one CrowdWallTracks; none: no argument, WALLS = false
+//   goal       one GoalRows
+//   samples    one CrowdSamples
+//   rings      one CrowdRings (never beside samples: the hand-over keeps them apart)
+//   footprint  one CrowdFootprint
+// and THE TABLE OF FORMS is crowd_form_legal: every combination of ROT, TRACKS, the wall kind and the goal without samples,
+// rings and footprint (12 per ROT), and under any of those three TRACKS forms only, never CrowdWalls (2 wall kinds x goal x
+// {samples, rings, neither} x footprint, less the plain one: 20 per ROT).  ROT exists under exact math only, so the library
+// holds 64 forms per BATCHED with EXACT and 32 without: 192.  tests/test_barebone_form_plan.py pins the table.
+enum CrowdWallKind { kCrowdWallsNone = 0, kCrowdWallsStatic = 1, kCrowdWallsTracks = 2 };
+struct CrowdForm {
+  bool rot = false;     // ROT: (cos, sin) by rotation
+  bool tracks = false;  // TRACKS: the discs as rows, one per step
+  CrowdWallKind walls = kCrowdWallsNone;
+  bool goal = false, samples = false, rings = false, footprint = false;
+  bool disc_row = false;  // static discs run as tracks of one row: DevParams::track_rows = 1
+  bool wall_row = false;  // static shared walls run as wall tracks of one row: their [wall] array is the [row][wall] array
+};
+constexpr bool crowd_form_legal(const CrowdForm& f) {
+  const bool extra = f.samples || f.rings || f.footprint;
+  return !(f.samples && f.rings) && (!extra || (f.tracks && f.walls != kCrowdWallsStatic));
+}
+
+// The normalisation rules.  Samples, a footprint and rings run as TRACKS forms: static discs become tracks of one row (the
+// samples are rows already), static shared walls wall tracks of one row.  rot: (cos, sin) by rotation -- launch_rollout_t
+// grants it under exact math only.  A choice with rings beside samples maps to a form that is not legal; the launcher refuses.
+inline CrowdForm crowd_form(const BareboneChoice& c, bool rot) {
+  CrowdForm f;
+  f.rot = rot;
+  f.goal = c.goal_form;
+  f.samples = c.samples > 0;
+  f.rings = c.rings > 0;
+  f.footprint = c.footprint > 0;
+  const bool extra = f.samples || f.rings || f.footprint;
+  f.tracks = c.discs == kDiscsTracks || extra;
+  f.disc_row = extra && c.discs != kDiscsTracks && c.discs != kDiscsSamples;
+  f.wall_row = extra && c.walls == 1;
+  f.walls = c.walls == 0 ? kCrowdWallsNone : (c.walls == 2 || extra ? kCrowdWallsTracks : kCrowdWallsStatic);
+  return f;
 }

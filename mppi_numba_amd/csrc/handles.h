@@ -4,6 +4,7 @@
 #include "map_plan.h"
 #include "noise_plan.h"
 #include "cvar_plan.h"
+#include "barebone_plan.h"
 
 // ---------------------------------------------------------------------------
 // TDM
@@ -309,13 +310,13 @@ struct mppi_planner {
   // the crowd kernel, which takes the rows by value (CrowdFootprint).  fp_gen: next_generation() at every change, 0 while
   // none is held -- what the graph signature holds of it
   int fp_count = 0;
-  float fp_host[8 * 3] = {};  // what was handed over: [disc][3]
+  float fp_host[kCrowdFootprintMax * 3] = {};  // what was handed over: [disc][3]
   uint64_t fp_gen = 0;
   // clearance rings (mppi_planner_set_clearance_rings; crowd mode only, and not beside disc samples): ring_count rows
   // (margin, penalty), one set for every problem.  While ring_count > 0 every rollout launch is a ring form of the crowd
   // kernel, which takes the rows by value (CrowdRings).  ring_gen: as fp_gen
   int ring_count = 0;
-  float ring_host[4 * 2] = {};  // what was handed over: [ring][2]
+  float ring_host[kCrowdRingsMax * 2] = {};  // what was handed over: [ring][2]
   uint64_t ring_gen = 0;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state

@@ -139,37 +139,15 @@
 #pragma once
 #include <type_traits>
 
+#include "barebone_plan.h"
 #include "crowd_fold.h"
 #include "rollout_kernels.h"
 
 namespace mppi {
 
-constexpr int kCrowdChunkMax = 16;   // steps per chunk at the most (the walker keeps a chunk's noise in registers)
+// kCrowdChunkMax, kCrowdFootprintMax, kCrowdRingsMax and the dynamic LDS -- crowd_lds(T, C, walls, samples, footprint,
+// rings), its layout drawn beside it -- are barebone_plan.h's: the kernel's pointers below walk that layout.
 constexpr int kCrowdWavesMax = 16;   // one workgroup: 1024 threads
-// dynamic LDS: [T] double2 control ratios | [2][C][64] double goal distance | [2][C][64] float2 position |
-// [2][C][64] int hits | two "tile done" words.  walls: [2][C + 1][64] positions (slot 0: the chunk's entry position)
-// disc samples (S > 0): [2][C][S][64] uint16 hits in place of the int hits, and [S][64] float running costs at the end
-// a body footprint: [2][C (+ 1 with walls)][64] float headings behind all of that, slot for slot beside the positions, and
-// [3][8] double, the footprint's rows (ox | oy | rho), behind them
-// clearance rings (R > 0, no samples): [2][C][1 + R][64] uint16 counts in place of the int hits
-__host__ __device__ constexpr size_t crowd_lds_bytes(int T, int C, bool walls = false, int samples = 0, bool footprint = false,
-                                                     int rings = 0) {
-  return sizeof(double2) * (size_t)T + (size_t)2 * C * 64 * sizeof(double) +
-         (samples > 0 ? (size_t)2 * C * samples * 64 * sizeof(unsigned short) + (size_t)samples * 64 * sizeof(float)
-          : rings > 0 ? (size_t)2 * C * (1 + rings) * 64 * sizeof(unsigned short)
-                      : (size_t)2 * C * 64 * sizeof(int)) +
-         (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float2) + 2 * sizeof(int) +
-         (footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * sizeof(float) + 3 * 8 * sizeof(double) : 0);
-}
-static_assert(crowd_lds_bytes(50, 14, true, 0) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 14 * 64 * 4 + 2 * 15 * 64 * 8 + 8 &&
-                  crowd_lds_bytes(50, 14, true, 2) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 14 * 2 * 64 * 2 + 2 * 64 * 4 + 2 * 15 * 64 * 8 + 8 &&
-                  crowd_lds_bytes(50, 16, false, 0, true) == crowd_lds_bytes(50, 16, false) + 2 * 16 * 64 * 4 + 192 &&
-                  crowd_lds_bytes(50, 14, true, 2, true) == crowd_lds_bytes(50, 14, true, 2) + 2 * 15 * 64 * 4 + 192,
-              "crowd_lds_bytes: without a footprint the layout as it was; with one, the heading plane and the rows on top of it");
-static_assert(crowd_lds_bytes(50, 14, true, 0, false, 0) == crowd_lds_bytes(50, 14, true) &&
-                  crowd_lds_bytes(50, 14, true, 0, false, 1) == crowd_lds_bytes(50, 14, true) &&
-                  crowd_lds_bytes(50, 14, true, 0, true, 4) == crowd_lds_bytes(50, 14, true, 0, true) + 2 * 14 * 64 * (5 * 2 - 4),
-              "crowd_lds_bytes: without rings the layout as it was; with R of them, 1 + R counts of 16 bits where the int hits were");
 
 // The walls of a launch (WALLS): seg[k] = (ax, ay, bx, by), halfwidth[k]; shared by every problem of a batch.
 struct CrowdWalls {
@@ -205,7 +183,6 @@ struct CrowdSamples {
 // group = 1, grouped = 0: every wall counts for itself.
 // (The rows are a struct of their own: a form without a footprint holds an empty CrowdFootprintRows where it always did,
 // and compiles to the code it compiled to before the two integers were there.)
-constexpr int kCrowdFootprintMax = 8;
 struct CrowdFootprintRows {
   double ox[kCrowdFootprintMax], oy[kCrowdFootprintMax], rho[kCrowdFootprintMax];  // (the float32 rows, widened on the host)
   int count;
@@ -215,7 +192,6 @@ struct CrowdFootprint : CrowdFootprintRows {
 };
 
 // The clearance rings of a launch: `count` rows (margin, penalty), the float32 rows widened on the host; margins ascending.
-constexpr int kCrowdRingsMax = 4;
 struct CrowdRings {
   int count;
   double margin[kCrowdRingsMax], penalty[kCrowdRingsMax];
@@ -417,33 +393,31 @@ __device__ __forceinline__ void crowd_body_wall_ring_hits(const double* rows, in
   for (int q = 0; q <= kCrowdRingsMax; ++q) n[q] += crowd_fold_count(mask[q], group, span);  // (a level past the last: an empty mask)
 }
 
-// obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.
+// The optional arguments of the kernel, one accessor each.  The walls, if there are any, are the first of the pack.
+// (obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.)
+template <typename Arg>
+constexpr bool kCrowdWallArg = std::is_same_v<Arg, CrowdWalls> || std::is_same_v<Arg, CrowdWallTracks>;
 __device__ __forceinline__ CrowdWalls crowd_walls_of() { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls) { return walls; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdWalls& walls, const GoalRows&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&) { return walls; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdSamples&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdSamples&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&) { return walls; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdSamples&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdSamples&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdFootprint&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdFootprint&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdSamples&, const CrowdFootprint&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdSamples&, const CrowdFootprint&) { return walls; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdRings&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdRings&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const CrowdRings&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWalls crowd_walls_of(const GoalRows&, const CrowdRings&, const CrowdFootprint&) { return CrowdWalls{nullptr, nullptr, 0}; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdRings&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdRings&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const CrowdRings&, const CrowdFootprint&) { return walls; }
-__device__ __forceinline__ CrowdWallTracks crowd_walls_of(const CrowdWallTracks& walls, const GoalRows&, const CrowdRings&, const CrowdFootprint&) { return walls; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ auto crowd_walls_of(const First& first, const Rest&...) {
+  if constexpr (kCrowdWallArg<First>) return first;
+  else return crowd_walls_of();
+}
+// The one order of the pack: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint -- each at most once, nothing else.
+template <typename Arg>
+constexpr int kCrowdArgRank = kCrowdWallArg<Arg> ? 0 : std::is_same_v<Arg, GoalRows> ? 1
+                              : (std::is_same_v<Arg, CrowdSamples> || std::is_same_v<Arg, CrowdRings>) ? 2
+                              : std::is_same_v<Arg, CrowdFootprint> ? 3 : -1;
+template <typename... WallArgs>
+constexpr bool crowd_pack_in_order() {
+  const int ranks[] = {kCrowdArgRank<WallArgs>..., 4};
+  int before = -1;
+  for (int r : ranks) {
+    if (r <= before) return false;
+    before = r;
+  }
+  return true;
+}
 template <typename... WallArgs>
 constexpr bool kCrowdRings = (std::is_same_v<WallArgs, CrowdRings> || ...);
 __device__ __forceinline__ CrowdRings crowd_rings_of() { return CrowdRings{0, {}, {}}; }
@@ -471,11 +445,14 @@ __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, con
   else return crowd_samples_of(rest...);
 }
 
-// WallArgs: nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
-// shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets); behind it, with a goal
-// that moves, one GoalRows; behind that, with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls) or, with clearance
-// rings, one CrowdRings (TRACKS, no CrowdWalls, no CrowdSamples); at the very end, with a body footprint, one CrowdFootprint
-// (TRACKS, and no CrowdWalls).
+// WallArgs, the optional arguments, in the one order crowd_pack_in_order polices -- the table of the forms that exist is
+// crowd_form_legal (barebone_plan.h), and launch_barebone_crowd (barebone_launch.h) builds the pack from it:
+//   walls      nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
+//              shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets)
+//   goal       with a goal that moves, one GoalRows
+//   samples    with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls), or
+//   rings      with clearance rings, one CrowdRings (TRACKS, no CrowdWalls, no CrowdSamples)
+//   footprint  with a body footprint, one CrowdFootprint (TRACKS, and no CrowdWalls)
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
@@ -488,6 +465,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                 "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; disc samples: "
                 "one CrowdSamples behind that, or clearance rings: one CrowdRings; a body footprint: one CrowdFootprint "
                 "behind that; else none");
+  static_assert(crowd_pack_in_order<WallArgs...>(), "the pack's order: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
   static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
   static_assert(!FOOT || (TRACKS && WTRK == WALLS), "a body footprint: TRACKS forms, walls as CrowdWallTracks");
