@@ -1,112 +1,110 @@
-// Crowd mode of the barebone rollout (mppi_planner_set_crowd): disc sets of any size, read from memory.
+// Crowd mode of the barebone rollout (mppi_planner_set_crowd): disc sets of any size, read from memory -- and every obstacle
+// kind that is counted rather than summed: walls, clearance rings, a body footprint, sampled futures of the discs.
 //
-// k_rollout_barebone keeps a row of disc slots per step in LDS (64 KiB: 39 moving discs at T = 100) and, above four discs,
-// appends one float32-rounded addition per disc and step to the one dependent chain of a lone wave.  Three facts let the
-// discs leave that chain without changing a bit of the result:
-//   - a rollout's state never depends on the discs,
-//   - a disc that is not hit adds +0.0 -- the identity: the running cost is never -0.0 (it starts at +0.0, and a sum is
+// WHY COUNTING IS ENOUGH.  k_rollout_barebone keeps a row of disc slots per step in LDS (64 KiB: 39 moving discs at T = 100)
+// and, above four discs, appends one float32-rounded addition per disc and step to the one dependent chain of a lone wave.
+// Three facts let the obstacles leave that chain without changing a bit of the result:
+//   - a rollout's state never depends on the obstacles,
+//   - an obstacle that is not hit adds +0.0 -- the identity: the running cost is never -0.0 (it starts at +0.0, and a sum is
 //     -0.0 only when both terms are),
-//   - every disc that is hit adds the same (double)obs_cost.
-// So the cost after step t depends on the discs only through HOW MANY of them the post-step position touches, an integer
-// that any number of waves may count in any order.  (obs_cost = +-inf is where the forms part: 0.0 * inf is NaN there.)
+//   - every obstacle that is hit adds the same (double)obs_cost.
+// So the cost after step t depends on the obstacles only through HOW MANY of them the step touches, an integer that any
+// number of waves may count in any order.  (obs_cost = +-inf is where the forms part: 0.0 * inf is NaN there.)
 //
-// One workgroup of W >= 3 waves serves one tile of 64 rollouts of one problem and walks the horizon in chunks of C steps.
-// The three phases of a chunk run on different waves, and the chunks are pipelined through double-buffered LDS -- in
-// interval i of the loop (one barrier per interval):
+// THE PIPELINE.  One workgroup of W >= 3 waves serves one tile of 64 rollouts of one problem and walks the horizon in chunks
+// of C steps.  The three phases of a chunk run on different waves, and the chunks are pipelined through double-buffered
+// LDS (crowd_lds, barebone_plan.h) -- in interval i of the loop, one barrier per interval:
 //   walk   wave 0       chunk i      the state step of k_rollout_barebone (barebone_next_pose), state in registers across
 //                                    chunks; post-step (x, y) -> LDS [step][lane]
-//   count  waves 2..W-1 chunk i-1    counter q takes the chunk's steps j = q, q + (W-2), ...: the lane's position against
-//                                    every disc of the problem at that step (tracks: row min(now + t + 1, last) of the
-//                                    [row][disc] copy, so a step's discs are contiguous) with the double-precision test
-//                                    of k_rollout_barebone; int32 hit count and the goal distance -> LDS [step][lane].
-//                                    A (step, lane) pair has one owner: no atomics.  64 discs at a time: every lane loads
-//                                    one disc (a coalesced load, the next tile's in flight during the tests), the tests
-//                                    read them lane by lane as wave-uniform values.
+//   count  waves 2..W-1 chunk i-1    counter q owns the chunk's steps j = q, q + (W-2), ...: a (step, lane) pair has one
+//                                    owner, so there are no atomics.  Counts and the goal distance -> LDS [step][lane]
 //   cost   wave 1       chunk i-2    the reference's chain: the distance term, then `hits` rounded additions of obs_cost
 //                                    (a wave-uniform loop to the wave's largest count, predicated per lane), then the freeze
 //                                    at the goal
 // and after the last chunk wave 1 adds the terminal term and the T control-cost terms as k_rollout_barebone does.
 // When every rollout of the tile has reached the goal the workgroup stops (what is left of the horizon adds nothing).
 //
-// WALLS (mppi_planner_set_walls): one more source of hits for the count waves, nothing else.  A wall is a segment A -> B
-// with a half-width h >= 0 (float32); step t moves the robot from P (the position before the step, x0 for t = 0) to Q, and
-// it hits the wall iff the distance between the closed segments PQ and AB is <= h: a step that jumps a thin wall is a hit
-// (no tunnelling).  crowd_wall_hit is the test: division-free, every operation in double on the widened float32 inputs, no
-// fma -- tests/wall_model.py is the same arithmetic in numpy, and tests/test_wall_model.py compares it with exact rational
-// arithmetic.  A wall hit counts like a disc hit: it goes into the same cnts[step][lane], and the cost wave adds obs_cost
-// once more.  The counter that owns a step goes on through the walls after the step's discs, 64 walls at a time: every lane
-// loads one wall and forms its constants (d = B - A, d.d, h*h), the tests read them lane by lane as wave-uniform values.
-// The counters need P as well as Q, and the position before a chunk's first step lies in the buffer the walker is
-// overwriting in that very interval -- so with WALLS a position buffer has C + 1 slots per lane: the walker stores the
-// chunk's entry position (x0 ahead of chunk 0) in slot 0 and the post-step positions behind it.
-// WALLS = false is the kernel as it was: same arguments, same LDS layout, and -- compared in the compiler's gfx950
-// assembly, all twelve forms -- the same instructions.
+// WHAT THE OWNER OF A (STEP, LANE) DOES -- the walk, `while (j < cl)`, in this order:
+//   1  the step's discs, 64 at a time: every lane loads one disc and its square (load_disc: a coalesced load, the next
+//      tile's in flight during the tests; tracks: row min(now + t + 1, last) of the [row][disc] copy, so a step's discs are
+//      contiguous), the tests read them lane by lane as wave-uniform values -- the double-precision test of
+//      k_rollout_barebone on the post-step position Q, four discs a trip
+//   2  behind the step's last disc tile, the walls, 64 at a time: every lane loads one wall and forms its constants
+//      (load_wall: d = B - A, d.d, h * h; the next tile in flight), the tests read them lane by lane.  A wall is a segment
+//      A -> B with a half-width h >= 0 (float32); step t moves the robot from P (the position before the step, x0 for
+//      t = 0) to Q, and it hits the wall iff the distance between the closed segments PQ and AB is <= h: a step that jumps
+//      a thin wall is a hit (no tunnelling).  crowd_wall_hit is the test: division-free, every operation in double on the
+//      widened float32 inputs, no fma -- tests/wall_model.py is the same arithmetic in numpy, and tests/test_wall_model.py
+//      compares it with exact rational arithmetic.  A wall hit counts like a disc hit, into the same count.
+//      The counters need P as well as Q, and the position before a chunk's first step lies in the buffer the walker is
+//      overwriting in that very interval -- so with walls a position buffer has C + 1 slots per lane: the walker stores
+//      the chunk's entry position (x0 ahead of chunk 0) in slot 0 and the post-step positions behind it
+//   3  the count store, int32 [step][lane], and the goal distance of Q
+// and the cost wave reads the count where the chain wants its `hits`.  Each feature below adds to this walk and nowhere else,
+// chosen by the type of an optional argument (`if constexpr`, and trip counts that are the literal 1 without the feature):
+// a form without the argument holds none of the feature's code.  The text holds the walk twice: once for the forms without
+// clearance rings (disc samples included) and once for the ring forms, with 1 + R counts where the other has one.
 //
-// WALL TRACKS (mppi_planner_set_wall_tracks): walls that move, and a wall set per problem -- a third form, selected by its
-// argument type (CrowdWallTracks in place of CrowdWalls); static shared walls launch the CrowdWalls form as before.  Every
-// wall has `rows` segments, row j the segment it occupies during control interval j (from j * dt to (j + 1) * dt after
-// "now"); step t of a rollout IS interval s + t (s: the problem's track offset, the one the disc tracks have), so it is
-// tested, with crowd_wall_hit unchanged, against row min(s + t, rows - 1) of every wall.  (A disc row is an instant, and the
-// post-step position is tested against row s + t + 1; a wall row is an interval.  Each kind clamps against its own row
-// count.)  The device copy is [row][wall], all problems' walls side by side, so a step's walls are contiguous; a problem's
-// range of a row is {wall0, count} of the range array (none: one set for every problem).  The walls now change with the
-// step, so the first tile is no longer loaded once per chunk: the counter that owns step c0 + j loads its tiles from that
-// step's row and keeps the next tile -- the first tile of its NEXT step behind a step's last -- in flight during the tests,
-// as it does with the disc tiles.  One row, or equal rows, is a static wall to the bit.  A wall that itself jumps over the
-// robot between two rows is seen only if its rows are sweeps: a row is tested where it lies.
+// STATIC WALLS, CrowdWalls (mppi_planner_set_walls): one set, shared by the problems.  The walls do not change with the
+// step, so the first tile is loaded once per chunk and every step starts from it.
 //
-// A GOAL THAT MOVES (mppi_planner_set_goal_tracks): one GoalRows argument behind the walls' (if any).  The only reader of the
-// goal is the count wave's goal distance, once per (step, lane): the counter that owns step c0 + j takes row
-// min(s + c0 + j + 1, rows - 1) of the problem's goal track -- a wave-uniform load -- where it took P.xg / P.yg.  The cost
-// wave, the walker and the wall code do not know.  Without the argument the kernel is what it was.
+// WALL TRACKS, CrowdWallTracks (mppi_planner_set_wall_tracks): walls that move, and a wall set per problem.  Every wall has
+// `rows` segments, row j the segment it occupies during control interval j (from j * dt to (j + 1) * dt after "now"); step
+// t of a rollout IS interval s + t (s: the problem's track offset, the one the disc tracks have), so it is tested against
+// row min(s + t, rows - 1) of every wall.  (A disc row is an instant, and the post-step position is tested against row
+// s + t + 1; a wall row is an interval.  Each kind clamps against its own row count.)  The device copy is [row][wall], all
+// problems' walls side by side, so a step's walls are contiguous; a problem's range of a row is {wall0, count} of the range
+// array (none: one set for every problem).  The walls change with the step, so the tile in flight behind a step's last wall
+// tile is the first tile of the owner's NEXT step -- as with the disc tiles.  One row, or equal rows, is a static wall to the
+// bit.  A wall that itself jumps over the robot between two rows is seen only if its rows are sweeps: a row is tested where
+// it lies.
+//
+// A GOAL THAT MOVES, GoalRows (mppi_planner_set_goal_tracks): the only reader of the goal is the walk's goal distance, once
+// per (step, lane): the owner of step c0 + j takes row min(s + c0 + j + 1, rows - 1) of the problem's goal track -- a
+// wave-uniform load -- where it took P.xg / P.yg.  The cost wave, the walker and the wall code do not know.
 //
 // A FLEET (mppi_planner_set_fleet; fleet_kernels.h): the per-problem wall sets are made by the library itself, of the
 // other problems' plans, ahead of every call -- so their row 0 is always "now".  One field of CrowdWallTracks says so
 // (relative): the walls' "now" is then 0 whatever the problem's track offset is, while the disc tracks and the goal track
 // of the same launch keep reading theirs at the offset.  Nothing else of the kernel knows.
 //
-// DISC SAMPLES (mppi_planner_set_disc_track_samples): S sampled futures of the moving discs, one CrowdSamples argument at the
-// end of the pack (TRACKS forms only; walls: the CrowdWallTracks form only, static shared walls as tracks of one row).  A
-// rollout's cost under sample s is the cost of the plain launch with that sample as its tracks, bit for bit; the rollout's
-// cost is the CVaR tail over its S costs (mppi.py:716-755 with block_width = S, as k_rollout_tdm restates it).  The device
-// copy is [row][sample][disc] -- disc_pitch = S * K: all that a step tests is contiguous.
-//   count  the owner of (step, lane) loads the position once and walks the step's S * ceil(K / 64) tiles, sample after
-//          sample, the next tile in flight; the walls are counted once, behind sample 0's last tile, and their number is
-//          added to every sample's count.  S counts of 16 bits (the hand-over refuses K + walls > 65535) -> LDS
-//          [step][sample][lane], one goal distance as before.
-//   cost   S chains that share nd2 and the done / reached / d2 freeze; the running costs live in LDS [S][64], the loop is
-//          sample-outer, steps-of-the-chunk-inner (a register array indexed by a run-time s would go to scratch memory).
+// DISC SAMPLES, CrowdSamples (mppi_planner_set_disc_track_samples): S sampled futures of the moving discs (TRACKS forms only;
+// walls: the CrowdWallTracks form only, static shared walls as tracks of one row).  A rollout's cost under sample s is the
+// cost of the plain launch with that sample as its tracks, bit for bit; the rollout's cost is the CVaR tail over its S costs
+// (mppi.py:716-755 with block_width = S, as k_rollout_tdm restates it).  The device copy is [row][sample][disc] --
+// disc_pitch = S * K: all that a step tests is contiguous.
+//   count  the owner loads the position once and walks the step's S * ceil(K / 64) disc tiles, sample after sample (sm); the
+//          walls are counted once, behind sample 0's last tile, and their number is added to every sample's count.  S counts
+//          of 16 bits (the hand-over refuses K + walls > 65535) -> LDS [step][sample][lane], one goal distance as before.
+//   cost   S chains that share nd2 and start from the same done / reached / d2 freeze; the running costs live in LDS
+//          [S][64], the loop is sample-outer, steps-of-the-chunk-inner (a register array indexed by a run-time s would go
+//          to scratch memory).  Without samples S is the literal 1 and the one chain is the loop's body.
 //   tail   the terminal term and the T control-cost terms onto each of the S costs in the existing order; the S values to
 //          the sample-cost array when recording is on; per lane a compare-exchange network over its LDS column (descending,
 //          iff cvar_alpha < 1), the strided float32 tree over the first numel entries walked serially -- the tree's shape
 //          fixes the bits, not who executes it --, the division in double.
-// Without the argument the kernel is what it was.
 //
-// A BODY FOOTPRINT (mppi_planner_set_footprint): the robot as up to kCrowdFootprintMax discs rigidly attached to its pose, one
-// CrowdFootprint argument at the very end of the pack -- by value, so its rows are wave-uniform (TRACKS forms only; walls:
-// the CrowdWallTracks form only, static discs and static shared walls as tracks of one row).  Body disc i = (ox, oy, rho) has
-// its centre at (float)(x + (ox * c - oy * s)), (float)(y + (ox * s + oy * c)): s, c the full sincos_f64<false> of the state's
-// float32 heading, products and sums in double, one rounding (crowd_body_centres).
+// A BODY FOOTPRINT, CrowdFootprint (mppi_planner_set_footprint): the robot as up to kCrowdFootprintMax discs rigidly attached
+// to its pose -- by value, so its rows are wave-uniform (TRACKS forms only; walls: the CrowdWallTracks form only, static
+// discs and static shared walls as tracks of one row).  Body disc i = (ox, oy, rho) has its centre at
+// (float)(x + (ox * c - oy * s)), (float)(y + (ox * s + oy * c)): s, c the full sincos_f64<false> of the state's float32
+// heading, products and sums in double, one rounding (crowd_body_centres).
 //   walk   beside each position the walker publishes the float32 heading: one more LDS plane, [2][C (+ 1)][64] float behind
 //          everything else, entry slot included -- one store, nothing on the walker's dependent chain.  The count waves set
 //          the pace of these forms and need the registers: the walker loads a chunk's noise at the chunk's head and carries
 //          none across the barrier (the other forms keep the next chunk's in flight: 32 registers live in every wave)
-//   count  the owner of (step, lane) forms the centres of the post-step state once per step, at the step's first disc tile,
-//          and keeps them in registers to its last -- loops unrolled to 8, predicated on the uniform count: a register array
-//          indexed at run time would go to scratch memory.  A disc is touched iff ANY body disc touches it, the existing
-//          test with pos := the centre and rr := (r + rho)^2 in double.  A wall is hit iff ANY body disc's chord, pre-step
-//          centre -> post-step centre, hits it: crowd_wall_hit unchanged with hh := (h + rho)^2.  Eight unrolled copies of
-//          that test cost some 900 bytes of scratch a lane, so the walls go the other way round (crowd_body_wall_hits): a
-//          run-time loop over the body's discs around ONE copy of the test, the rows read from LDS ([3][8] double behind
-//          the headings, written once), both centres formed on the spot from the two states and their sines and cosines
-//          (the second sincos_f64 of a step), one bit per wall OR-ed over the body.  One hit per obstacle, however many body
-//          discs reach it.  (An offset point of a turning body moves on an arc; the chord is what is tested: the arc
-//          leaves it by at most |o| * (1 - cos(dt * w / 2)).)  The compiler's report, gfx950, scratch bytes a lane: the 24
-//          forms without walls 0 .. 40 (the forms without a footprint and without walls: 0 .. 132), the 24 with walls
-//          248 .. 348 (theirs: 88 .. 248; before the grouped count below: 0 .. 36 and 232 .. 344) -- one wall test and
-//          what the other waves keep do not fit 128 registers together in either; zero was not reached.
+//   count  the owner forms the centres of the post-step state once per step, at the step's first disc tile, and keeps them
+//          in registers to its last -- loops unrolled to 8, predicated on the uniform count: a register array indexed at run
+//          time would go to scratch memory.  A lane holds its disc's radius, not the square: a disc is touched iff ANY body
+//          disc touches it, the test with pos := the centre and rr := (r + rho)^2 in double (crowd_body_touches), one disc a
+//          trip.  A wall is hit iff ANY body disc's chord, pre-step centre -> post-step centre, hits it: crowd_wall_hit
+//          unchanged with hh := (h + rho)^2.  Eight unrolled copies of that test cost some 900 bytes of scratch a lane, so
+//          the walls go the other way round (crowd_body_wall_hits): a run-time loop over the body's discs around ONE copy
+//          of the test, the rows read from LDS ([3][8] double behind the headings, written once), both centres formed on
+//          the spot from the two states and their sines and cosines (the second sincos_f64 of a step), one bit per wall
+//          OR-ed over the body.  One hit per obstacle, however many body discs reach it.  (An offset point of a turning
+//          body moves on an arc; the chord is what is tested: the arc leaves it by at most |o| * (1 - cos(dt * w / 2)).)
 //   cost   the cost wave, the tail and the CVaR tail do not know; the goal distance is the reference point's.
-// Without the argument the kernel is what it was.
 //
 // A FLEET OF BODIES (mppi_planner_set_fleet_bodies; fleet_kernels.h): a footprint form with fleet wall tracks in which the
 // first `grouped` walls of every problem's set are the other robots' body discs, `group` slots a robot -- a power of two, so
@@ -114,28 +112,36 @@
 // that is ONE hit: crowd_body_wall_hits folds the tile's hit mask group by group (crowd_fold.h: log2(group) shift-ORs and a
 // leader mask below g = clamp(grouped - wbase, 0, 64), a population count of the rest).  Two integers by value in
 // CrowdFootprint -- wave-uniform; group = 1, grouped = 0 is the plain population count.  The forms without a CrowdFootprint
-// hold the empty CrowdFootprintRows and compile to what they compiled to (compared in the gfx950 assembly, all 96).
+// hold the empty CrowdFootprintRows.
 //
-// CLEARANCE RINGS (mppi_planner_set_clearance_rings): a cost that rises on the way in, as a staircase -- so it stays a matter
-// of counting.  One CrowdRings argument behind the GoalRows (if any) and in front of the CrowdFootprint (if any): R <= 4 rows
-// (margin m_l, penalty c_l), by value, widened on the host (TRACKS forms only; walls: the CrowdWallTracks form only; no disc
-// samples).  Obstacle k is NEAR at ring l iff the step would touch it were it m_l larger: the disc test with
-// rr := ((double)r + m_l)^2 (a body: ((r + rho) + m_l)^2), the wall test with hh := ((double)h + m_l)^2 (a body:
-// ((h + rho) + m_l)^2); a step that crosses a wall is inside every ring.
-//   count  the owner of (step, lane) forms 1 + R counts: the hits as ever and n_l, the obstacles near at ring l (the hit
-//          ones among them).  A disc's d2 is formed once and held against 1 + R squares, which every lane forms for its
-//          disc when the tile is loaded.  A wall's test runs once as well: crowd_wall_parts gives the crossing bit and,
-//          of each of the four crowd_near calls, the pair (num, den) of the branch taken -- near(hh) is num <= hh * den,
-//          den = 1.0 in the two end branches (the product is exact) --, and level l's verdict is
-//          crossing || any(num_i <= hh_l * den_i): at level 0 crowd_wall_hit's on every input.  A body fleet folds each
-//          level's own mask (crowd_fold_count): a robot is near once, however many of its slots are.
-//          1 + R counts of 16 bits -> LDS [step][level][lane] (the hand-over refuses K + walls > 65535).
+// CLEARANCE RINGS, CrowdRings (mppi_planner_set_clearance_rings): a cost that rises on the way in, as a staircase -- so it
+// stays a matter of counting.  R <= 4 rows (margin m_l, penalty c_l), by value, widened on the host (TRACKS forms only;
+// walls: the CrowdWallTracks form only; no disc samples).  Obstacle k is NEAR at ring l iff the step would touch it were it
+// m_l larger: the disc test with rr := ((double)r + m_l)^2 (a body: ((r + rho) + m_l)^2), the wall test with
+// hh := ((double)h + m_l)^2 (a body: ((h + rho) + m_l)^2); a step that crosses a wall is inside every ring.
+//   count  the owner forms 1 + R counts where it formed one (its own copy of the walk, with its own loaders): the hits as
+//          ever and n_l, the obstacles near at ring l (the hit ones among them).  A disc's d2 is formed once and held against
+//          1 + R squares, which every lane forms for its disc when the tile is loaded.  A wall's test
+//          runs once as well: crowd_wall_parts gives the crossing bit and, of each of the four crowd_near calls, the pair
+//          (num, den) of the branch taken -- near(hh) is num <= hh * den, den = 1.0 in the two end branches (the product is
+//          exact) --, and level l's verdict is crossing || any(num_i <= hh_l * den_i): at level 0 crowd_wall_hit's on every
+//          input.  (The forms without rings keep crowd_wall_hit and its short-circuit.)  A body: crowd_body_ring_touches and
+//          crowd_body_wall_ring_hits, the footprint's two helpers at 1 + R sizes.  A body fleet folds each level's own
+//          mask (crowd_fold_count): a robot is near once, however many of its slots are.  1 + R counts of 16 bits -> LDS
+//          [step][level][lane] (the hand-over refuses K + walls > 65535).
 //   cost   behind the `hits` additions of obs_cost, for l = 1 .. R, n_l rounded additions of c_l -- the same wave-uniform,
 //          per-lane-predicated loop.  Repeated additions and not a product: a ring with c_l = obs_cost is a second copy of
 //          the obstacles, m_l larger, to the bit.  A ring with c_l = 0 adds +0.0: the identity (see above).
-// The compiler's report, gfx950, scratch bytes a lane of the 48 ring forms: without a footprint 0 .. 144 (no walls) and
-// 156 .. 284 (walls), with one 20 .. 52 and 308 .. 392.  Without the argument the kernel is what it was: the report's
-// figures of all 313 other kernels of the library are the parent's.
+//
+// REGISTERS.  One wall test and what the other waves keep do not fit 128 registers together: the compiler's report, gfx950,
+// scratch bytes a lane over the 192 forms (zero was not reached), read from the report of the commit that merged the plain
+// and the sample walk, whose figures are its parent's in every form --
+//                 no footprint, no walls   no footprint, walls   footprint, no walls   footprint, walls
+//   plain               0 .. 132               96 .. 248              0 .. 40             248 .. 348
+//   disc samples        0 .. 128               88 .. 208              0 .. 36             248 .. 340
+//   rings               0 .. 144              156 .. 284             20 .. 52             308 .. 392
+// The register allocator of this kernel answers to edits that change no operation (profiles/HISTORY.md has two entries on
+// it): a change of this file is compared with its parent in that report, form by form, before it is timed.
 #pragma once
 #include <type_traits>
 
@@ -447,7 +453,7 @@ __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, con
 
 // WallArgs, the optional arguments, in the one order crowd_pack_in_order polices -- the table of the forms that exist is
 // crowd_form_legal (barebone_plan.h), and launch_barebone_crowd (barebone_launch.h) builds the pack from it:
-//   walls      nothing (WALLS = false: the kernel's arguments are what they were), one CrowdWalls (WALLS = true: static walls
+//   walls      nothing (WALLS = false), one CrowdWalls (WALLS = true: static walls
 //              shared by the problems) or one CrowdWallTracks (WALLS = true: wall tracks, per-problem sets)
 //   goal       with a goal that moves, one GoalRows
 //   samples    with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls), or
@@ -609,42 +615,35 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
       if (ph >= 2) {  // ---- cost of chunk ph - 2
         const int c = ph - 2, c0 = c * C, cl = min(C, T - c0);
         const size_t at = (size_t)((c & 1) * C) * 64 + lane;
-        if constexpr (SAMPLES) {  // S chains, sample-outer; the freeze is the same for every sample: the last one keeps it
-          double d2_s = d2;
-          bool done_s = done, reached_s = reached;
-          for (int s = 0; s < S; ++s) {
-            float cs = scost[s * 64 + lane];
-            d2_s = d2; done_s = done; reached_s = reached;
-            for (int j = 0; j < cl; ++j) {
-              const double nd2 = nd2s[at + j * 64];
-              const int hits = cnts16[(at - lane + (size_t)j * 64) * S + s * 64 + lane];
-              float c1 = (float)((double)cs + P.dist_weight * nd2);
-              for (int h = 0; __any(h < hits); ++h)
-                if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
-              const bool hit_goal = nd2 <= (double)P.gt2, act = !done_s;
-              cs = act ? c1 : cs;
-              d2_s = act ? nd2 : d2_s;
-              reached_s = reached_s || (act && hit_goal);
-              done_s = done_s || hit_goal;
-            }
-            scost[s * 64 + lane] = cs;
+        // One chain per sample -- S is the literal 1 without samples --, sample-outer, steps-of-the-chunk-inner: the samples'
+        // running costs live in LDS (a register array indexed by a run-time s would go to scratch memory) and pass through
+        // `cost` one after the other.  The freeze is the same for every sample: each starts from the chunk's, the last one keeps it
+        [[maybe_unused]] const double d2_in = d2;
+        [[maybe_unused]] const bool done_in = done, reached_in = reached;
+        for (int s = 0; s < S; ++s) {
+          if constexpr (SAMPLES) {
+            cost = scost[s * 64 + lane];
+            d2 = d2_in; done = done_in; reached = reached_in;
           }
-          d2 = d2_s; done = done_s; reached = reached_s;
-        } else if constexpr (RINGS) {  // the chain with the rings' additions behind the hits'
           for (int j = 0; j < cl; ++j) {
             const double nd2 = nd2s[at + j * 64];
-            const unsigned short* cn = cnts16 + ((size_t)((c & 1) * C + j) * NL) * 64 + lane;
-            const int hits = cn[0];
+            [[maybe_unused]] const unsigned short* cn = cnts16 + ((size_t)((c & 1) * C + j) * NL) * 64 + lane;  // RINGS: [level][lane]
+            int hits;
+            if constexpr (SAMPLES) hits = cnts16[(at - lane + (size_t)j * 64) * S + s * 64 + lane];
+            else if constexpr (RINGS) hits = cn[0];
+            else hits = cnts[at + j * 64];
             float c1 = (float)((double)cost + P.dist_weight * nd2);
             for (int h = 0; __any(h < hits); ++h)
               if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
+            if constexpr (RINGS) {  // the rings' additions behind the hits'
 #pragma unroll
-            for (int q = 0; q < kCrowdRingsMax; ++q) {
-              if (q < rg.count) {  // (uniform)
-                const int near = cn[(q + 1) * 64];
-                const double pen = rg.penalty[q];
-                for (int h = 0; __any(h < near); ++h)
-                  if (h < near) c1 = (float)((double)c1 + pen);
+              for (int q = 0; q < kCrowdRingsMax; ++q) {
+                if (q < rg.count) {  // (uniform)
+                  const int near = cn[(q + 1) * 64];
+                  const double pen = rg.penalty[q];
+                  for (int h = 0; __any(h < near); ++h)
+                    if (h < near) c1 = (float)((double)c1 + pen);
+                }
               }
             }
             const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
@@ -653,19 +652,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
             reached = reached || (act && hit_goal);
             done = done || hit_goal;
           }
-        } else {
-          for (int j = 0; j < cl; ++j) {
-            const double nd2 = nd2s[at + j * 64];
-            const int hits = cnts[at + j * 64];
-            float c1 = (float)((double)cost + P.dist_weight * nd2);
-            for (int h = 0; __any(h < hits); ++h)
-              if (h < hits) c1 = (float)((double)c1 + (double)P.obs_cost);
-            const bool hit_goal = nd2 <= (double)P.gt2, act = !done;
-            cost = act ? c1 : cost;
-            d2 = act ? nd2 : d2;
-            reached = reached || (act && hit_goal);
-            done = done || hit_goal;
-          }
+          if constexpr (SAMPLES) scost[s * 64 + lane] = cost;
         }
         if (__all(done) && lane == 0) tile_done[ph & 1] = 1;
       }
@@ -677,12 +664,13 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         const size_t atp = (size_t)((c & 1) * CP + kEntry) * 64 + lane;  // poss[atp + j * 64]: the position after step c0 + j
         // this lane's disc of the tile [base, base + 64) as step c0 + j sees it; past the problem's last disc: a disc
         // nobody can touch (k_rollout_barebone's far slot)
-        auto load_disc = [&](int j, int base, float2& op, double& rr) {
+        auto load_disc = [&](int j, int sm, int base, float2& op, double& rr) {
           const int k = base + lane;
           op = make_float2(1e18f, 1e18f);
           float r = 0.0f;
           if (j < cl && k < K) {
             const float2* row = TRACKS ? obs_pos + (size_t)min(now + c0 + j + 1, last) * (size_t)disc_pitch : obs_pos;
+            if constexpr (SAMPLES) row += (size_t)sm * (size_t)K;  // (the row's samples lie side by side, K discs each)
             op = row[k];
             r = obs_r[k];
           }
@@ -870,35 +858,27 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
 #pragma unroll
             for (int q = 0; q < kSq; ++q) rr[q] = rr_nxt[q];
           }
-        } else if constexpr (SAMPLES) {
-          // sample sm's tile [base, base + 64) as step c0 + j sees it: the row's samples lie side by side, K discs each
-          auto load_sample_disc = [&](int j, int sm, int base, float2& op, double& rr) {
-            const int k = base + lane;
-            op = make_float2(1e18f, 1e18f);
-            float r = 0.0f;
-            if (j < cl && k < K) {
-              op = obs_pos[(size_t)min(now + c0 + j + 1, last) * (size_t)disc_pitch + (size_t)sm * (size_t)K + (size_t)k];
-              r = obs_r[k];
-            }
-            if constexpr (FOOT) rr = (double)r;
-            else rr = (double)r * (double)r;
-          };
-          int j = wave - 2, sm = 0, base = 0, hits = 0, whits = 0;
+        } else {
+          // One walk for the plain and the sample forms: a step's S sets of discs (no samples: the one set, sm = 0), tile after
+          // tile, the next tile in flight; the walls once per step, behind sample 0's last tile
+          int j = wave - 2, sm = 0, base = 0, hits = 0;
+          [[maybe_unused]] int whits = 0;  // SAMPLES: the step's wall hits, added to every sample's count
           float2 op;
           double rr;
-          load_sample_disc(j, sm, base, op, rr);
+          load_disc(j, sm, base, op, rr);
           while (j < cl) {
             int nj = j, nsm = sm, nbase = base + 64;
             if (nbase >= K) {
               nbase = 0;
-              if (++nsm == S) { nsm = 0; nj = j + NC; }
+              if constexpr (!SAMPLES) nj = j + NC;
+              else if (++nsm == S) { nsm = 0; nj = j + NC; }
             }
             float2 op_nxt;
             double rr_nxt;
-            load_sample_disc(nj, nsm, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
+            load_disc(nj, nsm, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
             const float2 pos = poss[atp + j * 64];
             if constexpr (FOOT) {
-              if (sm == 0 && base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
+              if ((!SAMPLES || sm == 0) && base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
             }
             const int kt = min(64, K - base);
             for (int l0 = 0; l0 < kt; l0 += kLanes) {
@@ -915,95 +895,47 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                 }
               }
             }
-            if (nbase == 0) {  // the sample's last tile
+            if (SAMPLES ? nbase == 0 : nj != j) {  // the sample's last tile (no samples: the step's)
               if constexpr (WALLS) {
-                if (sm == 0) {  // the step's walls, once: this problem's walls as this step sees them, against P -> Q
+                if (!SAMPLES || sm == 0) {  // the step's walls, once, against the step's segment P -> Q
                   const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
                   [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
                   [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
                   if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
                   float4 sg = sg0;
                   double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
-                  whits = 0;
-                  for (int wbase = 0; wbase < wcount; wbase += 64) {
-                    float4 sg_nxt;
-                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                    const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
-                    load_wall_row(more ? j : j + NC, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);
-                    const int wt = min(64, wcount - wbase);
-                    if constexpr (FOOT) {
-                      whits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt, wbase, fp.group, fp.grouped);
-                    } else {
-                      for (int l = 0; l < wt; ++l) {
-                        const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                        const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                        whits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                                crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                     ? 1 : 0;
+                  if constexpr (SAMPLES) whits = 0;
+                  if constexpr (WTRK) {  // this problem's walls as this step sees them
+                    for (int wbase = 0; wbase < wcount; wbase += 64) {
+                      float4 sg_nxt;
+                      double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                      const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
+                      load_wall_row(more ? j : SAMPLES ? j + NC : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                      const int wt = min(64, wcount - wbase);
+                      if constexpr (FOOT) {
+                        const int wh = crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt, wbase, fp.group, fp.grouped);
+                        if constexpr (SAMPLES) whits += wh;
+                        else hits += wh;
+                      } else {
+                        for (int l = 0; l < wt; ++l) {
+                          const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
+                          const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
+                          const int wh = crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
+                                                        crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
+                                             ? 1 : 0;
+                          if constexpr (SAMPLES) whits += wh;
+                          else hits += wh;
+                        }
                       }
+                      sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                     }
-                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
-                  }
-                  sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
-                }
-              }
-              cnts16[(at - lane + (size_t)j * 64) * S + sm * 64 + lane] = (unsigned short)(hits + whits);
-              if (sm == 0) {
-                if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
-                else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
-              }
-              hits = 0;
-            }
-            j = nj; sm = nsm; base = nbase; op = op_nxt; rr = rr_nxt;
-          }
-        } else {
-          int j = wave - 2, base = 0, hits = 0;
-          float2 op;
-          double rr;
-          load_disc(j, base, op, rr);
-          while (j < cl) {
-            int nj = j, nbase = base + 64;
-            if (nbase >= K) { nj = j + NC; nbase = 0; }
-            float2 op_nxt;
-            double rr_nxt;
-            load_disc(nj, nbase, op_nxt, rr_nxt);  // (in flight during this tile's tests)
-            const float2 pos = poss[atp + j * 64];
-            if constexpr (FOOT) {
-              if (base == 0) crowd_body_centres(fp, pos.x, pos.y, heads[atp + j * 64], qcx, qcy, sq, cq);  // (once per step)
-            }
-            const int kt = min(64, K - base);
-            for (int l0 = 0; l0 < kt; l0 += kLanes) {
-#pragma unroll
-              for (int l = l0; l < l0 + kLanes; ++l) {  // (kt is not a multiple of 4: the lanes past it hold the far disc)
-                const float ox = crowd_lane_f32(op.x, l), oy = crowd_lane_f32(op.y, l);
-                const double rrl = crowd_lane_f64(rr, l);
-                if constexpr (FOOT) {
-                  hits += crowd_body_touches(fp, qcx, qcy, ox, oy, rrl) ? 1 : 0;
-                } else {
-                  const double ex = (double)(pos.x - ox), ey = (double)(pos.y - oy);
-                  const double diff = fma(ex, ex, ey * ey) - rrl;
-                  hits += (diff > 0.0) ? 0 : 1;
-                }
-              }
-            }
-            if (nj != j) {  // the step's last tile
-              if constexpr (WALLS) {  // ... then the walls, against the step's segment P -> Q
-                const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
-                [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
-                [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
-                if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
-                float4 sg = sg0;
-                double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
-                if constexpr (WTRK) {  // this problem's walls as this step sees them
-                  for (int wbase = 0; wbase < wcount; wbase += 64) {
-                    float4 sg_nxt;
-                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                    const bool more = wbase + 64 < wcount;  // (else: the first tile of this counter's next step)
-                    load_wall_row(more ? j : nj, more ? wbase + 64 : 0, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
-                    const int wt = min(64, wcount - wbase);
-                    if constexpr (FOOT) {
-                      hits += crowd_body_wall_hits(fprows, fp.count, pre.x, pre.y, sp, cp, pos.x, pos.y, sq, cq, sg, dx, dy, LLd, hh, wt, wbase, fp.group, fp.grouped);
-                    } else {
+                    sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
+                  } else {  // static walls (never beside samples): every step starts from the chunk's first tile
+                    for (int wbase = 0; wbase < walls.count; wbase += 64) {
+                      float4 sg_nxt;
+                      double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
+                      load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
+                      const int wt = min(64, walls.count - wbase);
                       for (int l = 0; l < wt; ++l) {
                         const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
                         const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
@@ -1011,33 +943,20 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                                                crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
                                     ? 1 : 0;
                       }
+                      sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                     }
-                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
-                  }
-                  sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd; hh0 = hh;
-                } else {
-                  for (int wbase = 0; wbase < walls.count; wbase += 64) {
-                    float4 sg_nxt;
-                    double dx_nxt, dy_nxt, LLd_nxt, hh_nxt;
-                    load_wall(wbase + 64, sg_nxt, dx_nxt, dy_nxt, LLd_nxt, hh_nxt);  // (in flight during this tile's tests)
-                    const int wt = min(64, walls.count - wbase);
-                    for (int l = 0; l < wt; ++l) {
-                      const double ax = (double)crowd_lane_f32(sg.x, l), ay = (double)crowd_lane_f32(sg.y, l);
-                      const double bx = (double)crowd_lane_f32(sg.z, l), by = (double)crowd_lane_f32(sg.w, l);
-                      hits += crowd_wall_hit(px, py, qx, qy, ax, ay, bx, by, crowd_lane_f64(dx, l), crowd_lane_f64(dy, l),
-                                             crowd_lane_f64(LLd, l), crowd_lane_f64(hh, l))
-                                  ? 1 : 0;
-                    }
-                    sg = sg_nxt; dx = dx_nxt; dy = dy_nxt; LLd = LLd_nxt; hh = hh_nxt;
                   }
                 }
               }
-              cnts[at + j * 64] = hits;
-              if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
-              else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+              if constexpr (SAMPLES) cnts16[(at - lane + (size_t)j * 64) * S + sm * 64 + lane] = (unsigned short)(hits + whits);
+              else cnts[at + j * 64] = hits;
+              if (!SAMPLES || sm == 0) {
+                if constexpr (GOALS) nd2s[at + j * 64] = barebone_goal_d2(G.xy[min(gnow + c0 + j + 1, glast)], pos.x, pos.y);
+                else nd2s[at + j * 64] = barebone_goal_d2(P, pos.x, pos.y);
+              }
               hits = 0;
             }
-            j = nj; base = nbase; op = op_nxt; rr = rr_nxt;
+            j = nj; sm = nsm; base = nbase; op = op_nxt; rr = rr_nxt;
           }
         }
       }
@@ -1046,24 +965,35 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     if (tile_done[ph & 1]) break;  // (uniform: every rollout of the tile is at its goal)
   }
   if (wave != 1) return;
-  if constexpr (SAMPLES) {  // the tail onto each of the S costs, then the CVaR over the lane's column (wave 1 alone: no barrier)
-    for (int s = 0; s < S; ++s) scost[s * 64 + lane] = (float)((double)scost[s * 64 + lane] + (reached ? 0.0 : 1.0) * d2);
-    int t0 = 0;
-    for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {  // loads and products once, the rounded additions per sample in order
-      double cc[kNoiseBatch];
+  // The tail onto each of the S costs (S = 1: onto `cost` itself; the samples' pass through it), wave 1 alone -- no barrier:
+  // the terminal term, then the T control-cost terms -- loads and products once and batched, the float32-rounded additions
+  // per sample in order
+  for (int s = 0; s < S; ++s) {
+    if constexpr (SAMPLES) cost = scost[s * 64 + lane];
+    cost = (float)((double)cost + (reached ? 0.0 : 1.0) * d2);
+    if constexpr (SAMPLES) scost[s * 64 + lane] = cost;
+  }
+  int t0 = 0;
+  for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {
+    double cc[kNoiseBatch];
 #pragma unroll
-      for (int j = 0; j < kNoiseBatch; ++j) cc[j] = control_cost(P, uos[t0 + j], col[(size_t)(t0 + j) * 64]);
-      for (int s = 0; s < S; ++s) {
-        float cs = scost[s * 64 + lane];
+    for (int j = 0; j < kNoiseBatch; ++j) cc[j] = control_cost(P, uos[t0 + j], col[(size_t)(t0 + j) * 64]);
+    for (int s = 0; s < S; ++s) {
+      if constexpr (SAMPLES) cost = scost[s * 64 + lane];
 #pragma unroll
-        for (int j = 0; j < kNoiseBatch; ++j) cs = (float)((double)cs + cc[j]);
-        scost[s * 64 + lane] = cs;
-      }
+      for (int j = 0; j < kNoiseBatch; ++j) cost = (float)((double)cost + cc[j]);
+      if constexpr (SAMPLES) scost[s * 64 + lane] = cost;
     }
-    for (int t = t0; t < T; ++t) {
-      const double cc = control_cost(P, uos[t], col[(size_t)t * 64]);
-      for (int s = 0; s < S; ++s) scost[s * 64 + lane] = (float)((double)scost[s * 64 + lane] + cc);
+  }
+  for (int t = t0; t < T; ++t) {
+    const double cc = control_cost(P, uos[t], col[(size_t)t * 64]);
+    for (int s = 0; s < S; ++s) {
+      if constexpr (SAMPLES) cost = scost[s * 64 + lane];
+      cost = (float)((double)cost + cc);
+      if constexpr (SAMPLES) scost[s * 64 + lane] = cost;
     }
+  }
+  if constexpr (SAMPLES) {  // the CVaR over the lane's column
     if (smp.sample_costs && live)
       for (int s = 0; s < S; ++s) smp.sample_costs[(size_t)n * (size_t)S + s] = scost[s * 64 + lane];
     if (P.cvar_alpha < 1.0f) {  // descending: odd-even transposition, S rounds of compare-exchange
@@ -1077,20 +1007,8 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     const int numel = smp.numel;  // the strided float32 tree over the first numel entries (mppi.py:744-751)
     for (int st = 1; st < numel; st <<= 1)
       for (int i = 0; i + st < numel; i += 2 * st) scost[i * 64 + lane] = scost[i * 64 + lane] + scost[(i + st) * 64 + lane];
-    if (live) costs[n] = (float)((double)scost[lane] / (double)numel);
-    if (P.ktime && lane == 0) P.ktime[P.ktime_waves + blockIdx.x] = (unsigned long long)wall_clock64();
-    return;
+    cost = (float)((double)scost[lane] / (double)numel);
   }
-  cost = (float)((double)cost + (reached ? 0.0 : 1.0) * d2);
-  int t0 = 0;
-  for (; t0 + kNoiseBatch <= T; t0 += kNoiseBatch) {  // loads and products batched, the float32-rounded additions in order
-    double cc[kNoiseBatch];
-#pragma unroll
-    for (int j = 0; j < kNoiseBatch; ++j) cc[j] = control_cost(P, uos[t0 + j], col[(size_t)(t0 + j) * 64]);
-#pragma unroll
-    for (int j = 0; j < kNoiseBatch; ++j) cost = (float)((double)cost + cc[j]);
-  }
-  for (int t = t0; t < T; ++t) cost = (float)((double)cost + control_cost(P, uos[t], col[(size_t)t * 64]));
   if (live) costs[n] = cost;
   if (P.ktime && lane == 0) P.ktime[P.ktime_waves + blockIdx.x] = (unsigned long long)wall_clock64();
 }

@@ -13,7 +13,10 @@ Shapes: N = 100 (two tiles, 36 live lanes in the second), T = 18 (chunk 14: a se
 handle's noise and compared with it.  Disc samples: the documented identity is per sample -- sample s costs what the launch
 with samples[s] as its tracks costs -- so the (N, S) sample costs are compared column by column, and the launch's cost with
 the CVaR tail formed here on those columns (cvar_alpha = 1: the float32 tree (c + c) + c, divided by 3 in double; the mean of
-three equal float32 values is not always that value)."""
+three equal float32 values is not always that value).
+
+The same lattice at the tile and chunk edges (test_tile_and_chunk_edges): 0, 64 and 128 discs, 0, 1, 64 and 65 walls, T = 18
+and T = 5 -- one partial chunk --, one row per kind of count walk."""
 import gc
 import itertools
 
@@ -23,11 +26,12 @@ import pytest
 from test_gpu_barebone_batch import assert_bits, make_params
 from test_gpu_barebone_crowd import cfg_of, inputs, shape_of
 from test_gpu_barebone_fleet import fleet_ending, ring
-from test_gpu_barebone_walls import GOAL, building, discs_of
+from test_gpu_barebone_walls import DIAG, GOAL, building, discs_of
 
 pytestmark = pytest.mark.gpu
 
 N, NB, T, K, W, B, S, R = 100, 128, 18, 70, 65, 3, 3, 2
+T_SHORT = 5  # a horizon of one partial chunk (test_tile_and_chunk_edges)
 OBS_PENALTY = 1000.0  # (the default; a cost of a few hits keeps the distance terms in its low bits)
 WALLS, DISCS = ("none", "static", "tracks"), ("static", "tracks")
 EXTRAS = ((), ("samples",), ("rings",), ("footprint",), ("samples", "footprint"), ("rings", "footprint"))
@@ -43,18 +47,23 @@ def release_the_handles():
     gc.collect()
 
 
-def scene():
+def scene(K=K, W=W, T=T):
+    """K discs, W walls, T steps.  The horizon of T_SHORT steps starts 0.45 m down the diagonal, the discs and walls where they
+    are: the first discs and the first wall are then within its reach."""
     rng = np.random.default_rng(1818)
     params = make_params(0.1, 1.0)
     params["xgoal"], params["vrange"], params["obs_penalty"] = GOAL.copy(), np.array([0.0, 1.8]), OBS_PENALTY
     u_in, noise = inputs(rng, NB, T)
     pos, rad = discs_of(K, "static", T, params)
     seg, hw = building(W)
+    if T == T_SHORT:
+        params["x0"] = np.array([0.45 * DIAG[0], 0.45 * DIAG[1], np.pi / 4])
     return params, u_in, noise, pos, rad * np.float32(0.5), seg, hw  # (half the radii: a rollout meets some discs, not most)
 
 
 def row_params(sc, row):
-    params, _, _, pos, rad, seg, hw = sc
+    params, u_in, _, pos, rad, seg, hw = sc
+    K, T = len(pos), len(u_in)
     walls, goal, discs, extra, _ = row
     p = dict(params)
     p["obstacle_radius"] = rad
@@ -78,7 +87,7 @@ def row_params(sc, row):
     return p
 
 
-def tail_of(row):
+def tail_of(row, W=W, T=T):
     """What last_rollout_kernel() says behind the chunk."""
     walls, goal, discs, extra, batch = row
     return ((" tracks=1" if "samples" in extra or discs == "tracks" else "") + (" problems=%d" % B if batch else "") +
@@ -115,11 +124,11 @@ def cvar_tail(columns):
 class Lattice:
     """One handle per (single / batch); a row's launch is made once and kept."""
 
-    def __init__(self, math):
+    def __init__(self, math, K=K, W=W, T=T):
         from mppi_numba_amd.barebone import MPPI_Batch, MPPI_Numba
-        self.math, self.sc = math, scene()
+        self.math, self.sc, self.shape = math, scene(K, W, T), (K, W, T)
         self.single, self.batch = MPPI_Numba(cfg_of(N, T, True, math)), MPPI_Batch(cfg_of(NB, T, True, math), B)
-        self.kept = {}
+        self.kept, self.chunks = {}, set()
 
     def costs(self, row):
         """(N,) costs of a single row, (B, N) of a batch row -- and (N, S) sample costs of a single row with samples."""
@@ -145,10 +154,16 @@ class Lattice:
         if "samples" in row[3] and not batch:
             columns = planner.sample_costs()
         # (a) the launch names exactly the pieces the row asked for
+        K, W, T = self.shape
+        if not K and row[0] == "none":  # (nothing to count: not a crowd launch; the scene's cost without obstacles)
+            assert kernel.startswith("k_rollout_barebone ") and not row[3] and not batch, "%s: %s" % (row, kernel)
+            self.kept[row] = (costs, None)
+            return self.kept[row]
         chunk = shape_of(kernel)[1]
-        assert T > chunk, kernel
+        self.chunks.add(chunk)
+        assert T > chunk or T == T_SHORT, kernel  # (T_SHORT: one partial chunk, asked for as such)
         head = "k_rollout_barebone_crowd exact=%d rotation=%d waves=" % (self.math == "exact", self.math == "exact")
-        assert kernel.startswith(head) and kernel.endswith(" chunk=%d" % chunk + tail_of(row)), "%s: %s" % (row, kernel)
+        assert kernel.startswith(head) and kernel.endswith(" chunk=%d" % chunk + tail_of(row, W, T)), "%s: %s" % (row, kernel)
         self.kept[row] = (costs[:, :N] if batch else costs, columns)
         return self.kept[row]
 
@@ -167,9 +182,15 @@ class Lattice:
             assert_bits(costs[b] if row[4] else costs, want, what + (", problem %d" % b if row[4] else ""))
 
     def the_input_means_something(self):
-        free, walled = self.costs(("none", False, "static", (), False))[0], self.costs(("static", False, "static", (), False))[0]
-        assert (free >= OBS_PENALTY).any() and len(np.unique(free)) > N // 2, "bad input: no disc is hit, or the costs are alike"
-        assert (walled >= free + OBS_PENALTY).any(), "bad input: the walls cost nothing"
+        """(Of a scene without discs, or without walls, the half that it has.)"""
+        K, W, _ = self.shape
+        free = self.costs(("none", False, "static", (), False))[0]
+        assert len(np.unique(free)) > N // 2, "bad input: the costs are alike"
+        if K:
+            assert (free >= OBS_PENALTY).any(), "bad input: no disc is hit"
+        if W:
+            walled = self.costs(("static", False, "static", (), False))[0]
+            assert (walled >= free + OBS_PENALTY).any(), "bad input: the walls cost nothing"
 
 
 @pytest.mark.parametrize("math", ["exact", "fast"])
@@ -179,6 +200,24 @@ def test_every_form_equals_its_neighbour(math):
         lattice.check(row)  # (and, through the neighbours, every row below it)
     lattice.the_input_means_something()
     assert len(ROWS) == 120 and all(neighbour(row) is None or neighbour(row) in ROWS for row in ROWS)
+
+
+EDGE_EXTRAS = ((), ("samples",), ("rings",), ("samples", "footprint"), ("rings", "footprint"))
+
+
+@pytest.mark.parametrize("T", [T, T_SHORT])
+@pytest.mark.parametrize("K,W", [(0, 64), (64, 0), (64, 65), (128, 1)])
+def test_tile_and_chunk_edges(K, W, T):
+    """Disc and wall counts at the tile's edges -- none, exactly one tile, exactly two, one past a tile -- under every kind of
+    count walk, over a horizon with a second, partial chunk (T = 18) and one that is a single partial chunk (T = 5).  The
+    plain row has static discs and static walls; the others hold one-row tracks of both and reach it through their
+    neighbours."""
+    lattice = Lattice("exact", K, W, T)
+    for extra in EDGE_EXTRAS:
+        lattice.check(("tracks" if extra and W else "static" if W else "none", False, "tracks" if extra else "static", extra, False))
+    lattice.the_input_means_something()
+    if T == T_SHORT:
+        assert min(lattice.chunks) >= T, lattice.chunks  # (one chunk, and a partial one)
 
 
 def test_the_fleet_rows():
