@@ -5,26 +5,28 @@
 // (the Python mirror hands its arrays over with every solve: unchanged arrays cost a comparison, not a synchronisation and
 // two allocations); else synchronise, build the new device arrays, and only when that has succeeded free the old ones,
 // commit and drop the captured graphs, whose launches hold the arrays, the counts and the kernel form by value.  A failed
-// allocation or copy leaves the handle as it was.
+// allocation or copy leaves the handle as it was.  What is held lives in mppi_planner::scene (barebone_scene.h); behind the
+// setters' own checks the way above is written once per kind of set: hand_over_discs (the shared set, the per-problem sets,
+// the disc tracks), hand_over_walls (the static walls, the wall tracks), hand_over_rows (the footprint, the clearance rings).
 #pragma once
 
 // Barebone mode: every problem's range of the disc arrays its launch gets (BatchInst::disc0, n_discs) -- its own set
 // (mppi_planner_set_instance_disc_obstacles) or the shared one.  Uploaded with the start states.
 static void note_instance_discs(mppi_planner* p) {
   if (p->cfg.mode != MPPI_MODE_BAREBONE) return;
+  const BareboneScene& s = p->scene;
+  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
+  const DiscSet& d = s.tracks.on ? s.tracks : (s.own.on ? s.own : s.shared);
+  const bool own = d.counts.size() > 1;
   int k0 = 0;
   for (int b = 0; b < p->B; ++b) {
     BatchInst& I = p->inst_host[(size_t)b];
-    if (p->smp_on) {  // (disc samples: one set of K discs for every problem, the samples side by side within a row)
+    if (s.samples.on) {  // (disc samples: one set of K discs for every problem, the samples side by side within a row)
       I.disc0 = 0;
-      I.n_discs = p->smp_discs;
-    } else if (p->trk_on) {  // (discs that move take the place of both static sets: mppi_planner_set_disc_tracks)
-      const bool own = p->trk_counts_host.size() > 1;
-      I.disc0 = own ? k0 : 0;
-      I.n_discs = p->trk_counts_host[own ? (size_t)b : 0];
+      I.n_discs = s.samples.discs;
     } else {
-      I.disc0 = p->inst_obs_on ? k0 : 0;
-      I.n_discs = p->inst_obs_on ? p->inst_obs_counts_host[(size_t)b] : p->n_obstacles;
+      I.disc0 = own ? k0 : 0;
+      I.n_discs = d.on ? d.counts[own ? (size_t)b : 0] : 0;
     }
     k0 += I.n_discs;
   }
@@ -84,7 +86,8 @@ static int check_finite(const float* v, size_t n, size_t rows, size_t per_row, c
 //   - never when neither the old nor the new set moves (a set of one row is static: it leaves "now" alone).
 enum TrackKind { kGoalTracks = 0, kWallTracks = 1, kDiscTracks = 2 };
 static void reset_track_offsets(mppi_planner* p, TrackKind kind, bool moved, bool cleared) {
-  const bool above = (kind < kDiscTracks && (p->trk_on || p->smp_on)) || (kind < kWallTracks && p->wtrk_on && p->wtrk_rows > 1);
+  const BareboneScene& s = p->scene;
+  const bool above = (kind < kDiscTracks && (s.tracks.on || s.samples.on)) || (kind < kWallTracks && s.wall_tracks.on && s.wall_tracks.rows > 1);
   if (!moved || (cleared && above)) return;
   for (BatchInst& I : p->inst_host) I.track_off = 0;
   p->inst_dirty = true;
@@ -92,7 +95,8 @@ static void reset_track_offsets(mppi_planner* p, TrackKind kind, bool moved, boo
 
 // Staged upload.  dev_stage: one new device array of n items (one at the least), filled from the host.  staged: runs the
 // caller's sequence of them; a failure frees what the sequence had got, and the handle still holds what it held.
-// dev_take: the commit -- the old array goes, the handle takes the new one (or none).
+// The commit: the arrays are staged into a fresh struct of the set's kind (barebone_scene.h), which is completed on the
+// host; the held one is released and takes the fresh one's place whole, host mirrors and all.
 template <typename T>
 static int dev_stage(T** fresh, const void* src, size_t n) {
   TRY(dev_alloc(fresh, n));
@@ -105,11 +109,6 @@ static int staged(Stage&& stage, T*&... fresh) {
   if (rc != MPPI_OK) (dev_free(fresh), ...);
   return rc;
 }
-template <typename T>
-static void dev_take(T*& held, T* fresh) {
-  dev_free(held);
-  held = fresh;
-}
 
 // [item][row] as handed over -> [row][item], so that what a step reads is contiguous (crowd kernel: disc tracks, wall tracks)
 template <typename T>
@@ -121,32 +120,47 @@ static std::vector<T> by_row(const float* v, size_t items, size_t rows) {
 }
 
 // ---- discs ---------------------------------------------------------------------------------------------------------------
+// One disc set of the three (BareboneScene: shared, own, tracks), checked by its setter: `count` sets (0: the set is cleared)
+// of counts[b] discs, `total` in all and kmax in the largest, `rows` centres per disc.  tracks: the set counts rows -- a
+// change makes row 0 "now" again -- and crowd mode keeps its [row][disc] copy.
+static int hand_over_discs(mppi_planner* p, DiscSet& held, bool tracks, int count, const int* counts, long total, int kmax, int rows,
+                           const float* pos, const float* r) {
+  const size_t n_pos = (size_t)total * (size_t)rows;
+  if (count == 0 ? !held.on
+                 : (held.on && rows == held.rows && same_as_held(held.counts, counts, (size_t)count) &&
+                    same_as_held(held.pos_host, pos, 2 * n_pos) && same_as_held(held.r_host, r, (size_t)total)))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  DiscSet fresh;
+  if (count > 0)
+    TRY(staged([&]() -> int {
+      TRY(dev_stage(&fresh.pos, pos, n_pos));
+      TRY(dev_stage(&fresh.r, r, (size_t)total));
+      if (tracks && p->scene.crowd) TRY(dev_stage(&fresh.pos_rows, by_row<float2>(pos, (size_t)total, (size_t)rows).data(), n_pos));
+      return MPPI_OK;
+    }, fresh.pos, fresh.r, fresh.pos_rows));
+  fresh.on = count > 0;
+  fresh.rows = count > 0 ? rows : 0;
+  fresh.max = kmax;
+  fresh.counts.assign(counts, counts + count);
+  fresh.pos_host.assign(pos, pos + 2 * n_pos);
+  fresh.r_host.assign(r, r + (size_t)total);
+  held.release();
+  held = std::move(fresh);
+  drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
+  if (tracks) reset_track_offsets(p, kDiscTracks, true, count == 0);
+  note_instance_discs(p);
+  return MPPI_OK;
+}
+
+// The shared set: one set of one row for every problem.
 extern "C" int mppi_planner_set_disc_obstacles(mppi_planner* p, const float* positions, const float* radii,
                                                int count) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(count >= 0 && (count == 0 || (positions && radii)), MPPI_ERR_INVALID, "bad obstacle arrays");
   // (the barebone mirror hands the obstacles over with every solve(): barebone_mppi_numba.ipynb cell 3 uploads them per call)
-  if (count == p->n_obstacles && same_as_held(p->obs_pos_host, positions, 2 * (size_t)count) &&
-      same_as_held(p->obs_r_host, radii, (size_t)count))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float2* pos = nullptr;
-  float* r = nullptr;
-  if (count > 0)
-    TRY(staged([&]() -> int {
-      TRY(dev_stage(&pos, positions, (size_t)count));
-      TRY(dev_stage(&r, radii, (size_t)count));
-      return MPPI_OK;
-    }, pos, r));
-  dev_take(p->obs_pos, pos);
-  dev_take(p->obs_r, r);
-  p->obs_pos_host.assign(positions, positions + 2 * (size_t)count);
-  p->obs_r_host.assign(radii, radii + (size_t)count);
-  p->n_obstacles = count;
-  note_instance_discs(p);
-  drop_graphs(p);  // (the count is a by-value argument of the captured launches)
-  return MPPI_OK;
+  return hand_over_discs(p, p->scene.shared, false, count > 0 ? 1 : 0, &count, count, count, 1, positions, radii);
 }
 
 // Barebone batch: one disc set per problem, the sets one after the other.  count == 0: every problem back to the shared set.
@@ -159,46 +173,22 @@ extern "C" int mppi_planner_set_instance_disc_obstacles(mppi_planner* p, int cou
   long total = 0;
   int kmax = 0;
   if (count > 0) {
-    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+    REQUIRE(!p->scene.samples.on, MPPI_ERR_INVALID,
             "the handle holds disc samples, which every problem shares: clear them first (mppi_planner_set_disc_track_samples with samples 0)");
     REQUIRE(disc_counts, MPPI_ERR_INVALID, "NULL disc_counts");
     TRY(sum_counts(count, disc_counts, "disc", &total, &kmax));
     REQUIRE(total <= (1L << 30), MPPI_ERR_INVALID, "too many discs (%ld)", total);
     REQUIRE(total == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
     // what a launch holds in LDS at the least: the control ratios and the largest problem's discs (an empty set asks for nothing)
-    REQUIRE(p->crowd || kmax == 0 || barebone_lds(p->cfg.num_steps, kmax, false, false) <= kBareboneLdsMax, MPPI_ERR_INVALID,
+    REQUIRE(p->scene.crowd || kmax == 0 || barebone_lds(p->cfg.num_steps, kmax, false, false) <= kBareboneLdsMax, MPPI_ERR_INVALID,
             "a problem with %d disc obstacles and %d steps: more than 64 KiB of LDS", kmax, p->cfg.num_steps);
   }
-  if (count == 0 ? !p->inst_obs_on
-                 : (p->inst_obs_on && same_as_held(p->inst_obs_counts_host, disc_counts, (size_t)count) &&
-                    same_as_held(p->inst_obs_pos_host, positions, 2 * (size_t)total) &&
-                    same_as_held(p->inst_obs_r_host, radii, (size_t)total)))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float2* pos = nullptr;
-  float* r = nullptr;
-  if (count > 0)
-    TRY(staged([&]() -> int {
-      TRY(dev_stage(&pos, positions, (size_t)total));
-      TRY(dev_stage(&r, radii, (size_t)total));
-      return MPPI_OK;
-    }, pos, r));
-  dev_take(p->inst_obs_pos, pos);
-  dev_take(p->inst_obs_r, r);
-  p->inst_obs_on = count > 0;
-  p->inst_obs_max = kmax;
-  p->inst_obs_counts_host.assign(disc_counts, disc_counts + count);
-  p->inst_obs_pos_host.assign(positions, positions + 2 * (size_t)total);
-  p->inst_obs_r_host.assign(radii, radii + (size_t)total);
-  drop_graphs(p);  // (the arrays and the largest count are arguments of the captured launches)
-  note_instance_discs(p);
-  return MPPI_OK;
+  return hand_over_discs(p, p->scene.own, false, count, disc_counts, total, kmax, 1, positions, radii);
 }
 
 // Barebone mode: discs that move.  `rows` predicted centres per disc (row j: where it is j * dt from "now"), one set shared
 // by every problem (count == 1) or one per problem (count == B), laid out like the static per-problem sets.  A change makes
-// row 0 "now" again.  Crowd mode keeps the tracks once more as [row][disc] (trk_pos_rows).
+// row 0 "now" again.  Crowd mode keeps the tracks once more as [row][disc] (DiscSet::pos_rows).
 extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const int* disc_counts, int rows,
                                             const float* tracks, const float* radii) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
@@ -209,7 +199,7 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
   long total = 0;
   int kmax = 0;
   if (count > 0) {
-    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+    REQUIRE(!p->scene.samples.on, MPPI_ERR_INVALID,
             "the handle holds disc samples, the disc source of its launches: clear them first (mppi_planner_set_disc_track_samples with samples 0)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
     TRY(sum_counts(count, disc_counts, "disc", &total, &kmax));
@@ -217,38 +207,10 @@ extern "C" int mppi_planner_set_disc_tracks(mppi_planner* p, int count, const in
     REQUIRE(total == 0 || (tracks && radii), MPPI_ERR_INVALID, "NULL tracks or radii");
     // what a launch holds in LDS at the least: the control ratios and a row of the largest problem's discs per step
     const size_t lds = barebone_lds(p->cfg.num_steps, kmax, true, false);
-    REQUIRE(p->crowd || lds <= kBareboneLdsMax, MPPI_ERR_INVALID,
+    REQUIRE(p->scene.crowd || lds <= kBareboneLdsMax, MPPI_ERR_INVALID,
             "a problem with %d disc tracks and %d steps: %zu bytes, more than 64 KiB of LDS", kmax, p->cfg.num_steps, lds);
   }
-  const size_t n_pos = (size_t)total * (size_t)rows;
-  if (count == 0 ? !p->trk_on
-                 : (p->trk_on && rows == p->trk_rows && same_as_held(p->trk_counts_host, disc_counts, (size_t)count) &&
-                    same_as_held(p->trk_pos_host, tracks, 2 * n_pos) && same_as_held(p->trk_r_host, radii, (size_t)total)))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float2 *pos = nullptr, *pos_rows = nullptr;
-  float* r = nullptr;
-  if (count > 0)
-    TRY(staged([&]() -> int {
-      TRY(dev_stage(&pos, tracks, n_pos));
-      TRY(dev_stage(&r, radii, (size_t)total));
-      if (p->crowd) TRY(dev_stage(&pos_rows, by_row<float2>(tracks, (size_t)total, (size_t)rows).data(), n_pos));
-      return MPPI_OK;
-    }, pos, r, pos_rows));
-  dev_take(p->trk_pos, pos);
-  dev_take(p->trk_r, r);
-  dev_take(p->trk_pos_rows, pos_rows);
-  p->trk_on = count > 0;
-  p->trk_rows = count > 0 ? rows : 0;
-  p->trk_max = kmax;
-  p->trk_counts_host.assign(disc_counts, disc_counts + count);
-  p->trk_pos_host.assign(tracks, tracks + 2 * n_pos);
-  p->trk_r_host.assign(radii, radii + (size_t)total);
-  drop_graphs(p);  // (the arrays, the row count and the kernel form are arguments of the captured launches)
-  reset_track_offsets(p, kDiscTracks, true, count == 0);
-  note_instance_discs(p);
-  return MPPI_OK;
+  return hand_over_discs(p, p->scene.tracks, true, count, disc_counts, total, kmax, rows, tracks, radii);
 }
 
 // Disc samples (include/mppi_hip.h): S sampled futures of K moving discs, `rows` rows each, handed over [sample][disc][row]
@@ -260,16 +222,17 @@ extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples,
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "disc samples belong to the barebone mode (mode %d)", p->cfg.mode);
   REQUIRE(samples >= 0 && samples <= kCrowdSamplesMax, MPPI_ERR_INVALID, "samples %d: must be 0 (none) to %d", samples, kCrowdSamplesMax);
+  BareboneScene& s = p->scene;
   size_t n_pos = 0;
   if (samples > 0) {
-    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+    REQUIRE(s.crowd, MPPI_ERR_INVALID,
             "disc samples need crowd mode: only the crowd kernel has sample forms (mppi_planner_set_crowd(p, 1) first)");
-    REQUIRE(p->ring_count == 0, MPPI_ERR_INVALID,
+    REQUIRE(s.rings.count == 0, MPPI_ERR_INVALID,
             "the handle holds %d clearance rings, and the sample forms count no rings: clear them first "
-            "(mppi_planner_set_clearance_rings(p, NULL, 0))", p->ring_count);
+            "(mppi_planner_set_clearance_rings(p, NULL, 0))", s.rings.count);
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
     REQUIRE(disc_count >= 0, MPPI_ERR_INVALID, "negative disc count %d", disc_count);
-    const int walls = p->fleet_on ? p->fleet_slots : (p->wtrk_on ? p->wtrk_max : p->n_walls);
+    const int walls = s.fleet.on() ? s.fleet.slots : (s.wall_tracks.on ? s.wall_tracks.max : s.walls.max);
     REQUIRE((long)disc_count + (long)walls <= (long)kCrowdSampleHitsMax, MPPI_ERR_INVALID,
             "%d discs and %d walls: a sample form counts a step's hits in 16 bits, %d at the most", disc_count, walls, kCrowdSampleHitsMax);
     REQUIRE((long)samples * (long)disc_count * (long)rows <= (1L << 30), MPPI_ERR_INVALID,
@@ -277,38 +240,39 @@ extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples,
     REQUIRE(disc_count == 0 || (positions && radii), MPPI_ERR_INVALID, "NULL positions or radii");
     for (int k = 0; k < disc_count; ++k)
       REQUIRE(std::isfinite(radii[k]) && radii[k] >= 0.0f, MPPI_ERR_INVALID, "disc %d: radius %g is negative or not finite", k, (double)radii[k]);
-    REQUIRE(!p->inst_obs_on, MPPI_ERR_INVALID,
+    REQUIRE(!s.own.on, MPPI_ERR_INVALID,
             "the handle holds per-problem disc sets; disc samples are shared by every problem: clear the sets first "
             "(mppi_planner_set_instance_disc_obstacles with count 0)");
-    REQUIRE(!(p->trk_on && p->trk_counts_host.size() > 1), MPPI_ERR_INVALID,
+    REQUIRE(!(s.tracks.on && s.tracks.counts.size() > 1), MPPI_ERR_INVALID,
             "the handle holds per-problem disc tracks; disc samples are shared by every problem: clear the tracks first "
             "(mppi_planner_set_disc_tracks with count 0)");
     n_pos = (size_t)samples * (size_t)disc_count * (size_t)rows;
   }
-  if (samples == 0 ? !p->smp_on
-                   : (p->smp_on && samples == p->smp_count && disc_count == p->smp_discs && rows == p->smp_rows &&
-                      same_as_held(p->smp_pos_host, positions, 2 * n_pos) && same_as_held(p->smp_r_host, radii, (size_t)disc_count)))
+  DiscSamples& held = s.samples;
+  if (samples == 0 ? !held.on
+                   : (held.on && samples == held.count && disc_count == held.discs && rows == held.rows &&
+                      same_as_held(held.pos_host, positions, 2 * n_pos) && same_as_held(held.r_host, radii, (size_t)disc_count)))
     return MPPI_OK;
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
-  float2* pos_rows = nullptr;
-  float* r = nullptr;
-  if (samples > 0)  // [sample][disc][row] is [item][row] with S * K items: by_row gives [row][sample][disc]
+  DiscSamples fresh;
+  if (samples > 0) {  // [sample][disc][row] is [item][row] with S * K items: by_row gives [row][sample][disc]
     TRY(staged([&]() -> int {
-      TRY(dev_stage(&pos_rows, by_row<float2>(positions, (size_t)samples * (size_t)disc_count, (size_t)rows).data(), n_pos));
-      TRY(dev_stage(&r, radii, (size_t)disc_count));
+      TRY(dev_stage(&fresh.pos_rows, by_row<float2>(positions, (size_t)samples * (size_t)disc_count, (size_t)rows).data(), n_pos));
+      TRY(dev_stage(&fresh.r, radii, (size_t)disc_count));
       return MPPI_OK;
-    }, pos_rows, r));
-  dev_take(p->smp_pos_rows, pos_rows);
-  dev_take(p->smp_r, r);
-  const bool moved = p->smp_rows > 1 || (samples > 0 && rows > 1);  // (a set of one row is static: it leaves "now" alone)
-  p->smp_on = samples > 0;
-  p->smp_count = samples;
-  p->smp_discs = samples > 0 ? disc_count : 0;
-  p->smp_rows = samples > 0 ? rows : 0;
-  p->smp_gen = samples > 0 ? next_generation() : 0;
-  p->smp_pos_host.assign(positions, positions + 2 * n_pos);
-  p->smp_r_host.assign(radii, radii + (samples > 0 ? (size_t)disc_count : 0));
+    }, fresh.pos_rows, fresh.r));
+    fresh.on = true;
+    fresh.count = samples;
+    fresh.discs = disc_count;
+    fresh.rows = rows;
+    fresh.gen = next_generation();
+    fresh.pos_host.assign(positions, positions + 2 * n_pos);
+    fresh.r_host.assign(radii, radii + (size_t)disc_count);
+  }
+  const bool moved = held.rows > 1 || fresh.rows > 1;  // (a set of one row is static: it leaves "now" alone)
+  held.release();
+  held = std::move(fresh);
   drop_graphs(p);  // (the arrays, the counts and the kernel form are arguments of the captured launches)
   reset_track_offsets(p, kDiscTracks, moved, samples == 0);
   note_instance_discs(p);
@@ -321,46 +285,48 @@ extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples,
 extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  if ((on != 0) == p->crowd) return MPPI_OK;
+  BareboneScene& s = p->scene;
+  if ((on != 0) == s.crowd) return MPPI_OK;
   if (!on) {
-    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+    REQUIRE(!s.samples.on, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds disc samples, which only the crowd kernel rolls out (clear them first)");
-    REQUIRE(p->n_walls == 0, MPPI_ERR_INVALID,
-            "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", p->n_walls);
-    REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+    REQUIRE(s.walls.max == 0, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds %d walls, which only the crowd kernel tests (clear the walls first)", s.walls.max);
+    REQUIRE(!s.wall_tracks.on, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds wall tracks, which only the crowd kernel tests (clear them first)");
-    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+    REQUIRE(!s.fleet.on(), MPPI_ERR_INVALID,
             "crowd mode stays on: the handle is in fleet mode, whose walls only the crowd kernel tests (mppi_planner_set_fleet(p, 0, NULL) first)");
-    REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
+    REQUIRE(s.footprint.count == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds a footprint of %d discs, which only the crowd kernel tests (mppi_planner_set_footprint(p, NULL, 0) first)",
-            p->fp_count);
-    REQUIRE(p->ring_count == 0, MPPI_ERR_INVALID,
+            s.footprint.count);
+    REQUIRE(s.rings.count == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds %d clearance rings, which only the crowd kernel counts (mppi_planner_set_clearance_rings(p, NULL, 0) first)",
-            p->ring_count);
+            s.rings.count);
     BareboneHeld now = barebone_held(p);  // (without rotation: every set at its own size, the least a launch can ask for)
     now.crowd = false;
     BareboneHeld own = now, shared = now, tracks = now;
     tracks.gtrk_on = own.gtrk_on = shared.gtrk_on = false;
     own.trk_on = shared.trk_on = shared.inst_obs_on = false;
     const struct { bool held; BareboneHeld state; const char* what; } sets[] = {
-        {p->trk_on, tracks, "disc tracks"}, {p->inst_obs_on, own, "per-problem disc obstacles"},
-        {true, shared, "disc obstacles"}, {p->gtrk_on, now, "discs held with a goal track"}};
-    for (const auto& s : sets) {
-      const BareboneChoice c = barebone_choose(s.state);
-      REQUIRE(!s.held || c.family != kBareboneRefused, MPPI_ERR_INVALID,
-              "crowd mode stays on: the %s (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS", s.what, c.kmax, now.T, c.lds);
+        {s.tracks.on, tracks, "disc tracks"}, {s.own.on, own, "per-problem disc obstacles"},
+        {true, shared, "disc obstacles"}, {s.goal.on, now, "discs held with a goal track"}};
+    for (const auto& set : sets) {
+      const BareboneChoice c = barebone_choose(set.state);
+      REQUIRE(!set.held || c.family != kBareboneRefused, MPPI_ERR_INVALID,
+              "crowd mode stays on: the %s (%d discs, %d steps) need %zu bytes, more than 64 KiB of LDS", set.what, c.kmax, now.T, c.lds);
     }
   }
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   float2* pos_rows = nullptr;
-  if (on && p->trk_on)
+  if (on && s.tracks.on)
     TRY(staged([&]() -> int {
-      const size_t total = p->trk_r_host.size(), rows = (size_t)p->trk_rows;
-      return dev_stage(&pos_rows, by_row<float2>(p->trk_pos_host.data(), total, rows).data(), total * rows);
+      const size_t total = s.tracks.r_host.size(), rows = (size_t)s.tracks.rows;
+      return dev_stage(&pos_rows, by_row<float2>(s.tracks.pos_host.data(), total, rows).data(), total * rows);
     }, pos_rows));
-  dev_take(p->trk_pos_rows, pos_rows);
-  p->crowd = on != 0;
+  dev_free(s.tracks.pos_rows);
+  s.tracks.pos_rows = pos_rows;
+  s.crowd = on != 0;
   drop_graphs(p);  // (the kernel form is part of the captured launches)
   return MPPI_OK;
 }
@@ -368,23 +334,13 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
 extern "C" int mppi_planner_get_crowd(mppi_planner* p, int* on) {
   REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "crowd mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  *on = p->crowd ? 1 : 0;
+  *on = p->scene.crowd ? 1 : 0;
   return MPPI_OK;
 }
 
 // ---- fleet mode (include/mppi_hip.h; fleet_kernels.h) ------------------------------------------------------------------------
-// The device arrays of a fleet: built new-first, so that a failure leaves the handle with what it had.
-struct FleetArrays {
-  float4* seg_rows = nullptr;
-  float* hw = nullptr;
-  int2* range = nullptr;
-  float2* plan = nullptr;
-  float* heads = nullptr;      // a body fleet: [B][T + 1] headings ...
-  float2* centres = nullptr;   // ... and [B][T + 1][body] body disc centres
-  int slots = 0;
-  int group = 1, body = 0;     // slots per other robot; body discs per robot (0: a disc fleet)
-};
-
+// The device arrays of a fleet (FleetArrays, barebone_scene.h) are built new-first, so that a failure leaves the handle with
+// what it had.
 // pair_hw: [B][(B - 1) * group] half-widths, reader a's others in ascending order, `group` slots each (a disc fleet: 1; a
 // body fleet of `body` discs: that count rounded up to a power of two); the static walls (W of them) behind the others'
 // slots in every reader's range and in every row.  Until the first refresh a fleet slot holds the wall nobody can touch.
@@ -430,64 +386,81 @@ static int fleet_build(mppi_planner* p, const float* pair_hw, const float* wall_
   return MPPI_OK;
 }
 
-// (the stream has drained) the handle takes the new arrays and a new generation
+// (the stream has drained) the old arrays go; the handle takes the new ones (or none) and a new generation
 static void fleet_commit(mppi_planner* p, const FleetArrays& f) {
-  dev_take(p->fleet_seg_rows, f.seg_rows);
-  dev_take(p->fleet_hw, f.hw);
-  dev_take(p->fleet_range, f.range);
-  dev_take(p->fleet_plan, f.plan);
-  dev_take(p->fleet_heads, f.heads);
-  dev_take(p->fleet_centres, f.centres);
-  p->fleet_slots = f.slots;
-  p->fleet_group = f.group;
-  p->fleet_body = f.body;
-  p->fleet_on = f.seg_rows != nullptr;
-  p->fleet_gen = p->fleet_on ? next_generation() : 0;
+  p->scene.fleet.release();
+  p->scene.fleet = f;
+  p->scene.fleet.gen = f.on() ? next_generation() : 0;
 }
 
 // ---- walls ---------------------------------------------------------------------------------------------------------------
+// One wall set of the two (BareboneScene: walls, wall_tracks), checked by its setter: `count` sets (0: the set is cleared) of
+// counts[b] walls, `total` in all and wmax in the largest, `rows` segments per wall, handed over [wall][row] and kept
+// [row][wall].  ranges: {wall0, count} per problem beside them (the wall tracks).  also: staged behind the set's own arrays
+// in the same stage, so that a failure there leaves the walls as they were too (the static walls: the fleet's storage).
+// A change takes a new generation and, for walls that move (rows > 1), makes row 0 "now" again.
+template <typename Also>
+static int hand_over_walls(mppi_planner* p, WallSet& held, bool ranges, int count, const int* counts, long total, int wmax, int rows,
+                           const float* seg, const float* hw, Also&& also) {
+  const size_t n_seg = (size_t)total * (size_t)rows;
+  if (count == 0 ? !held.on
+                 : (held.on && rows == held.rows && same_as_held(held.counts, counts, (size_t)count) &&
+                    same_as_held(held.seg_host, seg, 4 * n_seg) && same_as_held(held.hw_host, hw, (size_t)total)))
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  WallSet fresh;
+  std::vector<int2> range((size_t)count);
+  for (int b = 0, k0 = 0; b < count; k0 += counts[b], ++b) range[(size_t)b] = make_int2(k0, counts[b]);
+  TRY(staged([&]() -> int {
+    if (count > 0) {
+      TRY(dev_stage(&fresh.seg_rows, by_row<float4>(seg, (size_t)total, (size_t)rows).data(), n_seg));
+      TRY(dev_stage(&fresh.hw, hw, (size_t)total));
+      if (ranges) TRY(dev_stage(&fresh.range, range.data(), range.size()));
+    }
+    return also();
+  }, fresh.seg_rows, fresh.hw, fresh.range));
+  fresh.on = count > 0;
+  fresh.rows = count > 0 ? rows : 0;
+  fresh.max = wmax;
+  fresh.gen = count > 0 ? next_generation() : 0;
+  fresh.counts.assign(counts, counts + count);
+  fresh.seg_host.assign(seg, seg + 4 * n_seg);
+  fresh.hw_host.assign(hw, hw + (size_t)total);
+  const bool moved = held.rows > 1 || fresh.rows > 1;
+  held.release();
+  held = std::move(fresh);
+  drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
+  reset_track_offsets(p, kWallTracks, moved, count == 0);
+  return MPPI_OK;
+}
+
 // Walls (include/mppi_hip.h): crowd mode only -- they are one more source of hits for the count waves of
-// k_rollout_barebone_crowd<..., WALLS> and nothing the default forms know.  A change takes a new generation (the graph
-// signature's view of the walls).
+// k_rollout_barebone_crowd<..., WALLS> and nothing the default forms know.  Static and shared by every problem: one set of
+// one row.
 extern "C" int mppi_planner_set_walls(mppi_planner* p, const float* segments, const float* halfwidths, int count) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "walls belong to the barebone mode (mode %d)", p->cfg.mode);
   REQUIRE(count >= 0 && count <= (1 << 24) && (count == 0 || (segments && halfwidths)), MPPI_ERR_INVALID, "bad wall arrays (count %d)", count);
-  REQUIRE(count == 0 || p->crowd, MPPI_ERR_INVALID,
+  BareboneScene& s = p->scene;
+  REQUIRE(count == 0 || s.crowd, MPPI_ERR_INVALID,
           "walls need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
   TRY(check_halfwidths(halfwidths, (size_t)count, "wall"));
   TRY(check_finite(segments, (size_t)count, 1, 4, "wall"));
-  if (count == p->n_walls && same_as_held(p->wall_seg_host, segments, 4 * (size_t)count) &&
-      same_as_held(p->wall_hw_host, halfwidths, (size_t)count))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float4* seg = nullptr;
-  float* hw = nullptr;
   // fleet mode: these walls lie behind the other robots in every reader's set -- the fleet storage is rebuilt with the
   // new walls, in the same stage
   FleetArrays fleet;
-  TRY(staged([&]() -> int {
-    if (count > 0) TRY(dev_stage(&seg, segments, (size_t)count));
-    if (count > 0) TRY(dev_stage(&hw, halfwidths, (size_t)count));
-    if (p->fleet_on) TRY(fleet_build(p, p->fleet_hw_host.data(), segments, halfwidths, count, p->fleet_group, p->fleet_body, &fleet));
-    return MPPI_OK;
-  }, seg, hw));
-  if (p->fleet_on) fleet_commit(p, fleet);
-  dev_take(p->wall_seg, seg);
-  dev_take(p->wall_hw, hw);
-  p->wall_seg_host.assign(segments, segments + 4 * (size_t)count);
-  p->wall_hw_host.assign(halfwidths, halfwidths + (size_t)count);
-  p->n_walls = count;
-  p->wall_gen = count > 0 ? next_generation() : 0;
-  drop_graphs(p);  // (the arrays, the count and the kernel form are arguments of the captured launches)
+  TRY(hand_over_walls(p, s.walls, false, count > 0 ? 1 : 0, &count, count, count, 1, segments, halfwidths, [&]() -> int {
+    if (!s.fleet.on()) return MPPI_OK;
+    return fleet_build(p, s.fleet_hw_host.data(), segments, halfwidths, count, s.fleet.group, s.fleet.body, &fleet);
+  }));
+  if (fleet.on()) fleet_commit(p, fleet);
   return MPPI_OK;
 }
 
 // Walls that move, and a wall set per problem (include/mppi_hip.h): crowd mode only, like the static walls.  `rows`
 // segments per wall, one set shared by every problem (count == 1) or one per problem (count == B), the sets one after the
-// other, each [wall][row].  The device keeps them [row][wall] -- a step's walls are contiguous -- with {wall0, count} per
-// problem beside them.  A change takes a new generation and, for walls that move (rows > 1), makes row 0 "now" again.
+// other, each [wall][row].
 extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_counts, int rows,
                                             const float* segments, const float* halfwidths) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
@@ -497,9 +470,9 @@ extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const in
   long total = 0;
   int wmax = 0;
   if (count > 0) {
-    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+    REQUIRE(!p->scene.fleet.on(), MPPI_ERR_INVALID,
             "the handle is in fleet mode, which owns the per-problem wall sets: turn it off first (mppi_planner_set_fleet(p, 0, NULL))");
-    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+    REQUIRE(p->scene.crowd, MPPI_ERR_INVALID,
             "wall tracks need crowd mode: only the crowd kernel tests them (mppi_planner_set_crowd(p, 1) first)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a wall track has at least one row", rows);
     TRY(sum_counts(count, wall_counts, "wall", &total, &wmax));
@@ -508,40 +481,7 @@ extern "C" int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const in
     TRY(check_halfwidths(halfwidths, (size_t)total, "wall"));
     TRY(check_finite(segments, (size_t)total, (size_t)rows, 4, "wall"));
   }
-  const size_t n_seg = (size_t)total * (size_t)rows;
-  if (count == 0 ? !p->wtrk_on
-                 : (p->wtrk_on && rows == p->wtrk_rows && same_as_held(p->wtrk_counts_host, wall_counts, (size_t)count) &&
-                    same_as_held(p->wtrk_seg_host, segments, 4 * n_seg) && same_as_held(p->wtrk_hw_host, halfwidths, (size_t)total)))
-    return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  float4* seg_rows = nullptr;
-  float* hw = nullptr;
-  int2* range = nullptr;
-  if (count > 0) {
-    std::vector<int2> ranges((size_t)count);
-    for (int b = 0, k0 = 0; b < count; k0 += wall_counts[b], ++b) ranges[(size_t)b] = make_int2(k0, wall_counts[b]);
-    TRY(staged([&]() -> int {
-      TRY(dev_stage(&seg_rows, by_row<float4>(segments, (size_t)total, (size_t)rows).data(), std::max<size_t>(1, n_seg)));
-      TRY(dev_stage(&hw, halfwidths, (size_t)total));
-      TRY(dev_stage(&range, ranges.data(), ranges.size()));
-      return MPPI_OK;
-    }, seg_rows, hw, range));
-  }
-  dev_take(p->wtrk_seg_rows, seg_rows);
-  dev_take(p->wtrk_hw, hw);
-  dev_take(p->wtrk_range, range);
-  const bool moved = p->wtrk_rows > 1 || (count > 0 && rows > 1);
-  p->wtrk_on = count > 0;
-  p->wtrk_rows = count > 0 ? rows : 0;
-  p->wtrk_max = wmax;
-  p->wtrk_gen = count > 0 ? next_generation() : 0;
-  p->wtrk_counts_host.assign(wall_counts, wall_counts + count);
-  p->wtrk_seg_host.assign(segments, segments + 4 * n_seg);
-  p->wtrk_hw_host.assign(halfwidths, halfwidths + (size_t)total);
-  drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
-  reset_track_offsets(p, kWallTracks, moved, count == 0);
-  return MPPI_OK;
+  return hand_over_walls(p, p->scene.wall_tracks, true, count, wall_counts, total, wmax, rows, segments, halfwidths, [] { return MPPI_OK; });
 }
 
 // ---- goal tracks ---------------------------------------------------------------------------------------------------------
@@ -560,20 +500,23 @@ extern "C" int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows
     n_xy = (size_t)count * (size_t)rows;
     TRY(check_finite(xy, (size_t)count, (size_t)rows, 2, "goal track"));
   }
-  if (count == 0 ? !p->gtrk_on
-                 : (p->gtrk_on && rows == p->gtrk_rows && count == p->gtrk_count && same_as_held(p->gtrk_host, xy, 2 * n_xy)))
+  GoalTracks& held = p->scene.goal;
+  if (count == 0 ? !held.on : (held.on && rows == held.rows && count == held.count && same_as_held(held.host, xy, 2 * n_xy)))
     return MPPI_OK;
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
-  float2* fresh = nullptr;
-  if (count > 0) TRY(staged([&]() -> int { return dev_stage(&fresh, xy, n_xy); }, fresh));
-  dev_take(p->gtrk_xy, fresh);
-  const bool moved = p->gtrk_rows > 1 || (count > 0 && rows > 1);
-  p->gtrk_on = count > 0;
-  p->gtrk_rows = count > 0 ? rows : 0;
-  p->gtrk_count = count;
-  p->gtrk_gen = count > 0 ? next_generation() : 0;
-  p->gtrk_host.assign(xy, xy + 2 * n_xy);
+  GoalTracks fresh;
+  if (count > 0) {
+    TRY(staged([&]() -> int { return dev_stage(&fresh.xy, xy, n_xy); }, fresh.xy));
+    fresh.on = true;
+    fresh.rows = rows;
+    fresh.count = count;
+    fresh.gen = next_generation();
+    fresh.host.assign(xy, xy + 2 * n_xy);
+  }
+  const bool moved = held.rows > 1 || fresh.rows > 1;
+  held.release();
+  held = std::move(fresh);
   drop_graphs(p);  // (the array, the row count and the kernel form are arguments of the captured launches)
   reset_track_offsets(p, kGoalTracks, moved, count == 0);
   return MPPI_OK;
@@ -588,18 +531,17 @@ static const char* const kFleetKinds =
 extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* halfwidths) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
+  BareboneScene& s = p->scene;
   if (count == 0) {
-    if (!p->fleet_on) return MPPI_OK;
+    if (!s.fleet.on()) return MPPI_OK;
     HIP_TRY(hipSetDevice(p->cfg.device));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->fleet_body > 0) {  // (a body fleet holds its body as the handle's footprint: it goes with the fleet)
-      memset(p->fp_host, 0, sizeof(p->fp_host));
-      p->fp_count = 0;
-      p->fp_gen = 0;
-      p->fleet_margin = 0.0;
+    if (s.fleet.body > 0) {  // (a body fleet holds its body as the handle's footprint: it goes with the fleet)
+      s.footprint.set(nullptr, 0, 0);
+      s.fleet_margin = 0.0;
     }
     fleet_commit(p, FleetArrays());
-    p->fleet_hw_host.clear();
+    s.fleet_hw_host.clear();
     drop_graphs(p);  // (the arrays and the kernel form are arguments of the captured launches)
     return MPPI_OK;
   }
@@ -607,25 +549,25 @@ extern "C" int mppi_planner_set_fleet(mppi_planner* p, int count, const float* h
           "fleet mode needs a batched handle of at least two problems, one per robot (num_instances %d)", p->B);
   REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 (off) or num_instances %d", count, p->B);
   REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "fleet mode drives an unsharded handle");
-  REQUIRE(p->crowd, MPPI_ERR_INVALID,
+  REQUIRE(s.crowd, MPPI_ERR_INVALID,
           "fleet mode needs crowd mode: only the crowd kernel tests walls (mppi_planner_set_crowd(p, 1) first)");
-  REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+  REQUIRE(!s.wall_tracks.on, MPPI_ERR_INVALID,
           "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
           "first (mppi_planner_set_wall_tracks with count 0)");
-  REQUIRE(!(p->fleet_on && p->fleet_body > 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
-  REQUIRE(p->fp_count == 0, MPPI_ERR_INVALID,
+  REQUIRE(!(s.fleet.on() && s.fleet.body > 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
+  REQUIRE(s.footprint.count == 0, MPPI_ERR_INVALID,
           "the handle holds a footprint; the fleet's half-widths already contain the reader's body: clear it first "
           "(mppi_planner_set_footprint(p, NULL, 0))");
   REQUIRE(halfwidths, MPPI_ERR_INVALID, "NULL halfwidths");
   const size_t pairs = (size_t)p->B * (size_t)(p->B - 1);
   TRY(check_halfwidths(halfwidths, pairs, "fleet pair"));
-  if (p->fleet_on && memcmp(halfwidths, p->fleet_hw_host.data(), sizeof(float) * pairs) == 0) return MPPI_OK;
+  if (s.fleet.on() && memcmp(halfwidths, s.fleet_hw_host.data(), sizeof(float) * pairs) == 0) return MPPI_OK;
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   FleetArrays fleet;
-  TRY(fleet_build(p, halfwidths, p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, 1, 0, &fleet));
+  TRY(fleet_build(p, halfwidths, s.walls.seg_host.data(), s.walls.hw_host.data(), s.walls.max, 1, 0, &fleet));
   fleet_commit(p, fleet);
-  p->fleet_hw_host.assign(halfwidths, halfwidths + pairs);
+  s.fleet_hw_host.assign(halfwidths, halfwidths + pairs);
   drop_graphs(p);
   return MPPI_OK;
 }
@@ -647,17 +589,18 @@ extern "C" int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const f
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
   if (count == 0) return mppi_planner_set_fleet(p, 0, nullptr);
+  BareboneScene& s = p->scene;
   REQUIRE(p->B >= 2, MPPI_ERR_INVALID,
           "fleet mode needs a batched handle of at least two problems, one per robot (num_instances %d)", p->B);
   REQUIRE(count == p->B, MPPI_ERR_INVALID, "count %d: must be 0 (off) or num_instances %d", count, p->B);
   REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "fleet mode drives an unsharded handle");
-  REQUIRE(p->crowd, MPPI_ERR_INVALID,
+  REQUIRE(s.crowd, MPPI_ERR_INVALID,
           "fleet mode needs crowd mode: only the crowd kernel tests walls (mppi_planner_set_crowd(p, 1) first)");
-  REQUIRE(!p->wtrk_on, MPPI_ERR_INVALID,
+  REQUIRE(!s.wall_tracks.on, MPPI_ERR_INVALID,
           "the handle holds wall tracks or per-problem wall sets; fleet mode makes every problem's set itself: clear them "
           "first (mppi_planner_set_wall_tracks with count 0)");
-  REQUIRE(!(p->fleet_on && p->fleet_body == 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
-  REQUIRE(p->fleet_body > 0 || p->fp_count == 0, MPPI_ERR_INVALID,
+  REQUIRE(!(s.fleet.on() && s.fleet.body == 0), MPPI_ERR_INVALID, "%s", kFleetKinds);
+  REQUIRE(s.fleet.body > 0 || s.footprint.count == 0, MPPI_ERR_INVALID,
           "the handle holds a footprint; a body fleet carries its own body: clear it first (mppi_planner_set_footprint(p, NULL, 0))");
   REQUIRE(n_discs >= 1 && n_discs <= kCrowdFootprintMax, MPPI_ERR_INVALID, "body of %d discs: must be 1 to %d", n_discs, kCrowdFootprintMax);
   REQUIRE(discs, MPPI_ERR_INVALID, "NULL discs");
@@ -666,8 +609,8 @@ extern "C" int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const f
   for (int k = 0; k < n_discs; ++k)
     REQUIRE((double)discs[3 * k + 2] + margin >= 0.0, MPPI_ERR_INVALID,
             "body disc %d: radius %g and margin %g give a negative half-width", k, (double)discs[3 * k + 2], margin);
-  if (p->fleet_on && p->fleet_body == n_discs && margin == p->fleet_margin &&
-      memcmp(discs, p->fp_host, sizeof(float) * 3 * (size_t)n_discs) == 0)
+  if (s.fleet.on() && s.fleet.body == n_discs && margin == s.fleet_margin &&
+      memcmp(discs, s.footprint.host, sizeof(float) * 3 * (size_t)n_discs) == 0)
     return MPPI_OK;
   int group = 1;
   while (group < n_discs) group *= 2;
@@ -682,14 +625,11 @@ extern "C" int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const f
   HIP_TRY(hipSetDevice(p->cfg.device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   FleetArrays fleet;
-  TRY(fleet_build(p, hw.data(), p->wall_seg_host.data(), p->wall_hw_host.data(), p->n_walls, group, n_discs, &fleet));
+  TRY(fleet_build(p, hw.data(), s.walls.seg_host.data(), s.walls.hw_host.data(), s.walls.max, group, n_discs, &fleet));
   fleet_commit(p, fleet);
-  p->fleet_hw_host = hw;
-  p->fleet_margin = margin;
-  memset(p->fp_host, 0, sizeof(p->fp_host));
-  memcpy(p->fp_host, discs, sizeof(float) * 3 * (size_t)n_discs);
-  p->fp_count = n_discs;
-  p->fp_gen = next_generation();
+  s.fleet_hw_host = hw;
+  s.fleet_margin = margin;
+  s.footprint.set(discs, n_discs, next_generation());
   drop_graphs(p);  // (the arrays, the rows, the counts and the kernel form are arguments of the captured launches)
   return MPPI_OK;
 }
@@ -698,68 +638,70 @@ extern "C" int mppi_planner_set_fleet_bodies(mppi_planner* p, int count, const f
 extern "C" int mppi_planner_get_fleet_bodies(mppi_planner* p, int* n_discs, double* margin) {
   REQUIRE(p && n_discs && margin, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  *n_discs = p->fleet_on ? p->fleet_body : 0;
-  *margin = p->fleet_on ? p->fleet_margin : 0.0;
+  *n_discs = p->scene.fleet.body;  // (0 while no body fleet is on)
+  *margin = p->scene.fleet.on() ? p->scene.fleet_margin : 0.0;
   return MPPI_OK;
 }
 
 extern "C" int mppi_planner_get_fleet(mppi_planner* p, int* on) {
   REQUIRE(p && on, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "fleet mode belongs to the barebone mode (mode %d)", p->cfg.mode);
-  *on = p->fleet_on ? p->B : 0;
+  *on = p->scene.fleet.on() ? p->B : 0;
   return MPPI_OK;
 }
 
-// ---- a body footprint ----------------------------------------------------------------------------------------------------
-// A body footprint (include/mppi_hip.h): crowd mode only, and not beside the fleet.  The rows are a by-value argument of the
-// launches: there is no device array, so nothing to stage -- but the stream is drained like everywhere else, and a change
-// takes a new generation (the graph signature's view of the footprint) and drops the captured graphs.
+// ---- rows by value: a body footprint, clearance rings ---------------------------------------------------------------------
+// The rows are a by-value argument of the launches: there is no device array, so nothing to stage -- but the stream is
+// drained like everywhere else, and a change takes a new generation (the graph signature's view of the rows) and drops the
+// captured graphs.
+template <int MaxRows, int Width>
+static int hand_over_rows(mppi_planner* p, ValueRows<MaxRows, Width>& held, const float* rows, int count) {
+  if (count == held.count && (count == 0 || memcmp(rows, held.host, sizeof(float) * Width * (size_t)count) == 0)) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  held.set(rows, count, count > 0 ? next_generation() : 0);
+  drop_graphs(p);  // (the rows, the count and the kernel form are arguments of the captured launches)
+  return MPPI_OK;
+}
+
+// A body footprint (include/mppi_hip.h): crowd mode only, and not beside the fleet.
 extern "C" int mppi_planner_set_footprint(mppi_planner* p, const float* discs, int count) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
   REQUIRE(count >= 0 && count <= kCrowdFootprintMax, MPPI_ERR_INVALID, "footprint of %d discs: must be 0 (none) to %d", count, kCrowdFootprintMax);
-  REQUIRE(!(p->fleet_on && p->fleet_body > 0), MPPI_ERR_INVALID,
+  const BareboneScene& s = p->scene;
+  REQUIRE(!(s.fleet.on() && s.fleet.body > 0), MPPI_ERR_INVALID,
           "the handle is in a body fleet, which carries its own body: turn the fleet off first (mppi_planner_set_fleet(p, 0, NULL))");
   if (count > 0) {
     REQUIRE(discs, MPPI_ERR_INVALID, "NULL discs");
-    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+    REQUIRE(s.crowd, MPPI_ERR_INVALID,
             "a footprint needs crowd mode: only the crowd kernel has footprint forms (mppi_planner_set_crowd(p, 1) first)");
-    REQUIRE(!p->fleet_on, MPPI_ERR_INVALID,
+    REQUIRE(!s.fleet.on(), MPPI_ERR_INVALID,
             "the handle is in fleet mode, whose half-widths already contain the reader's body: turn it off first "
             "(mppi_planner_set_fleet(p, 0, NULL))");
     TRY(check_footprint_rows(discs, count));
   }
-  if (count == p->fp_count && (count == 0 || memcmp(discs, p->fp_host, sizeof(float) * 3 * (size_t)count) == 0)) return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  memset(p->fp_host, 0, sizeof(p->fp_host));
-  if (count > 0) memcpy(p->fp_host, discs, sizeof(float) * 3 * (size_t)count);
-  p->fp_count = count;
-  p->fp_gen = count > 0 ? next_generation() : 0;
-  drop_graphs(p);  // (the rows, the count and the kernel form are arguments of the captured launches)
-  return MPPI_OK;
+  return hand_over_rows(p, p->scene.footprint, discs, count);
 }
 
 extern "C" int mppi_planner_get_footprint(mppi_planner* p, float* discs, int* count) {
   REQUIRE(p && discs && count, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "a footprint belongs to the barebone mode (mode %d)", p->cfg.mode);
-  memcpy(discs, p->fp_host, sizeof(p->fp_host));
-  *count = p->fp_count;
+  memcpy(discs, p->scene.footprint.host, sizeof(p->scene.footprint.host));
+  *count = p->scene.footprint.count;
   return MPPI_OK;
 }
 
-// ---- clearance rings -----------------------------------------------------------------------------------------------------
-// Clearance rings (include/mppi_hip.h): crowd mode only, and not beside disc samples.  Like the footprint's, the rows are a
-// by-value argument of the launches: nothing to stage, a new generation and no captured graphs at every change.
+// Clearance rings (include/mppi_hip.h): crowd mode only, and not beside disc samples.
 extern "C" int mppi_planner_set_clearance_rings(mppi_planner* p, const float* rings, int count) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "clearance rings belong to the barebone mode (mode %d)", p->cfg.mode);
   REQUIRE(count >= 0 && count <= kCrowdRingsMax, MPPI_ERR_INVALID, "%d clearance rings: must be 0 (none) to %d", count, kCrowdRingsMax);
   if (count > 0) {
     REQUIRE(rings, MPPI_ERR_INVALID, "NULL rings");
-    REQUIRE(p->crowd, MPPI_ERR_INVALID,
+    REQUIRE(p->scene.crowd, MPPI_ERR_INVALID,
             "clearance rings need crowd mode: only the crowd kernel has ring forms (mppi_planner_set_crowd(p, 1) first)");
-    REQUIRE(!p->smp_on, MPPI_ERR_INVALID,
+    REQUIRE(!p->scene.samples.on, MPPI_ERR_INVALID,
             "the handle holds disc samples, and the sample forms count no rings: clear them first "
             "(mppi_planner_set_disc_track_samples with samples 0)");
     for (int l = 0; l < count; ++l) {
@@ -770,22 +712,14 @@ extern "C" int mppi_planner_set_clearance_rings(mppi_planner* p, const float* ri
       REQUIRE(std::isfinite(c) && c >= 0.0f, MPPI_ERR_INVALID, "ring %d: penalty %g is negative or not finite", l, (double)c);
     }
   }
-  if (count == p->ring_count && (count == 0 || memcmp(rings, p->ring_host, sizeof(float) * 2 * (size_t)count) == 0)) return MPPI_OK;
-  HIP_TRY(hipSetDevice(p->cfg.device));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  memset(p->ring_host, 0, sizeof(p->ring_host));
-  if (count > 0) memcpy(p->ring_host, rings, sizeof(float) * 2 * (size_t)count);
-  p->ring_count = count;
-  p->ring_gen = count > 0 ? next_generation() : 0;
-  drop_graphs(p);  // (the rows, the count and the kernel form are arguments of the captured launches)
-  return MPPI_OK;
+  return hand_over_rows(p, p->scene.rings, rings, count);
 }
 
 extern "C" int mppi_planner_get_clearance_rings(mppi_planner* p, float* rings, int* count) {
   REQUIRE(p && rings && count, MPPI_ERR_INVALID, "NULL argument");
   REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "clearance rings belong to the barebone mode (mode %d)", p->cfg.mode);
-  memcpy(rings, p->ring_host, sizeof(p->ring_host));
-  *count = p->ring_count;
+  memcpy(rings, p->scene.rings.host, sizeof(p->scene.rings.host));
+  *count = p->scene.rings.count;
   return MPPI_OK;
 }
 
@@ -816,7 +750,8 @@ extern "C" int mppi_planner_get_track_offsets(mppi_planner* p, int count, int* o
 // closed_loop), once per call.  done: closed_loop's per-problem flags (a robot at its goal stands), else nullptr.
 // The arrays stay where they are: nothing a captured graph holds changes.
 static int fleet_refresh(mppi_planner* p, const int* done) {
-  if (!p->fleet_on) return MPPI_OK;
+  const FleetArrays& f = p->scene.fleet;
+  if (!f.on()) return MPPI_OK;
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   REQUIRE(p->inst_set, MPPI_ERR_STATE, "num_instances = %d: call mppi_planner_set_instances before solving", p->B);
   TRY(upload_instances(p));
@@ -824,32 +759,32 @@ static int fleet_refresh(mppi_planner* p, const int* done) {
   const int B = p->B, T = p->cfg.num_steps;
   REQUIRE((size_t)T * sizeof(double2) <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large", T);  // (as launch_rollout)
   const size_t lds = fleet_plans_lds_bytes(T);  // (28 bytes a step: 112 KiB at the 4096 steps the line above admits)
-  const bool exact = p->cfg.math == MPPI_MATH_EXACT, body = p->fleet_body > 0;
+  const bool exact = p->cfg.math == MPPI_MATH_EXACT, body = f.body > 0;
   auto plans = body ? (exact ? &k_fleet_plans<true, true> : &k_fleet_plans<false, true>)
                     : (exact ? &k_fleet_plans<true, false> : &k_fleet_plans<false, false>);
   if (lds > 64 * 1024)  // (a horizon of more than ~2300 steps)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(plans), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, p->fleet_plan, body ? p->fleet_heads : nullptr);
+  hipLaunchKernelGGL(plans, dim3(B), dim3(64), lds, p->stream, d, p->u, done, f.plan, body ? f.heads : nullptr);
   HIP_TRY(hipGetLastError());
   if (body) {  // the body discs' centres once per (robot, state), then the scatter into every reader's slots
-    const int states = B * (T + 1), F = p->fleet_body, Fp = p->fleet_group;
-    hipLaunchKernelGGL(k_fleet_body_centres, dim3(ceil_div(states, 256)), dim3(256), 0, p->stream, p->fleet_plan, p->fleet_heads,
-                       p->fleet_centres, states, footprint_arg(p));
+    const int states = B * (T + 1), F = f.body, Fp = f.group;
+    hipLaunchKernelGGL(k_fleet_body_centres, dim3(ceil_div(states, 256)), dim3(256), 0, p->stream, f.plan, f.heads, f.centres, states,
+                       footprint_arg(p));
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fleet_body_walls, dim3(ceil_div((long)B * (B - 1) * Fp, 256), T), dim3(256), 0, p->stream, p->fleet_centres,
-                       p->fleet_seg_rows, B, T, p->fleet_slots, F, Fp);
+    hipLaunchKernelGGL(k_fleet_body_walls, dim3(ceil_div((long)B * (B - 1) * Fp, 256), T), dim3(256), 0, p->stream, f.centres, f.seg_rows, B, T,
+                       f.slots, F, Fp);
     HIP_TRY(hipGetLastError());
     return MPPI_OK;
   }
-  hipLaunchKernelGGL(k_fleet_walls, dim3(ceil_div((long)B * (B - 1), 256), T), dim3(256), 0, p->stream, p->fleet_plan,
-                     p->fleet_seg_rows, B, T, p->fleet_slots);
+  hipLaunchKernelGGL(k_fleet_walls, dim3(ceil_div((long)B * (B - 1), 256), T), dim3(256), 0, p->stream, f.plan, f.seg_rows, B, T,
+                     f.slots);
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
 
 extern "C" int mppi_planner_fleet_refresh(mppi_planner* p) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
+  REQUIRE(p->scene.fleet.on(), MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
   HIP_TRY(hipSetDevice(p->cfg.device));
   TRY(fleet_refresh(p, nullptr));
   return drain_stream(p);

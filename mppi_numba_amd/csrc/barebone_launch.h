@@ -21,26 +21,29 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk);
 static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
-  return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, p->crowd, p->n_obstacles, p->inst_obs_on, p->inst_obs_max,
-                      p->trk_on, p->trk_max, p->trk_rows, p->n_walls, p->wtrk_on, p->fleet_on, p->gtrk_on,
-                      p->smp_on ? p->smp_count : 0, p->smp_discs, p->smp_rows, W, p->fp_count, p->ring_count};
+  const BareboneScene& s = p->scene;
+  return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, s.crowd, s.shared.max, s.own.on, s.own.max,
+                      s.tracks.on, s.tracks.max, s.tracks.rows, s.walls.max, s.wall_tracks.on, s.fleet.on(), s.goal.on,
+                      s.samples.on ? s.samples.count : 0, s.samples.discs, s.samples.rows, W, s.footprint.count, s.rings.count};
 }
 
 // The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
+static const DiscSet& barebone_disc_set(const mppi_planner* p, const BareboneChoice& c) {
+  return c.discs == kDiscsTracks ? p->scene.tracks : (c.discs == kDiscsOwn ? p->scene.own : p->scene.shared);
+}
 static const float2* barebone_disc_pos(const mppi_planner* p, const BareboneChoice& c) {
-  if (c.discs == kDiscsSamples) return p->smp_pos_rows;
-  if (c.discs == kDiscsTracks) return c.family == kBareboneCrowd ? p->trk_pos_rows : p->trk_pos;
-  return c.discs == kDiscsOwn ? p->inst_obs_pos : p->obs_pos;
+  if (c.discs == kDiscsSamples) return p->scene.samples.pos_rows;
+  return c.discs == kDiscsTracks && c.family == kBareboneCrowd ? p->scene.tracks.pos_rows : barebone_disc_set(p, c).pos;
 }
 static const float* barebone_disc_rad(const mppi_planner* p, const BareboneChoice& c) {
-  if (c.discs == kDiscsSamples) return p->smp_r;
-  return c.discs == kDiscsTracks ? p->trk_r : (c.discs == kDiscsOwn ? p->inst_obs_r : p->obs_r);
+  return c.discs == kDiscsSamples ? p->scene.samples.r : barebone_disc_set(p, c).r;
 }
 
 // The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.
 template <bool BATCHED>
 static GoalRows goal_rows_arg(const mppi_planner* p) {
-  return GoalRows{p->gtrk_xy, p->gtrk_rows, BATCHED && p->gtrk_count > 1 ? p->gtrk_rows : 0};
+  const GoalTracks& g = p->scene.goal;
+  return GoalRows{g.xy, g.rows, BATCHED && g.count > 1 ? g.rows : 0};
 }
 
 // The default family.  Static discs: <EXACT, ROT, KD, BATCHED>; disc tracks: the TRACKS forms, a row of disc slots per step;
@@ -74,10 +77,10 @@ static int launch_barebone_default(mppi_planner* p, DevParams d, const BareboneC
   p->last_rollout = "k_rollout_barebone exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot);
   if (BATCHED || c.track_form)  // (the classic single launch of a static set names no disc form)
     p->last_rollout += (c.kd > 0 ? " discs<=" + std::to_string(c.kd) : std::string(" discs=loop")) +
-                       (tracks ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
+                       (tracks ? " tracks=" + std::to_string(p->scene.tracks.rows) : std::string()) +
                        (!c.track_form && c.discs == kDiscsOwn ? " own_discs=1" : "") +
                        (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                       (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string());
+                       (c.goal_form ? " goal_rows=" + std::to_string(p->scene.goal.rows) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -97,17 +100,18 @@ static void crowd_shape(const mppi_planner* p, int* waves, int* chunk) {
 // (the classic single launch has one problem: the first set, which starts at wall 0)
 template <bool BATCHED>
 static CrowdWallTracks wall_tracks_arg(const mppi_planner* p) {
-  if (p->fleet_on)
-    return CrowdWallTracks{p->fleet_seg_rows, p->fleet_hw, p->fleet_range, p->fleet_slots, p->cfg.num_steps, p->B * p->fleet_slots, 1};
-  const bool own = BATCHED && p->wtrk_counts_host.size() > 1;
-  return CrowdWallTracks{p->wtrk_seg_rows, p->wtrk_hw, own ? p->wtrk_range : nullptr,
-                         own ? p->wtrk_max : p->wtrk_counts_host[0], p->wtrk_rows, (int)p->wtrk_hw_host.size(), 0};
+  const FleetArrays& f = p->scene.fleet;
+  if (f.on()) return CrowdWallTracks{f.seg_rows, f.hw, f.range, f.slots, p->cfg.num_steps, p->B * f.slots, 1};
+  const WallSet& w = p->scene.wall_tracks;
+  const bool own = BATCHED && w.counts.size() > 1;
+  return CrowdWallTracks{w.seg_rows, w.hw, own ? w.range : nullptr, own ? w.max : w.counts[0], w.rows, (int)w.hw_host.size(), 0};
 }
 
-// Static shared walls as wall tracks of one row (the sample, footprint and ring forms): their [wall] array IS the
-// [row][wall] array of one row.
+// Static shared walls as wall tracks of one row (the sample, footprint and ring forms): they are held as [row][wall] of
+// one row.
 static CrowdWallTracks wall_row_arg(const mppi_planner* p) {
-  return CrowdWallTracks{p->wall_seg, p->wall_hw, nullptr, p->n_walls, 1, p->n_walls, 0};
+  const WallSet& w = p->scene.walls;
+  return CrowdWallTracks{w.seg_rows, w.hw, nullptr, w.max, 1, w.max, 0};
 }
 
 // The disc samples as a launch takes them: the CVaR tail's length, and where the per-sample costs go while they are wanted.
@@ -118,14 +122,16 @@ static CrowdSamples samples_arg(const mppi_planner* p, const BareboneChoice& c, 
 // The body footprint as a launch takes it.
 static CrowdFootprint footprint_arg(const mppi_planner* p) {
   CrowdFootprint fp{};
-  fp.count = p->fp_count;
-  const bool bodies = p->fleet_on && p->fleet_body > 0;  // a body fleet: the others' slots count once per robot
-  fp.group = bodies ? p->fleet_group : 1;
-  fp.grouped = bodies ? (p->B - 1) * p->fleet_group : 0;
-  for (int i = 0; i < p->fp_count; ++i) {  // (the float32 rows widened here: exact, and the kernel's scalar operands as they are)
-    fp.ox[i] = (double)p->fp_host[3 * i];
-    fp.oy[i] = (double)p->fp_host[3 * i + 1];
-    fp.rho[i] = (double)p->fp_host[3 * i + 2];
+  const auto& held = p->scene.footprint;
+  const FleetArrays& f = p->scene.fleet;
+  fp.count = held.count;
+  const bool bodies = f.on() && f.body > 0;  // a body fleet: the others' slots count once per robot
+  fp.group = bodies ? f.group : 1;
+  fp.grouped = bodies ? (p->B - 1) * f.group : 0;
+  for (int i = 0; i < held.count; ++i) {  // (the float32 rows widened here: exact, and the kernel's scalar operands as they are)
+    fp.ox[i] = (double)held.host[3 * i];
+    fp.oy[i] = (double)held.host[3 * i + 1];
+    fp.rho[i] = (double)held.host[3 * i + 2];
   }
   return fp;
 }
@@ -133,10 +139,11 @@ static CrowdFootprint footprint_arg(const mppi_planner* p) {
 // The clearance rings as a launch takes them: the float32 rows widened (exact).
 static CrowdRings rings_arg(const mppi_planner* p) {
   CrowdRings rg{};
-  rg.count = p->ring_count;
-  for (int l = 0; l < p->ring_count; ++l) {
-    rg.margin[l] = (double)p->ring_host[2 * l];
-    rg.penalty[l] = (double)p->ring_host[2 * l + 1];
+  const auto& held = p->scene.rings;
+  rg.count = held.count;
+  for (int l = 0; l < held.count; ++l) {
+    rg.margin[l] = (double)held.host[2 * l];
+    rg.penalty[l] = (double)held.host[2 * l + 1];
   }
   return rg;
 }
@@ -173,6 +180,7 @@ static int crowd_append(bool has, Make make, Next next, Pack... pack) {
 template <bool EXACT, bool BATCHED>
 static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneChoice& c, bool rot) {
   const CrowdForm f = crowd_form(c, rot);
+  const BareboneScene& sc = p->scene;
   REQUIRE(!(f.rings && f.samples), MPPI_ERR_STATE, "clearance rings beside disc samples: the hand-over keeps them apart");
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
@@ -186,7 +194,7 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
   else if (f.samples)
     REQUIRE(fits, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS", c.samples, p->cfg.num_steps, lds);
   if (f.rings || f.samples) {  // (their counts of a step are 16 bits wide)
-    const int walls = c.walls == 2 ? (p->fleet_on ? p->fleet_slots : p->wtrk_max) : (c.walls == 1 ? p->n_walls : 0);
+    const int walls = c.walls == 2 ? (sc.fleet.on() ? sc.fleet.slots : sc.wall_tracks.max) : (c.walls == 1 ? sc.walls.max : 0);
     const bool counted = (long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax;
     if (f.rings)
       REQUIRE(counted, MPPI_ERR_INVALID, "clearance rings: %d discs and %d walls, more than the %d a step's 16-bit counter holds", c.kmax,
@@ -196,14 +204,14 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
               c.kmax, walls, kCrowdSampleHitsMax);
   }
   if (f.samples && p->want_sample_costs && !p->sample_costs) TRY(dev_alloc(&p->sample_costs, (size_t)p->n_local * (size_t)kCrowdSamplesMax));
-  if (c.walls == 2) REQUIRE(BATCHED || !p->fleet_on, MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
+  if (c.walls == 2) REQUIRE(BATCHED || !sc.fleet.on(), MPPI_ERR_STATE, "fleet mode: a launch over the problems of the batch (mppi_planner_set_instances)");
   if (c.walls != 0)  // (the launch without walls is left as it was: the attribute call below refuses what the device cannot hold)
     REQUIRE(fits, MPPI_ERR_INVALID, "%d steps and walls: the crowd kernel needs %zu bytes of LDS", p->cfg.num_steps, lds);
   if (f.disc_row) d.track_rows = 1;
   const bool tracks = c.discs == kDiscsTracks;
   const float2* pos = barebone_disc_pos(p, c);
   const float* rad = barebone_disc_rad(p, c);
-  const int pitch = c.samples > 0 ? c.samples * c.kmax : (tracks ? (int)p->trk_r_host.size() : 0);
+  const int pitch = c.samples > 0 ? c.samples * c.kmax : (tracks ? (int)sc.tracks.r_host.size() : 0);
   const dim3 grid(ceil_div(p->n_local, 64)), block(64 * W);
   auto dispatch = [&](auto rot_c, auto tracks_c) -> int {
     constexpr bool ROT = decltype(rot_c)::value, TRACKS = decltype(tracks_c)::value;
@@ -220,23 +228,23 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
     auto samples = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.samples, [&] { return samples_arg(p, c, d); }, rings, pack...); };
     auto goal = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.goal, [&] { return goal_rows_arg<BATCHED>(p); }, samples, pack...); };
     if (f.walls == kCrowdWallsTracks) return goal(f.wall_row ? wall_row_arg(p) : wall_tracks_arg<BATCHED>(p));
-    if (f.walls == kCrowdWallsStatic) return goal(CrowdWalls{p->wall_seg, p->wall_hw, p->n_walls});
+    if (f.walls == kCrowdWallsStatic) return goal(CrowdWalls{sc.walls.seg_rows, sc.walls.hw, sc.walls.max});
     return goal();
   };
   auto with_tracks = [&](auto rot_c) -> int { return f.tracks ? dispatch(rot_c, std::true_type()) : dispatch(rot_c, std::false_type()); };
   if constexpr (EXACT) TRY(f.rot ? with_tracks(std::true_type()) : with_tracks(std::false_type()));
   else TRY(with_tracks(std::false_type()));  // (ROT is exact math's alone: launch_rollout_t grants rot under it only)
-  const bool fleet = c.walls == 2 && p->fleet_on;
+  const bool fleet = c.walls == 2 && sc.fleet.on();
   p->last_rollout = "k_rollout_barebone_crowd exact=" + std::to_string((int)EXACT) + " rotation=" + std::to_string((int)rot) +
                     " waves=" + std::to_string(W) + " chunk=" + std::to_string(C) +
-                    (tracks ? " tracks=" + std::to_string(p->trk_rows) : std::string()) +
-                    (c.samples > 0 ? " tracks=" + std::to_string(p->smp_rows) : std::string()) +
+                    (tracks ? " tracks=" + std::to_string(p->scene.tracks.rows) : std::string()) +
+                    (c.samples > 0 ? " tracks=" + std::to_string(sc.samples.rows) : std::string()) +
                     (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                    (c.walls == 1 ? " walls=" + std::to_string(p->n_walls) : std::string()) +
-                    (c.walls == 2 && !fleet ? " walls=" + std::to_string(p->wtrk_max) + " wall_rows=" + std::to_string(p->wtrk_rows) : std::string()) +
-                    (fleet ? " walls=" + std::to_string(p->fleet_slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
+                    (c.walls == 1 ? " walls=" + std::to_string(sc.walls.max) : std::string()) +
+                    (c.walls == 2 && !fleet ? " walls=" + std::to_string(sc.wall_tracks.max) + " wall_rows=" + std::to_string(sc.wall_tracks.rows) : std::string()) +
+                    (fleet ? " walls=" + std::to_string(sc.fleet.slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
                                  " fleet=" + std::to_string(p->B) : std::string()) +
-                    (c.goal_form ? " goal_rows=" + std::to_string(p->gtrk_rows) : std::string()) +
+                    (c.goal_form ? " goal_rows=" + std::to_string(p->scene.goal.rows) : std::string()) +
                     (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
                                    : std::string()) +
                     (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string()) +

@@ -5,6 +5,7 @@
 #include "noise_plan.h"
 #include "cvar_plan.h"
 #include "barebone_plan.h"
+#include "barebone_scene.h"
 
 // ---------------------------------------------------------------------------
 // TDM
@@ -206,118 +207,8 @@ struct mppi_planner {
   bool want_sample_costs = false;
   uint64_t* states = nullptr;  // xoroshiro-compatible generator only
   long n_states = 0;
-  float2* obs_pos = nullptr;
-  float* obs_r = nullptr;
-  int n_obstacles = 0;
-  std::vector<float> obs_pos_host, obs_r_host;  // what the device arrays hold (mppi_planner_set_disc_obstacles)
-  // barebone batch, one disc set per problem (mppi_planner_set_instance_disc_obstacles): the sets one after the other;
-  // each problem's range is in its BatchInst (disc0, n_discs).  inst_obs_on == false: every problem has the shared set
-  bool inst_obs_on = false;
-  float2* inst_obs_pos = nullptr;
-  float* inst_obs_r = nullptr;
-  int inst_obs_max = 0;  // the largest problem's count
-  std::vector<int> inst_obs_counts_host;
-  std::vector<float> inst_obs_pos_host, inst_obs_r_host;
-  // discs that move (mppi_planner_set_disc_tracks): trk_rows predicted centres per disc, [disc][row]; one set for every
-  // problem (trk_counts_host has one entry) or one per problem, the sets one after the other as above.  While trk_on,
-  // the launches take these and neither static set; the row that is "now" is BatchInst::track_off of inst_host
-  // (problem 0's for the classic single launch: make_dev_params)
-  bool trk_on = false;
-  float2* trk_pos = nullptr;
-  float* trk_r = nullptr;
-  int trk_rows = 0;
-  int trk_max = 0;  // the largest problem's count
-  std::vector<int> trk_counts_host;
-  std::vector<float> trk_pos_host, trk_r_host;
-  // crowd mode (mppi_planner_set_crowd): no LDS limit on the disc sets; k_rollout_barebone_crowd reads them from memory.
-  // trk_pos_rows: the tracks once more as [row][disc] (all problems' discs side by side), kept while crowd && trk_on, so
-  // that the discs a step tests are contiguous
-  bool crowd = false;
-  float2* trk_pos_rows = nullptr;
-  // disc samples (mppi_planner_set_disc_track_samples; crowd mode only): smp_count sampled futures of smp_discs discs,
-  // smp_rows rows each, shared by every problem.  While smp_on they are the disc source -- the tracks' place: the shared
-  // static set rests, BatchInst::track_off is "now" -- and every rollout launch is a sample form of the crowd kernel.
-  // smp_pos_rows: [row][sample][disc], so that all a step tests is contiguous.  smp_gen: next_generation() at every change,
-  // 0 while off.  The per-sample costs go to sample_costs ([n_local][smp_count]) while want_sample_costs
-  bool smp_on = false;
-  float2* smp_pos_rows = nullptr;
-  float* smp_r = nullptr;
-  int smp_count = 0, smp_discs = 0, smp_rows = 0;
-  uint64_t smp_gen = 0;
-  std::vector<float> smp_pos_host, smp_r_host;  // what was handed over ([sample][disc][row])
-  // walls (mppi_planner_set_walls; crowd mode only): segments (ax, ay, bx, by) and half-widths, static and shared by every
-  // problem.  n_walls > 0: every rollout launch is the crowd kernel's WALLS form.  wall_gen: next_generation() at every
-  // change, 0 without walls -- what the graph signature holds of them
-  float4* wall_seg = nullptr;
-  float* wall_hw = nullptr;
-  int n_walls = 0;
-  uint64_t wall_gen = 0;
-  std::vector<float> wall_seg_host, wall_hw_host;  // what the device arrays hold
-  // walls that move and per-problem wall sets (mppi_planner_set_wall_tracks; crowd mode only): wtrk_rows segments per
-  // wall, one set for every problem (wtrk_counts_host has one entry) or one per problem, the sets one after the other.
-  // While wtrk_on the launches are the crowd kernel's CrowdWallTracks form and the static walls above rest.  wtrk_seg_rows:
-  // the segments as [row][wall] (all problems' walls side by side: a step's walls are contiguous); wtrk_range: {wall0,
-  // count} per problem (per-problem sets only).  The row that is "now" is the disc tracks' BatchInst::track_off.
-  // wtrk_gen: next_generation() at every change, 0 while off
-  bool wtrk_on = false;
-  float4* wtrk_seg_rows = nullptr;
-  float* wtrk_hw = nullptr;
-  int2* wtrk_range = nullptr;
-  int wtrk_rows = 0;
-  int wtrk_max = 0;  // the largest problem's count
-  uint64_t wtrk_gen = 0;
-  std::vector<int> wtrk_counts_host;
-  std::vector<float> wtrk_seg_host, wtrk_hw_host;  // what was handed over ([wall][row])
-  // fleet mode (mppi_planner_set_fleet; a batched handle in crowd mode): every problem's wall set is made of the OTHER
-  // problems' current plans, rebuilt on the device at the head of every call that starts iterations (fleet_kernels.h).
-  // fleet_seg_rows: [T][B * fleet_slots] in the layout of wtrk_seg_rows, problem a's slots at a * fleet_slots -- the B - 1
-  // others in ascending order, then the static walls of mppi_planner_set_walls as they were when the storage was built
-  // (they rest while per-problem sets are held, so they are copied into every row here); fleet_hw: [B * fleet_slots];
-  // fleet_range: {a * fleet_slots, fleet_slots}; fleet_plan: [B][T + 1] positions of the noise-free rollouts.  The rows
-  // are counted from "now" (CrowdWallTracks::relative): BatchInst::track_off is neither read for them nor advanced.
-  // fleet_gen: next_generation() whenever the storage is rebuilt (fleet mode set, static walls changed), 0 while off -- a
-  // refresh writes into the same arrays and changes nothing a captured launch holds
-  bool fleet_on = false;
-  float4* fleet_seg_rows = nullptr;
-  float* fleet_hw = nullptr;
-  int2* fleet_range = nullptr;
-  float2* fleet_plan = nullptr;
-  int fleet_slots = 0;
-  uint64_t fleet_gen = 0;
-  std::vector<float> fleet_hw_host;  // what was handed over: [B][B - 1]; a body fleet: what was made of it, [B][(B - 1) * Fp]
-  // a body fleet (mppi_planner_set_fleet_bodies): every robot is the same fleet_body discs (0: a disc fleet, or none), and
-  // reader a's fleet slots are the others' body discs, fleet_group = Fp slots a robot (the count rounded up to a power of
-  // two; the padding slots repeat the last disc) -- (B - 1) * Fp slots, then the static walls.  The rows are held in
-  // fp_host / fp_count as well, so that every launch is a footprint form with wall tracks (the reader's own body), which
-  // counts a robot once (CrowdFootprint::group, grouped).  fleet_heads: [B][T + 1] headings beside fleet_plan;
-  // fleet_centres: [B][T + 1][fleet_body] body disc centres (fleet_kernels.h)
-  int fleet_body = 0, fleet_group = 1;
-  double fleet_margin = 0.0;
-  float* fleet_heads = nullptr;
-  float2* fleet_centres = nullptr;
-  // a goal that moves (mppi_planner_set_goal_tracks): gtrk_rows positions per track, [track][row]; one track for every
-  // problem (gtrk_count == 1) or one per problem (gtrk_count == B).  While gtrk_on the rollouts measure the state after step
-  // t against row min(track_off + t + 1, gtrk_rows - 1) and params.xgoal / BatchInst::xg, yg rest; the default family
-  // launches its track forms only (static discs as tracks of one row).  gtrk_gen: next_generation() at every change, 0
-  // while off -- what the graph signature holds of the track
-  bool gtrk_on = false;
-  float2* gtrk_xy = nullptr;
-  int gtrk_rows = 0, gtrk_count = 0;
-  uint64_t gtrk_gen = 0;
-  std::vector<float> gtrk_host;  // what was handed over
-  // a body footprint (mppi_planner_set_footprint; crowd mode only, and not beside the fleet): fp_count discs (ox, oy, rho)
-  // in the robot frame, one footprint for every problem.  While fp_count > 0 every rollout launch is a footprint form of
-  // the crowd kernel, which takes the rows by value (CrowdFootprint).  fp_gen: next_generation() at every change, 0 while
-  // none is held -- what the graph signature holds of it
-  int fp_count = 0;
-  float fp_host[kCrowdFootprintMax * 3] = {};  // what was handed over: [disc][3]
-  uint64_t fp_gen = 0;
-  // clearance rings (mppi_planner_set_clearance_rings; crowd mode only, and not beside disc samples): ring_count rows
-  // (margin, penalty), one set for every problem.  While ring_count > 0 every rollout launch is a ring form of the crowd
-  // kernel, which takes the rows by value (CrowdRings).  ring_gen: as fp_gen
-  int ring_count = 0;
-  float ring_host[kCrowdRingsMax * 2] = {};  // what was handed over: [ring][2]
-  uint64_t ring_gen = 0;
+  // what the barebone mode's hand-overs have brought (barebone_scene.h; barebone_api.h sets it, barebone_launch.h reads it)
+  BareboneScene scene;
   float* state_rollout = nullptr;  // [V][T+1][3]
   // host state
   mppi_params params;

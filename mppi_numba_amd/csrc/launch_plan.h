@@ -65,12 +65,13 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.n_local = p->n_local;
   d.n_steps = p->cfg.num_steps;
   d.n_grids = p->cfg.num_grid_samples;
-  d.n_obstacles = p->n_obstacles;
+  const BareboneScene& sc = p->scene;
+  d.n_obstacles = sc.shared.max;
   // (discs that move: a batch reads each problem's offset from its BatchInst, as it reads the start state)
-  d.track_rows = p->smp_on ? p->smp_rows : (p->trk_on ? p->trk_rows : 0);  // (disc samples stand where the tracks do)
+  d.track_rows = sc.samples.on ? sc.samples.rows : sc.tracks.rows;  // (disc samples stand where the tracks do; no tracks: 0 rows)
   // (wall tracks share the offset: rollout_crowd_kernel.h clamps it against the walls' own row count)
   // (... and so does a goal track, against its own)
-  d.track_off = (p->trk_on || p->smp_on || p->wtrk_on || p->gtrk_on) && !p->inst_set ? p->inst_host[0].track_off : 0;
+  d.track_off = (sc.tracks.on || sc.samples.on || sc.wall_tracks.on || sc.goal.on) && !p->inst_set ? p->inst_host[0].track_off : 0;
   d.inst = p->inst_set ? p->inst_dev : nullptr;
   d.inst_tiles = p->inst_tiles;
   d.n_inst = p->n_inst;
@@ -1074,13 +1075,14 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.lin_maps = p->packed.lin_maps; sig.lin_grid = p->packed.lin_grid;
   sig.ang_maps = p->packed.ang_maps; sig.ang_grid = p->packed.ang_grid;
   sig.epoch_bias = p->noise_epoch - p->bumps_launched;
-  sig.wall_gen = p->wall_gen;  // (the walls' generation, not their address: a new set may land where the old one was)
-  sig.wtrk_gen = p->wtrk_gen;
-  sig.gtrk_gen = p->gtrk_gen;  // (the goal track's likewise)
-  sig.fleet_gen = p->fleet_gen;  // (the fleet storage's: renewed when it is rebuilt, not when its rows are refreshed)
-  sig.smp_gen = p->smp_gen;  // (the disc samples')
-  sig.fp_gen = p->fp_gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
-  sig.ring_gen = p->ring_gen;  // (the clearance rings' likewise)
+  const BareboneScene& sc = p->scene;
+  sig.wall_gen = sc.walls.gen;  // (the walls' generation, not their address: a new set may land where the old one was)
+  sig.wtrk_gen = sc.wall_tracks.gen;
+  sig.gtrk_gen = sc.goal.gen;  // (the goal track's likewise)
+  sig.fleet_gen = sc.fleet.gen;  // (the fleet storage's: renewed when it is rebuilt, not when its rows are refreshed)
+  sig.smp_gen = sc.samples.gen;  // (the disc samples')
+  sig.fp_gen = sc.footprint.gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
+  sig.ring_gen = sc.rings.gen;  // (the clearance rings' likewise)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

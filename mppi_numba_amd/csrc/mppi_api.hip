@@ -503,27 +503,7 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->cc_scratch);
   dev_free(p->sample_costs);
   dev_free(p->states);
-  dev_free(p->obs_pos);
-  dev_free(p->obs_r);
-  dev_free(p->inst_obs_pos);
-  dev_free(p->inst_obs_r);
-  dev_free(p->trk_pos);
-  dev_free(p->trk_pos_rows);
-  dev_free(p->smp_pos_rows);
-  dev_free(p->smp_r);
-  dev_free(p->trk_r);
-  dev_free(p->wall_seg);
-  dev_free(p->wall_hw);
-  dev_free(p->wtrk_seg_rows);
-  dev_free(p->wtrk_hw);
-  dev_free(p->wtrk_range);
-  dev_free(p->fleet_seg_rows);
-  dev_free(p->fleet_hw);
-  dev_free(p->fleet_range);
-  dev_free(p->fleet_plan);
-  dev_free(p->fleet_heads);
-  dev_free(p->fleet_centres);
-  dev_free(p->gtrk_xy);
+  p->scene.release();
   dev_free(p->state_rollout);
   dev_free(p->slabs);
   for (hipEvent_t e : p->ktime_events)
@@ -818,12 +798,13 @@ extern "C" int mppi_planner_set_instances(mppi_planner* p, int count, const floa
 // seg: [B][B - 1][T][4] -- reader a's others in ascending order, row j the segment (ax ay bx by) of control interval j
 extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {
   REQUIRE(p && seg, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->fleet_on, MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
-  REQUIRE(p->fleet_body == 0, MPPI_ERR_INVALID,
+  const FleetArrays& f = p->scene.fleet;
+  REQUIRE(f.on(), MPPI_ERR_STATE, "the handle is not in fleet mode (mppi_planner_set_fleet)");
+  REQUIRE(f.body == 0, MPPI_ERR_INVALID,
           "the handle is in a body fleet, whose walls have one more axis: mppi_planner_get_fleet_body_walls gives them");
-  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)p->fleet_slots, pitch = B * S;
+  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)f.slots, pitch = B * S;
   std::vector<float4> rows(pitch * T);
-  TRY(copy_out(p, rows.data(), p->fleet_seg_rows, sizeof(float4) * rows.size()));
+  TRY(copy_out(p, rows.data(), f.seg_rows, sizeof(float4) * rows.size()));
   for (size_t a = 0; a < B; ++a)
     for (size_t k = 0; k + 1 < B; ++k)
       for (size_t j = 0; j < T; ++j)
@@ -835,11 +816,12 @@ extern "C" int mppi_planner_get_fleet_walls(mppi_planner* p, float* seg) {
 // covers in control interval j; the padding slots are left out
 extern "C" int mppi_planner_get_fleet_body_walls(mppi_planner* p, float* seg) {
   REQUIRE(p && seg, MPPI_ERR_INVALID, "NULL argument");
-  REQUIRE(p->fleet_on && p->fleet_body > 0, MPPI_ERR_STATE, "the handle is not in a body fleet (mppi_planner_set_fleet_bodies)");
-  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)p->fleet_slots, pitch = B * S;
-  const size_t F = (size_t)p->fleet_body, Fp = (size_t)p->fleet_group;
+  const FleetArrays& f = p->scene.fleet;
+  REQUIRE(f.on() && f.body > 0, MPPI_ERR_STATE, "the handle is not in a body fleet (mppi_planner_set_fleet_bodies)");
+  const size_t B = (size_t)p->B, T = (size_t)p->cfg.num_steps, S = (size_t)f.slots, pitch = B * S;
+  const size_t F = (size_t)f.body, Fp = (size_t)f.group;
   std::vector<float4> rows(pitch * T);
-  TRY(copy_out(p, rows.data(), p->fleet_seg_rows, sizeof(float4) * rows.size()));
+  TRY(copy_out(p, rows.data(), f.seg_rows, sizeof(float4) * rows.size()));
   for (size_t a = 0; a < B; ++a)
     for (size_t o = 0; o + 1 < B; ++o)
       for (size_t k = 0; k < F; ++k)
@@ -1216,10 +1198,11 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.dt = dt > 0.0 ? dt : (double)p->params.dt;
     L.goal_tolerance = goal_tolerance;
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
-    L.advance_tracks = p->trk_on || p->smp_on || (p->wtrk_on && p->wtrk_rows > 1) || (p->gtrk_on && p->gtrk_rows > 1) ? 1 : 0;
-    L.goal_xy = p->gtrk_on ? p->gtrk_xy : nullptr;
-    L.goal_rows = p->gtrk_rows;
-    L.goal_stride = p->gtrk_count > 1 ? p->gtrk_rows : 0;
+    const BareboneScene& sc = p->scene;
+    L.advance_tracks = sc.tracks.on || sc.samples.on || (sc.wall_tracks.on && sc.wall_tracks.rows > 1) || (sc.goal.on && sc.goal.rows > 1) ? 1 : 0;
+    L.goal_xy = sc.goal.on ? sc.goal.xy : nullptr;
+    L.goal_rows = sc.goal.rows;
+    L.goal_stride = sc.goal.count > 1 ? sc.goal.rows : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)
@@ -1360,7 +1343,7 @@ extern "C" int mppi_planner_get_costs(mppi_planner* p, float* costs) {
 
 extern "C" int mppi_planner_get_sample_costs(mppi_planner* p, float* costs) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
-  const bool disc_samples = p->cfg.mode == MPPI_MODE_BAREBONE && p->smp_on;
+  const bool disc_samples = p->cfg.mode == MPPI_MODE_BAREBONE && p->scene.samples.on;
   REQUIRE(p->cfg.mode == MPPI_MODE_TDM || disc_samples, MPPI_ERR_STATE,
           "per-sample costs exist in MPPI_MODE_TDM, and in the barebone mode while disc samples are held");
   if (!costs) {  // arm: the next rollout records them
@@ -1368,7 +1351,7 @@ extern "C" int mppi_planner_get_sample_costs(mppi_planner* p, float* costs) {
     return MPPI_OK;
   }
   REQUIRE(p->sample_costs, MPPI_ERR_STATE, "call once with NULL before the rollout to arm recording");
-  if (disc_samples) return copy_out(p, costs, p->sample_costs, sizeof(float) * (size_t)p->n_local * (size_t)p->smp_count);
+  if (disc_samples) return copy_out(p, costs, p->sample_costs, sizeof(float) * (size_t)p->n_local * (size_t)p->scene.samples.count);
   // (samples sharded over GPUs: all M = count * num_grid_samples costs, gathered)
   return copy_out(p, costs, p->sample_costs,
                   sizeof(float) * (size_t)p->n_local * p->cfg.num_grid_samples * (size_t)p->m_count);
