@@ -463,6 +463,42 @@ int mppi_planner_set_clearance_rings(mppi_planner* p, const float* rings, int co
 /* rings (4, 2) float32: the first *count rows are the rings held (*count = 0: none) */
 int mppi_planner_get_clearance_rings(mppi_planner* p, float* rings, int* count);
 
+/* MPPI_MODE_BAREBONE with MPPI_RNG_PHILOX: time-correlated control noise.  beta = (beta_v, beta_w)
+ * float32, each in [0, 1), one coefficient for the linear and one for the angular control
+ * component.  With w[n, t, c] the float32 value the white generator stores for rollout n, step t,
+ * component c (u_std[c] times the Box-Muller normal of that rollout's Philox block under the block's
+ * epoch), every generated block holds, per rollout and component, in float32
+ *     g_c        = (float)sqrt(1 - (double)beta_c * (double)beta_c)                 (host, once)
+ *     e[n, 0, c] = w[n, 0, c]
+ *     e[n, t, c] = fadd_rn(fmul_rn(beta_c, e[n, t-1, c]), fmul_rn(g_c, w[n, t, c]))   t = 1 .. T-1
+ * -- two rounded products and one rounded sum, never an fma (csrc/noise_smooth.h).  Step 0 is the
+ * white draw and the gain is sqrt(1 - beta^2): every step keeps the standard deviation u_std[c], and
+ * the lag-k correlation is beta_c^k.  A component with beta_c = 0 keeps its white noise.  The
+ * recurrence restarts with every block: nothing is carried from one iteration or control step to
+ * the next.  Philox counters, epochs, the rollout offset of a shard and the device-side epoch count
+ * of graph replay are those of the white generator: the block a handle draws at epoch k is the
+ * filter of the block a handle with the same seed and no smoothing draws at epoch k.  Every
+ * generator launch of the handle follows -- in line, ahead on the second stream, beside the update,
+ * mppi_planner_sample_noise -- and so does what mppi_planner_get_noise returns;
+ * mppi_planner_set_noise stores what it is given, unfiltered.  The control-cost term of the rollout
+ * is unchanged (it weighs the noise by diag(u_std^2), as for white noise).  One setting for every
+ * problem of a batched handle.  NULL or (0, 0) clears: the white generator's launch, bit for bit.
+ * The coefficients travel by value in the generator's argument: a change drains the stream and
+ * drops the captured graphs, and a block already generated ahead is generated again, same epoch,
+ * under the new coefficients, so that from the next call on the noise is what a handle that had
+ * them from the start would draw at that epoch; equal values again cost a comparison.
+ * MPPI_ERR_INVALID, the handle keeping what it had: a coefficient that is not finite, < 0 or >= 1,
+ * a handle that is not in barebone mode (the map modes draw their noise inside the rollout launch),
+ * coefficients other than (0, 0) on a MPPI_RNG_XOROSHIRO handle (that generator exists for parity
+ * with the reference from the seed). */
+int mppi_planner_set_noise_smoothing(mppi_planner* p, const float beta[2]);
+int mppi_planner_get_noise_smoothing(mppi_planner* p, float beta[2]);
+/* (measurement) average duration in microseconds of the noise generator's launch alone -- the kernel
+ * the handle's smoothing setting selects -- over `reps` launches, each with its own start / stop
+ * events as in mppi_planner_time_kernels.  The launches write the noise buffer no iteration is
+ * reading and advance nothing.  MPPI_RNG_PHILOX only. */
+int mppi_planner_time_noise(mppi_planner* p, int reps, float* us_noise);
+
 /* MPPI_MODE_BAREBONE, a batched handle (B >= 2) in crowd mode: a body fleet -- fleet mode for
  * robots that are not discs.  Every robot of the batch is the same body of n_discs discs (1 .. 8),
  * discs (n_discs, 3) float32 with the rows and the rules of mppi_planner_set_footprint; count = B

@@ -124,6 +124,9 @@ SIGNATURES = {
     "mppi_planner_get_footprint": [_vp, _f32p, C.POINTER(C.c_int)],
     "mppi_planner_set_clearance_rings": [_vp, _f32p, C.c_int],
     "mppi_planner_get_clearance_rings": [_vp, _f32p, C.POINTER(C.c_int)],
+    "mppi_planner_set_noise_smoothing": [_vp, _f32p],
+    "mppi_planner_get_noise_smoothing": [_vp, _f32p],
+    "mppi_planner_time_noise": [_vp, C.c_int, _f32p],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

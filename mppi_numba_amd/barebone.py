@@ -113,6 +113,22 @@ freeze, terminal cost and control cost do not know about rings.  clearance_stair
 peak * (1 - gap/reach)^2.  Without the key nothing changes anywhere.  Limits: refused together with
 'obstacle_track_samples'; one ring set for every problem of a batch; the default kernel family has no rings (a handle that
 holds rings always launches the crowd kernel).
+
+Time-correlated control noise: params['noise_smoothing'], a scalar (both components) or (2,) = (beta_v, beta_w), rounded once
+to float32, each in [0, 1).  The notebook's noise is an independent draw per step, a jitter whose displacement largely
+averages out over the horizon; with the key every generated block is the white block w -- the same Philox counters and
+epochs, u_std times the Box-Muller normal -- filtered along t, per rollout and component, in float32:
+  g       = float32(sqrt(1 - float64(beta) * float64(beta)))
+  e[n, 0] = w[n, 0]
+  e[n, t] = float32(float32(beta * e[n, t-1]) + float32(g * w[n, t]))          t = 1 .. T-1
+two rounded products and one rounded sum, never an fma.  Step 0 is the white draw and the gain is sqrt(1 - beta^2), so every
+step keeps the standard deviation u_std and the lag-k correlation is beta^k; beta = 0 is the white noise.  The recurrence
+restarts with every block: nothing is carried from one iteration or control step to the next.  solve(), closed_loop(),
+graph replay and sample_noise() draw it on the device; set_noise() stores what it is given, unfiltered.  A change takes
+effect with the next call, as if the handle had had the value from the start; without the key -- or with 0 -- every bit is
+the notebook's.  Limits: philox only (rng="xoroshiro" is refused: that generator exists for parity with numba from the
+seed); one setting for every problem of a batch; first order only; the control-cost term of the rollouts still weighs the
+noise by diag(u_std^2), as for white noise.  The map-mode classes do not read the key.
 """
 import copy
 import ctypes as C
@@ -377,6 +393,7 @@ class MPPI_Numba(object):
         self._fleet_bodies = None     # MPPI_Batch.set_fleet_bodies: (rows (F, 3), margin) (None: off)
         self._footprint_key = None    # the footprint of params['footprint'] the library holds (None: none)
         self._rings_key = None        # the rings of params['clearance_rings'] the library holds (None: none)
+        self._smoothing_key = None    # the bytes of params['noise_smoothing'] the library holds (None: none)
         self.reset()
 
     def __del__(self):
@@ -554,6 +571,33 @@ class MPPI_Numba(object):
         rows, count = np.zeros((MAX_CLEARANCE_RINGS, 2), dtype=np.float32), C.c_int(0)
         _lib.call("mppi_planner_get_clearance_rings", self._handle, _lib.ptr(rows, C.c_float), C.byref(count))
         return rows[:count.value].copy() if count.value else None
+
+    # ------------------------------------------------------------------ time-correlated noise
+    def _hand_over_smoothing(self, p):
+        """params['noise_smoothing'], a scalar or (2,): handed over when its bytes have changed, cleared when the key has
+        gone.  A wrong shape is refused here (ValueError); a value outside [0, 1), the xoroshiro generator: the library
+        refuses them (MppiError) and keeps what it had."""
+        if "noise_smoothing" not in p:
+            if self._smoothing_key is not None:
+                _lib.call("mppi_planner_set_noise_smoothing", self._handle, None)
+                self._smoothing_key = None
+            return
+        sm = np.asarray(p['noise_smoothing'])
+        key = (sm.dtype.str, sm.shape, sm.tobytes())
+        if key == self._smoothing_key:
+            return
+        if sm.shape not in ((), (2,)):
+            raise ValueError("params['noise_smoothing'] is a scalar or has shape (2,), got {}".format(sm.shape))
+        beta = np.ascontiguousarray(np.broadcast_to(_f32(sm), (2,)))
+        _lib.call("mppi_planner_set_noise_smoothing", self._handle, _lib.ptr(beta, C.c_float))
+        self._smoothing_key = key
+
+    @property
+    def noise_smoothing(self):
+        """The smoothing coefficients the library holds: (2,) float32 (beta_v, beta_w), or None (white noise)."""
+        beta = np.zeros(2, dtype=np.float32)
+        _lib.call("mppi_planner_get_noise_smoothing", self._handle, _lib.ptr(beta, C.c_float))
+        return beta if beta.any() else None
 
     # ------------------------------------------------------------------ a goal that moves
     def _hand_over_goal_tracks(self, tracks, what="goal track"):
@@ -792,6 +836,8 @@ class MPPI_Numba(object):
         c.alpha_dyn = 1.0
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
+        if "noise_smoothing" in p or self._smoothing_key is not None:  # (the white noise's path pays one lookup for this)
+            self._hand_over_smoothing(p)
         self._hand_over_walls(p)
         if "footprint" in p or self._footprint_key is not None:  # (the point robot's path pays one lookup for this)
             self._hand_over_footprint(p)

@@ -152,6 +152,10 @@ struct mppi_planner {
   // what they are to do from it -- and all zero outside one
   NoiseChoice noise_now;
   bool noise_on_side_stream = false;  // the noise produced ahead is still in flight on noise_stream
+  // time-correlated noise (mppi_planner_set_noise_smoothing; barebone mode, Philox): the AR(1) coefficients of the two
+  // control components and their gains (noise_smooth.h) -- (0, 0): launch_noise launches k_noise, as ever
+  float smooth_beta[2] = {0.0f, 0.0f};
+  float smooth_gain[2] = {1.0f, 1.0f};
   float2* staging = nullptr;  // (n_local,T) host-layout staging for set/get_noise
   float2* u = nullptr;        // [T]
   float2* u_prev = nullptr;   // [T]

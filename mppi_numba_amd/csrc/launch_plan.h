@@ -236,10 +236,32 @@ static NoiseJob next_noise_job(mppi_planner* p, int extra) {
   return extra > 0 ? make_noise_job(p, p->noise_buf[p->noise_cur ^ 1]) : j;
 }
 
-static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nullptr, int back = 0) {
+// time-correlated noise is on (mppi_planner_set_noise_smoothing: barebone mode and Philox only)
+static bool noise_smoothing_on(const mppi_planner* p) { return p->smooth_beta[0] != 0.0f || p->smooth_beta[1] != 0.0f; }
+
+// The one place every generator launch comes from: in line, beside the rollout, beside the update, sample_noise, and a
+// block generated again (`back`).  The handle's smoothing coefficients pick the kernel: none, k_noise as ever; else
+// k_noise_smooth, a workgroup per tile, over the same job.  `ev_start` / `ev_stop` (mppi_planner_time_noise): the
+// dispatch's own begin / end.
+static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nullptr, int back = 0,
+                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
   long total = (long)noise_items(p->n_local, p->cfg.num_steps, p->cfg.rng == MPPI_RNG_PHILOX);  // one thread per item
   NoiseJob job = make_noise_job(p, target, back);
-  hipLaunchKernelGGL(k_noise, dim3(ceil_div(total, 256)), dim3(256), 0, stream ? stream : p->stream, job);
+  hipStream_t on = stream ? stream : p->stream;
+  if (noise_smoothing_on(p)) {
+    NoiseSmoothJob smooth;
+    smooth.job = job;
+    smooth.beta0 = p->smooth_beta[0]; smooth.beta1 = p->smooth_beta[1];
+    smooth.gain0 = p->smooth_gain[0]; smooth.gain1 = p->smooth_gain[1];
+    const dim3 tiles(ceil_div(p->n_local, 64)), threads(64 * kSmoothWaves);
+    const size_t lds = noise_smooth_lds(p->cfg.num_steps);
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_noise_smooth, tiles, threads, lds, on, ev_start, ev_stop, 0, smooth);
+    else hipLaunchKernelGGL(k_noise_smooth, tiles, threads, lds, on, smooth);
+  } else if (ev_start || ev_stop) {
+    hipExtLaunchKernelGGL(k_noise, dim3(ceil_div(total, 256)), dim3(256), 0, on, ev_start, ev_stop, 0, job);
+  } else {
+    hipLaunchKernelGGL(k_noise, dim3(ceil_div(total, 256)), dim3(256), 0, on, job);
+  }
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -1061,6 +1083,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     const void *cells, *cells16, *cc, *sample_costs, *u;
     uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
+    float smooth_beta[2];
   } sig;
   memset(&sig, 0, sizeof(sig));
   sig.d = d;
@@ -1083,6 +1106,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.smp_gen = sc.samples.gen;  // (the disc samples')
   sig.fp_gen = sc.footprint.gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
   sig.ring_gen = sc.rings.gen;  // (the clearance rings' likewise)
+  sig.smooth_beta[0] = p->smooth_beta[0]; sig.smooth_beta[1] = p->smooth_beta[1];  // (the noise smoothing's coefficients: by value in the generator's argument)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

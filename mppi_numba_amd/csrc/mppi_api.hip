@@ -1306,6 +1306,77 @@ extern "C" int mppi_planner_get_noise(mppi_planner* p, float* noise) {
   return MPPI_OK;
 }
 
+// Time-correlated control noise (include/mppi_hip.h; noise_smooth.h): the coefficients live in the handle and launch_noise
+// picks the generator from them.  They travel by value in the generator's argument, so a change drops the captured graphs;
+// a block generated ahead is generated again, same epoch, under the new coefficients.
+extern "C" int mppi_planner_set_noise_smoothing(mppi_planner* p, const float beta[2]) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID,
+          "noise smoothing belongs to the barebone mode (mode %d): the map modes draw their noise inside the rollout launch", p->cfg.mode);
+  float want[2] = {0.0f, 0.0f};
+  for (int c = 0; beta && c < 2; ++c) {
+    REQUIRE(noise_smooth_beta_valid(beta[c]), MPPI_ERR_INVALID, "noise smoothing coefficient %d is %g: must be finite and lie in [0, 1)", c, (double)beta[c]);
+    if (beta[c] != 0.0f) want[c] = beta[c];  // (-0 is 0)
+  }
+  REQUIRE((want[0] == 0.0f && want[1] == 0.0f) || p->cfg.rng == MPPI_RNG_PHILOX, MPPI_ERR_INVALID,
+          "noise smoothing needs the Philox generator: the xoroshiro one exists for parity with the reference from the seed");
+  if (want[0] == p->smooth_beta[0] && want[1] == p->smooth_beta[1]) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(join_noise_ahead(p));
+  TRY(drain_stream(p));
+  for (int c = 0; c < 2; ++c) {
+    p->smooth_beta[c] = want[c];
+    p->smooth_gain[c] = noise_smooth_gain(want[c]);
+  }
+  drop_graphs(p);
+  if (p->primed) {  // the next iteration's block, of epoch noise_epoch - 1, is there already: the same epoch once more
+    TRY(launch_noise(p, p->noise_buf[p->noise_cur ^ 1], nullptr, 1));
+    TRY(drain_stream(p));
+  }
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_noise_smoothing(mppi_planner* p, float beta[2]) {
+  REQUIRE(p && beta, MPPI_ERR_INVALID, "NULL argument");
+  beta[0] = p->smooth_beta[0];
+  beta[1] = p->smooth_beta[1];
+  return MPPI_OK;
+}
+
+// The generator launch alone: `reps` launches of what launch_noise launches for this handle, each with its own start /
+// stop events (the dispatch's begin / end, as mppi_planner_time_kernels times the rollout and the update).  They write the
+// noise buffer no iteration is reading -- the block generated ahead, if there is one, once more from its own epoch -- and
+// advance nothing.
+extern "C" int mppi_planner_time_noise(mppi_planner* p, int reps, float* us_noise) {
+  REQUIRE(p && us_noise, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(reps >= 1 && reps <= 4096, MPPI_ERR_INVALID, "reps %d", reps);
+  REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
+  REQUIRE(p->cfg.rng == MPPI_RNG_PHILOX, MPPI_ERR_INVALID, "the xoroshiro generator keeps state: a launch cannot be repeated");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(join_noise_ahead(p));
+  TRY(drain_stream(p));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipEventCreate(&ev[0]));
+  if (hipEventCreate(&ev[1]) != hipSuccess) {
+    (void)hipEventDestroy(ev[0]);
+    return fail(MPPI_ERR_HIP, "hipEventCreate");
+  }
+  double sum = 0.0;
+  int rc = MPPI_OK;
+  for (int r = -1; r < reps && rc == MPPI_OK; ++r) {  // (one launch first, not counted)
+    rc = launch_noise(p, p->noise_buf[p->noise_cur ^ 1], nullptr, 1, ev[0], ev[1]);
+    if (rc == MPPI_OK) rc = drain_stream(p);
+    float ms = 0.f;
+    if (rc == MPPI_OK && hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) rc = fail(MPPI_ERR_HIP, "hipEventElapsedTime");
+    if (r >= 0) sum += (double)ms;
+  }
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  TRY(rc);
+  *us_noise = (float)(1e3 * sum / reps);
+  return MPPI_OK;
+}
+
 extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");

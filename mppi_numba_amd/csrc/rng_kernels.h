@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "device_math.h"
+#include "noise_smooth.h"
 
 namespace mppi {
 
@@ -187,6 +188,77 @@ __device__ __forceinline__ void noise_generate(const NoiseJob& j, unsigned int w
 
 __global__ __launch_bounds__(256) void k_noise(NoiseJob job) {
   noise_generate(job, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), gridDim.x * (blockDim.x >> 6));
+}
+
+// ---------------- time-correlated control noise ----------------
+// The white block of k_noise (same counters, same epoch, same u_std * Box-Muller products) filtered along t by the AR(1)
+// recurrence of noise_smooth.h, per rollout and component; the recurrence restarts with every block.  The chain over t is
+// sequential by definition -- its bits are the specification -- the Philox and Box-Muller work is not: a workgroup owns
+// one tile of 64 rollouts, all its waves draw the tile's rows for a chunk of steps into LDS as [t][64] float2, and behind
+// a barrier one wave walks the chunk with e in registers, reading the draws of eight steps ahead of the chain, one
+// 512-byte store per step.  T > kSmoothChunk: the chunk loop repeats with e carried.
+struct NoiseSmoothJob {
+  NoiseJob job;  // (Philox: states == nullptr)
+  float beta0, beta1, gain0, gain1;
+};
+
+constexpr int kSmoothChunk = 128;  // steps of a tile in LDS at once: 64 KiB, what a launch gets without an attribute
+constexpr int kSmoothWaves = 4;
+constexpr int kSmoothAhead = 8;    // draws the walk reads ahead of the chain
+
+// LDS of a launch: the steps of a chunk, whole Philox blocks (two steps each)
+__host__ __device__ inline size_t noise_smooth_lds(int n_steps) {
+  const int rows = n_steps + 1 < kSmoothChunk ? ((n_steps + 1) & ~1) : kSmoothChunk;
+  return (size_t)rows * 64 * sizeof(float2);
+}
+
+__global__ __launch_bounds__(64 * kSmoothWaves) void k_noise_smooth(NoiseSmoothJob s) {
+  extern __shared__ float2 smooth_rows[];  // [step of the chunk][64]
+  const NoiseJob& j = s.job;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned int tile = blockIdx.x;
+  const int n = (int)tile * 64 + lane;
+  const bool live = n < j.n_local;  // (lanes past n_local in the last tile draw nothing and store nothing, as in noise_row)
+  const int T = j.n_steps;
+  const unsigned int pairs = (unsigned int)(T + 1) / 2u;
+  const uint64_t epoch = j.epoch + (j.gen_counter ? *j.gen_counter : 0ull);  // uniform: a scalar load
+  const uint64_t sub0 = (uint64_t)(j.n_offset + n) * (uint64_t)pairs;
+  float2* out = j.out + (size_t)tile * T * 64 + lane;
+  float2 e = make_float2(0.0f, 0.0f);
+  for (int t0 = 0; t0 < T; t0 += kSmoothChunk) {
+    const int len = min(kSmoothChunk, T - t0);
+    if (t0 > 0) __syncthreads();  // (the walk has read the previous chunk)
+    if (live) {
+      // the draws of noise_row, two steps per Philox block; the second half of the last block of an odd T lands in a row
+      // of LDS nobody reads
+      for (int r = 2 * wave; r < len; r += 2 * kSmoothWaves) {
+        const uint64_t sub = sub0 + (uint64_t)((t0 + r) >> 1);
+        uint4 x = philox4x32_10(make_uint4((unsigned int)epoch, (unsigned int)(epoch >> 32), (unsigned int)sub,
+                                           (unsigned int)(sub >> 32)),
+                                make_uint2((unsigned int)j.seed, (unsigned int)(j.seed >> 32)));
+        float2 a = box_muller_fast(x.x, x.y), b = box_muller_fast(x.z, x.w);
+        smooth_rows[r * 64 + lane] = make_float2(j.std0 * a.x, j.std1 * a.y);
+        smooth_rows[(r + 1) * 64 + lane] = make_float2(j.std0 * b.x, j.std1 * b.y);
+      }
+    }
+    __syncthreads();
+    if (wave == 0 && live) {
+      for (int r = 0; r < len; r += kSmoothAhead) {
+        float2 w[kSmoothAhead];
+#pragma unroll
+        for (int k = 0; k < kSmoothAhead; ++k) w[k] = smooth_rows[min(r + k, len - 1) * 64 + lane];
+#pragma unroll
+        for (int k = 0; k < kSmoothAhead; ++k) {
+          if (r + k < len) {
+            const bool head = t0 + r + k == 0;  // step 0 is the white draw itself
+            e.x = head ? w[k].x : noise_smooth_step(s.beta0, s.gain0, e.x, w[k].x);
+            e.y = head ? w[k].y : noise_smooth_step(s.beta1, s.gain1, e.y, w[k].y);
+            out[(size_t)(t0 + r + k) * 64] = e;
+          }
+        }
+      }
+    }
+  }
 }
 
 // out[0] = number of (seed, subsequence, offset) triples for which philox4x32_10() differs
