@@ -130,6 +130,7 @@ the notebook's.  Limits: philox only (rng="xoroshiro" is refused: that generator
 seed); one setting for every problem of a batch; first order only; the control-cost term of the rollouts still weighs the
 noise by diag(u_std^2), as for white noise.  The map-mode classes do not read the key.
 """
+import collections
 import copy
 import ctypes as C
 import time
@@ -353,6 +354,259 @@ def _is_wall_track_set(wall_set):
     return np.asarray(wall_set[0]).ndim == 4
 
 
+def _same_sets(new, now):
+    """Whether two lists of per-problem sets -- arrays, or tuples of arrays -- hold the same values."""
+    return all(np.array_equal(x, y) for a, b in zip(new, now) for x, y in (zip(a, b) if isinstance(a, tuple) else ((a, b),)))
+
+
+# ---------------------------------------------------------------------- what the library holds
+_STALE = "stale"  # a key: what the library holds of this kind is out of date -- hand the params' value over again, or clear
+_NOBODY, _PARAMS, _BATCH = "nobody", "params", "batch"  # who filled a slot (_BATCH: MPPI_Batch's per-problem sets)
+_KEEP, _FETCH, _ZERO = "keep", "fetch", "zero"  # what a change of a kind does to the mirror's track offsets
+_CTYPES = {np.dtype(np.float32): C.c_float, np.dtype(np.int32): C.c_int}
+
+
+class _Held:
+    """What the library holds of one kind of set.
+    key    the bytes of the params value that was handed over (None: nothing of params; _STALE, above)
+    owner  who filled the slot: _NOBODY, _PARAMS or -- the three track kinds -- _BATCH, whose per-problem sets win over the
+           shared key of params; when they go the slot is free and that key is handed over again at the next solve
+    sent   the setter's arguments the library holds, whoever sent them (None: nothing): the rows of the wall tracks, the
+           goal tracks and the number of disc samples are read from here"""
+    __slots__ = ("key", "owner", "sent")
+
+    def __init__(self):
+        self.key, self.owner, self.sent = None, _NOBODY, None
+
+
+def _pack_sets(sets, what, noun, others, width, prepare, finish=None):
+    """The packer of "a list of per-problem sets with a common row count": prepare(b, sets[b]) validates set b and gives
+    its array (count_b, L, ...), finish(b, array) validates what is looked at behind the row count; returns
+    (counts (len(sets),) int32, L, one contiguous float32 block (sum count_b * L, width))."""
+    rows, counts, flat = None, [], []
+    for b, one in enumerate(sets):
+        tr = prepare(b, one)
+        if tr.shape[1] < 1:
+            raise ValueError("{} {}: {} has at least one row (L = 0)".format(what, b, noun))
+        if rows not in (None, tr.shape[1]):
+            raise ValueError("{} {}: {} rows, other {} of this call have {}".format(what, b, tr.shape[1], others, rows))
+        rows = tr.shape[1]
+        if finish is not None:
+            finish(b, tr)
+        counts.append(len(tr))
+        flat.append(_f32(tr).reshape(-1, width))
+    return np.ascontiguousarray(counts, dtype=np.int32), int(rows), np.ascontiguousarray(np.concatenate(flat), dtype=np.float32)
+
+
+def _pack_disc_tracks(sets):
+    """sets: one (tracks (K, L, 2), radii (K,)) pair for every problem, or one per problem."""
+    rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in sets]
+
+    def prepare(b, pair):
+        tr = np.asarray(pair[0])
+        if tr.ndim != 3 or tr.shape[2] != 2:
+            raise ValueError("set {}: tracks have shape (K, L, 2), got {}".format(b, tr.shape))
+        if tr.shape[1] >= 1 and len(tr) != len(rad[b]):  # (a set without rows is refused first, by the packer)
+            raise ValueError("set {}: {} tracks and {} radii".format(b, len(tr), len(rad[b])))
+        return tr
+    counts, rows, pos_all = _pack_sets(sets, "set", "a track", "sets", 2, prepare)
+    return len(sets), counts, rows, pos_all, np.ascontiguousarray(np.concatenate(rad), dtype=np.float32)
+
+
+def _pack_wall_tracks(sets, what="wall set"):
+    """sets: one (tracks (W, L, 2, 2) or segments (W, 2, 2), half-widths: a scalar or (W,)) pair for every problem, or
+    one per problem."""
+    halves = []
+
+    def prepare(b, pair):
+        tr = np.asarray(pair[0])
+        shown = tr.shape
+        if tr.ndim == 3:  # a static set: tracks of one row
+            tr = tr.reshape(len(tr), 1, *tr.shape[1:])
+        if tr.ndim != 4 or (tr.size and tr.shape[2:] != (2, 2)):
+            raise ValueError("{} {}: shape (W, L, 2, 2) -- or (W, 2, 2) for static walls --, got {}".format(what, b, shown))
+        return tr
+
+    def finish(b, tr):
+        hw = np.asarray(sets[b][1])
+        if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(tr)):
+            raise ValueError("{} {}: the half-width is a scalar or has shape ({},), got {}".format(what, b, len(tr), hw.shape))
+        halves.append(np.broadcast_to(_f32(hw), (len(tr),)))
+    counts, rows, seg_all = _pack_sets(sets, what, "a wall track", "sets", 4, prepare, finish)
+    return len(sets), counts, rows, seg_all, np.ascontiguousarray(np.concatenate(halves), dtype=np.float32)
+
+
+def _pack_goal_tracks(planner, tracks, what="goal track"):
+    """tracks: one (L, 2) goal track for every problem, or one per problem with a common L."""
+    def prepare(b, tr):
+        tr = np.asarray(tr)
+        if tr.ndim != 2 or tr.shape[1] != 2:
+            raise ValueError("{} {}: shape (L, 2), got {}".format(what, b, tr.shape))
+        return tr[None]
+    _, rows, xy = _pack_sets(tracks, what, "a goal track", "tracks", 2, prepare)
+    if len(tracks) not in (1, planner.num_instances):
+        raise ValueError("{} goal tracks: one for every problem, or one per problem ({})".format(len(tracks), planner.num_instances))
+    return len(tracks), rows, xy.reshape(len(tracks), rows, 2)
+
+
+# The params-owned kinds: what MPPI_Numba._sync_kind needs to know of each.  read(planner, params) runs where the kind's
+# key is in params, whether or not its value has changed: it refuses what the kind excludes and gives the arrays whose bytes
+# are the key (None: treat the key as absent).  pack(planner, *arrays) runs when those bytes are new: it validates and gives
+# the setter's arguments, arrays as arrays.
+def _read_one(key):
+    return lambda planner, p: (np.asarray(p[key]),)
+
+
+def _read_goal(planner, p):
+    if "xgoal" in p:
+        raise ValueError("params hold both 'xgoal' and 'goal_track': the goal is static or has a track, give one of the two")
+    tr = np.asarray(p['goal_track'])
+    if tr.ndim != 2 or tr.shape[1] != 2:
+        raise ValueError("params['goal_track'] has shape (L, 2), got {}".format(tr.shape))
+    return (tr,)
+
+
+def _pack_smoothing(planner, sm):
+    """A wrong shape is refused here; a value outside [0, 1), the xoroshiro generator: the library refuses them (MppiError)
+    and keeps what it had."""
+    if sm.shape not in ((), (2,)):
+        raise ValueError("params['noise_smoothing'] is a scalar or has shape (2,), got {}".format(sm.shape))
+    return (np.ascontiguousarray(np.broadcast_to(_f32(sm), (2,))),)
+
+
+def _read_wall_tracks(planner, p):
+    if planner._held["fleet"].sent is not None or planner._held["fleet_bodies"].sent is not None:
+        raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
+                         "itself (set_fleet(None) first; 'wall_segments' stay in force beside it)")
+    if "wall_segments" in p:
+        raise ValueError("params hold both 'wall_segments' and 'wall_tracks': walls are static or have tracks, "
+                         "give one of the two")
+    tr = np.asarray(p['wall_tracks'])
+    if tr.ndim != 4:
+        raise ValueError("params['wall_tracks'] has shape (W, L, 2, 2), got {}".format(tr.shape))
+    return tr, np.asarray(p.get('wall_halfwidth', 0.0))
+
+
+def _read_walls(planner, p):
+    return np.asarray(p['wall_segments']), np.asarray(p.get('wall_halfwidth', 0.0))
+
+
+def _pack_walls(planner, seg, hw):
+    """Without crowd mode the library refuses walls (MppiError)."""
+    if seg.size and seg.shape[1:] != (2, 2):
+        raise ValueError("params['wall_segments'] has shape (W, 2, 2), got {}".format(seg.shape))
+    segs = np.ascontiguousarray(_f32(seg).reshape(-1, 4))
+    if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(segs)):
+        raise ValueError("params['wall_halfwidth'] is a scalar or has shape ({},), got {}".format(len(segs), hw.shape))
+    return segs, np.ascontiguousarray(np.broadcast_to(_f32(hw), (len(segs),))), len(segs)
+
+
+def _read_footprint(planner, p):
+    if planner._held["fleet"].sent is not None:
+        raise ValueError("params hold 'footprint' while the fleet is on: the fleet's half-widths already contain the "
+                         "reader's body (set_fleet(None) first, or drop the key)")
+    if planner._held["fleet_bodies"].sent is not None:
+        raise ValueError("params hold 'footprint' while the fleet of bodies is on: that fleet carries its own body "
+                         "(set_fleet(None) first, or drop the key)")
+    return (np.asarray(p['footprint']),)
+
+
+def _pack_rows(rows_of):
+    """Footprint and rings: (rows, count).  Without crowd mode -- rings: beside disc samples, or with a bad row -- the
+    library refuses them (MppiError)."""
+    def pack(planner, value):
+        rows = rows_of(value)
+        return rows, len(rows)
+    return pack
+
+
+def _read_samples(planner, p):
+    others = [k for k in ("obstacle_positions", "obstacle_tracks") if k in p]
+    if others:
+        raise ValueError("params hold both 'obstacle_track_samples' and '{}': discs are static, have tracks or have "
+                         "sampled tracks, give one of the three".format(others[0]))
+    if planner._held["problem_discs"].sent is not None:
+        raise ValueError("params hold 'obstacle_track_samples' while obstacle_sets are held: disc samples are shared by "
+                         "every problem (set_obstacle_sets(None) first)")
+    return np.asarray(p['obstacle_track_samples']), np.asarray(p['obstacle_radius'])
+
+
+def _pack_samples(planner, smp, orad):
+    """Once the samples have passed, the plain tracks that params held go, ahead of the samples' own hand-over."""
+    if smp.ndim != 4 or smp.shape[3] != 2 or smp.shape[0] < 1 or smp.shape[2] < 1:
+        raise ValueError("params['obstacle_track_samples'] has shape (S, K, L, 2) with S, L >= 1, got {}".format(smp.shape))
+    if smp.shape[0] > MAX_DISC_SAMPLES:
+        raise ValueError("params['obstacle_track_samples'] holds {} samples, more than {}".format(smp.shape[0], MAX_DISC_SAMPLES))
+    rad = np.ascontiguousarray(_f32(orad).reshape(-1))
+    if len(rad) != smp.shape[1]:
+        raise ValueError("params['obstacle_track_samples'] holds {} discs, params['obstacle_radius'] {} radii".format(
+            smp.shape[1], len(rad)))
+    tracks = planner._held["tracks"]
+    if tracks.owner is _PARAMS:  # (the params no longer hold them; "now" is fetched behind the samples)
+        _lib.call(_TRACKS.setter, planner._handle, *_TRACKS.clear)
+        tracks.key, tracks.owner, tracks.sent = None, _NOBODY, None
+    pos = np.ascontiguousarray(_f32(smp))
+    return (int(smp.shape[0]), int(smp.shape[1]), int(smp.shape[2]), pos if pos.size else np.zeros(2, np.float32),
+            rad if rad.size else np.zeros(1, np.float32))
+
+
+def _read_tracks(planner, p):
+    if "obstacle_positions" in p:
+        raise ValueError("params hold both 'obstacle_positions' and 'obstacle_tracks': discs are static or have "
+                         "tracks, give one of the two")
+    return np.asarray(p['obstacle_tracks']), np.asarray(p['obstacle_radius'])
+
+
+def _read_discs(planner, p):
+    return (np.asarray(p['obstacle_positions']), np.asarray(p['obstacle_radius'])) if "obstacle_radius" in p else None
+
+
+def _pack_discs(planner, op, orad):
+    pos = np.ascontiguousarray(_f32(op).reshape(-1, 2))
+    rad = np.ascontiguousarray(_f32(orad).reshape(-1))
+    assert len(pos) == len(rad)
+    return pos, rad, len(rad)
+
+
+# One row per hand-over, in hand-over order -- the one place that states it.  The goal's row is walked ahead of the params
+# struct (whose xgoal rests on it), the others behind it.
+#   name    the kind's record in MPPI_Numba._held        key     the params key whose presence means "there is one"
+#   read, pack  above (pack None: this row only clears)  setter  the library's entry point
+#   clear   the setter's arguments that clear (None: this row only sets)
+#   offsets what a change does to the mirror's track offsets: _KEEP, _FETCH from the library (new rows, or rows that have
+#           gone: row 0 is "now", unless other tracks count the rows), _ZERO here (disc tracks: row 0 is "now")
+#   over    the kind this one lies over: that kind rests while this one's key is in params, and is stale after a change
+# Rings and disc samples exclude each other in the library: rings that have gone are cleared ahead of the samples'
+# hand-over, rings that are there are handed over behind it -- hence two rows.
+_Kind = collections.namedtuple("_Kind", "name key read pack setter clear offsets over")
+_KINDS = (
+    _Kind("goal", "goal_track", _read_goal, lambda planner, tr: _pack_goal_tracks(planner, [tr], "params['goal_track']"),
+          "mppi_planner_set_goal_tracks", (0, 0, None), _FETCH, None),
+    _Kind("smoothing", "noise_smoothing", _read_one("noise_smoothing"), _pack_smoothing,
+          "mppi_planner_set_noise_smoothing", (None,), _KEEP, None),
+    _Kind("wall_tracks", "wall_tracks", _read_wall_tracks,
+          lambda planner, tr, hw: _pack_wall_tracks([(tr, hw)], "params['wall_tracks']"),
+          "mppi_planner_set_wall_tracks", (0, None, 0, None, None), _FETCH, None),
+    _Kind("walls", "wall_segments", _read_walls, _pack_walls, "mppi_planner_set_walls", (None, None, 0), _KEEP, None),
+    _Kind("footprint", "footprint", _read_footprint, _pack_rows(_footprint_rows),
+          "mppi_planner_set_footprint", (None, 0), _KEEP, None),
+    _Kind("rings", "clearance_rings", _read_one("clearance_rings"), None,
+          "mppi_planner_set_clearance_rings", (None, 0), _KEEP, None),
+    _Kind("samples", "obstacle_track_samples", _read_samples, _pack_samples,
+          "mppi_planner_set_disc_track_samples", (0, 0, 0, None, None), _FETCH, "discs"),
+    _Kind("rings", "clearance_rings", _read_one("clearance_rings"), _pack_rows(_ring_rows),
+          "mppi_planner_set_clearance_rings", None, _KEEP, None),
+    _Kind("tracks", "obstacle_tracks", _read_tracks, lambda planner, tr, orad: _pack_disc_tracks([(tr, orad)]),
+          "mppi_planner_set_disc_tracks", (0, None, 0, None, None), _ZERO, "discs"),
+    _Kind("discs", "obstacle_positions", _read_discs, _pack_discs, "mppi_planner_set_disc_obstacles", (None, None, 0), _KEEP, None),
+)
+_GOAL, _WALL_TRACKS, _FOOTPRINT, _TRACKS, _DISCS = (
+    next(kind for kind in _KINDS if kind.name == name) for name in ("goal", "wall_tracks", "footprint", "tracks", "discs"))
+_OPTIONAL_KEYS = frozenset(kind.key for kind in _KINDS if kind is not _DISCS)  # (the discs are there in every solve)
+_OPTIONAL_NAMES = tuple(sorted({kind.name for kind in _KINDS if kind is not _DISCS}))
+_RESTS_UNDER = {kind.name: tuple(k.key for k in _KINDS if k.over == kind.name) for kind in _KINDS}  # name -> the keys above it
+
+
 class MPPI_Numba(object):
 
     """Information-theoretic MPPI (Williams et al., Alg. 2) without maps.
@@ -378,22 +632,12 @@ class MPPI_Numba(object):
         self.rng_states_d = None
         self.state_rollout_batch_d = None
         self.device_var_initialized = False
-        self._discs_key = None  # what the device's disc arrays hold (None: nothing handed over yet)
-        self._tracks_from_params = False  # ... and whether they are the tracks of params['obstacle_tracks']
-        self._samples_key = None          # the disc samples of params['obstacle_track_samples'] the library holds (None: none)
-        self._own_tracks = False          # MPPI_Batch: per-problem tracks are set (they win over params')
-        self._walls_key = ()  # what the device's wall arrays hold (): none
-        self._wall_tracks_key = None  # the wall tracks of params['wall_tracks'] the library holds (None: none)
-        self._own_walls = False       # MPPI_Batch: per-problem wall sets are set (they win over the walls of params)
-        self._wall_rows = 0           # rows of the wall tracks held, whoever set them (0: none, 1: static sets)
-        self._goal_track_key = None   # the goal track of params['goal_track'] the library holds (None: none)
-        self._own_goals = False       # MPPI_Batch: per-problem goal tracks are set (they win over params['goal_track'])
-        self._goal_tracks = None      # the goal tracks held, whoever set them: (1 or B, L, 2) float32 (None: static goals)
-        self._fleet = None            # MPPI_Batch.set_fleet: (radii (B,), margin, half-widths (B, B - 1)) (None: off)
-        self._fleet_bodies = None     # MPPI_Batch.set_fleet_bodies: (rows (F, 3), margin) (None: off)
-        self._footprint_key = None    # the footprint of params['footprint'] the library holds (None: none)
-        self._rings_key = None        # the rings of params['clearance_rings'] the library holds (None: none)
-        self._smoothing_key = None    # the bytes of params['noise_smoothing'] the library holds (None: none)
+        # what the library holds: a record per kind of _KINDS, and of MPPI_Batch: "problem_discs", the per-problem disc sets
+        # of either kind (sent: its obstacle_sets); "fleet", sent = (radii (B,), margin, half-widths (B, B - 1)); "fleet_bodies",
+        # sent = (rows (F, 3), margin)
+        self._held = {name: _Held() for name in _OPTIONAL_NAMES + ("discs", "problem_discs", "fleet", "fleet_bodies")}
+        self._held["discs"].key = _STALE  # (nothing handed over yet: the first solve hands the discs over, or clears)
+        self._walk_all = False  # whether something of an optional kind is held of params (or a walk of _KINDS broke off)
         self.reset()
 
     def __del__(self):
@@ -444,102 +688,54 @@ class MPPI_Numba(object):
         Turning it off raises MppiError (and stays on) while the handle holds a set the default forms cannot launch."""
         _lib.call("mppi_planner_set_crowd", self._handle, int(bool(on)))
 
-    # ------------------------------------------------------------------ walls
-    def _hand_over_walls(self, p):
-        """params['wall_segments'] / ['wall_halfwidth']: handed over when they have changed, cleared when the keys have
-        gone.  Without crowd mode the library refuses them (MppiError)."""
-        if "wall_tracks" in p:
-            if self._fleet is not None or self._fleet_bodies is not None:
-                raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
-                                 "itself (set_fleet(None) first; 'wall_segments' stay in force beside it)")
-            if "wall_segments" in p:
-                raise ValueError("params hold both 'wall_segments' and 'wall_tracks': walls are static or have tracks, "
-                                 "give one of the two")
-            tr, hw = np.asarray(p['wall_tracks']), np.asarray(p.get('wall_halfwidth', 0.0))
-            key = (tr.dtype.str, tr.shape, tr.tobytes(), hw.dtype.str, hw.shape, hw.tobytes())
-            if tr.ndim != 4:
-                raise ValueError("params['wall_tracks'] has shape (W, L, 2, 2), got {}".format(tr.shape))
-            if key != self._wall_tracks_key and not self._own_walls:
-                self._hand_over_wall_tracks([(tr, hw)], "params['wall_tracks']")
-                self._wall_tracks_key = key
-        elif self._wall_tracks_key is not None:  # (the params no longer hold wall tracks)
-            if not self._own_walls:
-                self._hand_over_wall_tracks(None)
-            self._wall_tracks_key = None
-        if "wall_segments" not in p:
-            if self._walls_key != ():
-                _lib.call("mppi_planner_set_walls", self._handle, None, None, 0)
-                self._walls_key = ()
-            return
-        seg, hw = np.asarray(p['wall_segments']), np.asarray(p.get('wall_halfwidth', 0.0))
-        key = (seg.dtype.str, seg.shape, seg.tobytes(), hw.dtype.str, hw.shape, hw.tobytes())
-        if key == self._walls_key:
-            return
-        if seg.size and seg.shape[1:] != (2, 2):
-            raise ValueError("params['wall_segments'] has shape (W, 2, 2), got {}".format(seg.shape))
-        segs = np.ascontiguousarray(_f32(seg).reshape(-1, 4))
-        if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(segs)):
-            raise ValueError("params['wall_halfwidth'] is a scalar or has shape ({},), got {}".format(len(segs), hw.shape))
-        half = np.ascontiguousarray(np.broadcast_to(_f32(hw), (len(segs),)))
-        _lib.call("mppi_planner_set_walls", self._handle, _lib.ptr(segs, C.c_float), _lib.ptr(half, C.c_float), len(segs))
-        self._walls_key = key
+    # ------------------------------------------------------------------ hand-overs
+    def _send(self, kind, args, key=None, owner=_NOBODY):
+        """One call of a kind's setter -- args None: its clearing form -- and what goes with it: the kind's record, the
+        kind it lies over, the track offsets."""
+        _lib.call(kind.setter, self._handle, *[_lib.ptr(a, _CTYPES[a.dtype]) if isinstance(a, np.ndarray) else a
+                                               for a in (kind.clear if args is None else args)])
+        rec = self._held[kind.name]
+        rec.key, rec.owner, rec.sent = key, owner, args
+        if kind.over is not None:
+            self._held[kind.over].key = _STALE
+        if kind.offsets is _FETCH:
+            self._fetch_track_offset()
+        elif kind.offsets is _ZERO:
+            self._track_offset = np.zeros(self.num_instances, dtype=np.int32)
 
-    def _hand_over_wall_tracks(self, sets, what="wall set"):
-        """sets: one (tracks (W, L, 2, 2) or segments (W, 2, 2), half-widths: a scalar or (W,)) pair for every problem, or
-        one per problem; None clears, and the walls of mppi_planner_set_walls apply again."""
-        if sets is None:
-            _lib.call("mppi_planner_set_wall_tracks", self._handle, 0, None, 0, None, None)
-            self._wall_rows = 0
-            self._fetch_track_offset()  # (walls that moved have gone: row 0 is "now", unless disc tracks count the rows)
+    def _sync_kind(self, p, kind):
+        """The hand-over of one params-owned kind.  Its key absent: cleared if something of params is held, else nothing.
+        Its key there: nothing if the bytes are those held -- or per-problem sets own the slot --, else packed, handed over
+        and remembered."""
+        rec = self._held[kind.name]
+        values = kind.read(self, p) if kind.key in p else None
+        if values is None:
+            if rec.key is not None and kind.clear is not None:
+                self._send(kind, None)
             return
-        segs, halves, rows = [], [], None
-        for b, (tr, hw) in enumerate(sets):
-            tr, hw = np.asarray(tr), np.asarray(hw)
-            if tr.ndim == 3:  # a static set: tracks of one row
-                tr = tr.reshape(len(tr), 1, *tr.shape[1:])
-            if tr.ndim != 4 or (tr.size and tr.shape[2:] != (2, 2)):
-                raise ValueError("{} {}: shape (W, L, 2, 2) -- or (W, 2, 2) for static walls --, got {}".format(
-                    what, b, np.asarray(sets[b][0]).shape))
-            if tr.shape[1] < 1:
-                raise ValueError("{} {}: a wall track has at least one row (L = 0)".format(what, b))
-            if rows not in (None, tr.shape[1]):
-                raise ValueError("{} {}: {} rows, other sets of this call have {}".format(what, b, tr.shape[1], rows))
-            rows = tr.shape[1]
-            if hw.ndim not in (0, 1) or (hw.ndim == 1 and len(hw) != len(tr)):
-                raise ValueError("{} {}: the half-width is a scalar or has shape ({},), got {}".format(what, b, len(tr), hw.shape))
-            segs.append(_f32(tr).reshape(-1, 4))
-            halves.append(np.broadcast_to(_f32(hw), (len(tr),)))
-        counts = np.ascontiguousarray([len(h) for h in halves], dtype=np.int32)
-        seg_all = np.ascontiguousarray(np.concatenate(segs), dtype=np.float32)
-        half_all = np.ascontiguousarray(np.concatenate(halves), dtype=np.float32)
-        _lib.call("mppi_planner_set_wall_tracks", self._handle, len(sets), _lib.ptr(counts, C.c_int), int(rows),
-                  _lib.ptr(seg_all, C.c_float), _lib.ptr(half_all, C.c_float))
-        self._wall_rows = int(rows)
-        self._fetch_track_offset()  # (new walls that move: row 0 is "now"; a set of one row is static and leaves it alone)
+        key = [(v.dtype, v.shape, v.tobytes()) for v in values]  # (dtype.str would cost more than the rest of the key)
+        if key != rec.key and rec.owner is not _BATCH and kind.pack is not None:
+            self._send(kind, kind.pack(self, *values), key, _PARAMS)
+
+    def _sync(self, p, kinds):
+        for kind in kinds:
+            if not any(key in p for key in _RESTS_UNDER[kind.name]):
+                self._sync_kind(p, kind)
+
+    def _own_slot(self, kind, held, now=None, pack=None):
+        """The owner rule of the three track kinds, for MPPI_Batch's per-problem sets `held` (`now`: those of before).
+        None: they go -- the slot is free, and the shared key of params is handed over again at the next solve.  Unchanged:
+        nothing, "now" stays where it is.  Else they take the slot, and the caller keeps `held`: returns True."""
+        rec = self._held[kind.name]
+        if held is None:
+            if rec.owner is _BATCH:
+                self._send(kind, None)
+        elif not (rec.owner is _BATCH and now is not None and _same_sets(held, now)):
+            self._send(kind, pack(), None, _BATCH)
+            return True
+        return False
 
     # ------------------------------------------------------------------ a body footprint
-    def _hand_over_footprint(self, p):
-        """params['footprint'] (F, 3): handed over when its bytes have changed, cleared when the key has gone.  Without
-        crowd mode the library refuses it (MppiError); beside the fleet it is refused here (ValueError)."""
-        if "footprint" not in p:
-            if self._footprint_key is not None:
-                _lib.call("mppi_planner_set_footprint", self._handle, None, 0)
-                self._footprint_key = None
-            return
-        if self._fleet is not None:
-            raise ValueError("params hold 'footprint' while the fleet is on: the fleet's half-widths already contain the "
-                             "reader's body (set_fleet(None) first, or drop the key)")
-        if self._fleet_bodies is not None:
-            raise ValueError("params hold 'footprint' while the fleet of bodies is on: that fleet carries its own body "
-                             "(set_fleet(None) first, or drop the key)")
-        fp = np.asarray(p['footprint'])
-        key = (fp.dtype.str, fp.shape, fp.tobytes())
-        if key == self._footprint_key:
-            return
-        rows = _footprint_rows(fp)
-        _lib.call("mppi_planner_set_footprint", self._handle, _lib.ptr(rows, C.c_float), len(rows))
-        self._footprint_key = key
-
     @property
     def footprint(self):
         """The footprint the library holds: (F, 3) float32, or None (the robot is its reference point).  While a fleet of
@@ -549,22 +745,6 @@ class MPPI_Numba(object):
         return rows[:count.value].copy() if count.value else None
 
     # ------------------------------------------------------------------ clearance rings
-    def _hand_over_rings(self, p):
-        """params['clearance_rings'] (R, 2): handed over when its bytes have changed, cleared when the key has gone.
-        Without crowd mode, beside disc samples, or with a bad row the library refuses it (MppiError)."""
-        if "clearance_rings" not in p:
-            if self._rings_key is not None:
-                _lib.call("mppi_planner_set_clearance_rings", self._handle, None, 0)
-                self._rings_key = None
-            return
-        rg = np.asarray(p['clearance_rings'])
-        key = (rg.dtype.str, rg.shape, rg.tobytes())
-        if key == self._rings_key:
-            return
-        rows = _ring_rows(rg)
-        _lib.call("mppi_planner_set_clearance_rings", self._handle, _lib.ptr(rows, C.c_float), len(rows))
-        self._rings_key = key
-
     @property
     def clearance_rings(self):
         """The clearance rings the library holds: (R, 2) float32 rows (margin, penalty), or None."""
@@ -573,25 +753,6 @@ class MPPI_Numba(object):
         return rows[:count.value].copy() if count.value else None
 
     # ------------------------------------------------------------------ time-correlated noise
-    def _hand_over_smoothing(self, p):
-        """params['noise_smoothing'], a scalar or (2,): handed over when its bytes have changed, cleared when the key has
-        gone.  A wrong shape is refused here (ValueError); a value outside [0, 1), the xoroshiro generator: the library
-        refuses them (MppiError) and keeps what it had."""
-        if "noise_smoothing" not in p:
-            if self._smoothing_key is not None:
-                _lib.call("mppi_planner_set_noise_smoothing", self._handle, None)
-                self._smoothing_key = None
-            return
-        sm = np.asarray(p['noise_smoothing'])
-        key = (sm.dtype.str, sm.shape, sm.tobytes())
-        if key == self._smoothing_key:
-            return
-        if sm.shape not in ((), (2,)):
-            raise ValueError("params['noise_smoothing'] is a scalar or has shape (2,), got {}".format(sm.shape))
-        beta = np.ascontiguousarray(np.broadcast_to(_f32(sm), (2,)))
-        _lib.call("mppi_planner_set_noise_smoothing", self._handle, _lib.ptr(beta, C.c_float))
-        self._smoothing_key = key
-
     @property
     def noise_smoothing(self):
         """The smoothing coefficients the library holds: (2,) float32 (beta_v, beta_w), or None (white noise)."""
@@ -600,59 +761,17 @@ class MPPI_Numba(object):
         return beta if beta.any() else None
 
     # ------------------------------------------------------------------ a goal that moves
-    def _hand_over_goal_tracks(self, tracks, what="goal track"):
-        """tracks: one (L, 2) goal track for every problem, or one per problem with a common L; None clears, and the
-        static goals apply again."""
-        if tracks is None:
-            _lib.call("mppi_planner_set_goal_tracks", self._handle, 0, 0, None)
-            self._goal_tracks = None
-            self._fetch_track_offset()  # (a goal that moved has gone: row 0 is "now", unless other tracks count the rows)
-            return
-        held, rows = [], None
-        for b, tr in enumerate(tracks):
-            tr = np.asarray(tr)
-            if tr.ndim != 2 or tr.shape[1] != 2:
-                raise ValueError("{} {}: shape (L, 2), got {}".format(what, b, tr.shape))
-            if tr.shape[0] < 1:
-                raise ValueError("{} {}: a goal track has at least one row (L = 0)".format(what, b))
-            if rows not in (None, tr.shape[0]):
-                raise ValueError("{} {}: {} rows, other tracks of this call have {}".format(what, b, tr.shape[0], rows))
-            rows = tr.shape[0]
-            held.append(_f32(tr))
-        if len(held) not in (1, self.num_instances):
-            raise ValueError("{} goal tracks: one for every problem, or one per problem ({})".format(len(held), self.num_instances))
-        xy = np.ascontiguousarray(np.stack(held), dtype=np.float32)
-        _lib.call("mppi_planner_set_goal_tracks", self._handle, len(held), int(rows), _lib.ptr(xy, C.c_float))
-        self._goal_tracks = xy
-        self._fetch_track_offset()  # (a new goal that moves: row 0 is "now"; a track of one row is static and leaves it alone)
-
-    def _hand_over_goal(self, p):
-        """params['goal_track']: handed over when it has changed, cleared when the key has gone."""
-        if "goal_track" in p:
-            if "xgoal" in p:
-                raise ValueError("params hold both 'xgoal' and 'goal_track': the goal is static or has a track, give one of "
-                                 "the two")
-            tr = np.asarray(p['goal_track'])
-            key = (tr.dtype.str, tr.shape, tr.tobytes())
-            if tr.ndim != 2 or tr.shape[1] != 2:
-                raise ValueError("params['goal_track'] has shape (L, 2), got {}".format(tr.shape))
-            if key != self._goal_track_key and not self._own_goals:
-                self._hand_over_goal_tracks([tr], "params['goal_track']")
-                self._goal_track_key = key
-        elif self._goal_track_key is not None:  # (the params no longer hold a goal track)
-            if not self._own_goals:
-                self._hand_over_goal_tracks(None)
-            self._goal_track_key = None
-
     def _goal_track_on(self):
-        return self._goal_tracks is not None and self._goal_tracks.shape[1] > 1
+        goal = self._held["goal"]
+        return goal.sent is not None and goal.sent[1] > 1  # (sent: count, rows, the tracks (1 or B, L, 2) float32)
 
     @property
     def goal_now(self):
         """The goal where it is now: row min(track_offset, L - 1) of the goal track -- (2,) float32, (B, 2) for a batch --
         or the static goal when no track is set.  The closed loop's goal test of a new state, after shift_and_update."""
-        tracks = self._goal_tracks
-        if not self._own_goals and self.params is not None:  # (params['goal_track'] may not have been handed over yet)
+        goal = self._held["goal"]
+        tracks = None if goal.sent is None else goal.sent[2]
+        if goal.owner is not _BATCH and self.params is not None:  # (params['goal_track'] may not have been handed over yet)
             tracks = _f32(self.params['goal_track'])[None] if "goal_track" in self.params else None
         if tracks is None:
             if self.num_instances > 1:
@@ -663,50 +782,13 @@ class MPPI_Numba(object):
         return now[0].copy() if self.num_instances == 1 else now.copy()
 
     def _tracks_on(self):
-        return self._tracks_from_params or self._own_tracks or self._samples_key is not None
+        return self._held["tracks"].sent is not None or self._held["samples"].sent is not None
+
+    def _wall_tracks_on(self):
+        walls = self._held["wall_tracks"]
+        return walls.sent is not None and walls.sent[2] > 1  # (sent: sets, counts, rows -- 1: static sets --, ...)
 
     # ------------------------------------------------------------------ disc samples
-    def _hand_over_samples(self, p):
-        """params['obstacle_track_samples'] (S, K, L, 2) with params['obstacle_radius'] (K,): handed over when they have
-        changed, cleared when the key has gone (row 0 is "now" again, as for tracks).  True while samples are held."""
-        if "obstacle_track_samples" not in p:
-            if self._samples_key is not None:
-                _lib.call("mppi_planner_set_disc_track_samples", self._handle, 0, 0, 0, None, None)
-                self._samples_key = None
-                self._discs_key = None  # (the static discs below are handed over again)
-                self._fetch_track_offset()
-            return False
-        others = [k for k in ("obstacle_positions", "obstacle_tracks") if k in p]
-        if others:
-            raise ValueError("params hold both 'obstacle_track_samples' and '{}': discs are static, have tracks or have "
-                             "sampled tracks, give one of the three".format(others[0]))
-        if getattr(self, "obstacle_sets", None) is not None:
-            raise ValueError("params hold 'obstacle_track_samples' while obstacle_sets are held: disc samples are shared by "
-                             "every problem (set_obstacle_sets(None) first)")
-        smp, orad = np.asarray(p['obstacle_track_samples']), np.asarray(p['obstacle_radius'])
-        key = (smp.dtype.str, smp.shape, smp.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
-        if key == self._samples_key:
-            return True
-        if smp.ndim != 4 or smp.shape[3] != 2 or smp.shape[0] < 1 or smp.shape[2] < 1:
-            raise ValueError("params['obstacle_track_samples'] has shape (S, K, L, 2) with S, L >= 1, got {}".format(smp.shape))
-        if smp.shape[0] > MAX_DISC_SAMPLES:
-            raise ValueError("params['obstacle_track_samples'] holds {} samples, more than {}".format(smp.shape[0], MAX_DISC_SAMPLES))
-        rad = np.ascontiguousarray(_f32(orad).reshape(-1))
-        if len(rad) != smp.shape[1]:
-            raise ValueError("params['obstacle_track_samples'] holds {} discs, params['obstacle_radius'] {} radii".format(
-                smp.shape[1], len(rad)))
-        if self._tracks_from_params:  # (the params no longer hold plain tracks)
-            self._hand_over_tracks(None)
-            self._tracks_from_params = False
-        pos = np.ascontiguousarray(_f32(smp))
-        _lib.call("mppi_planner_set_disc_track_samples", self._handle, int(smp.shape[0]), int(smp.shape[1]), int(smp.shape[2]),
-                  _lib.ptr(pos if pos.size else np.zeros(2, np.float32), C.c_float),
-                  _lib.ptr(rad if rad.size else np.zeros(1, np.float32), C.c_float))
-        self._samples_key = key
-        self._discs_key = None
-        self._fetch_track_offset()  # (a new set of more than one row: row 0 is "now")
-        return True
-
     def record_sample_costs(self):
         """From the next rollout on the per-sample costs are kept (while disc samples are held); sample_costs() fetches."""
         self.move_mppi_task_vars_to_device()
@@ -715,42 +797,14 @@ class MPPI_Numba(object):
     def sample_costs(self):
         """(N, S) float32 -- (B, N, S) for a batch: every rollout's cost under each disc sample, before the CVaR tail, in
         sample order."""
-        if self._samples_key is None:
+        samples = self._held["samples"]
+        if samples.sent is None:
             raise ValueError("sample_costs: no disc samples are held (params['obstacle_track_samples'])")
-        S = int(np.asarray(self.params['obstacle_track_samples']).shape[0])
+        S = samples.sent[0]
         lead = () if self.num_instances == 1 else (self.num_instances,)
         out = np.empty(lead + (self.num_control_rollouts, S), dtype=np.float32)
         _lib.call("mppi_planner_get_sample_costs", self._handle, _lib.ptr(out, C.c_float))
         return out
-
-    def _wall_tracks_on(self):
-        return self._wall_rows > 1
-
-    def _hand_over_tracks(self, sets):
-        """sets: one (tracks (K, L, 2), radii (K,)) pair for every problem, or one per problem; None clears."""
-        if sets is None:
-            _lib.call("mppi_planner_set_disc_tracks", self._handle, 0, None, 0, None, None)
-            return
-        tracks = [np.asarray(tr) for tr, _ in sets]
-        rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in sets]
-        rows = None
-        for b, tr in enumerate(tracks):
-            if tr.ndim != 3 or tr.shape[2] != 2:
-                raise ValueError("set {}: tracks have shape (K, L, 2), got {}".format(b, tr.shape))
-            if tr.shape[1] < 1:
-                raise ValueError("set {}: a track has at least one row (L = 0)".format(b))
-            if len(tr) != len(rad[b]):
-                raise ValueError("set {}: {} tracks and {} radii".format(b, len(tr), len(rad[b])))
-            if rows not in (None, tr.shape[1]):
-                raise ValueError("set {}: {} rows, other sets of this call have {}".format(b, tr.shape[1], rows))
-            rows = tr.shape[1]
-        counts = np.ascontiguousarray([len(r) for r in rad], dtype=np.int32)
-        flat = [_f32(tr).reshape(-1, 2) for tr in tracks if len(tr)]
-        pos_all = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 2), np.float32))
-        rad_all = np.ascontiguousarray(np.concatenate(rad) if counts.sum() else np.zeros(0, np.float32))
-        _lib.call("mppi_planner_set_disc_tracks", self._handle, len(sets), _lib.ptr(counts, C.c_int), int(rows),
-                  _lib.ptr(pos_all, C.c_float), _lib.ptr(rad_all, C.c_float))
-        self._track_offset = np.zeros(self.num_instances, dtype=np.int32)  # (new tracks: row 0 is "now")
 
     def init_device_vars_before_solving(self):
         if self.device_var_initialized:
@@ -808,12 +862,15 @@ class MPPI_Numba(object):
         """Pack the task description as notebook cell 3 casts it (np.float32 everywhere except dist_weight) and hand it to
         the library.  (Assigning a Python / numpy scalar to a c_float field rounds float64 -> float32 to nearest, which is
         what the np.float32(...) casts do: no numpy temporaries on the control path -- the notebook times solve() as a
-        whole, `bench.py --workload bb` likewise.)"""
+        whole, `bench.py --workload bb` likewise.)  Around it, one walk over _KINDS; the path with no optional key in params
+        and nothing optional held pays one test of the params' keys for all of them, and the discs' hand-over."""
         p = self.params
         c = _lib.Params()
-        moving_goal = "goal_track" in p
-        if moving_goal or self._goal_track_key is not None:  # (the static goal's path pays one lookup for this)
-            self._hand_over_goal(p)
+        walk_all = self._walk_all or not _OPTIONAL_KEYS.isdisjoint(p)
+        moving_goal = walk_all and "goal_track" in p
+        if walk_all:
+            self._walk_all = True  # (until the walk has come to its end)
+            self._sync_kind(p, _GOAL)
         for name, count in _TASK_VECTORS_GOAL_TRACK if moving_goal else _TASK_VECTORS:
             src, dst = p[name], getattr(c, name)
             for i in range(count):
@@ -836,50 +893,11 @@ class MPPI_Numba(object):
         c.alpha_dyn = 1.0
         c.num_opt = int(p['num_opt'])
         _lib.call("mppi_planner_set_params", self._handle, C.byref(c))
-        if "noise_smoothing" in p or self._smoothing_key is not None:  # (the white noise's path pays one lookup for this)
-            self._hand_over_smoothing(p)
-        self._hand_over_walls(p)
-        if "footprint" in p or self._footprint_key is not None:  # (the point robot's path pays one lookup for this)
-            self._hand_over_footprint(p)
-        # rings and disc samples exclude each other: a key that has gone is cleared ahead of the samples' hand-over, a key
-        # that is there is handed over behind it (the path without the key pays one lookup for this)
-        rings = "clearance_rings" in p
-        if not rings and self._rings_key is not None:
-            self._hand_over_rings(p)
-        sampled = ("obstacle_track_samples" in p or self._samples_key is not None) and self._hand_over_samples(p)
-        if rings:
-            self._hand_over_rings(p)
-        if sampled:
-            return
-        # the discs: handed over when they have changed (the notebook uploads them with every solve)
-        if "obstacle_tracks" in p:
-            if "obstacle_positions" in p:
-                raise ValueError("params hold both 'obstacle_positions' and 'obstacle_tracks': discs are static or have "
-                                 "tracks, give one of the two")
-            tr, orad = np.asarray(p['obstacle_tracks']), np.asarray(p['obstacle_radius'])
-            key = ("tracks", tr.dtype.str, tr.shape, tr.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
-            if key != self._discs_key and not self._own_tracks:
-                self._hand_over_tracks([(tr, orad)])
-                self._discs_key, self._tracks_from_params = key, True
-            return
-        if self._tracks_from_params:  # (the params no longer hold tracks: the static discs below apply again)
-            self._hand_over_tracks(None)
-            self._tracks_from_params = False
-            self._discs_key = None
-            self._track_offset = np.zeros(self.num_instances, dtype=np.int32)
-        if "obstacle_positions" in p and "obstacle_radius" in p:
-            op, orad = np.asarray(p['obstacle_positions']), np.asarray(p['obstacle_radius'])
-            key = (op.dtype.str, op.shape, op.tobytes(), orad.dtype.str, orad.shape, orad.tobytes())
-            if key != self._discs_key:
-                pos = np.ascontiguousarray(_f32(op).reshape(-1, 2))
-                rad = np.ascontiguousarray(_f32(orad).reshape(-1))
-                assert len(pos) == len(rad)
-                _lib.call("mppi_planner_set_disc_obstacles", self._handle, _lib.ptr(pos, C.c_float),
-                          _lib.ptr(rad, C.c_float), len(rad))
-                self._discs_key = key
-        elif self._discs_key != ():
-            _lib.call("mppi_planner_set_disc_obstacles", self._handle, None, None, 0)
-            self._discs_key = ()
+        if walk_all:
+            self._sync(p, _KINDS[1:])
+            self._walk_all = any(self._held[name].key is not None for name in _OPTIONAL_NAMES)
+        else:
+            self._sync_kind(p, _DISCS)
 
     def solve(self):
         if not self.check_solve_conditions():
@@ -1074,16 +1092,14 @@ class MPPI_Batch(MPPI_Numba):
         problem has the shared set of params['obstacle_positions'] / ['obstacle_radius'].  A set whose first element
         is 3-D, (K_b, L, 2), is a set of tracks (discs that move; L common to the sets of a call); one call is all
         static or all tracks."""
-        if self._own_tracks and (obstacle_sets is None or not _is_track_set(obstacle_sets[0])):
-            self._hand_over_tracks(None)  # (per-problem tracks go; shared ones of the params are handed over again)
-            self._own_tracks = False
-            self._discs_key = None
-            self._track_offset = np.zeros(self.num_instances, dtype=np.int32)
+        problem_discs = self._held["problem_discs"]
+        if obstacle_sets is None or not _is_track_set(obstacle_sets[0]):
+            self._own_slot(_TRACKS, None)
         if obstacle_sets is None:
             _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
-            self.obstacle_sets = None
+            self.obstacle_sets = problem_discs.sent = None
             return
-        if self._samples_key is not None or (self.params is not None and "obstacle_track_samples" in self.params):
+        if self._held["samples"].key is not None or (self.params is not None and "obstacle_track_samples" in self.params):
             raise ValueError("set_obstacle_sets while params hold 'obstacle_track_samples': disc samples are shared by every "
                              "problem (drop the key first)")
         assert len(obstacle_sets) == self.num_instances, "one disc set per problem"
@@ -1091,15 +1107,10 @@ class MPPI_Batch(MPPI_Numba):
         if len(kinds) > 1:
             raise ValueError("obstacle_sets mix static sets and track sets: one call is all static or all tracks")
         if kinds == {True}:
-            same = self._own_tracks and self.obstacle_sets is not None and all(
-                np.array_equal(_f32(np.asarray(a[0])), b[0]) and np.array_equal(_f32(np.asarray(a[1])).reshape(-1), b[1])
-                for a, b in zip(obstacle_sets, self.obstacle_sets))
-            if same:
-                return  # (unchanged: "now" stays where it is)
-            self._hand_over_tracks(list(obstacle_sets))
-            _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
-            self._own_tracks, self._tracks_from_params, self._discs_key = True, False, None
-            self.obstacle_sets = [(_f32(np.asarray(tr)).copy(), _f32(np.asarray(r)).reshape(-1).copy()) for tr, r in obstacle_sets]
+            held = [(_f32(np.asarray(tr)), _f32(np.asarray(r)).reshape(-1)) for tr, r in obstacle_sets]
+            if self._own_slot(_TRACKS, held, self.obstacle_sets, lambda: _pack_disc_tracks(obstacle_sets)):
+                _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, 0, None, None, None)
+                self.obstacle_sets = problem_discs.sent = held
             return
         pos = [_f32(np.asarray(op)).reshape(-1, 2) for op, _ in obstacle_sets]
         rad = [_f32(np.asarray(orad)).reshape(-1) for _, orad in obstacle_sets]
@@ -1110,7 +1121,7 @@ class MPPI_Batch(MPPI_Numba):
         rad_all = np.ascontiguousarray(np.concatenate(rad) if counts.sum() else np.zeros(0, np.float32))
         _lib.call("mppi_planner_set_instance_disc_obstacles", self._handle, self.num_instances,
                   _lib.ptr(counts, C.c_int), _lib.ptr(pos_all, C.c_float), _lib.ptr(rad_all, C.c_float))
-        self.obstacle_sets = [(p.copy(), r.copy()) for p, r in zip(pos, rad)]
+        self.obstacle_sets = problem_discs.sent = [(p.copy(), r.copy()) for p, r in zip(pos, rad)]
 
     def set_wall_sets(self, sets):
         """One wall set per problem (crowd mode): a list of B (segments (W_b, 2, 2), half-width: a scalar or (W_b,)) pairs,
@@ -1118,44 +1129,33 @@ class MPPI_Batch(MPPI_Numba):
         (W_b, Lw, 2, 2), is a set of wall tracks (Lw common to the sets of a call); one call is all static or all tracks.
         Per-problem sets win over the walls of params.  New tracks make row 0 "now"; unchanged ones leave it alone."""
         if sets is None:
-            if self._own_walls:
-                self._hand_over_wall_tracks(None)  # (shared wall tracks of the params are handed over again)
-                self._own_walls, self._wall_tracks_key = False, None
+            self._own_slot(_WALL_TRACKS, None)
             self.wall_sets = None
             return
-        if self._fleet is not None or self._fleet_bodies is not None:
+        if self._held["fleet"].sent is not None or self._held["fleet_bodies"].sent is not None:
             raise ValueError("set_wall_sets while the fleet is on: the fleet makes every problem's wall set itself "
                              "(set_fleet(None) first)")
         assert len(sets) == self.num_instances, "one wall set per problem"
         kinds = {_is_wall_track_set(s) for s in sets}
         if len(kinds) > 1:
             raise ValueError("wall sets mix static sets and track sets: one call is all static or all tracks")
-        held = [(_f32(np.asarray(seg)).copy(), _f32(np.asarray(hw)).copy()) for seg, hw in sets]
-        if self._own_walls and self.wall_sets is not None and all(
-                np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(held, self.wall_sets)):
-            return  # (unchanged: "now" stays where it is)
-        self._hand_over_wall_tracks(list(sets))
-        self._own_walls, self._wall_tracks_key = True, None
-        self.wall_sets = held
+        held = [(_f32(np.asarray(seg)), _f32(np.asarray(hw))) for seg, hw in sets]
+        if self._own_slot(_WALL_TRACKS, held, self.wall_sets, lambda: _pack_wall_tracks(sets)):
+            self.wall_sets = held
 
     def set_goal_tracks(self, tracks):
         """One goal track per problem: (B, L, 2), or a list of B arrays (L, 2) with a common L -- or None: every problem
         has its goal of `goals` again (or the shared track of params['goal_track']).  Per-problem tracks win over
         params['goal_track'].  New tracks of more than one row make row 0 "now"; unchanged ones leave it alone."""
         if tracks is None:
-            if self._own_goals:
-                self._hand_over_goal_tracks(None)  # (a shared track of the params is handed over again)
-                self._own_goals, self._goal_track_key = False, None
+            self._own_slot(_GOAL, None)
             self.goal_tracks = None
             return
         if len(tracks) != self.num_instances:
             raise ValueError("{} goal tracks for {} problems: one per problem".format(len(tracks), self.num_instances))
         held = [_f32(np.asarray(tr)) for tr in tracks]
-        if self._own_goals and self.goal_tracks is not None and all(np.array_equal(a, b) for a, b in zip(held, self.goal_tracks)):
-            return  # (unchanged: "now" stays where it is)
-        self._hand_over_goal_tracks(list(tracks))
-        self._own_goals, self._goal_track_key = True, None
-        self.goal_tracks = held
+        if self._own_slot(_GOAL, held, self.goal_tracks, lambda: _pack_goal_tracks(self, tracks)):
+            self.goal_tracks = held
 
     # ------------------------------------------------------------------ a fleet
     def set_fleet(self, radii, margin=0.0):
@@ -1166,9 +1166,9 @@ class MPPI_Batch(MPPI_Numba):
         from the float32 radii.  Raises while per-problem wall sets or params['wall_tracks'] are held."""
         if radii is None:  # (either kind of fleet)
             _lib.call("mppi_planner_set_fleet", self._handle, 0, None)
-            self._fleet = self._fleet_bodies = None
+            self._held["fleet"].sent = self._held["fleet_bodies"].sent = None
             return
-        if self._fleet_bodies is not None:
+        if self._held["fleet_bodies"].sent is not None:
             raise ValueError("set_fleet while the fleet of bodies is on: the two kinds change through off (set_fleet(None) first)")
         B = self.num_instances
         r = np.ascontiguousarray(np.broadcast_to(_f32(radii), (B,)))
@@ -1177,21 +1177,22 @@ class MPPI_Batch(MPPI_Numba):
         if self.params is not None and "footprint" in self.params:
             raise ValueError("set_fleet while params hold 'footprint': the fleet's half-widths already contain the reader's "
                              "body (drop the key first)")
-        if self._footprint_key is not None:  # (the key has gone and the library has not heard yet)
-            self._hand_over_footprint(self.params if self.params is not None else {})
-        if self._own_walls or self._wall_tracks_key is not None:
+        if self._held["footprint"].key is not None:  # (the key has gone and the library has not heard yet)
+            self._sync_kind(self.params if self.params is not None else {}, _FOOTPRINT)
+        if self._held["wall_tracks"].owner is not _NOBODY:
             raise ValueError("set_fleet while per-problem wall sets or params['wall_tracks'] are held: the fleet makes every "
                              "problem's wall set itself (set_wall_sets(None) / drop the key first)")
         r64 = r.astype(np.float64)
         full = ((r64[:, None] + r64[None, :]) + np.float64(margin)).astype(np.float32)
         half = np.ascontiguousarray(full[np.arange(B)[:, None], fleet_others(B)], dtype=np.float32).reshape(B, max(B - 1, 0))
         _lib.call("mppi_planner_set_fleet", self._handle, B, _lib.ptr(half if half.size else np.zeros(1, np.float32), C.c_float))
-        self._fleet = (r.copy(), float(margin), half)
+        self._held["fleet"].sent = (r.copy(), float(margin), half)
 
     @property
     def fleet(self):
         """None while fleet mode is off, else (radii (B,) float32, margin)."""
-        return None if self._fleet is None else (self._fleet[0].copy(), self._fleet[1])
+        fleet = self._held["fleet"].sent
+        return None if fleet is None else (fleet[0].copy(), fleet[1])
 
     def set_fleet_bodies(self, footprint, margin=0.0):
         """A fleet of bodies (crowd mode, B >= 2): the fleet of set_fleet() for robots that are the discs of `footprint`
@@ -1207,34 +1208,35 @@ class MPPI_Batch(MPPI_Numba):
         if not (np.isfinite(rows).all() and (rows[:, 2] >= 0).all() and np.isfinite(margin)
                 and (rows[:, 2].astype(np.float64) + margin >= 0).all()):
             raise ValueError("a fleet's body has finite rows with rho >= 0, and a finite margin with rho + margin >= 0")
-        if self._fleet is not None:
+        if self._held["fleet"].sent is not None:
             raise ValueError("set_fleet_bodies while the disc fleet is on: the two kinds change through off (set_fleet(None) first)")
         if self.params is not None and "footprint" in self.params:
             raise ValueError("set_fleet_bodies while params hold 'footprint': the fleet of bodies carries its own body "
                              "(drop the key first)")
-        if self._footprint_key is not None:  # (the key has gone and the library has not heard yet)
-            self._hand_over_footprint(self.params if self.params is not None else {})
-        if self._own_walls or self._wall_tracks_key is not None:
+        if self._held["footprint"].key is not None:  # (the key has gone and the library has not heard yet)
+            self._sync_kind(self.params if self.params is not None else {}, _FOOTPRINT)
+        if self._held["wall_tracks"].owner is not _NOBODY:
             raise ValueError("set_fleet_bodies while per-problem wall sets or params['wall_tracks'] are held: the fleet makes "
                              "every problem's wall set itself (set_wall_sets(None) / drop the key first)")
         _lib.call("mppi_planner_set_fleet_bodies", self._handle, self.num_instances, _lib.ptr(rows, C.c_float), len(rows),
                   C.c_double(margin))
-        self._fleet_bodies = (rows.copy(), margin)
+        self._held["fleet_bodies"].sent = (rows.copy(), margin)
 
     @property
     def fleet_bodies(self):
         """None while no fleet of bodies is on, else (rows (F, 3) float32, margin)."""
-        return None if self._fleet_bodies is None else (self._fleet_bodies[0].copy(), self._fleet_bodies[1])
+        bodies = self._held["fleet_bodies"].sent
+        return None if bodies is None else (bodies[0].copy(), bodies[1])
 
     def fleet_body_walls(self):
         """What the last refresh of a fleet of bodies left: (segments (B, B - 1, F, T, 2, 2) float32, half-widths (F,)
         float32, others (B, B - 1) int) -- segments[a, o, k, j] is the segment body disc k of robot others[a, o] covers
         in control interval j from "now", halfwidths[k] = float32(rho_k + margin) the half-width every reader is given it
         with.  The padding slots are left out."""
-        if self._fleet_bodies is None:
+        if self._held["fleet_bodies"].sent is None:
             raise ValueError("fleet_body_walls: no fleet of bodies is on (set_fleet_bodies)")
         B, t = self.num_instances, self.num_steps
-        rows, margin = self._fleet_bodies
+        rows, margin = self._held["fleet_bodies"].sent
         seg = np.empty((B, B - 1, len(rows), t, 2, 2), dtype=np.float32)
         _lib.call("mppi_planner_get_fleet_body_walls", self._handle, _lib.ptr(seg, C.c_float))
         return seg, (rows[:, 2].astype(np.float64) + np.float64(margin)).astype(np.float32), fleet_others(B)
@@ -1249,14 +1251,14 @@ class MPPI_Batch(MPPI_Numba):
         """What the last refresh left: (segments (B, B - 1, T, 2, 2) float32, half-widths (B, B - 1) float32, others
         (B, B - 1) int) -- segments[a, k, j] is the segment robot others[a, k] covers in control interval j from "now",
         as reader a is given it."""
-        if self._fleet_bodies is not None:
+        if self._held["fleet_bodies"].sent is not None:
             raise ValueError("fleet_walls: a fleet of bodies is on, whose walls have one more axis (fleet_body_walls)")
-        if self._fleet is None:
+        if self._held["fleet"].sent is None:
             raise ValueError("fleet_walls: the fleet is off (set_fleet)")
         B, t = self.num_instances, self.num_steps
         seg = np.empty((B, B - 1, t, 2, 2), dtype=np.float32)
         _lib.call("mppi_planner_get_fleet_walls", self._handle, _lib.ptr(seg, C.c_float))
-        return seg, self._fleet[2].copy(), fleet_others(B)
+        return seg, self._held["fleet"].sent[2].copy(), fleet_others(B)
 
     def check_solve_conditions(self):
         if self.x0s is None:
