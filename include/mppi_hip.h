@@ -353,6 +353,63 @@ int mppi_planner_set_wall_tracks(mppi_planner* p, int count, const int* wall_cou
  * coordinate. */
 int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows, const float* xy);
 
+/* MPPI_MODE_BAREBONE: a guide round the walls.  The rollouts steer by the straight-line distance
+ * to the goal and look T * dt ahead; in a room whose door lies on the side away from the goal that
+ * is a wall to lean on for ever.  While the guide is on the device keeps, per problem, a
+ * shortest-path distance field from the problem's static goal (params.xgoal, or the goal of
+ * mppi_planner_set_instances) over a grid whose cells the shared static walls of
+ * mppi_planner_set_walls block, and fills the problem's goal rows with "carrots" on the shortest
+ * path from its start.  Every value is an integer or a double rounded once (csrc/guide_grid.h):
+ *   grid     nx * ny <= 36864 cells (192 x 192) of side res > 0; cell (iy, ix) has the centre
+ *            cx = (double)x_min + ((double)ix + 0.5) * (double)res, cy likewise; a point belongs to
+ *            cell clamp(floor(((double)x - (double)x_min) / (double)res), 0, nx - 1): outside the
+ *            grid, to the nearest border cell
+ *   blocked  a cell whose centre is within h_k + inflate of some wall k (the rollouts' own
+ *            point-to-segment test with hh = ((double)h_k + (double)inflate)^2).  inflate >= 0 and
+ *            2 * inflate^2 >= res^2: then no move between free neighbouring centres touches a
+ *            wall, diagonal moves included.  Discs, disc tracks, wall tracks, per-problem wall
+ *            sets and the fleet's walls are NOT rasterised: the rollouts' hit tests deal with them
+ *   field    uint32 [ny][nx]: 0xFFFFFFFF blocked, 0xFFFFFFFE free without a path, else the length
+ *            of the shortest path to the goal's cell over free cells, 12 a straight move, 17 a
+ *            diagonal one.  A goal in a blocked cell: status 1, every free cell without a path
+ *   descent  from the start's cell c_0 to the in-grid neighbour with a path that minimises
+ *            D[n] + w, the first minimum in the order (1,0) (0,1) (-1,0) (0,-1) (1,1) (-1,1)
+ *            (-1,-1) (1,-1); R_i the length still to go (a start in a blocked cell walks out the
+ *            cheapest way: R_0 = D[c_1] + w; without such a neighbour: status 2)
+ *   rows     units(m) = floor((double)m / (double)res * 12.0); for j = 0 .. T row j is the centre,
+ *            rounded to float32, of the first c_i with R_0 - R_i >= units(lead) + j * units(pace),
+ *            or the goal itself when there is none, when that cell is the goal's, or under status
+ *            1 or 2.  lead, pace >= 0 and units(lead) + T * units(pace) < 2^31
+ * The state after step t of a rollout is measured against row t + 1 as against a goal track's row
+ * (stage term, goal test, freeze, terminal term), whatever the track offsets are: the guide
+ * neither reads nor advances nor resets them.  Both kernel families take the rows, the crowd
+ * kernel with every form that takes goal tracks; mppi_planner_describe_last_rollout ends in
+ * " goal_rows=<T+1> guide=<nx>x<ny>".  The field is built on the planner's stream at the head of
+ * the next call that starts iterations -- mppi_planner_solve, mppi_planner_iterate_async,
+ * mppi_planner_rollout, each control step of mppi_planner_closed_loop -- and only when the guide,
+ * the static walls or a goal has changed; the rows are walked at the head of every such call,
+ * behind the fleet's refresh, from the start states as they are on the device (closed_loop: a
+ * problem that has arrived gets the goal in every row, and arrival is tested against the true
+ * goal).  A refresh writes into the same arrays: captured graphs stay valid.  Keep lead above the
+ * goal tolerance: a rollout that catches its carrot freezes as with any goal track.
+ * An unchanged hand-over costs a comparison; a change drains the stream and drops the captured
+ * graphs; on = 0 turns the guide off (the other arguments are ignored).  MPPI_ERR_INVALID, the
+ * handle keeping what it held: a map mode, world_size > 1, goal tracks held (and
+ * mppi_planner_set_goal_tracks with count > 0 while the guide is on), a value that is not finite,
+ * res <= 0, nx or ny < 1 or more than 36864 cells, inflate < 0 or 2 * inflate^2 < res^2, lead or
+ * pace < 0, or units that do not fit. */
+int mppi_planner_set_guide(mppi_planner* p, int on, float x_min, float y_min, float res, int nx, int ny,
+                           float inflate, float lead, float pace);
+/* *fields_built: how often this handle has built the field */
+int mppi_planner_get_guide(mppi_planner* p, int* on, int* nx, int* ny, unsigned long long* fields_built);
+/* the refresh alone -- the field if something it depends on changed, then the rows -- and a wait
+ * for the stream: for drawing and for tests.  MPPI_ERR_STATE without a guide */
+int mppi_planner_guide_refresh(mppi_planner* p);
+/* out: [B][ny][nx], the field of the last build (MPPI_ERR_STATE before the first) */
+int mppi_planner_get_guide_field(mppi_planner* p, unsigned* out);
+/* xy: [B][T+1][2], status: [B] -- of the last refresh */
+int mppi_planner_get_guide_rows(mppi_planner* p, float* xy, int* status);
+
 /* MPPI_MODE_BAREBONE, a batched handle (num_instances B >= 2) in crowd mode: fleet mode -- the
  * problems are robots that avoid each other's plans.  count = B turns it on, halfwidths (B, B-1)
  * float32: row a holds reader a's half-width against every other robot b in ascending b, a

@@ -113,6 +113,11 @@ SIGNATURES = {
     "mppi_planner_set_walls": [_vp, _f32p, _f32p, C.c_int],
     "mppi_planner_set_wall_tracks": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p],
     "mppi_planner_set_goal_tracks": [_vp, C.c_int, C.c_int, _f32p],
+    "mppi_planner_set_guide": [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float],
+    "mppi_planner_get_guide": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)],
+    "mppi_planner_guide_refresh": [_vp],
+    "mppi_planner_get_guide_field": [_vp, C.POINTER(C.c_uint)],
+    "mppi_planner_get_guide_rows": [_vp, _f32p, C.POINTER(C.c_int)],
     "mppi_planner_set_fleet": [_vp, C.c_int, _f32p],
     "mppi_planner_get_fleet": [_vp, C.POINTER(C.c_int)],
     "mppi_planner_fleet_refresh": [_vp],

@@ -129,6 +129,29 @@ effect with the next call, as if the handle had had the value from the start; wi
 the notebook's.  Limits: philox only (rng="xoroshiro" is refused: that generator exists for parity with numba from the
 seed); one setting for every problem of a batch; first order only; the control-cost term of the rollouts still weighs the
 noise by diag(u_std^2), as for white noise.  The map-mode classes do not read the key.
+
+A guide round the walls: params['guide'], a dict with 'origin' (x, y), 'resolution', 'shape' (ny, nx) and optionally
+'inflate' (default: the resolution), 'pace' (default vrange[1] * dt) and 'lead' (default 2 * pace), all rounded once to
+float32.  The rollouts steer by the straight-line distance to the goal and look T * dt ahead: in a room whose door lies on
+the side away from the goal they lean on the wall nearest the goal for ever.  With the key the device computes, per problem,
+a shortest-path distance field from params['xgoal'] over a grid of ny * nx <= 36864 cells (192 x 192) -- cell (iy, ix) has
+its centre at origin + (ix + 0.5, iy + 0.5) * resolution; a point outside the grid belongs to the nearest border cell; a
+cell is blocked iff its centre is within wall_halfwidth + inflate of a wall of params['wall_segments']; a straight move
+costs 12 and a diagonal one 17, so one unit is resolution / 12 -- and at the head of every solve(), rollout() and control
+step of closed_loop() it walks the descent from the robot's cell and fills a goal table of T + 1 rows with "carrots": row
+j is the centre of the first cell on the shortest path that is floor(lead / resolution * 12) + j * floor(pace / resolution
+* 12) units nearer to the goal than the start is, or the goal itself once the path ends.  Step t of a rollout is measured
+against row t + 1 exactly as against a goal track's row -- stage cost, goal test, freeze and terminal cost -- whatever
+track_offset is; the guide neither reads nor advances it.  2 * inflate^2 >= resolution^2 is required: then no move between
+two free neighbouring centres touches a wall, diagonal moves included.  Only the static shared walls are rasterised: discs,
+disc tracks, wall tracks, per-problem wall sets and the fleet's walls are not in the field -- the rollouts' hit tests deal
+with them locally.  A goal in a blocked cell (guide_status() 1) or a start with no way out (2: a sealed pocket) makes every
+row the goal; a start inside the inflated band walks out the cheapest way.  Keep lead above goal_tolerance: a rollout that
+catches its carrot freezes, as it does with any goal track.  The field is rebuilt only when the guide, the walls or a goal
+changed; guide_field(), guide_rows(), guide_status() fetch what the last refresh left, refresh_guide() refreshes alone (for
+drawing), goal_now stays the true goal and closed_loop()'s arrival test is against it.  guide_grid() makes origin and shape
+from the walls' bounding box.  Limits: 'guide' and 'goal_track' exclude each other (the guide owns the goal rows);
+params['xgoal'] is required; one grid for every problem of a batch, whose goals and starts are set_instances()'.
 """
 import collections
 import copy
@@ -249,6 +272,7 @@ def _footprint_rows(footprint):
 
 
 MAX_CLEARANCE_RINGS = 4  # (kCrowdRingsMax of the library)
+MAX_GUIDE_CELLS = 36864  # (kGuideCellsMax of the library: 192 x 192)
 
 
 def clearance_staircase(reach, peak, count):
@@ -338,6 +362,22 @@ def polyline_walls(points, closed=False):
     if closed and len(pts) >= 3:
         starts, ends = pts, np.roll(pts, -1, axis=0)
     return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.float32)
+
+
+def guide_grid(segments, resolution, margin=None):
+    """(origin (x, y), shape (ny, nx)) for params['guide']: the bounding box of the wall segments (W, 2, 2), grown by
+    `margin` on every side (default: two cells), cut into cells of `resolution`.  ValueError without walls, for a
+    resolution that is not positive, or for more than 36864 cells."""
+    seg = np.asarray(segments, dtype=np.float64).reshape(-1, 2)
+    resolution = float(resolution)
+    if not (len(seg) and np.isfinite(seg).all() and np.isfinite(resolution) and resolution > 0.0):
+        raise ValueError("guide_grid: at least one finite wall segment and a resolution > 0")
+    margin = 2.0 * resolution if margin is None else float(margin)
+    lo, hi = seg.min(axis=0) - margin, seg.max(axis=0) + margin
+    nx, ny = (max(1, int(np.ceil((hi[i] - lo[i]) / resolution))) for i in range(2))
+    if nx * ny > MAX_GUIDE_CELLS:
+        raise ValueError("guide_grid: {} x {} cells, more than {}: a coarser resolution".format(ny, nx, MAX_GUIDE_CELLS))
+    return (float(lo[0]), float(lo[1])), (ny, nx)
 
 
 def fleet_others(count):
@@ -466,6 +506,32 @@ def _read_goal(planner, p):
     return (tr,)
 
 
+def _read_guide(planner, p):
+    if "goal_track" in p:
+        raise ValueError("params hold both 'goal_track' and 'guide': the guide owns the goal rows, give one of the two")
+    if "xgoal" not in p:
+        raise ValueError("params['guide'] needs params['xgoal']: the field is measured from it")
+    g = p['guide']
+    shape = np.asarray(g['shape'])
+    if shape.shape != (2,) or shape.dtype.kind not in "iu" or (shape < 1).any() or int(shape[0]) * int(shape[1]) > MAX_GUIDE_CELLS:
+        raise ValueError("params['guide']['shape'] is (ny, nx), integers >= 1 with ny * nx <= {}, got {}".format(MAX_GUIDE_CELLS, g['shape']))
+    origin = np.asarray(g['origin'], dtype=np.float64).reshape(-1)
+    if origin.shape != (2,):
+        raise ValueError("params['guide']['origin'] is (x, y), got {}".format(g['origin']))
+    res = float(g['resolution'])
+    pace = float(g['pace']) if 'pace' in g else float(p['vrange'][1]) * float(p['dt'])
+    lead = float(g['lead']) if 'lead' in g else 2.0 * pace
+    inflate = float(g['inflate']) if 'inflate' in g else res
+    return _f32([origin[0], origin[1], res, inflate, lead, pace]), shape.astype(np.int32)
+
+
+def _pack_guide(planner, values, shape):
+    """Values that are not finite, a resolution <= 0, an inflation below resolution / sqrt(2), goal tracks held per problem:
+    the library refuses them (MppiError) and keeps what it had."""
+    x, y, res, inflate, lead, pace = (float(v) for v in values)
+    return 1, x, y, res, int(shape[1]), int(shape[0]), inflate, lead, pace
+
+
 def _pack_smoothing(planner, sm):
     """A wrong shape is refused here; a value outside [0, 1), the xoroshiro generator: the library refuses them (MppiError)
     and keeps what it had."""
@@ -576,18 +642,21 @@ def _pack_discs(planner, op, orad):
 #   offsets what a change does to the mirror's track offsets: _KEEP, _FETCH from the library (new rows, or rows that have
 #           gone: row 0 is "now", unless other tracks count the rows), _ZERO here (disc tracks: row 0 is "now")
 #   over    the kind this one lies over: that kind rests while this one's key is in params, and is stale after a change
+#   excludes  kinds the library refuses beside this one: what params no longer hold of them is cleared ahead of this
+#           kind's hand-over (the guide owns the goal rows: a guide that has gone makes way for the goal track)
 # Rings and disc samples exclude each other in the library: rings that have gone are cleared ahead of the samples'
 # hand-over, rings that are there are handed over behind it -- hence two rows.
-_Kind = collections.namedtuple("_Kind", "name key read pack setter clear offsets over")
+_Kind = collections.namedtuple("_Kind", "name key read pack setter clear offsets over excludes", defaults=((),))
 _KINDS = (
     _Kind("goal", "goal_track", _read_goal, lambda planner, tr: _pack_goal_tracks(planner, [tr], "params['goal_track']"),
-          "mppi_planner_set_goal_tracks", (0, 0, None), _FETCH, None),
+          "mppi_planner_set_goal_tracks", (0, 0, None), _FETCH, None, ("guide",)),
     _Kind("smoothing", "noise_smoothing", _read_one("noise_smoothing"), _pack_smoothing,
           "mppi_planner_set_noise_smoothing", (None,), _KEEP, None),
     _Kind("wall_tracks", "wall_tracks", _read_wall_tracks,
           lambda planner, tr, hw: _pack_wall_tracks([(tr, hw)], "params['wall_tracks']"),
           "mppi_planner_set_wall_tracks", (0, None, 0, None, None), _FETCH, None),
     _Kind("walls", "wall_segments", _read_walls, _pack_walls, "mppi_planner_set_walls", (None, None, 0), _KEEP, None),
+    _Kind("guide", "guide", _read_guide, _pack_guide, "mppi_planner_set_guide", (0, 0.0, 0.0, 1.0, 1, 1, 1.0, 0.0, 0.0), _KEEP, None),
     _Kind("footprint", "footprint", _read_footprint, _pack_rows(_footprint_rows),
           "mppi_planner_set_footprint", (None, 0), _KEEP, None),
     _Kind("rings", "clearance_rings", _read_one("clearance_rings"), None,
@@ -715,7 +784,11 @@ class MPPI_Numba(object):
             return
         key = [(v.dtype, v.shape, v.tobytes()) for v in values]  # (dtype.str would cost more than the rest of the key)
         if key != rec.key and rec.owner is not _BATCH and kind.pack is not None:
-            self._send(kind, kind.pack(self, *values), key, _PARAMS)
+            args = kind.pack(self, *values)
+            for other in (k for k in _KINDS if k.name in kind.excludes and k.clear is not None):
+                if self._held[other.name].key is not None and other.key not in p:
+                    self._send(other, None)
+            self._send(kind, args, key, _PARAMS)
 
     def _sync(self, p, kinds):
         for kind in kinds:
@@ -780,6 +853,53 @@ class MPPI_Numba(object):
         rows = np.minimum(self._track_offset.astype(np.int64), tracks.shape[1] - 1)
         now = tracks[np.arange(self.num_instances) % len(tracks), rows]
         return now[0].copy() if self.num_instances == 1 else now.copy()
+
+    # ------------------------------------------------------------------ a guide round the walls
+    def _guide_sent(self, what):
+        sent = self._held["guide"].sent
+        if sent is None:
+            raise ValueError("{}: no guide is held (params['guide'])".format(what))
+        return sent  # (on, x_min, y_min, res, nx, ny, inflate, lead, pace)
+
+    def refresh_guide(self):
+        """The refresh alone, as solve() makes it at its head: the field if the guide, the walls or a goal changed, then
+        the rows from the current start states.  For drawing and for tests; guide_field() / guide_rows() fetch the result."""
+        self.move_mppi_task_vars_to_device()
+        self._guide_sent("refresh_guide")
+        _lib.call("mppi_planner_guide_refresh", self._handle)
+
+    def guide_field(self):
+        """The field of the last build: (ny, nx) uint32 -- (B, ny, nx) for a batch --, 0xFFFFFFFF a blocked cell, 0xFFFFFFFE
+        a free cell without a path, else the length of the shortest path to the goal's cell in units of resolution / 12."""
+        sent = self._guide_sent("guide_field")
+        lead = () if self.num_instances == 1 else (self.num_instances,)
+        out = np.empty(lead + (sent[5], sent[4]), dtype=np.uint32)
+        _lib.call("mppi_planner_get_guide_field", self._handle, _lib.ptr(out, C.c_uint))
+        return out
+
+    def _guide_rows_and_status(self, what):
+        self._guide_sent(what)
+        B = self.num_instances
+        xy, status = np.empty((B, self.num_steps + 1, 2), dtype=np.float32), np.empty(B, dtype=np.int32)
+        _lib.call("mppi_planner_get_guide_rows", self._handle, _lib.ptr(xy, C.c_float), _lib.ptr(status, C.c_int))
+        return (xy[0], int(status[0])) if B == 1 else (xy, status)
+
+    def guide_rows(self):
+        """The rows of the last refresh: (T + 1, 2) float32 -- (B, T + 1, 2) for a batch.  Row 0 is the carrot now; step t
+        of a rollout is measured against row t + 1."""
+        return self._guide_rows_and_status("guide_rows")[0]
+
+    def guide_status(self):
+        """Of the last refresh, an int -- (B,) int32 for a batch: 0, or 1 (the goal's cell is blocked) or 2 (no way out of
+        the start's cell), where every row is the goal."""
+        return self._guide_rows_and_status("guide_status")[1]
+
+    @property
+    def guide_fields_built(self):
+        """How often the handle has built the field since it was created (0 while no guide is held)."""
+        on, nx, ny, built = C.c_int(0), C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+        _lib.call("mppi_planner_get_guide", self._handle, C.byref(on), C.byref(nx), C.byref(ny), C.byref(built))
+        return int(built.value)
 
     def _tracks_on(self):
         return self._held["tracks"].sent is not None or self._held["samples"].sent is not None
@@ -871,6 +991,8 @@ class MPPI_Numba(object):
         if walk_all:
             self._walk_all = True  # (until the walk has come to its end)
             self._sync_kind(p, _GOAL)
+            if "guide" in p:  # (its refusals -- no 'xgoal' among them -- ahead of the params struct, which reads 'xgoal')
+                _read_guide(self, p)
         for name, count in _TASK_VECTORS_GOAL_TRACK if moving_goal else _TASK_VECTORS:
             src, dst = p[name], getattr(c, name)
             for i in range(count):

@@ -309,7 +309,7 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
     own.trk_on = shared.trk_on = shared.inst_obs_on = false;
     const struct { bool held; BareboneHeld state; const char* what; } sets[] = {
         {s.tracks.on, tracks, "disc tracks"}, {s.own.on, own, "per-problem disc obstacles"},
-        {true, shared, "disc obstacles"}, {s.goal.on, now, "discs held with a goal track"}};
+        {true, shared, "disc obstacles"}, {s.goal.on || s.guide.on, now, "discs held with a goal track"}};
     for (const auto& set : sets) {
       const BareboneChoice c = barebone_choose(set.state);
       REQUIRE(!set.held || c.family != kBareboneRefused, MPPI_ERR_INVALID,
@@ -432,6 +432,7 @@ static int hand_over_walls(mppi_planner* p, WallSet& held, bool ranges, int coun
   held = std::move(fresh);
   drop_graphs(p);  // (the arrays, the counts, the row count and the kernel form are arguments of the captured launches)
   reset_track_offsets(p, kWallTracks, moved, count == 0);
+  if (!ranges) p->scene.guide.dirty = true;  // (the static walls have changed: the guide's field is rasterised from them)
   return MPPI_OK;
 }
 
@@ -494,6 +495,8 @@ extern "C" int mppi_planner_set_goal_tracks(mppi_planner* p, int count, int rows
   TRY(check_set_count(p, count, "track"));
   size_t n_xy = 0;
   if (count > 0) {
+    REQUIRE(!p->scene.guide.on, MPPI_ERR_INVALID,
+            "the handle holds a guide, which owns the goal rows: turn it off first (mppi_planner_set_guide with on 0)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a goal track has at least one row", rows);
     REQUIRE((long)count * (long)rows <= (1L << 28), MPPI_ERR_INVALID, "too many goal track rows (%d tracks x %d)", count, rows);
     REQUIRE(xy, MPPI_ERR_INVALID, "NULL xy");
@@ -790,3 +793,149 @@ extern "C" int mppi_planner_fleet_refresh(mppi_planner* p) {
   return drain_stream(p);
 }
 
+
+// ---- a guide round the walls (include/mppi_hip.h; guide_kernels.h, guide_grid.h) ---------------------------------------------
+// The hand-over: the parameters are checked, an unchanged hand-over does nothing, a change drains the stream, builds the new
+// arrays before the old ones are freed, takes a new generation, drops the captured graphs and marks the field dirty.  Nothing
+// is launched here: the field is built on the planner's stream at the head of the next call that starts iterations.
+extern "C" int mppi_planner_set_guide(mppi_planner* p, int on, float x_min, float y_min, float res, int nx, int ny, float inflate,
+                                      float lead, float pace) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "the guide belongs to the barebone mode (mode %d)", p->cfg.mode);
+  GuideArrays& held = p->scene.guide;
+  if (!on) {
+    if (!held.on) return MPPI_OK;
+    HIP_TRY(hipSetDevice(p->cfg.device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    GuideArrays off;
+    off.fields_built = held.fields_built;
+    held.release();
+    held = off;
+    drop_graphs(p);  // (the rows and the kernel form are arguments of the captured launches)
+    return MPPI_OK;
+  }
+  const int T = p->cfg.num_steps;
+  REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "the guide drives an unsharded handle (world_size %d)", p->cfg.world_size);
+  REQUIRE(!p->scene.goal.on, MPPI_ERR_INVALID,
+          "the handle holds goal tracks; the guide owns the goal rows: clear them first (mppi_planner_set_goal_tracks with count 0)");
+  REQUIRE(std::isfinite(x_min) && std::isfinite(y_min) && std::isfinite(res) && std::isfinite(inflate) && std::isfinite(lead) &&
+              std::isfinite(pace), MPPI_ERR_INVALID, "guide: a value is not finite");
+  REQUIRE(res > 0.0f, MPPI_ERR_INVALID, "guide: resolution %g must be > 0", (double)res);
+  REQUIRE(nx >= 1 && ny >= 1 && (long)nx * (long)ny <= (long)kGuideCellsMax, MPPI_ERR_INVALID,
+          "guide: a grid of %d x %d cells: both at least 1 and %d cells (192 x 192) at the most", ny, nx, kGuideCellsMax);
+  REQUIRE(inflate >= 0.0f && 2.0 * (double)inflate * (double)inflate >= (double)res * (double)res, MPPI_ERR_INVALID,
+          "guide: inflate %g is below resolution / sqrt(2) = %g: a diagonal move between free cells could touch a wall", (double)inflate,
+          (double)res / std::sqrt(2.0));
+  REQUIRE(lead >= 0.0f && pace >= 0.0f, MPPI_ERR_INVALID, "guide: lead %g and pace %g must be >= 0", (double)lead, (double)pace);
+  const double lead_u = guide_units(lead, res), pace_u = guide_units(pace, res);
+  REQUIRE(lead_u + (double)T * pace_u < 2147483648.0, MPPI_ERR_INVALID,
+          "guide: lead %g and pace %g over %d steps at resolution %g: more than 2^31 units of resolution / 12", (double)lead, (double)pace, T,
+          (double)res);
+  if (held.on && x_min == held.x_min && y_min == held.y_min && res == held.res && nx == held.nx && ny == held.ny &&
+      inflate == held.inflate && lead == held.lead && pace == held.pace)
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  GuideArrays fresh;
+  const size_t cells = (size_t)nx * (size_t)ny, B = (size_t)p->B, rows = B * (size_t)(T + 1);
+  TRY(staged([&]() -> int {
+    TRY(dev_alloc(&fresh.field, B * cells));
+    TRY(dev_alloc(&fresh.moves, B * cells));
+    TRY(dev_alloc(&fresh.rows, rows));
+    TRY(dev_alloc(&fresh.status, B));
+    HIP_TRY(hipMemset(fresh.rows, 0, sizeof(float2) * rows));
+    HIP_TRY(hipMemset(fresh.status, 0, sizeof(int) * B));
+    return MPPI_OK;
+  }, fresh.field, fresh.moves, fresh.rows, fresh.status));
+  fresh.on = true;
+  fresh.x_min = x_min; fresh.y_min = y_min; fresh.res = res; fresh.inflate = inflate; fresh.lead = lead; fresh.pace = pace;
+  fresh.nx = nx; fresh.ny = ny;
+  fresh.lead_u = (int)lead_u; fresh.pace_u = (int)pace_u;
+  fresh.gen = next_generation();
+  fresh.dirty = true;
+  fresh.fields_built = held.fields_built;
+  held.release();
+  held = std::move(fresh);
+  drop_graphs(p);  // (the rows, their count and the kernel form are arguments of the captured launches)
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_guide(mppi_planner* p, int* on, int* nx, int* ny, unsigned long long* fields_built) {
+  REQUIRE(p && on && nx && ny && fields_built, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "the guide belongs to the barebone mode (mode %d)", p->cfg.mode);
+  const GuideArrays& g = p->scene.guide;
+  *on = g.on ? 1 : 0;
+  *nx = g.nx;
+  *ny = g.ny;
+  *fields_built = g.fields_built;
+  return MPPI_OK;
+}
+
+// The guide's refresh, on the planner's stream at the head of every call that starts iterations, behind the fleet's: the
+// field when something it depends on has changed -- the guide or the static walls (dirty), or a goal, seen here against the
+// goals of the last build --, then the rows from the start states as they are on the device.  done: closed_loop's
+// per-problem flags (a parked problem's rows are the goal), else nullptr.  The arrays stay where they are: nothing a
+// captured graph holds changes.
+static int guide_refresh(mppi_planner* p, const int* done) {
+  GuideArrays& g = p->scene.guide;
+  if (!g.on) return MPPI_OK;
+  REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
+  REQUIRE(p->B == 1 || p->inst_set, MPPI_ERR_STATE, "num_instances = %d: call mppi_planner_set_instances before solving", p->B);
+  TRY(upload_instances(p));
+  const DevParams d = make_dev_params(p);
+  const int B = p->B, cells = g.nx * g.ny;
+  auto goal_of = [&](int b, int k) {  // the goals as the launches will see them
+    return p->inst_set ? (k == 0 ? p->inst_host[(size_t)b].xg : p->inst_host[(size_t)b].yg) : p->params.xgoal[k];
+  };
+  bool moved = g.goals_built.size() != (size_t)2 * B;  // (compared as numbers: -0.0 is 0.0, and no allocation on this path)
+  for (int b = 0; b < B && !moved; ++b)
+    moved = g.goals_built[(size_t)2 * b] != goal_of(b, 0) || g.goals_built[(size_t)2 * b + 1] != goal_of(b, 1);
+  const GuideGrid grid{g.x_min, g.y_min, g.res, g.inflate, g.nx, g.ny, g.lead_u, g.pace_u};
+  if (g.dirty || moved) {
+    const WallSet& w = p->scene.walls;
+    const size_t lds = sizeof(uint32_t) * (size_t)cells;
+    if (lds + kGuideFieldStaticLds > 64 * 1024)  // (from about 124 x 124 cells on: the wall tile's static LDS counts too)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_guide_field), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_guide_field, dim3(B), dim3(kGuideFieldThreads), lds, p->stream, d, grid, w.on ? w.seg_rows : nullptr,
+                       w.on ? w.hw : nullptr, w.on ? w.max : 0, g.field, g.moves);
+    HIP_TRY(hipGetLastError());
+    g.goals_built.resize((size_t)2 * B);
+    for (int b = 0; b < B; ++b) {
+      g.goals_built[(size_t)2 * b] = goal_of(b, 0);
+      g.goals_built[(size_t)2 * b + 1] = goal_of(b, 1);
+    }
+    g.dirty = false;
+    ++g.fields_built;
+  }
+  hipLaunchKernelGGL(k_guide_rows, dim3(B), dim3(kGuideRowsThreads), (size_t)cells, p->stream, d, grid, g.field, g.moves, done, g.rows,
+                     g.status);
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_guide_refresh(mppi_planner* p) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->scene.guide.on, MPPI_ERR_STATE, "the handle holds no guide (mppi_planner_set_guide)");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(guide_refresh(p, nullptr));
+  return drain_stream(p);
+}
+
+// out: [B][ny][nx], the field of the last build
+extern "C" int mppi_planner_get_guide_field(mppi_planner* p, unsigned* out) {
+  REQUIRE(p && out, MPPI_ERR_INVALID, "NULL argument");
+  const GuideArrays& g = p->scene.guide;
+  REQUIRE(g.on, MPPI_ERR_STATE, "the handle holds no guide (mppi_planner_set_guide)");
+  REQUIRE(!g.goals_built.empty(), MPPI_ERR_STATE, "the guide's field has not been built yet (mppi_planner_guide_refresh, or a solve)");
+  return copy_out(p, out, g.field, sizeof(uint32_t) * (size_t)p->B * (size_t)g.nx * (size_t)g.ny);
+}
+
+// xy: [B][T + 1][2]; status: [B] -- of the last refresh
+extern "C" int mppi_planner_get_guide_rows(mppi_planner* p, float* xy, int* status) {
+  REQUIRE(p && xy && status, MPPI_ERR_INVALID, "NULL argument");
+  const GuideArrays& g = p->scene.guide;
+  REQUIRE(g.on, MPPI_ERR_STATE, "the handle holds no guide (mppi_planner_set_guide)");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipMemcpyAsync(status, g.status, sizeof(int) * (size_t)p->B, hipMemcpyDeviceToHost, p->stream));
+  return copy_out(p, xy, g.rows, sizeof(float2) * (size_t)p->B * (size_t)(p->cfg.num_steps + 1));
+}

@@ -23,7 +23,7 @@ static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
   crowd_shape(p, &W, &C);
   const BareboneScene& s = p->scene;
   return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, s.crowd, s.shared.max, s.own.on, s.own.max,
-                      s.tracks.on, s.tracks.max, s.tracks.rows, s.walls.max, s.wall_tracks.on, s.fleet.on(), s.goal.on,
+                      s.tracks.on, s.tracks.max, s.tracks.rows, s.walls.max, s.wall_tracks.on, s.fleet.on(), s.goal.on || s.guide.on,
                       s.samples.on ? s.samples.count : 0, s.samples.discs, s.samples.rows, W, s.footprint.count, s.rings.count};
 }
 
@@ -39,11 +39,20 @@ static const float* barebone_disc_rad(const mppi_planner* p, const BareboneChoic
   return c.discs == kDiscsSamples ? p->scene.samples.r : barebone_disc_set(p, c).r;
 }
 
-// The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.
+// The goal tracks as a launch takes them: a batched launch reads problem b's rows at b * rows, or everybody's at 0.  While
+// the guide is on (mppi_planner_set_guide) the rows are its own: T + 1 per problem, counted from "now" (relative = 1).
+static int goal_rows_held(const mppi_planner* p) { return p->scene.guide.on ? p->cfg.num_steps + 1 : p->scene.goal.rows; }
 template <bool BATCHED>
 static GoalRows goal_rows_arg(const mppi_planner* p) {
+  const int rows = goal_rows_held(p);
+  if (p->scene.guide.on) return GoalRows{p->scene.guide.rows, rows, BATCHED ? rows : 0, 1};
   const GoalTracks& g = p->scene.goal;
-  return GoalRows{g.xy, g.rows, BATCHED && g.count > 1 ? g.rows : 0};
+  return GoalRows{g.xy, rows, BATCHED && g.count > 1 ? rows : 0, 0};
+}
+// ... and what mppi_planner_describe_last_rollout says of them
+static std::string goal_rows_text(const mppi_planner* p) {
+  const GuideArrays& g = p->scene.guide;
+  return " goal_rows=" + std::to_string(goal_rows_held(p)) + (g.on ? " guide=" + std::to_string(g.nx) + "x" + std::to_string(g.ny) : std::string());
 }
 
 // The default family.  Static discs: <EXACT, ROT, KD, BATCHED>; disc tracks: the TRACKS forms, a row of disc slots per step;
@@ -80,7 +89,7 @@ static int launch_barebone_default(mppi_planner* p, DevParams d, const BareboneC
                        (tracks ? " tracks=" + std::to_string(p->scene.tracks.rows) : std::string()) +
                        (!c.track_form && c.discs == kDiscsOwn ? " own_discs=1" : "") +
                        (BATCHED ? " problems=" + std::to_string(p->B) : std::string()) +
-                       (c.goal_form ? " goal_rows=" + std::to_string(p->scene.goal.rows) : std::string());
+                       (c.goal_form ? goal_rows_text(p) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }
@@ -244,7 +253,7 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
                     (c.walls == 2 && !fleet ? " walls=" + std::to_string(sc.wall_tracks.max) + " wall_rows=" + std::to_string(sc.wall_tracks.rows) : std::string()) +
                     (fleet ? " walls=" + std::to_string(sc.fleet.slots) + " wall_rows=" + std::to_string(p->cfg.num_steps) +
                                  " fleet=" + std::to_string(p->B) : std::string()) +
-                    (c.goal_form ? " goal_rows=" + std::to_string(p->scene.goal.rows) : std::string()) +
+                    (c.goal_form ? goal_rows_text(p) : std::string()) +
                     (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
                                    : std::string()) +
                     (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string()) +

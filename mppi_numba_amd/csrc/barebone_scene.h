@@ -94,6 +94,28 @@ struct GoalTracks {
   void release() { dev_free(xy); }
 };
 
+// A guide round the walls (mppi_planner_set_guide; guide_kernels.h): per problem a shortest-path field from its goal over a
+// grid whose cells the shared static walls block, and T + 1 goal rows on the shortest path from its start, which the
+// launches take as GoalRows (relative: counted from "now").  field: [B][ny * nx]; moves: [B][ny * nx], the move a descent
+// takes from every cell; rows: [B][T + 1]; status: [B].  The parameters are as handed over; lead_u, pace_u: lead and pace in
+// the field's units.  dirty: the field is rebuilt at the head of the next call that starts iterations -- set by a change of
+// the guide or of the static walls; a changed goal is seen there, against goals_built, the goals of the last build.
+// gen: renewed when the guide is set -- a refresh writes into the same arrays and changes nothing a captured launch holds.
+struct GuideArrays {
+  bool on = false;
+  float x_min = 0.0f, y_min = 0.0f, res = 1.0f, inflate = 0.0f, lead = 0.0f, pace = 0.0f;
+  int nx = 0, ny = 0, lead_u = 0, pace_u = 0;
+  uint32_t* field = nullptr;
+  uint8_t* moves = nullptr;
+  float2* rows = nullptr;
+  int* status = nullptr;
+  uint64_t gen = 0;
+  bool dirty = false;
+  unsigned long long fields_built = 0;
+  std::vector<float> goals_built;
+  void release() { dev_free(field); dev_free(moves); dev_free(rows); dev_free(status); }
+};
+
 // Rows that the launches take by value (crowd mode only): no device array, `count` rows of Width floats as handed over.
 template <int MaxRows, int Width>
 struct ValueRows {
@@ -124,6 +146,8 @@ struct BareboneScene {
   std::vector<float> fleet_hw_host;  // what was handed over: [B][B - 1]; a body fleet: what was made of it, [B][(B - 1) * Fp]
   double fleet_margin = 0.0;
   GoalTracks goal;
+  // the guide owns the goal rows while it is on: goal tracks and the guide exclude each other
+  GuideArrays guide;
   // a body footprint (mppi_planner_set_footprint; not beside the fleet, whose body fleet holds its own here): discs
   // (ox, oy, rho) in the robot frame, one footprint for every problem -- CrowdFootprint takes the rows
   ValueRows<kCrowdFootprintMax, 3> footprint;
@@ -132,6 +156,6 @@ struct BareboneScene {
   ValueRows<kCrowdRingsMax, 2> rings;
   void release() {
     shared.release(); own.release(); tracks.release(); samples.release();
-    walls.release(); wall_tracks.release(); fleet.release(); goal.release();
+    walls.release(); wall_tracks.release(); fleet.release(); goal.release(); guide.release();
   }
 };

@@ -1081,7 +1081,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen, guide_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
     float smooth_beta[2];
   } sig;
@@ -1106,6 +1106,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.smp_gen = sc.samples.gen;  // (the disc samples')
   sig.fp_gen = sc.footprint.gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
   sig.ring_gen = sc.rings.gen;  // (the clearance rings' likewise)
+  sig.guide_gen = sc.guide.gen;  // (the guide's: renewed when it is set, not when its field or its rows are refreshed)
   sig.smooth_beta[0] = p->smooth_beta[0]; sig.smooth_beta[1] = p->smooth_beta[1];  // (the noise smoothing's coefficients: by value in the generator's argument)
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;

@@ -23,6 +23,7 @@
 #include "rollout_kernels.h"
 #include "rollout_crowd_kernel.h"
 #include "fleet_kernels.h"
+#include "guide_kernels.h"
 #include "rollout_scan_kernel.h"
 #include "rollout_scan_exact_kernel.h"
 #include "map_kernels.h"
@@ -545,7 +546,20 @@ static int planner_alloc(mppi_planner* p) {
   const mppi_planner_cfg& c = p->cfg;
   const size_t N = (size_t)p->n_local, T = (size_t)c.num_steps;
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&p->noise_stream, hipStreamNonBlocking));
+  // The second stream gets a priority of its own.  The runtime maps the streams of one priority onto a pool of a few
+  // hardware queues (GPU_MAX_HW_QUEUES; 4 by default), a stream takes its queue at its first use -- the queue of the pool
+  // that the fewest live streams refer to -- and two streams on one queue run one after the other.  Which queue a stream
+  // gets therefore depends on every stream the process has created and destroyed before: after enough handle churn the
+  // second stream landed on the queue of its own planner's stream, the launch that waits for the generator
+  // (DevParams::noise_flag) sat in front of it in that queue, and the bounded wait gave up (check_flag_fault:
+  // MPPI_ERR_BUSY).  Streams of another priority have a pool of their own (mppi_debug_occupy_cus relies on the same), so
+  // the generator never queues behind the launch that waits for it; it is the higher priority because that launch is
+  // waiting for it.
+  {
+    int least = 0, greatest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_TRY(hipStreamCreateWithPriority(&p->noise_stream, hipStreamNonBlocking, greatest));
+  }
   HIP_TRY(hipEventCreateWithFlags(&p->ev_buf_free, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&p->ev_noise_ready, hipEventDisableTiming));
   TRY(dev_alloc(&p->noise_flag_dev, (size_t)1));
@@ -835,6 +849,7 @@ extern "C" int mppi_planner_iterate_async(mppi_planner* p, mppi_tdm* lin, mppi_t
   REQUIRE(iterations >= 0, MPPI_ERR_INVALID, "iterations < 0");
   HIP_TRY(hipSetDevice(p->cfg.device));
   TRY(fleet_refresh(p, nullptr));
+  TRY(guide_refresh(p, nullptr));
   return run_iterations(p, lin, ang, iterations);
 }
 
@@ -995,6 +1010,7 @@ extern "C" int mppi_planner_solve(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang,
   TRY(sample_for_solve(p, lin, ang));
   p->mirror_done = false;
   TRY(fleet_refresh(p, nullptr));
+  TRY(guide_refresh(p, nullptr));
   TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false, /*mirror_last=*/true));
   const size_t u_bytes = sizeof(float2) * (size_t)p->B * (size_t)p->cfg.num_steps;
   // with at least one iteration the last update kernel has written the host-mapped mirror (a
@@ -1200,7 +1216,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.xlo = (double)p->params.xlo; L.ylo = (double)p->params.ylo; L.res = (double)plan.res;
     const BareboneScene& sc = p->scene;
     L.advance_tracks = sc.tracks.on || sc.samples.on || (sc.wall_tracks.on && sc.wall_tracks.rows > 1) || (sc.goal.on && sc.goal.rows > 1) ? 1 : 0;
-    L.goal_xy = sc.goal.on ? sc.goal.xy : nullptr;
+    L.goal_xy = sc.goal.on ? sc.goal.xy : nullptr;  // (the guide's rows are carrots, not the goal: arrival is tested against the true goal)
     L.goal_rows = sc.goal.rows;
     L.goal_stride = sc.goal.count > 1 ? sc.goal.rows : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
@@ -1222,6 +1238,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     TRY(sample_for_solve(p, lin, ang));
     if (step == 0) TRY(plan_loop());  // (needs the sampled grids packed: after the first draw)
     TRY(fleet_refresh(p, p->loop_done));  // (fleet mode: the others' plans as the last control step left them)
+    TRY(guide_refresh(p, p->loop_done));  // (the guide: the carrots from where the last control step left every robot)
     TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false));
     hipLaunchKernelGGL(k_world_step, dim3(B), dim3(256), sizeof(float2) * (size_t)T, p->stream, G, L, p->inst_dev, p->u,
                        T, step);
@@ -1382,6 +1399,7 @@ extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* an
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   HIP_TRY(hipSetDevice(p->cfg.device));
   TRY(fleet_refresh(p, nullptr));
+  TRY(guide_refresh(p, nullptr));
   DevParams d;
   TRY(prepare_launch(p, lin, ang, &d));
   TRY(launch_rollout(p, d));

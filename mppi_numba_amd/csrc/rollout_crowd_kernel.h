@@ -573,7 +573,9 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   [[maybe_unused]] int glast = 0, gnow = 0;
   if constexpr (GOALS) {
     glast = G.rows - 1;
-    gnow = min(max(P.track_off, 0), glast);
+    // (relative is 0 or 1: the mask keeps the offset or clears it -- G.relative ? 0 : min(max(P.track_off, 0), glast), in
+    // the form that leaves the scratch of every goal form what it was: profiles/HISTORY.md, "Barebone guide")
+    gnow = min(max(P.track_off, 0) & (G.relative - 1), glast);
   }
 
   for (int ph = 0; ph < n_chunks + 2; ++ph) {

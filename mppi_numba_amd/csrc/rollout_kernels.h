@@ -1528,12 +1528,15 @@ __device__ __forceinline__ double barebone_goal_d2(float2 g, float nx, float ny)
 }
 
 // The goal tracks of a launch (mppi_planner_set_goal_tracks): xy[b * stride + j], row j of problem b's track; stride is
-// `rows` for one track per problem and 0 for a track every problem shares.
+// `rows` for one track per problem and 0 for a track every problem shares.  relative != 0 (the guide,
+// mppi_planner_set_guide): the rows are rebuilt ahead of every call and always counted from "now" -- step t meets row
+// min(t + 1, rows - 1) whatever the problem's track offset is (CrowdWallTracks::relative likewise).
 struct GoalRows {
   const float2* xy;
   int rows, stride;
+  int relative;
 };
-__device__ __forceinline__ GoalRows goal_rows_of() { return GoalRows{nullptr, 1, 0}; }
+__device__ __forceinline__ GoalRows goal_rows_of() { return GoalRows{nullptr, 1, 0, 0}; }
 template <typename First, typename... Rest>
 __device__ __forceinline__ GoalRows goal_rows_of(const First& first, const Rest&... rest) {
   if constexpr (std::is_same_v<First, GoalRows>) return first;
@@ -1590,7 +1593,7 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
   // GOALS: [T] float2 behind the disc rows (the host sizes a row at one slot at the least), row t what step t measures against
   [[maybe_unused]] float2* goals = reinterpret_cast<float2*>(discs + P.n_steps * max(slots, 1));
   if constexpr (GOALS) {
-    const int glast = G.rows - 1, gnow = min(max(P.track_off, 0), glast);  // (the same raw offset, the goal track's own clamp)
+    const int glast = G.rows - 1, gnow = G.relative ? 0 : min(max(P.track_off, 0), glast);  // (the same raw offset, the goal track's own clamp)
     for (int t = threadIdx.x; t < P.n_steps; t += 64) goals[t] = G.xy[min(gnow + t + 1, glast)];
   }
   stage_control_ratios(P, u, uos);  // (ends with a barrier)
