@@ -556,6 +556,42 @@ int mppi_planner_get_noise_smoothing(mppi_planner* p, float beta[2]);
  * reading and advance nothing.  MPPI_RNG_PHILOX only. */
 int mppi_planner_time_noise(mppi_planner* p, int reps, float* us_noise);
 
+/* MPPI_MODE_BAREBONE: acceleration limits on the sampled controls.  accel = (a_v, a_w) float32, m/s^2 and rad/s^2, each
+ * > 0; +inf leaves a component as drawn.  While limits are held, every noise block an iteration is about to consume is
+ * passed through one more kernel, k_noise_limit, in place, between "the block is there" and the rollout launch.  Per
+ * rollout and component, with u[t] the control sequence the rollout launch reads, e[t] the block as generated (white,
+ * or filtered by mppi_planner_set_noise_smoothing), (lo, hi) the component's range of mppi_params, a the problem's
+ * applied control (below), all in float32, every operation rounded once (csrc/control_limits.h):
+ *     d     = fmul_rn(accel_c, params.dt)                                   (host, at the launch)
+ *     p     = clip(a, lo, hi)
+ *     c     = clip(fadd_rn(u[t], e[t]), lo, hi)                             t = 0 .. T-1
+ *     p     = fminf(fmaxf(c, fsub_rn(p, d)), fadd_rn(p, d))
+ *     e'[t] = fsub_rn(p, u[t])
+ * and the block holds e' -- the effective noise -- from then on: the rollouts, the control-cost term, the update and
+ * mppi_planner_get_noise all see it.  The set "inside the box, no step larger than d, counted from the anchor" is convex
+ * and every p sequence lies in it, so the update's weighted mean u + sum(w e') / sum(w) lies in it too, whatever u was
+ * before.  What the rollouts re-form as clip(fl(u + e')) differs from p by rounding only: consecutive applied controls
+ * differ by at most d + 2^-20 * (max(|lo|, |hi|) + d).  The recurrence restarts with every block from the anchor.  The
+ * pass runs on the planner's stream behind the previous update (it needs the u that update left), so a block generated
+ * ahead on the second stream is waited for first and the generator keeps producing unlimited blocks.
+ * mppi_planner_sample_noise limits what it draws; mppi_planner_set_noise stores what it is given;
+ * mppi_planner_limit_noise runs the pass alone over the block the handle holds (MPPI_ERR_STATE without limits).  One
+ * pair for every problem of a batched handle; symmetric (no separate braking bound); first differences only.
+ * NULL clears.  The steps and the box travel by value in the launch: a change drains the stream and drops the captured
+ * graphs; equal values again cost a comparison.  MPPI_ERR_INVALID, the handle keeping what it had: a value that is NaN
+ * or <= 0, a handle that is not in barebone mode. */
+int mppi_planner_set_control_limits(mppi_planner* p, const float accel[2]);
+/* *held = 1 and accel = the pair held, or *held = 0 and accel untouched */
+int mppi_planner_get_control_limits(mppi_planner* p, float accel[2], int* held);
+int mppi_planner_limit_noise(mppi_planner* p);
+/* MPPI_MODE_BAREBONE: the control in force when the next plan starts -- the anchor the limits count from.  u (count, 2)
+ * float32 rows (v, w), finite; count = 1 (every problem) or B.  A device array of B rows, zero at creation, stored
+ * whether or not limits are held and read by the pass at its launch (at replay, for a captured one): a new anchor drops
+ * no graph.  mppi_planner_closed_loop stores the u0 it applies into it at every control step while limits are held (a
+ * problem that has arrived is left alone).  mppi_planner_get_applied_control: u (B, 2). */
+int mppi_planner_set_applied_control(mppi_planner* p, int count, const float* u);
+int mppi_planner_get_applied_control(mppi_planner* p, float* u);
+
 /* MPPI_MODE_BAREBONE, a batched handle (B >= 2) in crowd mode: a body fleet -- fleet mode for
  * robots that are not discs.  Every robot of the batch is the same body of n_discs discs (1 .. 8),
  * discs (n_discs, 3) float32 with the rows and the rules of mppi_planner_set_footprint; count = B

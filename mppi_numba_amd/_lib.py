@@ -132,6 +132,11 @@ SIGNATURES = {
     "mppi_planner_set_noise_smoothing": [_vp, _f32p],
     "mppi_planner_get_noise_smoothing": [_vp, _f32p],
     "mppi_planner_time_noise": [_vp, C.c_int, _f32p],
+    "mppi_planner_set_control_limits": [_vp, _f32p],
+    "mppi_planner_get_control_limits": [_vp, _f32p, C.POINTER(C.c_int)],
+    "mppi_planner_limit_noise": [_vp],
+    "mppi_planner_set_applied_control": [_vp, C.c_int, _f32p],
+    "mppi_planner_get_applied_control": [_vp, _f32p],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

@@ -152,6 +152,33 @@ changed; guide_field(), guide_rows(), guide_status() fetch what the last refresh
 drawing), goal_now stays the true goal and closed_loop()'s arrival test is against it.  guide_grid() makes origin and shape
 from the walls' bounding box.  Limits: 'guide' and 'goal_track' exclude each other (the guide owns the goal rows);
 params['xgoal'] is required; one grid for every problem of a batch, whose goals and starts are set_instances()'.
+
+Acceleration limits on the sampled controls: params['accel_limits'], a scalar (both components) or (2,) = (a_v, a_w) in
+m/s^2 and rad/s^2, rounded once to float32, each > 0; np.inf leaves a component as drawn.  The notebook's rollouts may
+command vrange[1] in one step and vrange[0] in the next, and so may the sequence solve() returns: no base follows that, and
+the first control handed out may be out of reach of the velocity the robot has now.  With the key every block an iteration
+is about to consume passes through one more kernel, in place: per rollout and component, with u the sequence the rollouts
+read, e the block as generated (white or smoothed), (lo, hi) the component's range and a the applied control, in float32,
+every operation rounded once:
+  d     = float32(float32(accel) * float32(dt))
+  p     = clip(a, lo, hi)
+  c     = clip(float32(u[t] + e[n, t]), lo, hi)                                 t = 0 .. T-1
+  p     = min(max(c, float32(p - d)), float32(p + d))
+  e'[n, t] = float32(p - u[t])
+and the block holds e', the effective noise: the rollouts simulate feasible sequences, the control-cost term weighs the
+deviation actually applied, and the update u + sum(w e') / sum(w) is a convex combination of feasible sequences -- the set
+"inside the box, no step larger than d, counted from the anchor" is convex -- and so feasible itself, whatever u was.  What
+the rollouts re-form as clip(u + e') differs from p by rounding only: consecutive controls differ by at most d + 2^-20 *
+(max(|lo|, |hi|) + d).  The anchor is applied_control, zero at first: set_applied_control(u) sets it -- (2,), or (B, 2) for a
+batch --, shift_and_update(x, u_cur, k) sets it to u_cur[k - 1] while the key is in params (a user with odometry calls
+set_applied_control(measured) after it), closed_loop() stores every u0 it applies.  The recurrence restarts with every
+block from the anchor.  Composes with both kernel families, every crowd form, batches, fleets (whose plans are noise-free
+rollouts of u, feasible after the first update), the guide, tracks, disc samples, rings, the footprint, 'noise_smoothing'
+(limited after filtering), both generators, math="fast", graph replay (a new anchor needs no new capture) and closed_loop().
+sample_noise() limits what it draws; set_noise() stores what it is given and limit_noise() runs the pass alone over it.
+Without the key every bit and every call is as before.  Limits: one pair for every problem of a batch; symmetric (no
+separate braking bound); first differences only (no jerk bound); the visualisation rollouts read the block as it stands;
+the control-cost term weighs e'.  The map-mode classes do not read the key.
 """
 import collections
 import copy
@@ -540,6 +567,13 @@ def _pack_smoothing(planner, sm):
     return (np.ascontiguousarray(np.broadcast_to(_f32(sm), (2,))),)
 
 
+def _pack_limits(planner, acc):
+    """A wrong shape is refused here; a value that is NaN or <= 0: the library refuses it (MppiError) and keeps what it had."""
+    if acc.shape not in ((), (2,)):
+        raise ValueError("params['accel_limits'] is a scalar or has shape (2,), got {}".format(acc.shape))
+    return (np.ascontiguousarray(np.broadcast_to(_f32(acc), (2,))),)
+
+
 def _read_wall_tracks(planner, p):
     if planner._held["fleet"].sent is not None or planner._held["fleet_bodies"].sent is not None:
         raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
@@ -652,6 +686,8 @@ _KINDS = (
           "mppi_planner_set_goal_tracks", (0, 0, None), _FETCH, None, ("guide",)),
     _Kind("smoothing", "noise_smoothing", _read_one("noise_smoothing"), _pack_smoothing,
           "mppi_planner_set_noise_smoothing", (None,), _KEEP, None),
+    _Kind("limits", "accel_limits", _read_one("accel_limits"), _pack_limits,
+          "mppi_planner_set_control_limits", (None,), _KEEP, None),
     _Kind("wall_tracks", "wall_tracks", _read_wall_tracks,
           lambda planner, tr, hw: _pack_wall_tracks([(tr, hw)], "params['wall_tracks']"),
           "mppi_planner_set_wall_tracks", (0, None, 0, None, None), _FETCH, None),
@@ -832,6 +868,43 @@ class MPPI_Numba(object):
         beta = np.zeros(2, dtype=np.float32)
         _lib.call("mppi_planner_get_noise_smoothing", self._handle, _lib.ptr(beta, C.c_float))
         return beta if beta.any() else None
+
+    # ------------------------------------------------------------------ acceleration limits
+    @property
+    def accel_limits(self):
+        """The acceleration limits the library holds: (2,) float32 (a_v, a_w), or None."""
+        acc, held = np.zeros(2, dtype=np.float32), C.c_int(0)
+        _lib.call("mppi_planner_get_control_limits", self._handle, _lib.ptr(acc, C.c_float), C.byref(held))
+        return acc if held.value else None
+
+    @property
+    def applied_control(self):
+        """The control in force when the next plan starts -- the anchor the limits count from: (2,) float32, (B, 2) for a
+        batch.  Zero at first; set_applied_control(), shift_and_update() while 'accel_limits' is in params, and
+        closed_loop() set it."""
+        rows = np.zeros((self.num_instances, 2), dtype=np.float32)
+        _lib.call("mppi_planner_get_applied_control", self._handle, _lib.ptr(rows, C.c_float))
+        return rows[0] if self.num_instances == 1 else rows
+
+    def set_applied_control(self, u):
+        """(2,) = (v, w): every problem's; (B, 2): one per problem.  Finite (else MppiError)."""
+        rows = np.asarray(u)
+        if rows.shape not in ((2,), (1, 2), (self.num_instances, 2)):
+            raise ValueError("an applied control has shape (2,) or ({}, 2), got {}".format(self.num_instances, rows.shape))
+        rows = np.ascontiguousarray(_f32(rows).reshape(-1, 2))
+        _lib.call("mppi_planner_set_applied_control", self._handle, len(rows), _lib.ptr(rows, C.c_float))
+
+    def limit_noise(self):
+        """The pass alone, over the block the handle holds (stage level: set_noise() stores what it is given); MppiError
+        while no limits are held."""
+        self.move_mppi_task_vars_to_device()
+        _lib.call("mppi_planner_limit_noise", self._handle)
+
+    def _anchor_after_shift(self, u_cur, num_shifts):
+        # the control applied last becomes the anchor of the next plan -- only while the key is there
+        if "accel_limits" in self.params:
+            u = np.asarray(u_cur, dtype=np.float32).reshape(self.num_instances, self.num_steps, 2)
+            self.set_applied_control(u[:, int(num_shifts) - 1])
 
     # ------------------------------------------------------------------ a goal that moves
     def _goal_track_on(self):
@@ -1037,6 +1110,7 @@ class MPPI_Numba(object):
     def shift_and_update(self, new_x0, u_cur, num_shifts=1):
         self.params["x0"] = new_x0.copy()
         self.shift_optimal_control_sequence(u_cur, num_shifts)
+        self._anchor_after_shift(u_cur, num_shifts)
         self._advance_tracks(num_shifts)
 
     def _advance_tracks(self, num_shifts):
@@ -1394,11 +1468,14 @@ class MPPI_Batch(MPPI_Numba):
         self.set_instances(new_x0s)
         self.params["x0"] = np.asarray(new_x0s[0]).copy()
         self.shift_optimal_control_sequence(u_cur, num_shifts)
+        self._anchor_after_shift(u_cur, num_shifts)
         self._advance_tracks(num_shifts)
 
     def shift_and_update_on_device(self, new_x0s, num_shifts=1):
         self.set_instances(new_x0s)
         self.params["x0"] = np.asarray(new_x0s[0]).copy()
+        if "accel_limits" in self.params:  # (the control applied last, fetched ahead of the shift)
+            self._anchor_after_shift(self.u_cur_d.copy_to_host(), num_shifts)
         _lib.call("mppi_planner_shift_u", self._handle, int(num_shifts))
         self._advance_tracks(num_shifts)
 

@@ -156,6 +156,14 @@ struct mppi_planner {
   // control components and their gains (noise_smooth.h) -- (0, 0): launch_noise launches k_noise, as ever
   float smooth_beta[2] = {0.0f, 0.0f};
   float smooth_gain[2] = {1.0f, 1.0f};
+  // acceleration limits on the sampled controls (mppi_planner_set_control_limits; barebone mode; control_limits.h): while
+  // they are held every block an iteration is about to consume is passed through k_noise_limit (launch_iteration).  The
+  // step d = accel * dt is formed at the launch, from the params in force.
+  bool limits_held = false;
+  float limit_accel[2] = {0.0f, 0.0f};
+  // the control in force when the plan starts (mppi_planner_set_applied_control; k_world_step in closed_loop): the limits
+  // count from it.  Stored whether or not limits are held; zero at creation.
+  float2* anchor = nullptr;  // [B]
   float2* staging = nullptr;  // (n_local,T) host-layout staging for set/get_noise
   float2* u = nullptr;        // [T]
   float2* u_prev = nullptr;   // [T]

@@ -266,6 +266,39 @@ static int launch_noise(mppi_planner* p, float2* target, hipStream_t stream = nu
   return MPPI_OK;
 }
 
+// ---- acceleration limits on the sampled controls (mppi_planner_set_control_limits; control_limits.h) ------------------
+// The steps of the two components under the params in force: +inf where a component stays as drawn.
+static void control_limit_steps(const mppi_planner* p, float d[2]) {
+  for (int c = 0; c < 2; ++c) d[c] = p->limits_held ? control_limit_step_size(p->limit_accel[c], p->params.dt) : INFINITY;
+}
+// limits are held and at least one of them binds: the pass has something to do
+static bool control_limits_on(const mppi_planner* p) {
+  float d[2];
+  control_limit_steps(p, d);
+  return control_limit_binds(d[0]) || control_limit_binds(d[1]);
+}
+
+// The pass over `block`, in place, on the main stream: the block becomes the effective noise of the feasible sequences
+// next to the u the stream holds at that point -- the one the coming rollout launch reads -- and the anchors.  u and the
+// anchors are read from device memory; the box and the steps travel by value (graph_signature).
+static int launch_noise_limit(mppi_planner* p, float2* block) {
+  NoiseLimitJob j;
+  j.block = block;
+  j.u = p->u;
+  j.anchor = p->anchor;
+  j.n_local = p->n_local; j.n_steps = p->cfg.num_steps; j.inst_tiles = p->inst_tiles;
+  j.lo0 = p->params.vrange[0]; j.hi0 = p->params.vrange[1];
+  j.lo1 = p->params.wrange[0]; j.hi1 = p->params.wrange[1];
+  float d[2];
+  control_limit_steps(p, d);
+  j.d0 = d[0]; j.d1 = d[1];
+  const size_t lds = noise_limit_lds(p->cfg.num_steps);  // (the problem's controls)
+  REQUIRE(lds <= 64 * 1024, MPPI_ERR_INVALID, "num_steps %d too large for the control limits", p->cfg.num_steps);
+  hipLaunchKernelGGL(k_noise_limit, dim3(ceil_div(p->n_local, 64)), dim3(64), lds, p->stream, j);
+  HIP_TRY(hipGetLastError());
+  return MPPI_OK;
+}
+
 // ---- the map modes: what the launch choice depends on (map_plan.h), read off a handle ----------------------------
 static MapHeld map_held(const mppi_planner* p) {
   const mppi_params& a = p->params;
@@ -1010,6 +1043,14 @@ static int launch_iteration(mppi_planner* p, const DevParams& d, bool& have_nois
     TRY(launch_noise(p, p->noise_buf[p->noise_cur]));
   }
   p->noise = p->noise_buf[p->noise_cur];
+  // Acceleration limits: this iteration's block is there (a block produced ahead once the main stream has waited for its
+  // generator, as the rollout launch would have), and so is the u the previous update left -- which is why the pass is
+  // in line, behind both, and the generator ahead keeps producing unlimited blocks.
+  if (control_limits_on(p)) {
+    TraceRange tr("mppi:noise_limit");
+    settle_noise_wait(p);
+    TRY(launch_noise_limit(p, p->noise));
+  }
   if (prof) HIP_TRY(hipEventRecord(p->ev_stage[1], p->stream));
   // (the other noise buffer was last read by the previous update, which is behind us on this stream)
   if (noise.record_front) HIP_TRY(hipEventRecord(p->ev_buf_free, p->stream));
@@ -1084,6 +1125,8 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen, guide_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
     float smooth_beta[2];
+    float limit_steps[2];
+    int limits_held, pad2;
   } sig;
   memset(&sig, 0, sizeof(sig));
   sig.d = d;
@@ -1108,6 +1151,8 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.ring_gen = sc.rings.gen;  // (the clearance rings' likewise)
   sig.guide_gen = sc.guide.gen;  // (the guide's: renewed when it is set, not when its field or its rows are refreshed)
   sig.smooth_beta[0] = p->smooth_beta[0]; sig.smooth_beta[1] = p->smooth_beta[1];  // (the noise smoothing's coefficients: by value in the generator's argument)
+  control_limit_steps(p, sig.limit_steps);  // (the acceleration limits: the steps, on or off, and -- in params -- the box: by value)
+  sig.limits_held = p->limits_held ? 1 : 0;
   sig.noise_cur = p->noise_cur; sig.inst_set = p->inst_set; sig.want_sample_costs = p->want_sample_costs;
   sig.speculation_off = p->speculation_off ? 1 : 0; sig.debug_flags = p->debug_flags;
   sig.pad = (p->p2p_on ? 2 : 0) | (p->p2p_index & 1);  // (the inbox set of the peer exchange is a by-value argument)

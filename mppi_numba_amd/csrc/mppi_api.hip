@@ -490,6 +490,7 @@ extern "C" int mppi_planner_destroy(mppi_planner* p) {
   dev_free(p->u);
   dev_free(p->u_prev);
   dev_free(p->u_alt);
+  dev_free(p->anchor);
   dev_free(p->costs);
   dev_free(p->weights_out);
   dev_free(p->w_rel);
@@ -585,6 +586,7 @@ static int planner_alloc(mppi_planner* p) {
   TRY(dev_alloc(&p->u, B * T));
   TRY(dev_alloc(&p->u_prev, B * T));
   TRY(dev_alloc(&p->u_alt, B * T));
+  TRY(dev_alloc(&p->anchor, B));
   TRY(dev_alloc(&p->inst_dev, B));
   HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->u_host), B * T * sizeof(float2), hipHostMallocMapped));
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&p->u_host_dev), p->u_host, 0));
@@ -615,6 +617,7 @@ static int planner_alloc(mppi_planner* p) {
   HIP_TRY(hipMemsetAsync(p->u, 0, B * T * sizeof(float2), p->stream));  // u_seq0 = zeros (mppi.py:93)
   HIP_TRY(hipMemsetAsync(p->u_prev, 0, B * T * sizeof(float2), p->stream));
   HIP_TRY(hipMemsetAsync(p->u_alt, 0, B * T * sizeof(float2), p->stream));
+  HIP_TRY(hipMemsetAsync(p->anchor, 0, B * sizeof(float2), p->stream));
   HIP_TRY(hipMemsetAsync(p->costs, 0, N * sizeof(float), p->stream));
   {
     std::vector<double> initial_stats(2 * B);
@@ -1219,6 +1222,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.goal_xy = sc.goal.on ? sc.goal.xy : nullptr;  // (the guide's rows are carrots, not the goal: arrival is tested against the true goal)
     L.goal_rows = sc.goal.rows;
     L.goal_stride = sc.goal.count > 1 ? sc.goal.rows : 0;
+    L.anchor = nominal && p->limits_held ? p->anchor : nullptr;  // (the limits of the next plan count from the u0 applied)
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)
@@ -1288,11 +1292,13 @@ extern "C" int mppi_planner_sample_noise(mppi_planner* p) {
     p->noise = p->noise_buf[p->noise_cur];
     p->primed = false;
     p->noise_virtual = false;
+    if (control_limits_on(p)) TRY(launch_noise_limit(p, p->noise));  // (the generator ahead produces unlimited blocks)
     TRY(drain_stream(p));
     return MPPI_OK;
   }
   p->noise_virtual = false;
   TRY(launch_noise(p, p->noise));
+  if (control_limits_on(p)) TRY(launch_noise_limit(p, p->noise));
   TRY(drain_stream(p));
   return MPPI_OK;
 }
@@ -1392,6 +1398,68 @@ extern "C" int mppi_planner_time_noise(mppi_planner* p, int reps, float* us_nois
   TRY(rc);
   *us_noise = (float)(1e3 * sum / reps);
   return MPPI_OK;
+}
+
+// Acceleration limits on the sampled controls (include/mppi_hip.h; control_limits.h): the limits live in the handle and
+// launch_iteration passes every block it is about to consume through k_noise_limit while they are held.  The steps and
+// the box travel by value in that launch, so a change drops the captured graphs; the anchors and u are device memory.
+extern "C" int mppi_planner_set_control_limits(mppi_planner* p, const float accel[2]) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID,
+          "control limits belong to the barebone mode (mode %d): the map modes draw their noise inside the rollout launch", p->cfg.mode);
+  for (int c = 0; accel && c < 2; ++c)
+    REQUIRE(control_limit_valid(accel[c]), MPPI_ERR_INVALID, "control limit %d is %g: must be > 0 (+inf: no limit on the component)", c,
+            (double)accel[c]);
+  const bool held = accel != nullptr;
+  if (held == p->limits_held && (!held || (accel[0] == p->limit_accel[0] && accel[1] == p->limit_accel[1]))) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(drain_stream(p));
+  p->limits_held = held;
+  for (int c = 0; c < 2; ++c) p->limit_accel[c] = held ? accel[c] : 0.0f;
+  drop_graphs(p);
+  return MPPI_OK;
+}
+
+// *held = 0: no limits, accel untouched
+extern "C" int mppi_planner_get_control_limits(mppi_planner* p, float accel[2], int* held) {
+  REQUIRE(p && accel && held, MPPI_ERR_INVALID, "NULL argument");
+  *held = p->limits_held ? 1 : 0;
+  if (p->limits_held) {
+    accel[0] = p->limit_accel[0];
+    accel[1] = p->limit_accel[1];
+  }
+  return MPPI_OK;
+}
+
+// The control in force when the next plan starts: one row for every problem, or one per problem.  Device memory the
+// pass reads at its launch -- a captured one at replay --, so a new anchor drops nothing.
+extern "C" int mppi_planner_set_applied_control(mppi_planner* p, int count, const float* u) {
+  REQUIRE(p && u, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "the applied control belongs to the barebone mode (mode %d)", p->cfg.mode);
+  REQUIRE(count == 1 || count == p->B, MPPI_ERR_INVALID, "%d applied controls: one for every problem, or one per problem (%d)", count, p->B);
+  for (int i = 0; i < 2 * count; ++i) REQUIRE(std::isfinite(u[i]), MPPI_ERR_INVALID, "applied control %d is %g: must be finite", i, (double)u[i]);
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  std::vector<float2> rows((size_t)p->B);
+  for (int b = 0; b < p->B; ++b) rows[(size_t)b] = make_float2(u[2 * (count == 1 ? 0 : b)], u[2 * (count == 1 ? 0 : b) + 1]);
+  HIP_TRY(hipMemcpyAsync(p->anchor, rows.data(), sizeof(float2) * (size_t)p->B, hipMemcpyHostToDevice, p->stream));
+  return drain_stream(p);  // (the rows are this call's own)
+}
+
+// u (B, 2)
+extern "C" int mppi_planner_get_applied_control(mppi_planner* p, float* u) {
+  REQUIRE(p && u, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "the applied control belongs to the barebone mode (mode %d)", p->cfg.mode);
+  return copy_out(p, u, p->anchor, sizeof(float2) * (size_t)p->B);
+}
+
+// The pass alone, over the block the handle holds (stage level: mppi_planner_set_noise stores what it is given).
+extern "C" int mppi_planner_limit_noise(mppi_planner* p) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
+  REQUIRE(p->limits_held, MPPI_ERR_STATE, "no control limits are held (mppi_planner_set_control_limits)");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  if (control_limits_on(p)) TRY(launch_noise_limit(p, p->noise));
+  return drain_stream(p);
 }
 
 extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang) {

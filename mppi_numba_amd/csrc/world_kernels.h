@@ -100,6 +100,9 @@ struct WorldLoop {
   // the time of the new state: row min(track_off, goal_rows - 1) once the offset has advanced
   const float2* goal_xy;
   int goal_rows, goal_stride;
+  // barebone mode with acceleration limits (mppi_planner_set_control_limits): [B] the control in force when the next plan
+  // starts -- the u0 just applied; nullptr: no limits are held (the map modes never set it)
+  float2* anchor;
 };
 
 // One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4; barebone_mppi_numba.ipynb
@@ -123,6 +126,7 @@ __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ i
     const double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
     const float2 u0 = shifted[0];
     L.uhist[(size_t)b * L.max_steps + step] = u0;
+    if (L.anchor) L.anchor[b] = u0;
     double lt = 1.0, at = 1.0;
     if (G.lin) world_lookup(G, x, y, lt, at);
     const double x1 = x + L.dt * lt * cos(th) * (double)u0.x;
