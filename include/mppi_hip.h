@@ -410,6 +410,54 @@ int mppi_planner_get_guide_field(mppi_planner* p, unsigned* out);
 /* xy: [B][T+1][2], status: [B] -- of the last refresh */
 int mppi_planner_get_guide_rows(mppi_planner* p, float* xy, int* status);
 
+/* MPPI_MODE_BAREBONE, crowd mode: an occupancy grid -- a costmap -- as one more counted obstacle.
+ * cells: [ny][nx] bytes, non-zero = occupied; 1 <= nx, ny <= 512; one grid for every problem of a
+ * batch.  The device keeps the clearance field D2, uint32 [ny][nx]: the least
+ * (ix - jx)^2 + (iy - jy)^2 over the occupied cells (jy, jx) -- 0 on an occupied cell, 0xFFFFFFFF
+ * everywhere when none is occupied -- built by k_occupancy_field (csrc/occupancy_kernels.h) on the
+ * planner's stream at the head of the next call that starts iterations, only when the cells have
+ * changed.  Every value of the test is an integer or a double formed from widened float32 inputs
+ * in the order written, no product fused into a sum (csrc/occupancy_grid.h):
+ *   points   a point robot is the body of one disc (0, 0, 0); for body disc i of radius rho_i, A
+ *            and B are its float32 centres at the pre-step and the post-step state (the centres
+ *            of mppi_planner_set_footprint; step 0: the start state, heading included).  With
+ *            M = substeps, test point k = 1 .. M is (double)B for k == M, else
+ *            (double)A + ((double)k / (double)M) * ((double)B - (double)A), the product rounded
+ *   inside   q = floor((X - (double)origin) / (double)res) per axis; inside iff 0 <= q <= n - 1 on
+ *            both (a NaN is outside).  A point outside the grid is free
+ *   verdict  at level l (0: the hit; l >= 1: clearance ring l of margin m_l): inside and
+ *            D2[cell] <= thr[i][l], thr = min(floor(R * R / (res * res)), 0xFFFFFFFE) with
+ *            R = ((double)inflate + (double)rho_i) + m_l
+ *   count    the grid is ONE obstacle: a step whose any test point of any body disc hits adds one
+ *            hit (one more rounded addition of obs_penalty); a step near at ring l adds one to n_l
+ * A chord without a hit keeps every point of it more than
+ * R - |AB| / (2 M) - res * sqrt(2) / 2 from every occupied cell's centre: choose inflate and
+ * substeps from that; substeps = 1 is the post-step test, as for discs.  Every launch of a handle
+ * that holds a grid is a grid form of the crowd kernel -- a footprint form with one CrowdGrid last
+ * in the pack -- and mppi_planner_describe_last_rollout ends in " grid=<nx>x<ny>".  While a guide
+ * is on as well, a guide cell whose centre lies inside the grid on a cell with D2 <= thr_g,
+ * R = (double)inflate + (double)inflate_guide, is blocked too; the grid's field is built ahead of
+ * the guide's, and new cells rebuild both.
+ * An unchanged hand-over costs a comparison.  New cells of the same shape, geometry, inflate and
+ * substeps land in the same arrays: captured graphs stay valid.  Any other change drains the
+ * stream and drops the captured graphs; on = 0 clears (the other arguments are ignored).
+ * MPPI_ERR_INVALID, the handle keeping what it held: a map mode, crowd mode off (and
+ * mppi_planner_set_crowd(p, 0) while a grid is held), world_size > 1, disc samples held (and
+ * mppi_planner_set_disc_track_samples while a grid is held), a value that is not finite,
+ * res <= 0, inflate < 0, nx or ny outside 1 .. 512, substeps outside 1 .. 8, NULL cells.
+ * Limits: outside the grid is free; one obs_penalty for the grid as a whole; the grid does not
+ * move (a new grid per control step is the way to move it); the fleet's refresh and the
+ * simulated world do not read it; the chord stands in for the arc, as with any footprint. */
+int mppi_planner_set_occupancy(mppi_planner* p, int on, float x_min, float y_min, float res, int nx, int ny,
+                               float inflate, int substeps, const unsigned char* cells);
+/* *fields_built: how often this handle has built the clearance field */
+int mppi_planner_get_occupancy(mppi_planner* p, int* on, int* nx, int* ny, unsigned long long* fields_built);
+/* the field's build alone, if the cells have changed, and a wait for the stream: for drawing and
+ * for tests.  MPPI_ERR_STATE without a grid */
+int mppi_planner_occupancy_refresh(mppi_planner* p);
+/* out: [ny][nx], the clearance field (MPPI_ERR_STATE while it has not been built for the cells held) */
+int mppi_planner_get_occupancy_field(mppi_planner* p, unsigned* out);
+
 /* MPPI_MODE_BAREBONE, a batched handle (num_instances B >= 2) in crowd mode: fleet mode -- the
  * problems are robots that avoid each other's plans.  count = B turns it on, halfwidths (B, B-1)
  * float32: row a holds reader a's half-width against every other robot b in ascending b, a

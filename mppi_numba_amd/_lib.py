@@ -118,6 +118,10 @@ SIGNATURES = {
     "mppi_planner_guide_refresh": [_vp],
     "mppi_planner_get_guide_field": [_vp, C.POINTER(C.c_uint)],
     "mppi_planner_get_guide_rows": [_vp, _f32p, C.POINTER(C.c_int)],
+    "mppi_planner_set_occupancy": [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte)],
+    "mppi_planner_get_occupancy": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)],
+    "mppi_planner_occupancy_refresh": [_vp],
+    "mppi_planner_get_occupancy_field": [_vp, C.POINTER(C.c_uint)],
     "mppi_planner_set_fleet": [_vp, C.c_int, _f32p],
     "mppi_planner_get_fleet": [_vp, C.POINTER(C.c_int)],
     "mppi_planner_fleet_refresh": [_vp],

@@ -179,6 +179,38 @@ sample_noise() limits what it draws; set_noise() stores what it is given and lim
 Without the key every bit and every call is as before.  Limits: one pair for every problem of a batch; symmetric (no
 separate braking bound); first differences only (no jerk bound); the visualisation rollouts read the block as it stands;
 the control-cost term weighs e'.  The map-mode classes do not read the key.
+
+Occupancy-grid obstacles: params['occupancy'], a dict with 'origin' (x, y), 'resolution', 'cells' (ny, nx) -- any integer or
+bool dtype, non-zero means occupied -- and optionally 'inflate' (default 0; for a point robot its radius) and 'substeps' (an
+int in 1 .. 8, default 1); the floats rounded once to float32.  A costmap as it comes from a lidar, without fitting discs or
+segments to it: the device keeps the clearance field D2, uint32 (ny, nx), D2[iy, ix] = the least (ix - jx)^2 + (iy - jy)^2
+over the occupied cells (jy, jx) -- 0 on an occupied cell, 0xFFFFFFFF everywhere when none is occupied; integers only --,
+rebuilt by a kernel of its own at the head of the next solve(), rollout() or control step only when the cells changed, and
+the crowd kernel counts the grid as ONE more obstacle.  A point robot is the body of one disc (0, 0, 0); for body disc i of
+radius rho_i, A and B are its float32 centres at the pre-step and the post-step state (the footprint's centres; step 0: the
+start state, heading included), and with M = substeps test point k = 1 .. M is
+  k == M      X = float64(B)                                                   (M = 1: the notebook's post-step test)
+  otherwise   X = float64(A) + (float64(k) / float64(M)) * (float64(B) - float64(A))       the product rounded, never an fma
+  cell        q = floor((X - float64(origin)) / float64(resolution)) per axis; inside iff 0 <= q <= n - 1 on both axes (a NaN
+              is outside); a point outside the grid is free: no hit, and near at no ring
+  level l     (0: the hit; l >= 1: clearance ring l of margin m_l) inside and D2[cell] <= thr[i][l],
+              thr = min(floor(R * R / (res * res)), 0xFFFFFFFE), R = (float64(inflate) + float64(rho_i)) + m_l
+A step whose any test point of any body disc hits adds 1 to the step's hits -- one more float32-rounded addition of
+float64(obs_penalty) --, a step near at ring l through any point adds 1 to n_l; goal distance, freeze, terminal term, control
+cost and the CVaR tail are as they were.  What a miss means: a chord with no hit keeps every point of it more than
+R - |AB| / (2 M) - resolution * sqrt(2) / 2 from every occupied cell's centre -- choose 'inflate' and 'substeps' from that;
+with the default substeps = 1 it is the notebook's post-step test, as for discs.  Composes with discs, disc tracks and
+per-problem disc sets, walls, wall tracks and per-problem wall sets, goal tracks and the guide, both fleets (a fleet of
+bodies: the fleet's body; a disc fleet: the point), 'footprint', 'clearance_rings', 'noise_smoothing', 'accel_limits',
+math="fast", graph replay (new cells of the same shape need no new capture) and closed_loop().  With 'guide' as well, a guide
+cell is blocked also when its centre lies inside the grid on a cell with D2 <= thr_g, R = inflate_occupancy + inflate_guide;
+the two grids need not coincide, and new cells rebuild the guide's field too.  occupancy_field() fetches D2,
+refresh_occupancy() builds it alone (for drawing), rasterise_obstacles() makes cells from walls and discs.  Without the key
+every bit, every launch and every kernel name is as before.  Limits: crowd mode only (a handle that holds a grid always
+launches the crowd kernel); 1 <= nx, ny <= 512, resolution > 0, inflate >= 0, all finite; refused together with
+'obstacle_track_samples'; one grid for every problem of a batch; one obs_penalty for the grid as a whole; outside the grid is
+free; the grid does not move (a new grid per control step is the way to move it); the fleet's refresh and the simulated
+world do not read it; the chord stands in for the arc, as with any footprint.
 """
 import collections
 import copy
@@ -300,6 +332,8 @@ def _footprint_rows(footprint):
 
 MAX_CLEARANCE_RINGS = 4  # (kCrowdRingsMax of the library)
 MAX_GUIDE_CELLS = 36864  # (kGuideCellsMax of the library: 192 x 192)
+MAX_OCCUPANCY_DIM = 512  # (kOccupancyDimMax of the library)
+MAX_OCCUPANCY_SUBSTEPS = 8  # (kOccupancySubstepsMax of the library)
 
 
 def clearance_staircase(reach, peak, count):
@@ -407,6 +441,34 @@ def guide_grid(segments, resolution, margin=None):
     return (float(lo[0]), float(lo[1])), (ny, nx)
 
 
+def rasterise_obstacles(origin, resolution, shape, segments=None, halfwidth=0.0, discs=None, radii=None):
+    """Cells for params['occupancy']: (ny, nx) uint8, 1 where the cell's centre -- origin + (ix + 0.5, iy + 0.5) *
+    resolution -- lies within its half-width of a wall segment (segments (W, 2, 2); halfwidth a scalar or (W,)) or inside a
+    disc (discs (K, 2), radii (K,); the rim included), in float64."""
+    ny, nx = int(shape[0]), int(shape[1])
+    origin = np.asarray(origin, dtype=np.float64).reshape(2)
+    res = float(resolution)
+    cx = origin[0] + (np.arange(nx, dtype=np.float64) + 0.5) * res
+    cy = origin[1] + (np.arange(ny, dtype=np.float64) + 0.5) * res
+    X, Y = np.meshgrid(cx, cy)  # (ny, nx)
+    cells = np.zeros((ny, nx), dtype=bool)
+    if segments is not None:
+        seg = np.asarray(segments, dtype=np.float64).reshape(-1, 2, 2)
+        hw = np.broadcast_to(np.asarray(halfwidth, dtype=np.float64), (len(seg),))
+        for (a, b), h in zip(seg, hw):
+            d = b - a
+            LL = float(d @ d)
+            wx, wy = X - a[0], Y - a[1]
+            t = np.clip((wx * d[0] + wy * d[1]) / LL, 0.0, 1.0) if LL > 0.0 else np.zeros_like(X)
+            cells |= (wx - t * d[0]) ** 2 + (wy - t * d[1]) ** 2 <= h * h
+    if discs is not None:
+        pos = np.asarray(discs, dtype=np.float64).reshape(-1, 2)
+        rad = np.broadcast_to(np.asarray(radii, dtype=np.float64), (len(pos),))
+        for (px, py), r in zip(pos, rad):
+            cells |= (X - px) ** 2 + (Y - py) ** 2 <= r * r
+    return cells.astype(np.uint8)
+
+
 def fleet_others(count):
     """(B, B - 1) int: row a holds the other robots of reader a in ascending order -- the order of a fleet's wall slots."""
     count = int(count)
@@ -430,7 +492,7 @@ def _same_sets(new, now):
 _STALE = "stale"  # a key: what the library holds of this kind is out of date -- hand the params' value over again, or clear
 _NOBODY, _PARAMS, _BATCH = "nobody", "params", "batch"  # who filled a slot (_BATCH: MPPI_Batch's per-problem sets)
 _KEEP, _FETCH, _ZERO = "keep", "fetch", "zero"  # what a change of a kind does to the mirror's track offsets
-_CTYPES = {np.dtype(np.float32): C.c_float, np.dtype(np.int32): C.c_int}
+_CTYPES = {np.dtype(np.float32): C.c_float, np.dtype(np.int32): C.c_int, np.dtype(np.uint8): C.c_ubyte}
 
 
 class _Held:
@@ -557,6 +619,31 @@ def _pack_guide(planner, values, shape):
     the library refuses them (MppiError) and keeps what it had."""
     x, y, res, inflate, lead, pace = (float(v) for v in values)
     return 1, x, y, res, int(shape[1]), int(shape[0]), inflate, lead, pace
+
+
+def _read_occupancy(planner, p):
+    if "obstacle_track_samples" in p:
+        raise ValueError("params hold both 'occupancy' and 'obstacle_track_samples': the sample forms look up no grid, give one of the two")
+    g = p['occupancy']
+    cells = np.asarray(g['cells'])
+    if cells.ndim != 2 or cells.dtype.kind not in "iub" or not (1 <= cells.shape[0] <= MAX_OCCUPANCY_DIM and 1 <= cells.shape[1] <= MAX_OCCUPANCY_DIM):
+        raise ValueError("params['occupancy']['cells'] is (ny, nx) of an integer or bool dtype with 1 <= ny, nx <= {}, got {} {}".format(
+            MAX_OCCUPANCY_DIM, cells.dtype, cells.shape))
+    origin = np.asarray(g['origin'], dtype=np.float64).reshape(-1)
+    if origin.shape != (2,):
+        raise ValueError("params['occupancy']['origin'] is (x, y), got {}".format(g['origin']))
+    substeps = g.get('substeps', 1)
+    if isinstance(substeps, bool) or not isinstance(substeps, (int, np.integer)) or not 1 <= int(substeps) <= MAX_OCCUPANCY_SUBSTEPS:
+        raise ValueError("params['occupancy']['substeps'] is an int in 1 .. {}, got {!r}".format(MAX_OCCUPANCY_SUBSTEPS, substeps))
+    values = _f32([origin[0], origin[1], float(g['resolution']), float(g.get('inflate', 0.0))])
+    return values, np.asarray([int(substeps)], dtype=np.int32), np.ascontiguousarray(cells != 0, dtype=np.uint8)
+
+
+def _pack_occupancy(planner, values, substeps, cells):
+    """Values that are not finite, a resolution <= 0, a negative inflation, no crowd mode, disc samples held: the library
+    refuses them (MppiError) and keeps what it had."""
+    x, y, res, inflate = (float(v) for v in values)
+    return 1, x, y, res, int(cells.shape[1]), int(cells.shape[0]), inflate, int(substeps[0]), cells
 
 
 def _pack_smoothing(planner, sm):
@@ -692,6 +779,8 @@ _KINDS = (
           lambda planner, tr, hw: _pack_wall_tracks([(tr, hw)], "params['wall_tracks']"),
           "mppi_planner_set_wall_tracks", (0, None, 0, None, None), _FETCH, None),
     _Kind("walls", "wall_segments", _read_walls, _pack_walls, "mppi_planner_set_walls", (None, None, 0), _KEEP, None),
+    _Kind("occupancy", "occupancy", _read_occupancy, _pack_occupancy,
+          "mppi_planner_set_occupancy", (0, 0.0, 0.0, 1.0, 1, 1, 0.0, 1, None), _KEEP, None, ("samples",)),
     _Kind("guide", "guide", _read_guide, _pack_guide, "mppi_planner_set_guide", (0, 0.0, 0.0, 1.0, 1, 1, 1.0, 0.0, 0.0), _KEEP, None),
     _Kind("footprint", "footprint", _read_footprint, _pack_rows(_footprint_rows),
           "mppi_planner_set_footprint", (None, 0), _KEEP, None),
@@ -972,6 +1061,36 @@ class MPPI_Numba(object):
         """How often the handle has built the field since it was created (0 while no guide is held)."""
         on, nx, ny, built = C.c_int(0), C.c_int(0), C.c_int(0), C.c_ulonglong(0)
         _lib.call("mppi_planner_get_guide", self._handle, C.byref(on), C.byref(nx), C.byref(ny), C.byref(built))
+        return int(built.value)
+
+    # ------------------------------------------------------------------ occupancy-grid obstacles
+    def _occupancy_sent(self, what):
+        sent = self._held["occupancy"].sent
+        if sent is None:
+            raise ValueError("{}: no occupancy grid is held (params['occupancy'])".format(what))
+        return sent  # (on, x_min, y_min, res, nx, ny, inflate, substeps, cells)
+
+    def refresh_occupancy(self):
+        """The clearance field's build alone, as solve() makes it at its head when the cells changed.  For drawing and for
+        tests; occupancy_field() fetches the result."""
+        self.move_mppi_task_vars_to_device()
+        self._occupancy_sent("refresh_occupancy")
+        _lib.call("mppi_planner_occupancy_refresh", self._handle)
+
+    def occupancy_field(self):
+        """The clearance field of the cells held: (ny, nx) uint32, the squared distance in cells to the nearest occupied cell
+        -- 0 on an occupied cell, 0xFFFFFFFF everywhere when none is occupied.  Builds it first if the cells are new."""
+        self.refresh_occupancy()
+        sent = self._occupancy_sent("occupancy_field")
+        out = np.empty((sent[5], sent[4]), dtype=np.uint32)
+        _lib.call("mppi_planner_get_occupancy_field", self._handle, _lib.ptr(out, C.c_uint))
+        return out
+
+    @property
+    def occupancy_fields_built(self):
+        """How often the handle has built the clearance field since it was created (0 while no grid was ever held)."""
+        on, nx, ny, built = C.c_int(0), C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+        _lib.call("mppi_planner_get_occupancy", self._handle, C.byref(on), C.byref(nx), C.byref(ny), C.byref(built))
         return int(built.value)
 
     def _tracks_on(self):

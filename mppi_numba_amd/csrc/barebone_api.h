@@ -230,6 +230,8 @@ extern "C" int mppi_planner_set_disc_track_samples(mppi_planner* p, int samples,
     REQUIRE(s.rings.count == 0, MPPI_ERR_INVALID,
             "the handle holds %d clearance rings, and the sample forms count no rings: clear them first "
             "(mppi_planner_set_clearance_rings(p, NULL, 0))", s.rings.count);
+    REQUIRE(!s.occupancy.on, MPPI_ERR_INVALID,
+            "the handle holds an occupancy grid, and the sample forms look up no grid: clear it first (mppi_planner_set_occupancy with on 0)");
     REQUIRE(rows >= 1 && rows <= (1 << 20), MPPI_ERR_INVALID, "rows %d: a track has at least one row", rows);
     REQUIRE(disc_count >= 0, MPPI_ERR_INVALID, "negative disc count %d", disc_count);
     const int walls = s.fleet.on() ? s.fleet.slots : (s.wall_tracks.on ? s.wall_tracks.max : s.walls.max);
@@ -302,6 +304,8 @@ extern "C" int mppi_planner_set_crowd(mppi_planner* p, int on) {
     REQUIRE(s.rings.count == 0, MPPI_ERR_INVALID,
             "crowd mode stays on: the handle holds %d clearance rings, which only the crowd kernel counts (mppi_planner_set_clearance_rings(p, NULL, 0) first)",
             s.rings.count);
+    REQUIRE(!s.occupancy.on, MPPI_ERR_INVALID,
+            "crowd mode stays on: the handle holds an occupancy grid, which only the crowd kernel looks up (mppi_planner_set_occupancy with on 0 first)");
     BareboneHeld now = barebone_held(p);  // (without rotation: every set at its own size, the least a launch can ask for)
     now.crowd = false;
     BareboneHeld own = now, shared = now, tracks = now;
@@ -793,6 +797,141 @@ extern "C" int mppi_planner_fleet_refresh(mppi_planner* p) {
   return drain_stream(p);
 }
 
+// ---- an occupancy grid (include/mppi_hip.h; occupancy_kernels.h, occupancy_grid.h) ---------------------------------------------
+// The hand-over: the values are checked, an unchanged hand-over costs a comparison.  New cells of the same shape, geometry,
+// inflate and substeps are packed into the host copy of the mask and mark the field dirty: the arrays stay where they are,
+// the captured graphs stay valid.  Anything else drains the stream, builds the new arrays before the old ones are freed,
+// takes a new generation and drops the captured graphs.  Nothing is launched here: the field is built on the planner's
+// stream at the head of the next call that starts iterations (occupancy_refresh).
+static void occupancy_pack(const unsigned char* cells, int nx, int ny, std::vector<unsigned long long>& mask) {
+  const size_t words = (size_t)((nx + 63) / 64);
+  mask.resize(words * (size_t)ny);
+  for (int y = 0; y < ny; ++y) {
+    const unsigned char* row = cells + (size_t)y * (size_t)nx;
+    for (size_t w = 0; w < words; ++w) {  // (no branch on a cell's value: a lidar's grid is noise to a predictor)
+      const int n = std::min(64, nx - (int)(64 * w));
+      unsigned long long bits = 0ull;
+      for (int i = 0; i < n; ++i) bits |= (unsigned long long)(row[64 * w + (size_t)i] != 0) << i;
+      mask[(size_t)y * words + w] = bits;
+    }
+  }
+}
+
+extern "C" int mppi_planner_set_occupancy(mppi_planner* p, int on, float x_min, float y_min, float res, int nx, int ny, float inflate,
+                                          int substeps, const unsigned char* cells) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "an occupancy grid belongs to the barebone mode (mode %d)", p->cfg.mode);
+  BareboneScene& s = p->scene;
+  OccupancyArrays& held = s.occupancy;
+  if (!on) {
+    if (!held.on) return MPPI_OK;
+    HIP_TRY(hipSetDevice(p->cfg.device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    OccupancyArrays off;
+    off.fields_built = held.fields_built;
+    held.release();
+    held = std::move(off);
+    drop_graphs(p);  // (the field, the geometry and the kernel form are arguments of the captured launches)
+    s.guide.dirty = true;  // (the guide's blocked cells were the grid's as well)
+    return MPPI_OK;
+  }
+  REQUIRE(s.crowd, MPPI_ERR_INVALID,
+          "an occupancy grid needs crowd mode: only the crowd kernel has grid forms (mppi_planner_set_crowd(p, 1) first)");
+  REQUIRE(p->cfg.world_size == 1, MPPI_ERR_INVALID, "an occupancy grid drives an unsharded handle (world_size %d)", p->cfg.world_size);
+  REQUIRE(!s.samples.on, MPPI_ERR_INVALID,
+          "the handle holds disc samples, and the sample forms look up no grid: clear them first "
+          "(mppi_planner_set_disc_track_samples with samples 0)");
+  REQUIRE(cells, MPPI_ERR_INVALID, "NULL cells");
+  REQUIRE(std::isfinite(x_min) && std::isfinite(y_min) && std::isfinite(res) && std::isfinite(inflate), MPPI_ERR_INVALID,
+          "occupancy: a value is not finite");
+  REQUIRE(res > 0.0f, MPPI_ERR_INVALID, "occupancy: resolution %g must be > 0", (double)res);
+  REQUIRE(inflate >= 0.0f, MPPI_ERR_INVALID, "occupancy: inflate %g must be >= 0", (double)inflate);
+  REQUIRE(nx >= 1 && ny >= 1 && nx <= kOccupancyDimMax && ny <= kOccupancyDimMax, MPPI_ERR_INVALID,
+          "occupancy: a grid of %d x %d cells: both 1 to %d", ny, nx, kOccupancyDimMax);
+  REQUIRE(substeps >= 1 && substeps <= kOccupancySubstepsMax, MPPI_ERR_INVALID, "occupancy: substeps %d: must be 1 to %d", substeps,
+          kOccupancySubstepsMax);
+  const size_t n_cells = (size_t)nx * (size_t)ny;
+  const bool same_arrays = held.on && nx == held.nx && ny == held.ny && x_min == held.x_min && y_min == held.y_min && res == held.res &&
+                           inflate == held.inflate && substeps == held.substeps;
+  if (same_arrays) {
+    if (memcmp(cells, held.cells_host.data(), n_cells) == 0) return MPPI_OK;
+    std::vector<unsigned long long> mask;  // (compared as "occupied or not": any non-zero value is an occupied cell)
+    occupancy_pack(cells, nx, ny, mask);
+    held.cells_host.assign(cells, cells + n_cells);
+    if (mask == held.mask_host) return MPPI_OK;
+    held.mask_host.swap(mask);
+    held.dirty = true;
+    return MPPI_OK;
+  }
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  OccupancyArrays fresh;
+  fresh.nx = nx; fresh.ny = ny;
+  TRY(staged([&]() -> int {
+    TRY(dev_alloc(&fresh.mask, (size_t)fresh.words() * (size_t)ny));
+    TRY(dev_alloc(&fresh.field, n_cells));
+    return MPPI_OK;
+  }, fresh.mask, fresh.field));
+  fresh.on = true;
+  fresh.x_min = x_min; fresh.y_min = y_min; fresh.res = res; fresh.inflate = inflate;
+  fresh.substeps = substeps;
+  fresh.gen = next_generation();
+  fresh.dirty = true;
+  fresh.fields_built = held.fields_built;
+  fresh.cells_host.assign(cells, cells + n_cells);
+  occupancy_pack(cells, nx, ny, fresh.mask_host);
+  held.release();
+  held = std::move(fresh);
+  drop_graphs(p);  // (the field, the geometry, the thresholds and the kernel form are arguments of the captured launches)
+  s.guide.dirty = true;
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_occupancy(mppi_planner* p, int* on, int* nx, int* ny, unsigned long long* fields_built) {
+  REQUIRE(p && on && nx && ny && fields_built, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "an occupancy grid belongs to the barebone mode (mode %d)", p->cfg.mode);
+  const OccupancyArrays& o = p->scene.occupancy;
+  *on = o.on ? 1 : 0;
+  *nx = o.nx;
+  *ny = o.ny;
+  *fields_built = o.fields_built;
+  return MPPI_OK;
+}
+
+// The grid's refresh, on the planner's stream at the head of every call that starts iterations, ahead of the guide's (whose
+// blocked cells read the field): the mask goes to the device and the field is built when the cells have changed, else
+// nothing.  The arrays stay where they are: nothing a captured graph holds changes.
+static int occupancy_refresh(mppi_planner* p) {
+  OccupancyArrays& o = p->scene.occupancy;
+  if (!o.on || !o.dirty) return MPPI_OK;
+  const int words = o.words();
+  HIP_TRY(hipMemcpyAsync(o.mask, o.mask_host.data(), sizeof(unsigned long long) * o.mask_host.size(), hipMemcpyHostToDevice, p->stream));
+  hipLaunchKernelGGL(k_occupancy_field, dim3(words, ceil_div(o.ny, kOccupancyBand)), dim3(64, kOccupancyBand),
+                     sizeof(unsigned short) * 64 * (size_t)o.ny, p->stream, o.mask, o.nx, o.ny, words, o.field);
+  HIP_TRY(hipGetLastError());
+  o.dirty = false;
+  ++o.fields_built;
+  p->scene.guide.dirty = true;  // (the guide's blocked cells are the grid's as well)
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_occupancy_refresh(mppi_planner* p) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->scene.occupancy.on, MPPI_ERR_STATE, "the handle holds no occupancy grid (mppi_planner_set_occupancy)");
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(occupancy_refresh(p));
+  return drain_stream(p);
+}
+
+// out: [ny][nx], the field of the last build
+extern "C" int mppi_planner_get_occupancy_field(mppi_planner* p, unsigned* out) {
+  REQUIRE(p && out, MPPI_ERR_INVALID, "NULL argument");
+  const OccupancyArrays& o = p->scene.occupancy;
+  REQUIRE(o.on, MPPI_ERR_STATE, "the handle holds no occupancy grid (mppi_planner_set_occupancy)");
+  REQUIRE(o.fields_built > 0 && !o.dirty, MPPI_ERR_STATE,
+          "the clearance field has not been built for these cells yet (mppi_planner_occupancy_refresh, or a solve)");
+  return copy_out(p, out, o.field, sizeof(uint32_t) * (size_t)o.nx * (size_t)o.ny);
+}
 
 // ---- a guide round the walls (include/mppi_hip.h; guide_kernels.h, guide_grid.h) ---------------------------------------------
 // The hand-over: the parameters are checked, an unchanged hand-over does nothing, a change drains the stream, builds the new
@@ -893,11 +1032,15 @@ static int guide_refresh(mppi_planner* p, const int* done) {
   const GuideGrid grid{g.x_min, g.y_min, g.res, g.inflate, g.nx, g.ny, g.lead_u, g.pace_u};
   if (g.dirty || moved) {
     const WallSet& w = p->scene.walls;
+    // the occupancy grid, if one is held: its cells within inflate_occ + inflate_guide of an occupied one block as well
+    const OccupancyArrays& o = p->scene.occupancy;
+    GuideOccupancy occ{};
+    if (o.on) occ = GuideOccupancy{o.field, o.x_min, o.y_min, o.res, o.nx, o.ny, occupancy_threshold(o.inflate, (double)g.inflate, 0.0, o.res)};
     const size_t lds = sizeof(uint32_t) * (size_t)cells;
     if (lds + kGuideFieldStaticLds > 64 * 1024)  // (from about 124 x 124 cells on: the wall tile's static LDS counts too)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_guide_field), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_guide_field, dim3(B), dim3(kGuideFieldThreads), lds, p->stream, d, grid, w.on ? w.seg_rows : nullptr,
-                       w.on ? w.hw : nullptr, w.on ? w.max : 0, g.field, g.moves);
+                       w.on ? w.hw : nullptr, w.on ? w.max : 0, g.field, g.moves, occ);
     HIP_TRY(hipGetLastError());
     g.goals_built.resize((size_t)2 * B);
     for (int b = 0; b < B; ++b) {
@@ -917,6 +1060,7 @@ extern "C" int mppi_planner_guide_refresh(mppi_planner* p) {
   REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
   REQUIRE(p->scene.guide.on, MPPI_ERR_STATE, "the handle holds no guide (mppi_planner_set_guide)");
   HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(occupancy_refresh(p));
   TRY(guide_refresh(p, nullptr));
   return drain_stream(p);
 }

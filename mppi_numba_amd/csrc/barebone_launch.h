@@ -7,7 +7,7 @@
 // The KD forms are chosen by the LARGEST problem's count; a smaller problem's slots past its own count hold the far,
 // radius-0 disc (+0.0 added), so every problem keeps the bits of its own single-problem launch.
 // The crowd family, k_rollout_barebone_crowd (rollout_crowd_kernel.h): crowd mode from kCrowdMinDiscs discs on, for sets
-// that do not fit in LDS, and for every launch with walls, disc samples, a body footprint or clearance rings.  Which of its
+// that do not fit in LDS, and for every launch with walls, disc samples, a body footprint, clearance rings or an occupancy grid.  Which of its
 // forms runs is crowd_form's answer (barebone_plan.h: the table of forms and the rules); launch_barebone_crowd builds the
 // kernel's argument pack from it once, one crowd_append step per optional argument.
 #pragma once
@@ -24,7 +24,8 @@ static BareboneHeld barebone_held(const mppi_planner* p, bool rot = false) {
   const BareboneScene& s = p->scene;
   return BareboneHeld{p->cfg.num_steps, p->inst_set, rot, s.crowd, s.shared.max, s.own.on, s.own.max,
                       s.tracks.on, s.tracks.max, s.tracks.rows, s.walls.max, s.wall_tracks.on, s.fleet.on(), s.goal.on || s.guide.on,
-                      s.samples.on ? s.samples.count : 0, s.samples.discs, s.samples.rows, W, s.footprint.count, s.rings.count};
+                      s.samples.on ? s.samples.count : 0, s.samples.discs, s.samples.rows, W, s.footprint.count, s.rings.count,
+                      s.occupancy.on};
 }
 
 // The disc arrays of a choice.  Crowd family: the tracks as their [row][disc] copy.
@@ -128,12 +129,13 @@ static CrowdSamples samples_arg(const mppi_planner* p, const BareboneChoice& c, 
   return CrowdSamples{p->want_sample_costs ? p->sample_costs : nullptr, c.samples, cvar_numel(c.samples, d.cvar_alpha)};
 }
 
-// The body footprint as a launch takes it.
+// The body footprint as a launch takes it.  A grid form without a footprint held: the point robot as the one-disc body
+// (0, 0, 0) -- the zeroed rows, one of them.
 static CrowdFootprint footprint_arg(const mppi_planner* p) {
   CrowdFootprint fp{};
   const auto& held = p->scene.footprint;
   const FleetArrays& f = p->scene.fleet;
-  fp.count = held.count;
+  fp.count = held.count == 0 && p->scene.occupancy.on ? 1 : held.count;
   const bool bodies = f.on() && f.body > 0;  // a body fleet: the others' slots count once per robot
   fp.group = bodies ? f.group : 1;
   fp.grouped = bodies ? (p->B - 1) * f.group : 0;
@@ -157,6 +159,21 @@ static CrowdRings rings_arg(const mppi_planner* p) {
   return rg;
 }
 
+// The occupancy grid as a launch takes it: thr[i][l] of body disc i at level l (0: the hit, l >= 1: ring l), formed here once
+// per launch in double on the widened float32 inputs (occupancy_threshold); the body is the one footprint_arg gives.
+static CrowdGrid grid_arg(const mppi_planner* p) {
+  const OccupancyArrays& o = p->scene.occupancy;
+  const CrowdFootprint fp = footprint_arg(p);
+  const CrowdRings rg = rings_arg(p);
+  CrowdGrid g{};
+  g.field = o.field;
+  g.x_min = o.x_min; g.y_min = o.y_min; g.res = o.res;
+  g.nx = o.nx; g.ny = o.ny; g.substeps = o.substeps;
+  for (int i = 0; i < fp.count; ++i)
+    for (int l = 0; l <= rg.count; ++l) g.thr[i][l] = occupancy_threshold(o.inflate, fp.rho[i], l == 0 ? 0.0 : rg.margin[l - 1], o.res);
+  return g;
+}
+
 // The form a TRACKS flag and a pack of argument types name, and one optional argument of the pack: if the form has it, go on
 // with it appended, else go on without.  An argument that the table (crowd_form_legal) has no form for behind the pack so
 // far is never appended, so no kernel outside the table is ever named.
@@ -169,6 +186,7 @@ constexpr CrowdForm crowd_form_of() {
   f.samples = kCrowdSamples<Pack...>;
   f.rings = kCrowdRings<Pack...>;
   f.footprint = kCrowdFootprint<Pack...>;
+  f.grid = kCrowdGrid<Pack...>;
   return f;
 }
 template <bool TRACKS, typename Make, typename Next, typename... Pack>
@@ -181,7 +199,7 @@ static int crowd_append(bool has, Make make, Next next, Pack... pack) {
 
 // The crowd family: k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, pack...>.  crowd_form (barebone_plan.h) turns
 // the choice into the form -- the table of forms and every normalisation rule are there -- and the pack is built here once, in
-// its one order: walls, goal, samples or rings, footprint.  The disc set: the tracks ([row][disc] copy), the samples
+// its one order: walls, goal, samples or rings, footprint, grid.  The disc set: the tracks ([row][disc] copy), the samples
 // ([row][sample][disc]), a problem's own static set, or the shared one.  The walls: CrowdWalls, static walls shared by the
 // problems; CrowdWallTracks, wall tracks and per-problem sets -- they come first: while they are held the static walls rest --,
 // fleet mode, which takes the same form with the sets it makes itself, the static walls copied into them, and static walls as
@@ -191,10 +209,11 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
   const CrowdForm f = crowd_form(c, rot);
   const BareboneScene& sc = p->scene;
   REQUIRE(!(f.rings && f.samples), MPPI_ERR_STATE, "clearance rings beside disc samples: the hand-over keeps them apart");
+  REQUIRE(!(f.grid && f.samples), MPPI_ERR_STATE, "an occupancy grid beside disc samples: the hand-over keeps them apart");
   int W = 0, C = 0;
   crowd_shape(p, &W, &C);
   if (f.samples || f.footprint || f.rings) C = c.chunk;  // (the chunk of the choice: a sample form's shrinks to its LDS)
-  const size_t lds = crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, c.footprint > 0, c.rings);
+  const size_t lds = crowd_lds(p->cfg.num_steps, C, c.walls != 0, c.samples, f.footprint, c.rings, f.grid);
   const bool fits = lds <= (size_t)p->lds_per_cu;
   if (f.rings)
     REQUIRE(fits, MPPI_ERR_INVALID, "%d clearance rings and %d steps: the crowd kernel needs %zu bytes of LDS", c.rings, p->cfg.num_steps, lds);
@@ -204,7 +223,7 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
     REQUIRE(fits, MPPI_ERR_INVALID, "%d disc samples and %d steps: the crowd kernel needs %zu bytes of LDS", c.samples, p->cfg.num_steps, lds);
   if (f.rings || f.samples) {  // (their counts of a step are 16 bits wide)
     const int walls = c.walls == 2 ? (sc.fleet.on() ? sc.fleet.slots : sc.wall_tracks.max) : (c.walls == 1 ? sc.walls.max : 0);
-    const bool counted = (long)c.kmax + (long)walls <= (long)kCrowdSampleHitsMax;
+    const bool counted = (long)c.kmax + (long)walls + (f.grid ? 1 : 0) <= (long)kCrowdSampleHitsMax;  // (the grid is one obstacle)
     if (f.rings)
       REQUIRE(counted, MPPI_ERR_INVALID, "clearance rings: %d discs and %d walls, more than the %d a step's 16-bit counter holds", c.kmax,
               walls, kCrowdSampleHitsMax);
@@ -232,7 +251,8 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
       MPPI_KLAUNCH(kern, grid, block, lds, p->stream, d, pos, rad, p->noise, p->u, p->costs, C, pitch, pack...);
       return MPPI_OK;
     };
-    auto footprint = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.footprint, [&] { return footprint_arg(p); }, launch, pack...); };
+    auto grid_l = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.grid, [&] { return grid_arg(p); }, launch, pack...); };
+    auto footprint = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.footprint, [&] { return footprint_arg(p); }, grid_l, pack...); };
     auto rings = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.rings, [&] { return rings_arg(p); }, footprint, pack...); };
     auto samples = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.samples, [&] { return samples_arg(p, c, d); }, rings, pack...); };
     auto goal = [&](auto... pack) -> int { return crowd_append<TRACKS>(f.goal, [&] { return goal_rows_arg<BATCHED>(p); }, samples, pack...); };
@@ -257,7 +277,8 @@ static int launch_barebone_crowd(mppi_planner* p, DevParams d, const BareboneCho
                     (c.samples > 0 ? " samples=" + std::to_string(c.samples) + " numel=" + std::to_string(cvar_numel(c.samples, d.cvar_alpha))
                                    : std::string()) +
                     (c.footprint > 0 ? " footprint=" + std::to_string(c.footprint) : std::string()) +
-                    (c.rings > 0 ? " rings=" + std::to_string(c.rings) : std::string());
+                    (c.rings > 0 ? " rings=" + std::to_string(c.rings) : std::string()) +
+                    (c.grid ? " grid=" + std::to_string(sc.occupancy.nx) + "x" + std::to_string(sc.occupancy.ny) : std::string());
   HIP_TRY(hipGetLastError());
   return MPPI_OK;
 }

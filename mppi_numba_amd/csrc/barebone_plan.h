@@ -47,11 +47,14 @@ constexpr int kCrowdRingsMax = 4;           // clearance rings (mppi_planner_set
 //   ... | [2][C][1 + R][64] uint16 counts in place of the int hits                     the ring forms (R clearance rings)
 //   ... | [2][C (+ 1 with walls)][64] float heading, slot for slot beside the positions | [3][8] double, the footprint's
 //   rows (ox | oy | rho)                                                               the footprint forms (behind all of that)
-constexpr size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false, int rings = 0) {
+//   ... | [8][1 + 4] uint32, the grid's thresholds; the positions and the headings with the entry slot, as with walls
+//                                                                                      the grid forms (footprint forms all)
+constexpr size_t crowd_lds(int T, int C, bool walls, int samples = 0, bool footprint = false, int rings = 0, bool grid = false) {
   const size_t hits = samples > 0 ? (size_t)2 * C * samples * 64 * 2 + (size_t)samples * 64 * 4
                       : rings > 0 ? (size_t)2 * C * (1 + rings) * 64 * 2 : (size_t)2 * C * 64 * 4;
-  const size_t heading = footprint ? (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 4 + 3 * 8 * 8 : 0;
-  return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + (walls ? 1 : 0)) * 64 * 8 + hits + 8 + heading;
+  const size_t entry = walls || grid ? 1 : 0;
+  const size_t heading = footprint ? (size_t)2 * (C + entry) * 64 * 4 + 3 * 8 * 8 : 0;
+  return 16 * (size_t)T + (size_t)2 * C * 64 * 8 + (size_t)2 * (C + entry) * 64 * 8 + hits + 8 + heading + (grid ? 8 * 5 * 4 : 0);
 }
 static_assert(crowd_lds(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 &&
                   crowd_lds(50, 14, true) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 64 * 4 + 8 &&
@@ -60,8 +63,11 @@ static_assert(crowd_lds(100, 16, false) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) 
                   crowd_lds(100, 16, false, 0, true) == 16 * 100 + 2 * 16 * 64 * (8 + 8 + 4) + 8 + 2 * 16 * 64 * 4 + 192 &&
                   crowd_lds(37, 14, true, 3, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 3 * 64 * 2 + 3 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 &&
                   crowd_lds(100, 16, false, 0, false, 1) == 16 * 100 + 2 * 16 * 64 * (8 + 8) + 2 * 16 * 2 * 64 * 2 + 8 &&
-                  crowd_lds(37, 14, true, 0, true, 4) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192,
-              "crowd_lds: the layout above, byte for byte -- plain, sample, footprint and ring forms");
+                  crowd_lds(37, 14, true, 0, true, 4) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192 &&
+                  crowd_lds(37, 14, false, 0, true, 0, true) == 16 * 37 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 64 * 4 + 8 + 2 * 15 * 64 * 4 + 192 + 160 &&
+                  crowd_lds(37, 14, true, 0, true, 0, true) == crowd_lds(37, 14, true, 0, true) + 160 &&
+                  crowd_lds(50, 14, false, 0, true, 4, true) == 16 * 50 + 2 * 14 * 64 * 8 + 2 * 15 * 64 * 8 + 2 * 14 * 5 * 64 * 2 + 8 + 2 * 15 * 64 * 4 + 192 + 160,
+              "crowd_lds: the layout above, byte for byte -- plain, sample, footprint, ring and grid forms");
 
 // C steps per chunk for a workgroup of W waves: the largest multiple of the W - 2 counters within kCrowdChunkMax, every
 // counter the same share.  A sample form gives up whole shares while its LDS is above kCrowdSampleLdsAim (one share stays).
@@ -90,6 +96,7 @@ struct BareboneHeld {
   int crowd_waves = 16;              // crowd family: waves per workgroup (crowd_shape of barebone_launch.h)
   int footprint = 0;                 // body footprint: F discs (0: the robot is its reference point)
   int rings = 0;                     // clearance rings: R rows (0: none held)
+  bool grid = false;                 // an occupancy grid (mppi_planner_set_occupancy) is held
 };
 
 enum BareboneFamily { kBareboneDefault = 0, kBareboneCrowd = 1, kBareboneRefused = 2 };
@@ -113,6 +120,7 @@ struct BareboneChoice {
   int chunk = 0;            // a sample form: steps per chunk; a footprint form, a ring form: likewise
   int footprint = 0;        // crowd family: 0, or the footprint form over this many body discs
   int rings = 0;            // crowd family: 0, or the ring form over this many clearance rings
+  bool grid = false;        // crowd family: the grid form (a footprint form: a point robot runs as the one-disc body (0, 0, 0))
 };
 
 // Crowd mode: does a launch go to the crowd kernel?  own_lds: what the default form holds at the least.  Walls are the
@@ -131,10 +139,14 @@ inline bool crowd_launch(const BareboneHeld& h, int kmax, size_t own_lds) {
 // discs as tracks of one row, static shared walls as wall tracks of one row, with the chunk and the LDS of the choice.
 // Clearance rings (mppi_planner_set_clearance_rings) likewise: the crowd family always, a TRACKS form with the chunk and the
 // LDS of the choice, with or without a footprint.  (The hand-over keeps rings and disc samples apart.)
+// An occupancy grid (mppi_planner_set_occupancy; the hand-over wants crowd mode and keeps it apart from disc samples)
+// likewise: the crowd family always -- no discs and no walls included --, a footprint form with the chunk and the LDS of the
+// choice, whether or not a footprint is held.
 inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   BareboneChoice c;
   c.footprint = h.footprint;
   c.rings = h.rings;
+  c.grid = h.grid;
   if (h.rings > 0 && !h.crowd) {
     c.family = kBareboneRefused;
     c.limit = kLimitRingsNeedCrowd;
@@ -168,11 +180,11 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
   c.track_form = h.trk_on || h.gtrk_on;
   c.walls = (h.wtrk_on || h.fleet_on) ? 2 : (h.n_walls > 0 ? 1 : 0);
   const size_t own_lds = barebone_lds(h.T, c.kmax, c.track_form, c.goal_form);
-  if (h.footprint > 0 || h.rings > 0) {
+  if (h.footprint > 0 || h.rings > 0 || h.grid) {
     c.family = kBareboneCrowd;
     c.track_form = true;
     c.chunk = crowd_chunk(h.crowd_waves);
-    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, 0, h.footprint > 0, h.rings);
+    c.lds = crowd_lds(h.T, c.chunk, c.walls != 0, 0, h.footprint > 0 || h.grid, h.rings, h.grid);
     return c;
   }
   if (crowd_launch(h, c.kmax, own_lds)) {
@@ -197,40 +209,46 @@ inline BareboneChoice barebone_choose(const BareboneHeld& h) {
 
 // The form of a crowd launch: which instantiation of k_rollout_barebone_crowd<EXACT, ROT, BATCHED, TRACKS, WALLS, pack...>
 // a choice of the crowd family runs, and what the launcher (launch_barebone_crowd of barebone_launch.h) does to the
-// arguments on the way.  The pack is in one order -- walls, goal, samples or rings, footprint:
+// arguments on the way.  The pack is in one order -- walls, goal, samples or rings, footprint, grid:
 //   walls      kCrowdWallsStatic: one CrowdWalls; kCrowdWallsTracks: one CrowdWallTracks; none: no argument, WALLS = false
 //   goal       one GoalRows
 //   samples    one CrowdSamples
 //   rings      one CrowdRings (never beside samples: the hand-over keeps them apart)
 //   footprint  one CrowdFootprint
+//   grid       one CrowdGrid (always behind a CrowdFootprint, never beside samples)
 // and THE TABLE OF FORMS is crowd_form_legal: every combination of ROT, TRACKS, the wall kind and the goal without samples,
 // rings and footprint (12 per ROT), and under any of those three TRACKS forms only, never CrowdWalls (2 wall kinds x goal x
 // {samples, rings, neither} x footprint, less the plain one: 20 per ROT).  ROT exists under exact math only, so the library
 // holds 64 forms per BATCHED with EXACT and 32 without: 192.  tests/test_barebone_form_plan.py pins the table.
+// The grid forms on top: TRACKS forms with a CrowdFootprint, 2 wall kinds x goal x rings = 8 per ROT, 48 in the library:
+// 240.  tests/test_occupancy_plan.py pins those.
 enum CrowdWallKind { kCrowdWallsNone = 0, kCrowdWallsStatic = 1, kCrowdWallsTracks = 2 };
 struct CrowdForm {
   bool rot = false;     // ROT: (cos, sin) by rotation
   bool tracks = false;  // TRACKS: the discs as rows, one per step
   CrowdWallKind walls = kCrowdWallsNone;
   bool goal = false, samples = false, rings = false, footprint = false;
+  bool grid = false;      // an occupancy grid: one CrowdGrid, last of the pack
   bool disc_row = false;  // static discs run as tracks of one row: DevParams::track_rows = 1
   bool wall_row = false;  // static shared walls run as wall tracks of one row: their [wall] array is the [row][wall] array
 };
 constexpr bool crowd_form_legal(const CrowdForm& f) {
-  const bool extra = f.samples || f.rings || f.footprint;
-  return !(f.samples && f.rings) && (!extra || (f.tracks && f.walls != kCrowdWallsStatic));
+  const bool extra = f.samples || f.rings || f.footprint || f.grid;
+  return !(f.samples && f.rings) && (!extra || (f.tracks && f.walls != kCrowdWallsStatic)) && (!f.grid || (f.footprint && !f.samples));
 }
 
 // The normalisation rules.  Samples, a footprint and rings run as TRACKS forms: static discs become tracks of one row (the
 // samples are rows already), static shared walls wall tracks of one row.  rot: (cos, sin) by rotation -- launch_rollout_t
-// grants it under exact math only.  A choice with rings beside samples maps to a form that is not legal; the launcher refuses.
+// grants it under exact math only.  A grid form carries a footprint whether or not one is held.  A choice with rings or a
+// grid beside samples maps to a form that is not legal; the launcher refuses.
 inline CrowdForm crowd_form(const BareboneChoice& c, bool rot) {
   CrowdForm f;
   f.rot = rot;
   f.goal = c.goal_form;
   f.samples = c.samples > 0;
   f.rings = c.rings > 0;
-  f.footprint = c.footprint > 0;
+  f.grid = c.grid;
+  f.footprint = c.footprint > 0 || c.grid;
   const bool extra = f.samples || f.rings || f.footprint;
   f.tracks = c.discs == kDiscsTracks || extra;
   f.disc_row = extra && c.discs != kDiscsTracks && c.discs != kDiscsSamples;

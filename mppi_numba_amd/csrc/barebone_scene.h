@@ -116,6 +116,27 @@ struct GuideArrays {
   void release() { dev_free(field); dev_free(moves); dev_free(rows); dev_free(status); }
 };
 
+// An occupancy grid (mppi_planner_set_occupancy; crowd mode only; occupancy_kernels.h, occupancy_grid.h): one grid for every
+// problem.  mask: the cells bit-packed, [ny][words] uint64; field: [ny][nx] uint32, the clearance field the launches read
+// through CrowdGrid.  cells_host: the cells as handed over (an unchanged hand-over is recognised by them); mask_host: what
+// goes to `mask` at the next build.  dirty: the field is rebuilt at the head of the next call that starts iterations -- new
+// cells of the same shape land in the same arrays and change nothing a captured launch holds.  gen: renewed when the shape,
+// the geometry, inflate or substeps change.
+struct OccupancyArrays {
+  bool on = false;
+  float x_min = 0.0f, y_min = 0.0f, res = 1.0f, inflate = 0.0f;
+  int nx = 0, ny = 0, substeps = 1;
+  unsigned long long* mask = nullptr;
+  uint32_t* field = nullptr;
+  uint64_t gen = 0;
+  bool dirty = false;
+  unsigned long long fields_built = 0;
+  std::vector<unsigned char> cells_host;
+  std::vector<unsigned long long> mask_host;
+  int words() const { return (nx + 63) / 64; }
+  void release() { dev_free(mask); dev_free(field); }
+};
+
 // Rows that the launches take by value (crowd mode only): no device array, `count` rows of Width floats as handed over.
 template <int MaxRows, int Width>
 struct ValueRows {
@@ -154,8 +175,11 @@ struct BareboneScene {
   // clearance rings (mppi_planner_set_clearance_rings; not beside disc samples): rows (margin, penalty), one set for every
   // problem -- CrowdRings takes the rows
   ValueRows<kCrowdRingsMax, 2> rings;
+  // an occupancy grid (mppi_planner_set_occupancy; not beside disc samples): one more counted obstacle of every launch, and
+  // blocked cells of the guide
+  OccupancyArrays occupancy;
   void release() {
     shared.release(); own.release(); tracks.release(); samples.release();
-    walls.release(); wall_tracks.release(); fleet.release(); goal.release(); guide.release();
+    walls.release(); wall_tracks.release(); fleet.release(); goal.release(); guide.release(); occupancy.release();
   }
 };

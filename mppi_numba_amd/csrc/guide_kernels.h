@@ -2,7 +2,8 @@
 // goal over a grid whose cells the shared static walls block, and per time step a "carrot", the point on the shortest path
 // from the robot's cell that is lead + j * pace ahead.  The rollouts meet the carrots as they meet a goal track (GoalRows,
 // relative = 1: step t reads row t + 1 whatever the track offset is).  The arithmetic is guide_grid.h's; the bits are pinned
-// by tests/guide_model.py.
+// by tests/guide_model.py.  While an occupancy grid is held as well (mppi_planner_set_occupancy), its cells block too:
+// GuideOccupancy, below; tests/occupancy_model.py has that mask.
 //
 // Two plain launches on the planner's stream, at the head of a call that starts iterations, behind the fleet's refresh: no
 // flags, no atomics, no waits between workgroups, every loop bounded and every index clamped.
@@ -26,6 +27,7 @@
 // (guide_first_reach): row j is the first cell that is lead_u + j * pace_u nearer to the goal than the start.
 #pragma once
 #include "guide_grid.h"
+#include "occupancy_grid.h"
 #include "rollout_kernels.h"
 
 namespace mppi {
@@ -37,6 +39,16 @@ struct GuideGrid {
   int lead_u, pace_u;
 };
 
+// The occupancy grid as k_guide_field takes it (mppi_planner_set_occupancy; field nullptr: none held): a guide cell whose
+// centre lies inside the grid on a cell with D2 <= thr is blocked -- thr: occupancy_threshold with R = inflate_occ +
+// inflate_guide, formed on the host.  The two grids need not coincide.
+struct GuideOccupancy {
+  const uint32_t* field;
+  float x_min, y_min, res;
+  int nx, ny;
+  uint32_t thr;
+};
+
 constexpr int kGuideFieldThreads = 1024;
 constexpr size_t kGuideFieldStaticLds = 4096;  // an upper bound of k_guide_field's static LDS (the wall tile: 3072 bytes, and the barrier's word)
 constexpr int kGuideRowsThreads = 256;
@@ -45,7 +57,8 @@ constexpr int kGuideStretch = 256;  // cells of the descent thread 0 walks betwe
 // dynamic LDS: [ny * nx] uint32, the field.  seg / hw: the shared static walls (one row: [wall]).  field, moves: [B][ny * nx]
 __global__ __launch_bounds__(kGuideFieldThreads) void k_guide_field(DevParams P, GuideGrid g, const float4* __restrict__ seg,
                                                                     const float* __restrict__ hw, int n_walls,
-                                                                    uint32_t* __restrict__ field, uint8_t* __restrict__ moves) {
+                                                                    uint32_t* __restrict__ field, uint8_t* __restrict__ moves,
+                                                                    GuideOccupancy occ) {
   extern __shared__ uint32_t guide_field_lds[];
   __shared__ GuideWall tile[64];
   static_assert(sizeof(tile) + 512 <= kGuideFieldStaticLds, "kGuideFieldStaticLds: what the host adds to the dynamic size");
@@ -76,6 +89,16 @@ __global__ __launch_bounds__(kGuideFieldThreads) void k_guide_field(DevParams P,
       bool hit = false;
       for (int k = 0; k < nk && !hit; ++k) hit = guide_blocked(cx, cy, tile[k]);
       if (hit) D[c] = kGuideBlocked;
+    }
+  }
+  if (occ.field != nullptr) {  // (uniform; a thread's own cells: no barrier needed)
+    for (int c = c_lo; c < c_hi; ++c) {
+      const int iy = c / nx, ix = c - iy * nx;
+      int ox = 0, oy = 0;
+      if (occupancy_cell(guide_centre(g.x_min, g.res, ix), occ.x_min, occ.res, occ.nx, &ox) &&
+          occupancy_cell(guide_centre(g.y_min, g.res, iy), occ.y_min, occ.res, occ.ny, &oy) &&
+          occ.field[(size_t)oy * (size_t)occ.nx + (size_t)ox] <= occ.thr)
+        D[c] = kGuideBlocked;
     }
   }
   __syncthreads();

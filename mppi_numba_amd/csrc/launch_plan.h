@@ -1122,7 +1122,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
     DevParams d;
     mppi_params params;
     const void *cells, *cells16, *cc, *sample_costs, *u;
-    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen, guide_gen;
+    uint64_t lin_maps, lin_grid, ang_maps, ang_grid, epoch_bias, wall_gen, wtrk_gen, gtrk_gen, fleet_gen, smp_gen, fp_gen, ring_gen, guide_gen, occ_gen;
     int noise_cur, inst_set, want_sample_costs, speculation_off, debug_flags, pad;
     float smooth_beta[2];
     float limit_steps[2];
@@ -1150,6 +1150,7 @@ static void graph_signature(const mppi_planner* p, const DevParams& d, std::vect
   sig.fp_gen = sc.footprint.gen;  // (the body footprint's: its rows are a by-value argument of the captured launches)
   sig.ring_gen = sc.rings.gen;  // (the clearance rings' likewise)
   sig.guide_gen = sc.guide.gen;  // (the guide's: renewed when it is set, not when its field or its rows are refreshed)
+  sig.occ_gen = sc.occupancy.gen;  // (the occupancy grid's: renewed with its shape, geometry, inflate or substeps, not with its cells)
   sig.smooth_beta[0] = p->smooth_beta[0]; sig.smooth_beta[1] = p->smooth_beta[1];  // (the noise smoothing's coefficients: by value in the generator's argument)
   control_limit_steps(p, sig.limit_steps);  // (the acceleration limits: the steps, on or off, and -- in params -- the box: by value)
   sig.limits_held = p->limits_held ? 1 : 0;

@@ -24,6 +24,7 @@
 #include "rollout_crowd_kernel.h"
 #include "fleet_kernels.h"
 #include "guide_kernels.h"
+#include "occupancy_kernels.h"
 #include "rollout_scan_kernel.h"
 #include "rollout_scan_exact_kernel.h"
 #include "map_kernels.h"
@@ -852,6 +853,7 @@ extern "C" int mppi_planner_iterate_async(mppi_planner* p, mppi_tdm* lin, mppi_t
   REQUIRE(iterations >= 0, MPPI_ERR_INVALID, "iterations < 0");
   HIP_TRY(hipSetDevice(p->cfg.device));
   TRY(fleet_refresh(p, nullptr));
+  TRY(occupancy_refresh(p));
   TRY(guide_refresh(p, nullptr));
   return run_iterations(p, lin, ang, iterations);
 }
@@ -1013,6 +1015,7 @@ extern "C" int mppi_planner_solve(mppi_planner* p, mppi_tdm* lin, mppi_tdm* ang,
   TRY(sample_for_solve(p, lin, ang));
   p->mirror_done = false;
   TRY(fleet_refresh(p, nullptr));
+  TRY(occupancy_refresh(p));
   TRY(guide_refresh(p, nullptr));
   TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false, /*mirror_last=*/true));
   const size_t u_bytes = sizeof(float2) * (size_t)p->B * (size_t)p->cfg.num_steps;
@@ -1242,6 +1245,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     TRY(sample_for_solve(p, lin, ang));
     if (step == 0) TRY(plan_loop());  // (needs the sampled grids packed: after the first draw)
     TRY(fleet_refresh(p, p->loop_done));  // (fleet mode: the others' plans as the last control step left them)
+    TRY(occupancy_refresh(p));
     TRY(guide_refresh(p, p->loop_done));  // (the guide: the carrots from where the last control step left every robot)
     TRY(run_iterations(p, lin, ang, p->params.num_opt, /*timed=*/false));
     hipLaunchKernelGGL(k_world_step, dim3(B), dim3(256), sizeof(float2) * (size_t)T, p->stream, G, L, p->inst_dev, p->u,
@@ -1467,6 +1471,7 @@ extern "C" int mppi_planner_rollout(mppi_planner* p, mppi_tdm* lin, mppi_tdm* an
   REQUIRE(p->params_set, MPPI_ERR_STATE, "params not set");
   HIP_TRY(hipSetDevice(p->cfg.device));
   TRY(fleet_refresh(p, nullptr));
+  TRY(occupancy_refresh(p));
   TRY(guide_refresh(p, nullptr));
   DevParams d;
   TRY(prepare_launch(p, lin, ang, &d));

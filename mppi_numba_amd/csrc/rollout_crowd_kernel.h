@@ -133,6 +133,22 @@
 //          per-lane-predicated loop.  Repeated additions and not a product: a ring with c_l = obs_cost is a second copy of
 //          the obstacles, m_l larger, to the bit.  A ring with c_l = 0 adds +0.0: the identity (see above).
 //
+// AN OCCUPANCY GRID, CrowdGrid (mppi_planner_set_occupancy; occupancy_grid.h, occupancy_kernels.h): a costmap as ONE more
+// counted obstacle.  The launch takes the clearance field D2 -- uint32 [ny][nx], the squared distance in cells to the nearest
+// occupied cell, built by k_occupancy_field ahead of the launch, 1 MiB at the cap and L2-resident -- and thr[i][l], the
+// threshold of body disc i at level l (0: the hit, l >= 1: ring l), formed on the host.  A grid form is always a footprint
+// form (a point robot runs as the one-disc body (0, 0, 0): its centres are the stored positions to the bit), a TRACKS form,
+// never beside CrowdWalls or CrowdSamples; CrowdGrid is the last of the pack.
+//   walk   the position buffer and the heading plane have the entry slot (C + 1) whether or not there are walls: with
+//          substeps > 1 the counters need the pre-step pose
+//   count  behind the step's last wall tile the owner walks the body's discs (a run-time loop, rows and thresholds from LDS
+//          -- [8][1 + 4] uint32 behind the footprint's rows) and the M = substeps test points of each chord (occupancy_point:
+//          k == M is the post-step centre itself, so M = 1 never forms the pre-step centre), finds each point's cell
+//          (occupancy_cell: a point outside the grid, or a NaN, is free) and holds ONE load of D2 against the 1 + R
+//          thresholds: level l is touched iff D2 <= thr[i][l] for some point of some disc.  The step's count of every level
+//          touched rises by one.  M, F and 1 + R are wave-uniform; the loads are per lane
+//   cost   the cost wave and the tail do not know
+//
 // REGISTERS.  One wall test and what the other waves keep do not fit 128 registers together: the compiler's report, gfx950,
 // scratch bytes a lane over the 192 forms (zero was not reached), read from the report of the commit that merged the plain
 // and the sample walk, whose figures are its parent's in every form --
@@ -142,11 +158,17 @@
 //   rings               0 .. 144              156 .. 284             20 .. 52             308 .. 392
 // The register allocator of this kernel answers to edits that change no operation (profiles/HISTORY.md has two entries on
 // it): a change of this file is compared with its parent in that report, form by form, before it is timed.
+// The 48 grid forms (the commit that added them; the 192 forms above kept their registers, scratch, LDS and SGPR spills, three
+// batched ring-footprint-wall forms report fewer spilled VGPRs in the same scratch) -- scratch bytes a lane:
+//                 footprint + grid, no walls   footprint + grid, walls
+//   plain                60 .. 104                  320 .. 408
+//   rings                80 .. 128                  372 .. 468
 #pragma once
 #include <type_traits>
 
 #include "barebone_plan.h"
 #include "crowd_fold.h"
+#include "occupancy_grid.h"
 #include "rollout_kernels.h"
 
 namespace mppi {
@@ -201,6 +223,17 @@ struct CrowdFootprint : CrowdFootprintRows {
 struct CrowdRings {
   int count;
   double margin[kCrowdRingsMax], penalty[kCrowdRingsMax];
+};
+
+// The occupancy grid of a launch (mppi_planner_set_occupancy): the clearance field [ny][nx] (occupancy_kernels.h), the
+// geometry, `substeps` test points per chord and thr[i][l], the threshold of body disc i at level l (0: the hit, l >= 1:
+// ring l) in squared cells -- formed on the host (occupancy_threshold), non-decreasing in l; rows past the body and levels
+// past the last ring are not read.
+struct CrowdGrid {
+  const uint32_t* field;
+  float x_min, y_min, res;
+  int nx, ny, substeps;
+  uint32_t thr[kCrowdFootprintMax][1 + kCrowdRingsMax];
 };
 
 __device__ __forceinline__ float crowd_lane_f32(float v, int l) {
@@ -399,6 +432,38 @@ __device__ __forceinline__ void crowd_body_wall_ring_hits(const double* rows, in
   for (int q = 0; q <= kCrowdRingsMax; ++q) n[q] += crowd_fold_count(mask[q], group, span);  // (a level past the last: an empty mask)
 }
 
+// The occupancy grid: at which of `levels` levels (0: the hit, then the rings) does the step touch the grid?  any[l] is set
+// iff some test point of some body disc's chord lies inside the grid on a cell whose clearance is within the disc's
+// threshold of the level.  A run-time loop over the body around one copy of the lookup, as crowd_body_wall_hits: the rows
+// and the thresholds (thr: [8][1 + 4] uint32) come from LDS, both centres are formed on the spot in crowd_body_centres'
+// arithmetic -- the pre-step one only when there is a test point short of the chord's end.  The trip counts are uniform.
+template <int LEVELS>
+__device__ __forceinline__ void crowd_grid_touches(const CrowdGrid& g, const uint32_t* thr, const double* rows, int count, float px,
+                                                   float py, double sp, double cp, float qx, float qy, double sq, double cq,
+                                                   int levels, bool (&any)[LEVELS]) {
+  const int M = g.substeps;
+  for (int i = 0; i < count; ++i) {
+    const double ox = rows[i], oy = rows[kCrowdFootprintMax + i];
+    const float bx = (float)((double)qx + (ox * cq - oy * sq)), by = (float)((double)qy + (ox * sq + oy * cq));
+    float ax = bx, ay = by;
+    if (M > 1) {
+      ax = (float)((double)px + (ox * cp - oy * sp));
+      ay = (float)((double)py + (ox * sp + oy * cp));
+    }
+    for (int k = 1; k <= M; ++k) {
+      int ix = 0, iy = 0;
+      if (occupancy_cell(occupancy_point(ax, bx, k, M), g.x_min, g.res, g.nx, &ix) &&
+          occupancy_cell(occupancy_point(ay, by, k, M), g.y_min, g.res, g.ny, &iy)) {
+        const uint32_t d2 = g.field[(size_t)iy * (size_t)g.nx + (size_t)ix];
+#pragma unroll
+        for (int q = 0; q < LEVELS; ++q) {
+          if (q < levels) any[q] = any[q] || d2 <= thr[i * (1 + kCrowdRingsMax) + q];
+        }
+      }
+    }
+  }
+}
+
 // The optional arguments of the kernel, one accessor each.  The walls, if there are any, are the first of the pack.
 // (obs_pos: static discs [disc]; TRACKS: the [row][disc] copy of the tracks, `disc_pitch` discs per row.)
 template <typename Arg>
@@ -409,14 +474,15 @@ __device__ __forceinline__ auto crowd_walls_of(const First& first, const Rest&..
   if constexpr (kCrowdWallArg<First>) return first;
   else return crowd_walls_of();
 }
-// The one order of the pack: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint -- each at most once, nothing else.
+// The one order of the pack: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint, CrowdGrid -- each at most once,
+// nothing else.
 template <typename Arg>
 constexpr int kCrowdArgRank = kCrowdWallArg<Arg> ? 0 : std::is_same_v<Arg, GoalRows> ? 1
                               : (std::is_same_v<Arg, CrowdSamples> || std::is_same_v<Arg, CrowdRings>) ? 2
-                              : std::is_same_v<Arg, CrowdFootprint> ? 3 : -1;
+                              : std::is_same_v<Arg, CrowdFootprint> ? 3 : std::is_same_v<Arg, CrowdGrid> ? 4 : -1;
 template <typename... WallArgs>
 constexpr bool crowd_pack_in_order() {
-  const int ranks[] = {kCrowdArgRank<WallArgs>..., 4};
+  const int ranks[] = {kCrowdArgRank<WallArgs>..., 5};
   int before = -1;
   for (int r : ranks) {
     if (r <= before) return false;
@@ -444,6 +510,22 @@ __device__ __forceinline__ auto crowd_footprint_of(const First& first, const Res
   if constexpr (std::is_same_v<First, CrowdFootprint>) return first;
   else return crowd_footprint_of(rest...);
 }
+// (what a grid form keeps of the step's pre-step heading between the walls and the grid; nothing in the other forms)
+template <bool GRID>
+struct CrowdGridHeading {};
+template <>
+struct CrowdGridHeading<true> {
+  double s = 0.0, c = 1.0;
+};
+template <typename... WallArgs>
+constexpr bool kCrowdGrid = (std::is_same_v<WallArgs, CrowdGrid> || ...);
+struct CrowdNoGrid {};
+__device__ __forceinline__ CrowdNoGrid crowd_grid_of() { return CrowdNoGrid{}; }
+template <typename First, typename... Rest>
+__device__ __forceinline__ auto crowd_grid_of(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<First, CrowdGrid>) return first;
+  else return crowd_grid_of(rest...);
+}
 __device__ __forceinline__ CrowdSamples crowd_samples_of() { return CrowdSamples{nullptr, 0, 1}; }
 template <typename First, typename... Rest>
 __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, const Rest&... rest) {
@@ -459,6 +541,8 @@ __device__ __forceinline__ CrowdSamples crowd_samples_of(const First& first, con
 //   samples    with disc samples, one CrowdSamples (TRACKS, and no CrowdWalls), or
 //   rings      with clearance rings, one CrowdRings (TRACKS, no CrowdWalls, no CrowdSamples)
 //   footprint  with a body footprint, one CrowdFootprint (TRACKS, and no CrowdWalls)
+//   grid       with an occupancy grid, one CrowdGrid (behind a CrowdFootprint -- a point robot is the one-disc body
+//              (0, 0, 0) --, never beside CrowdSamples)
 template <bool EXACT, bool ROT, bool BATCHED, bool TRACKS, bool WALLS = false, typename... WallArgs>
 __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
     DevParams P, const float2* __restrict__ obs_pos, const float* __restrict__ obs_r, const float2* __restrict__ noise,
@@ -467,15 +551,18 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   constexpr bool SAMPLES = kCrowdSamples<WallArgs...>;
   constexpr bool FOOT = kCrowdFootprint<WallArgs...>;
   constexpr bool RINGS = kCrowdRings<WallArgs...>;
-  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0) + (RINGS ? 1 : 0) + (FOOT ? 1 : 0),
+  constexpr bool GRID = kCrowdGrid<WallArgs...>;
+  static_assert(sizeof...(WallArgs) == (WALLS ? 1 : 0) + (GOALS ? 1 : 0) + (SAMPLES ? 1 : 0) + (RINGS ? 1 : 0) + (FOOT ? 1 : 0) + (GRID ? 1 : 0),
                 "WALLS: one CrowdWalls or CrowdWallTracks argument; a goal that moves: one GoalRows behind it; disc samples: "
                 "one CrowdSamples behind that, or clearance rings: one CrowdRings; a body footprint: one CrowdFootprint "
-                "behind that; else none");
-  static_assert(crowd_pack_in_order<WallArgs...>(), "the pack's order: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint");
+                "behind that; an occupancy grid: one CrowdGrid behind that; else none");
+  static_assert(crowd_pack_in_order<WallArgs...>(), "the pack's order: walls, GoalRows, CrowdSamples or CrowdRings, CrowdFootprint, CrowdGrid");
   constexpr bool WTRK = kCrowdWallTracks<WallArgs...>;
   static_assert(!SAMPLES || (TRACKS && WTRK == WALLS), "disc samples: TRACKS forms, walls as CrowdWallTracks");
   static_assert(!FOOT || (TRACKS && WTRK == WALLS), "a body footprint: TRACKS forms, walls as CrowdWallTracks");
   static_assert(!RINGS || (TRACKS && WTRK == WALLS && !SAMPLES), "clearance rings: TRACKS forms, walls as CrowdWallTracks, no disc samples");
+  static_assert(!GRID || (FOOT && !SAMPLES), "an occupancy grid: footprint forms (a point robot: the one-disc body), no disc samples");
+  [[maybe_unused]] const auto grid = crowd_grid_of(wall_args...);  // (CrowdGrid, or nothing)
   [[maybe_unused]] const CrowdRings rg = crowd_rings_of(wall_args...);
   [[maybe_unused]] const int NL = 1 + rg.count;  // RINGS: counts per (step, lane)
   [[maybe_unused]] const auto fp = crowd_footprint_of(wall_args...);  // (CrowdFootprint, or the empty rows)
@@ -507,7 +594,7 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
   }
   const int T = P.n_steps, K = P.n_obstacles;
   double* nd2s = reinterpret_cast<double*>(uos + T);
-  constexpr int kEntry = WALLS ? 1 : 0;  // position slots ahead of a chunk's first step
+  constexpr int kEntry = (WALLS || GRID) ? 1 : 0;  // position slots ahead of a chunk's first step
   const int CP = C + kEntry;
   float2* poss = reinterpret_cast<float2*>(nd2s + 2 * C * 64);
   int* cnts = reinterpret_cast<int*>(poss + 2 * CP * 64);
@@ -538,6 +625,16 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
         fprows[kCrowdFootprintMax + i] = fp.oy[i];
         fprows[2 * kCrowdFootprintMax + i] = fp.rho[i];
       }
+    }
+  }
+  // GRID: ... and behind those the grid's thresholds, [8][1 + 4] uint32, for the same reason
+  [[maybe_unused]] uint32_t* gthr = nullptr;
+  if constexpr (GRID) {
+    gthr = reinterpret_cast<uint32_t*>(fprows + 3 * kCrowdFootprintMax);
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 0; i < kCrowdFootprintMax * (1 + kCrowdRingsMax); ++i)
+        gthr[i] = grid.thr[i / (1 + kCrowdRingsMax)][i % (1 + kCrowdRingsMax)];
     }
   }
   if (threadIdx.x < 2) tile_done[threadIdx.x] = 0;
@@ -593,10 +690,10 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
           for (int j = 0; j < kCrowdChunkMax; ++j) e_nxt[j] = col[(size_t)min(c0 + C + j, T - 1) * 64];
         }
         float2* out = poss + (size_t)((ph & 1) * CP + kEntry) * 64 + lane;
-        if constexpr (WALLS) out[-64] = make_float2(x, y);  // where the chunk's first step starts
+        if constexpr (WALLS || GRID) out[-64] = make_float2(x, y);  // where the chunk's first step starts
         [[maybe_unused]] float* hout = nullptr;
         if constexpr (FOOT) hout = heads + (size_t)((ph & 1) * CP + kEntry) * 64 + lane;
-        if constexpr (FOOT && WALLS) hout[-64] = th;  // ... and how the body lies there
+        if constexpr (FOOT && (WALLS || GRID)) hout[-64] = th;  // ... and how the body lies there
 #pragma unroll
         for (int j = 0; j < kCrowdChunkMax; ++j) {
           if (j < cl) {
@@ -809,11 +906,13 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
               }
             }
             if (nj != j) {  // the step's last tile
+              [[maybe_unused]] CrowdGridHeading<GRID> gh;  // GRID: sine and cosine of the heading before the step
               if constexpr (WALLS) {  // ... then this problem's walls as this step sees them, against P -> Q
                 const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
                 [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
                 [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
                 if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
+                if constexpr (GRID) { gh.s = sp; gh.c = cp; }
                 float4 sg = sg0;
                 double dx = dx0, dy = dy0, LLd = LLd0, hq[kSq];
 #pragma unroll
@@ -846,6 +945,16 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                 sg0 = sg; dx0 = dx; dy0 = dy; LLd0 = LLd;
 #pragma unroll
                 for (int q = 0; q < kSq; ++q) hq0[q] = hq[q];
+              }
+              if constexpr (GRID) {  // ... then the grid: one more obstacle, counted once at every level it is touched at
+                const float2 pre = poss[atp + j * 64 - 64];
+                if constexpr (!WALLS) {
+                  if (grid.substeps > 1) sincos_f64<false>((double)heads[atp + j * 64 - 64], gh.s, gh.c);
+                }
+                bool any[1 + kCrowdRingsMax] = {};
+                crowd_grid_touches(grid, gthr, fprows, fp.count, pre.x, pre.y, gh.s, gh.c, pos.x, pos.y, sq, cq, NL, any);
+#pragma unroll
+                for (int q = 0; q <= kCrowdRingsMax; ++q) n[q] += any[q] ? 1 : 0;
               }
               unsigned short* cn = cnts16 + ((size_t)((c & 1) * C + j) * NL) * 64 + lane;
 #pragma unroll
@@ -898,12 +1007,14 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
               }
             }
             if (SAMPLES ? nbase == 0 : nj != j) {  // the sample's last tile (no samples: the step's)
+              [[maybe_unused]] CrowdGridHeading<GRID> gh;  // GRID: sine and cosine of the heading before the step
               if constexpr (WALLS) {
                 if (!SAMPLES || sm == 0) {  // the step's walls, once, against the step's segment P -> Q
                   const float2 pre = poss[atp + j * 64 - 64];  // (j = 0: the entry slot)
                   [[maybe_unused]] const double px = (double)pre.x, py = (double)pre.y, qx = (double)pos.x, qy = (double)pos.y;
                   [[maybe_unused]] double sp = 0.0, cp = 1.0;  // FOOT: of the heading before the step
                   if constexpr (FOOT) sincos_f64<false>((double)heads[atp + j * 64 - 64], sp, cp);
+                  if constexpr (GRID) { gh.s = sp; gh.c = cp; }
                   float4 sg = sg0;
                   double dx = dx0, dy = dy0, LLd = LLd0, hh = hh0;
                   if constexpr (SAMPLES) whits = 0;
@@ -949,6 +1060,15 @@ __global__ __launch_bounds__(64 * kCrowdWavesMax) void k_rollout_barebone_crowd(
                     }
                   }
                 }
+              }
+              if constexpr (GRID) {  // ... then the grid: one more obstacle, one hit however many test points touch it
+                const float2 pre = poss[atp + j * 64 - 64];
+                if constexpr (!WALLS) {
+                  if (grid.substeps > 1) sincos_f64<false>((double)heads[atp + j * 64 - 64], gh.s, gh.c);
+                }
+                bool any[1] = {};
+                crowd_grid_touches(grid, gthr, fprows, fp.count, pre.x, pre.y, gh.s, gh.c, pos.x, pos.y, sq, cq, 1, any);
+                hits += any[0] ? 1 : 0;
               }
               if constexpr (SAMPLES) cnts16[(at - lane + (size_t)j * 64) * S + sm * 64 + lane] = (unsigned short)(hits + whits);
               else cnts[at + j * 64] = hits;
