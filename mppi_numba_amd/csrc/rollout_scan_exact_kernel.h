@@ -32,14 +32,17 @@
 //
 //   chunk wave g                      walker
 //   A  noise (GEN: Philox; else read), clipped controls, dt*w          -> a_done[g]
+//      the control-cost products (mppi.py:1007-1009), while the wave
+//      would only wait for its headings (noise still in registers)     -> cc_done[g]
 //                                     theta walk over group g          -> th_done[g]
 //   B  sin / cos of the 8 headings, (dt*v)*cos, (dt*v)*sin             -> b_done[g]
+//      (at priority 3 from th_done[g] seen to b_done[g] raised, then
+//       back to the wave's table priority for C and D')
 //                                     x | y walk over group g          -> xy_done[g]
 //   C  lookups, goal distances, sqrt, stage costs; freeze / goal events, the vote; what a rollout that
 //      stops here goes on paying -> its (chunk, rollout) slot
 //      (after ev_done[g-1]: all earlier events are known)              -> ev_done[g]
 //   D' first event wins, per-step addends                              -> c_done[g]
-//      last of all: the control-cost products (mppi.py:1007-1009)      -> cc_done[g]
 //                                     cost walk over group g (stage, obstacle, unknown per step)
 //   (a rollout stopped in a zero-traction cell keeps paying where it stands: ordinary records)
 //   ... then, by the cost wave: terminal cost, the T control-cost terms
@@ -54,7 +57,10 @@
 // measured at 87 cycles per step, throughput-bound), the cost walk, which runs last, is wave 1.  The
 // chunk waves fill the remaining slots -- 2, 3, 4, 4 per SIMD -- and carry falling priorities in the
 // order their groups are needed, so that on every SIMD the Philox blocks of the early groups finish
-// first (kGroupOfWave); the two on SIMD 0 own the last groups.
+// first (kGroupOfWave); the two on SIMD 0 own the last groups.  The table priority holds for A, C and D';
+// B runs at priority 3 in every chunk wave off SIMD 0 (the position walk needs the increments in group
+// order, one B behind the headings), and the theta and x | y walks look at a group's flag one group
+// late, behind which they request its operands at once (walk_groups_late_look).
 // A failed vote: the tile is rolled out sequentially by the cost wave with the arithmetic of
 // k_rollout_map<DET, exact> (map_step) -- the same bits again, slowly; the host stops launching this
 // kernel on a map where most tiles fail (review_speculation).
@@ -502,6 +508,51 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       if (v1) fetch(PhaseTag<1>(), gi + 3);
     }
   };
+  // The theta and the x | y walk: the same walk with the look at a group's flag one group LATER.  When a register set
+  // falls free the flag of the group it is for is read relaxed and the group's operands are requested BEHIND that
+  // read, unconditionally; the answer is looked at after the other set's group has been walked.  The LDS serves a
+  // wave's reads in issue order (the argument finish_tile's look ahead rests on): operands requested behind a flag that
+  // was up are the stored ones; if it was not up they are dropped, the flag is polled and the operands are requested
+  // again -- the miss path of walk_groups.  A flag has one group's walk (~0.5k cycles) longer to come up before the
+  // walk misses it, and the path of a hit is the one above instruction for instruction.  No new flag, no new wait.
+  // (The cost walk stays on walk_groups: its last fetch carries the look ahead of the tail.)
+  auto walk_groups_late_look = [&](const int* in_flags, auto&& fetch, auto&& run) {
+    int v0 = wait_for(&in_flags[0]);
+    fetch(PhaseTag<0>(), 0);
+    int raw1 = 0;
+    if (W > 1) {
+      raw1 = glance(&in_flags[1]);
+      pin_memory_order();
+      fetch(PhaseTag<1>(), 1);
+    }
+    for (int gi = 0; gi < W; gi += 2) {
+      run(PhaseTag<0>(), gi, v0);
+      if (gi + 1 >= W) break;
+      int v1 = settle(raw1);
+      if (!v1) {
+        v1 = wait_for(&in_flags[gi + 1]);
+        fetch(PhaseTag<1>(), gi + 1);
+      }
+      int raw0 = 0;
+      if (gi + 2 < W) {
+        raw0 = glance(&in_flags[gi + 2]);
+        pin_memory_order();
+        fetch(PhaseTag<0>(), gi + 2);
+      }
+      run(PhaseTag<1>(), gi + 1, v1);
+      if (gi + 2 >= W) break;
+      v0 = settle(raw0);
+      if (!v0) {
+        v0 = wait_for(&in_flags[gi + 2]);
+        fetch(PhaseTag<0>(), gi + 2);
+      }
+      if (gi + 3 < W) {
+        raw1 = glance(&in_flags[gi + 3]);
+        pin_memory_order();
+        fetch(PhaseTag<1>(), gi + 3);
+      }
+    }
+  };
 
   // what every tile ends with, by its cost wave (wave 1): the control cost of all T steps after the terminal cost, the
   // cost, the weights relative to the tile's minimum and the header of the tile's packet
@@ -622,23 +673,22 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       double v64 = (double)vf;
       out[0] = vf;  // row 0: the value before step 0
       double inc[2][8];
-      walk_groups(
-          in_flags,
-          [&](auto set, int gi) {
-            const double* at = reinterpret_cast<const double*>(grp + (size_t)gi * 4096 + half) + r;
+      auto fetch = [&](auto set, int gi) {
+        const double* at = reinterpret_cast<const double*>(grp + (size_t)gi * 4096 + half) + r;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) inc[decltype(set)::value][q] = at[(size_t)q * R];
-          },
-          [&](auto set, int gi, int) {
-            float* to = out + (size_t)(8 * gi + 1) * OS;
+        for (int q = 0; q < 8; ++q) inc[decltype(set)::value][q] = at[(size_t)q * R];
+      };
+      auto run = [&](auto set, int gi, int) {
+        float* to = out + (size_t)(8 * gi + 1) * OS;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              vf = (float)fma(coeff, inc[decltype(set)::value][q], v64);
-              v64 = (double)vf;
-              to[q * OS] = vf;  // row t + 1: the value after step t
-            }
-            raise(&out_flags[gi], 1);
-          });
+        for (int q = 0; q < 8; ++q) {
+          vf = (float)fma(coeff, inc[decltype(set)::value][q], v64);
+          v64 = (double)vf;
+          to[q * OS] = vf;  // row t + 1: the value after step t
+        }
+        raise(&out_flags[gi], 1);
+      };
+      walk_groups_late_look(in_flags, fetch, run);
     };
     if (walker == 0) {
       // theta: rows of R floats (the upper lanes mirror the lower ones: the same value to the same address)
@@ -832,11 +882,20 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
     // Here, while the theta walk has not reached this group yet (every group waits >= 0.5k cycles for its headings):
     // at the end of the wave they competed with the late groups' lookups and records for the SIMD, and the noise
     // stayed in registers all the way
+    // (behind b_done instead, in the stretch where the wave waits for its positions: measured slower, or equal --
+    //  profiles/HISTORY.md, "C2 rollout: position increments ahead of the position walk")
     chunk_ccr();
     MPPI_STAMP(stamp_wg && c < 16, stamp_base + 2);
 
     // ---------------------------------------------------------------- B: sin / cos of this wave's headings
+    // At priority 3 from the moment the headings are seen until b_done is up, whatever the wave's table priority: the
+    // x | y walk needs the increments in group order, about one B behind th_done[g], and the SIMD-mates of a late
+    // group's wave are in C / D' of early groups by then -- records the stage-cost walk is thousands of cycles away
+    // from.  Not waves 8 and 12: they share SIMD 0 with the two walkers and stay at 0 (measured both ways).
     (void)wait_for(&th_done[g]);
+    const int prio_cd = (c & 3) == 0 ? 0 : prio;  // (what the wave carries in C and D')
+    const bool b_raised = prio_cd != 3 && (c & 3) != 0;  // (wave-uniform: s_setprio does not look at EXEC)
+    if (b_raised) __builtin_amdgcn_s_setprio(3);
     {
       // (one full evaluation per lane; its other three headings by the exact-increment rotation of the
       //  pipelined kernels when the increment is small enough for it -- |delta| <= 0.36 rad, else in full)
@@ -857,6 +916,13 @@ __global__ __launch_bounds__(1024) void k_rollout_scan_exact(DevParams P, const 
       }
     }
     raise(&b_done[g], 1);
+    if (b_raised) {  // (back to the table value for C and D')
+      switch (prio_cd) {
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        default: __builtin_amdgcn_s_setprio(0); break;
+      }
+    }
     MPPI_STAMP(stamp_wg && c < 16, stamp_base + 3);
 
     // ---------------------------------------------------------------- C: lookups, stage costs, events

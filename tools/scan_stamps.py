@@ -17,7 +17,8 @@ earlier groups' events (12), events published (5), own events looked up and term
 (14), selects (15), records stored (6); every wave: end (8), first barrier passed
 (9); chunk waves: noise generated (10), control-cost products (2: after the records).
 k_rollout_scan_exact as it is launched today: the cost walk is wave 1 (the x | y walk wave 4), and under each
-workgroup's rows a derived table sets the stage-cost walk against its producers, group by group (stage_walk_table).
+workgroup's rows a derived table sets the stage-cost walk against its producers, group by group (stage_walk_table),
+and a second one the position walk against the chunk waves' B phases (increments_table).
 A stamp is not free: one more in the cost walker's loop moved its later stamps by 0.2-0.5k cycles
 (profiles/HISTORY.md, "C2 rollout: the stage-cost walk")."""
 import argparse
@@ -64,12 +65,60 @@ def stage_walk_table(rows, t0):
     print("  walk done %d, last records ready %d: %d behind" % (done, ready_last, done - ready_last))
 
 
+def increments_table(rows, t0, glance_back=2):
+    """The middle of the launch: position increments against the position walk, group by group.  Per group: when its
+    heading increments were stored (slot 1 of its chunk wave), when its headings were there (th_done: NOT stamped --
+    the theta walker carries no stamp inside its loop; derived from its end, slot 1 of wave 0, and a constant rate
+    since group 0's increments, never earlier than the group's own increments + one group), the chunk wave behind its
+    control-cost terms (2), behind b_done (3), xy_done seen (4), the lag xy_done seen - b_done, and whether the walk's
+    look at b_done[g] can have hit: the look for group g is issued when the walk has published group g - glance_back
+    (2: walk_groups_late_look, the walk as it is; 3: walk_groups, the walk before the look was moved), read here as
+    `xy_done[g - glance_back] seen` by that group's chunk wave -- at most a poll late.  Groups 0 and 1 are waited for /
+    looked at once at the start of the walk: no glance.  Last lines: both walks' ends, and the
+    control-cost terms (cc_done raised: slot 2) against the last records (c_done: slot 6) -- the cost wave looks at
+    cc_done with its last fetch."""
+    wave_of = {g: c for c, g in GROUP_OF_WAVE.items() if rows[c][0]}
+    if not wave_of or not rows[0][1] or not rows[4][1]:
+        return
+    groups = sorted(wave_of)
+    at = lambda g, slot: int(rows[wave_of[g]][slot] - t0) if rows[wave_of[g]][slot] else None  # noqa: E731
+    th_end, xy_end = int(rows[0][1] - t0), int(rows[4][1] - t0)
+    a0 = at(0, 1) or 0
+    rate = (th_end - a0) / len(groups)
+    print(" position increments: group, wave, a_done, th_done (derived), ccr done, b_done, xy_done seen, B after th_done,"
+          " xy - b, glance")
+    th, misses = {}, 0
+    for g in groups:
+        a, ccr, b, xy = at(g, 1), at(g, 2), at(g, 3), at(g, 4)
+        th[g] = int(max(th_end - (groups[-1] - g) * rate, (a or 0) + rate))
+        if g >= 2 and b is not None:
+            # (a look issued before the walk has published anything: when it starts on group 0)
+            seen = at(g - glance_back, 4) if g >= glance_back else (at(0, 3) or 0)
+            hit = seen is not None and b < seen
+            misses += 0 if hit else 1
+            glance = "hit" if hit else "MISS"
+        else:
+            glance = "-"
+        print("  %5d %4d %8s %8d %8s %8s %8s %8s %8s   %s" % (
+            g, wave_of[g], a, th[g], ccr, b, xy, b - th[g] if b is not None else "-",
+            xy - b if None not in (xy, b) else "-", glance))
+    cc_last = max(at(g, 2) or 0 for g in groups)
+    c_last = at(groups[-1], 6)
+    print("  theta walk done %d (%.0f per group), x | y walk done %d, %d behind; %d glances missed" % (
+        th_end, rate, xy_end, xy_end - th_end, misses))
+    if c_last is not None:
+        print("  last control-cost terms %d, last group's records %d: the terms %d ahead" % (cc_last, c_last, c_last - cc_last))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--math", default="fast", choices=["fast", "exact"])
     ap.add_argument("--workload", default="c2", help="c2s / c2c: the exact three-wave schedule inside the kernel (direct mode; slots 11 .. 15 of waves 0 state, 1 cost, 2 producer: entered, first barrier passed, chunk 0 done, chunk 6 done, loop end)")
+    ap.add_argument("--glance-back", type=int, default=2, dest="glance_back",
+                    help="position-increments table: the x | y walk looks at b_done[g] when it has published group g - this many "
+                         "(2: the kernel as it is; 3: a library from before the look was moved)")
     ap.add_argument("--iterations", type=int, default=1, help="iterations per call (>1: the last launch folds the previous update)")
     args = ap.parse_args()
     from mppi_numba_amd import _lib
@@ -102,6 +151,7 @@ def main():
                 print("%5d  " % c + "".join("%8s" % (int(v - t0) if v else "-") for v in r))
         if args.math == "exact" and args.workload in ("c2", "c2m"):
             stage_walk_table(rows, t0)
+            increments_table(rows, t0, args.glance_back)
     rows = [st[64 + 16 * c: 64 + 16 * c + 12] for c in range(16)]
     t0 = min(int(r[0]) for r in rows if r[0])
     # every workgroup's entry / exit (slots 2048 + 2 b, 2049 + 2 b) when the kernel records them
