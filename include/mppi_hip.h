@@ -640,6 +640,25 @@ int mppi_planner_limit_noise(mppi_planner* p);
 int mppi_planner_set_applied_control(mppi_planner* p, int count, const float* u);
 int mppi_planner_get_applied_control(mppi_planner* p, float* u);
 
+/* MPPI_MODE_BAREBONE: the vehicle.  MPPI_DRIVE_UNICYCLE (the notebook's, at creation): the second control is the yaw
+ * rate w.  MPPI_DRIVE_CAR: the second control is the path curvature kappa in 1/m -- tan(steering angle) / wheelbase --
+ * and the yaw rate a step applies is the float32 product w = fmul_rn(v, kappa) of the clipped controls, rounded once,
+ * never an fma: the car turns only while it moves, and reversing with the wheel turned left swings the heading the other
+ * way.  wrange of mppi_params is then the curvature range, u_std[1] the curvature noise, and the second component of
+ * mppi_planner_set_control_limits bounds the curvature's rate (k_noise_limit is unchanged).  The rollouts of both kernel
+ * families, the visualisation rollouts (row 0: u_cur unclipped, w = fmul_rn(v, kappa)), the fleets' plans and the
+ * simulated world of mppi_planner_closed_loop (float64: th += dt * ((double)v * (double)kappa), the product exact) follow;
+ * everything downstream of the pose is what it was.  The host's bounds on the heading increment -- (cos, sin) by rotation
+ * iff dt * max|w| <= 0.36 rad -- take max|w| = max|v| * max|kappa|.  mppi_planner_last_rollout_kernel gains " drive=car"
+ * at the end, in both families; with MPPI_DRIVE_UNICYCLE every bit, every launch and every name is as before.  The value
+ * travels by value in the launches: a change drains the stream and drops the captured graphs; an equal value again costs
+ * a comparison.  One drive for every problem of a batched handle.  MPPI_ERR_INVALID, the handle keeping what it had: a
+ * handle that is not in barebone mode, a value that is neither of the two. */
+#define MPPI_DRIVE_UNICYCLE 0
+#define MPPI_DRIVE_CAR 1
+int mppi_planner_set_drive(mppi_planner* p, int drive);
+int mppi_planner_get_drive(mppi_planner* p, int* drive);
+
 /* MPPI_MODE_BAREBONE, a batched handle (B >= 2) in crowd mode: a body fleet -- fleet mode for
  * robots that are not discs.  Every robot of the batch is the same body of n_discs discs (1 .. 8),
  * discs (n_discs, 3) float32 with the rows and the rules of mppi_planner_set_footprint; count = B

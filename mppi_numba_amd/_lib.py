@@ -16,6 +16,7 @@ MPPI_OK = 0
 MODE_DET, MODE_SPEED_MAP, MODE_TDM, MODE_BAREBONE = 0, 1, 2, 3
 RNG_PHILOX, RNG_XOROSHIRO = 0, 1
 MATH_EXACT, MATH_FAST = 0, 1
+DRIVE_UNICYCLE, DRIVE_CAR = 0, 1
 COMM_ID_BYTES = 128
 PREP_TDM, PREP_DET, PREP_SPEED = 0, 1, 2
 DEBUG_NO_SPEC_KERNEL, DEBUG_NO_SPECULATION, DEBUG_NO_DEEP_KERNEL, DEBUG_CC_GLOBAL = 1, 2, 4, 8
@@ -141,6 +142,8 @@ SIGNATURES = {
     "mppi_planner_limit_noise": [_vp],
     "mppi_planner_set_applied_control": [_vp, C.c_int, _f32p],
     "mppi_planner_get_applied_control": [_vp, _f32p],
+    "mppi_planner_set_drive": [_vp, C.c_int],
+    "mppi_planner_get_drive": [_vp, C.POINTER(C.c_int)],
     "mppi_planner_set_u": [_vp, _f32p],
     "mppi_planner_get_u": [_vp, _f32p],
     "mppi_planner_get_u_prev": [_vp, _f32p],

@@ -180,6 +180,29 @@ Without the key every bit and every call is as before.  Limits: one pair for eve
 separate braking bound); first differences only (no jerk bound); the visualisation rollouts read the block as it stands;
 the control-cost term weighs e'.  The map-mode classes do not read the key.
 
+Car-like steering: params['drive'] = 'car' ('unicycle' is the key left out; any other string raises ValueError).  The
+notebook's vehicle is a unicycle: w is commanded independently of v, so every rollout -- and the sequence solve() returns --
+may turn on the spot, which no tugger, forklift or Ackermann cart can follow.  With 'car' the second control is the path
+curvature kappa in 1/m instead of the yaw rate: wrange is the curvature range, +-tan(max_steer) / wheelbase
+(curvature_of_steering(); steering_of_curvature() goes back), u_std[1] the curvature noise, and the second component of
+'accel_limits' a bound on the curvature's rate -- a steering-rate bound.  A step, in float32, every operation rounded once:
+  v = clip(float32(u[t][0] + e[n, t][0]), vrange)      kappa = clip(float32(u[t][1] + e[n, t][1]), wrange)
+  w = float32(v * kappa)                               never an fma; the unicycle: w = kappa
+  x, y                                                 as ever, from the heading BEFORE the step and float32(dt * v)
+  th' = float32(th + float32(dt * w))
+so the car turns only while it moves, its turning radius is never below 1 / max|kappa|, and reversing with the wheel turned
+left swings the heading the other way.  Everything downstream of the pose is untouched: goal distance, discs, walls,
+footprint chords, rings, occupancy, disc samples, control cost (on the curvature's noise), the update and the guide.  The
+rollouts of both kernel families, get_state_rollout() (row 0: u_cur unclipped, w = float32(v * kappa)), the plans of both
+fleets and closed_loop()'s world (float64: th += dt * (float64(v) * float64(kappa))) follow; shift_and_update(),
+set_applied_control() and closed_loop() keep their meaning with the second component read as curvature.  The host bounds
+the heading increment of a step by dt * max|v| * max|kappa| where it bounded it by dt * max|w|: (cos, sin) by rotation needs
+that at 0.36 rad at the most.  last_rollout_kernel() ends in ' drive=car'; the `drive` property reads the library's value
+back.  Without the key every bit, every launch and every kernel name is as before.  Limits: kappa is not the steering angle
+delta (convert with the two helpers); a steering-rate bound through 'accel_limits' is a bound on kappa's rate, not on
+delta's; reverse costs what forward costs (no separate reverse-gear cost: keep vrange[0] >= 0 to forbid it); one drive for
+every problem of a batch.  The map-mode classes do not read the key.
+
 Occupancy-grid obstacles: params['occupancy'], a dict with 'origin' (x, y), 'resolution', 'cells' (ny, nx) -- any integer or
 bool dtype, non-zero means occupied -- and optionally 'inflate' (default 0; for a point robot its radius) and 'substeps' (an
 int in 1 .. 8, default 1); the floats rounded once to float32.  A costmap as it comes from a lidar, without fitting discs or
@@ -475,6 +498,18 @@ def fleet_others(count):
     return np.array([[b for b in range(count) if b != a] for a in range(count)], dtype=np.int64).reshape(count, max(count - 1, 0))
 
 
+def curvature_of_steering(steer, wheelbase):
+    """The path curvature in 1/m of a car whose front wheel is turned by `steer` rad (the bicycle model): tan(steer) /
+    wheelbase.  With params['drive'] = 'car', wrange is +-curvature_of_steering(max_steer, wheelbase)."""
+    return np.tan(np.asarray(steer, dtype=np.float64)) / np.asarray(wheelbase, dtype=np.float64)
+
+
+def steering_of_curvature(kappa, wheelbase):
+    """The steering angle in rad that follows a curvature: arctan(wheelbase * kappa) -- what to command from a car plan's
+    second component."""
+    return np.arctan(np.asarray(wheelbase, dtype=np.float64) * np.asarray(kappa, dtype=np.float64))
+
+
 def _is_track_set(obstacle_set):
     return np.asarray(obstacle_set[0]).ndim == 3
 
@@ -661,6 +696,17 @@ def _pack_limits(planner, acc):
     return (np.ascontiguousarray(np.broadcast_to(_f32(acc), (2,))),)
 
 
+_DRIVES = {"unicycle": _lib.DRIVE_UNICYCLE, "car": _lib.DRIVE_CAR}
+
+
+def _read_drive(planner, p):
+    """'unicycle' is the key left out (None): nothing is handed over unless a car was."""
+    drive = p['drive']
+    if not isinstance(drive, str) or drive not in _DRIVES:
+        raise ValueError("params['drive'] is 'unicycle' or 'car', got {!r}".format(drive))
+    return None if drive == "unicycle" else (np.asarray([_DRIVES[drive]], dtype=np.int32),)
+
+
 def _read_wall_tracks(planner, p):
     if planner._held["fleet"].sent is not None or planner._held["fleet_bodies"].sent is not None:
         raise ValueError("params hold 'wall_tracks' while the fleet is on: the fleet makes every problem's wall set "
@@ -775,6 +821,7 @@ _KINDS = (
           "mppi_planner_set_noise_smoothing", (None,), _KEEP, None),
     _Kind("limits", "accel_limits", _read_one("accel_limits"), _pack_limits,
           "mppi_planner_set_control_limits", (None,), _KEEP, None),
+    _Kind("drive", "drive", _read_drive, lambda planner, drive: (int(drive[0]),), "mppi_planner_set_drive", (0,), _KEEP, None),
     _Kind("wall_tracks", "wall_tracks", _read_wall_tracks,
           lambda planner, tr, hw: _pack_wall_tracks([(tr, hw)], "params['wall_tracks']"),
           "mppi_planner_set_wall_tracks", (0, None, 0, None, None), _FETCH, None),
@@ -965,6 +1012,14 @@ class MPPI_Numba(object):
         acc, held = np.zeros(2, dtype=np.float32), C.c_int(0)
         _lib.call("mppi_planner_get_control_limits", self._handle, _lib.ptr(acc, C.c_float), C.byref(held))
         return acc if held.value else None
+
+    # ------------------------------------------------------------------ car-like steering
+    @property
+    def drive(self):
+        """The vehicle the library holds: 'unicycle', or 'car' (params['drive']: the second control is the curvature)."""
+        drive = C.c_int(0)
+        _lib.call("mppi_planner_get_drive", self._handle, C.byref(drive))
+        return next(name for name, value in _DRIVES.items() if value == drive.value)
 
     @property
     def applied_control(self):
@@ -1181,6 +1236,8 @@ class MPPI_Numba(object):
         walk_all = self._walk_all or not _OPTIONAL_KEYS.isdisjoint(p)
         moving_goal = walk_all and "goal_track" in p
         if walk_all:
+            if "drive" in p:  # (a string that names no drive: refused ahead of every call)
+                _read_drive(self, p)
             self._walk_all = True  # (until the walk has come to its end)
             self._sync_kind(p, _GOAL)
             if "guide" in p:  # (its refusals -- no 'xgoal' among them -- ahead of the params struct, which reads 'xgoal')

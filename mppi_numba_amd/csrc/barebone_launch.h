@@ -306,6 +306,8 @@ static int launch_barebone(mppi_planner* p, DevParams d, bool rot) {
   const BareboneChoice c = barebone_choose(held);
   if (!BATCHED) d.n_obstacles = c.kmax;  // (the classic single launch: the count is a kernel argument, the set the one chosen)
   if (c.family == kBareboneRefused) return barebone_refuse(c, held.T);
-  if (c.family == kBareboneCrowd) return launch_barebone_crowd<EXACT, BATCHED>(p, d, c, rot);
-  return launch_barebone_default<EXACT, BATCHED>(p, d, c, rot);
+  TRY(c.family == kBareboneCrowd ? (launch_barebone_crowd<EXACT, BATCHED>(p, d, c, rot))
+                                 : (launch_barebone_default<EXACT, BATCHED>(p, d, c, rot)));
+  if (d.car) p->last_rollout += " drive=car";  // (car-like steering, mppi_planner_set_drive: either family, last of the text)
+  return MPPI_OK;
 }

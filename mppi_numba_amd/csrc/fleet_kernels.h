@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void k_fleet_plans(DevParams P, const float2* _
     if (t < T) {  // barebone_next_pose's controls with e = 0
       const float2 ut = u[t];
       const float v = clip_f32(ut.x + 0.0f, P.v_lo, P.v_hi);
-      const float w = clip_f32(ut.y + 0.0f, P.w_lo, P.w_hi);
+      const float w = barebone_yaw_rate(P, v, clip_f32(ut.y + 0.0f, P.w_lo, P.w_hi));
       dtv = P.dt * v;
       dtw = P.dt * w;
     }

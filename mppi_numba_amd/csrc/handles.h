@@ -161,6 +161,9 @@ struct mppi_planner {
   // step d = accel * dt is formed at the launch, from the params in force.
   bool limits_held = false;
   float limit_accel[2] = {0.0f, 0.0f};
+  // the vehicle of the barebone mode (mppi_planner_set_drive): MPPI_DRIVE_UNICYCLE, or MPPI_DRIVE_CAR -- the second control
+  // is the path curvature and a step turns by dt * v * kappa (DevParams::car, WorldLoop::car, MapHeld::drive)
+  int drive = 0;
   // the control in force when the plan starts (mppi_planner_set_applied_control; k_world_step in closed_loop): the limits
   // count from it.  Stored whether or not limits are held; zero at creation.
   float2* anchor = nullptr;  // [B]

@@ -80,6 +80,7 @@ static DevParams make_dev_params(const mppi_planner* p) {
   d.cc_k1 = (float)((double)a.lambda_weight / d.s1sq);
   d.inv_v_post_den = 1.0 / d.v_post_den;
   d.neg_log2e_over_lambda = -1.4426950408889634 / (double)a.lambda_weight;
+  d.car = p->drive == MPPI_DRIVE_CAR ? 1 : 0;
   return d;
 }
 
@@ -316,6 +317,7 @@ static MapHeld map_held(const mppi_planner* p) {
   h.dt = a.dt; h.res = a.res; h.xlo = a.xlo; h.ylo = a.ylo;
   h.vrange[0] = a.vrange[0]; h.vrange[1] = a.vrange[1]; h.wrange[0] = a.wrange[0]; h.wrange[1] = a.wrange[1];
   h.x0 = a.x0[0]; h.y0 = a.x0[1];
+  h.drive = p->drive;
   const MapStartBounds inside = map_start_bounds(h);
   h.starts_inside = map_start_inside(inside, h.x0, h.y0);
   if (p->inst_set)  // (the host mirror of the per-problem starts: what the window origins are planned from, apply_window)

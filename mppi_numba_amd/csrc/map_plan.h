@@ -25,12 +25,14 @@ struct MapHeld {
   int starts_inside;  // every start cell is a cell of the map (map_start_inside): x0, and each problem's of a batched handle
   double lin_lo, lin_ratio, ang_lo, ang_ratio;
   float dt, res, xlo, ylo, vrange[2], wrange[2], x0, y0;
+  int drive;  // barebone mode: MPPI_DRIVE_UNICYCLE (0), or MPPI_DRIVE_CAR: wrange is the curvature range, the yaw rate v * kappa
 };
 
 inline int map_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- how far a rollout gets ----------------------------------------------------------------------------------------
-// vmax, wmax: max |v|, max |w| of the control ranges; trmax_*: max |traction| of the packed grids (barebone mode: 1);
+// vmax, wmax: max |v|, max |w| of the control ranges (car mode: max |w| = max |v| * max |kappa|, the largest yaw rate a step
+// can apply); trmax_*: max |traction| of the packed grids (barebone mode: 1);
 // step_cells: cells per step at the most, dt * max|v| * max|traction| / res; reach_m: metres within the horizon, finite or not
 struct MapReach {
   double vmax, wmax, trmax_lin, trmax_ang, step_cells, reach_m;
@@ -41,6 +43,7 @@ inline MapReach map_reach(const MapHeld& h) {
   MapReach r;
   r.vmax = std::fmax(std::fabs((double)h.vrange[0]), std::fabs((double)h.vrange[1]));
   r.wmax = std::fmax(std::fabs((double)h.wrange[0]), std::fabs((double)h.wrange[1]));
+  if (h.mode == MPPI_MODE_BAREBONE && h.drive == MPPI_DRIVE_CAR) r.wmax = r.vmax * r.wmax;
   r.trmax_lin = std::fmax(std::fabs(h.lin_lo), std::fabs(h.lin_lo + (double)h.lin_max_byte * h.lin_ratio));
   r.trmax_ang = h.mode == MPPI_MODE_BAREBONE
                     ? 1.0

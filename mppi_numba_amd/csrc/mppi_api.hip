@@ -1226,6 +1226,7 @@ extern "C" int mppi_planner_closed_loop(mppi_planner* p, mppi_tdm* lin, mppi_tdm
     L.goal_rows = sc.goal.rows;
     L.goal_stride = sc.goal.count > 1 ? sc.goal.rows : 0;
     L.anchor = nominal && p->limits_held ? p->anchor : nullptr;  // (the limits of the next plan count from the u0 applied)
+    L.car = nominal && p->drive == MPPI_DRIVE_CAR ? 1 : 0;
     L.map_rows = plan.rows; L.map_pitch = p->pitch16;
     L.win_rows = plan.win_rows; L.win_cols = plan.win_cols;
     // (a window smaller than the map is a reach square: its half width is what plan_lds_window used)
@@ -1432,6 +1433,29 @@ extern "C" int mppi_planner_get_control_limits(mppi_planner* p, float accel[2], 
     accel[0] = p->limit_accel[0];
     accel[1] = p->limit_accel[1];
   }
+  return MPPI_OK;
+}
+
+// The vehicle of the barebone mode (include/mppi_hip.h): the drive lives in the handle; make_dev_params, map_held and the
+// closed loop's WorldLoop read it, so it travels by value in every launch and a change drops the captured graphs.
+extern "C" int mppi_planner_set_drive(mppi_planner* p, int drive) {
+  REQUIRE(p, MPPI_ERR_INVALID, "NULL planner");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID,
+          "the drive belongs to the barebone mode (mode %d): the map modes integrate the unicycle with traction", p->cfg.mode);
+  REQUIRE(drive == MPPI_DRIVE_UNICYCLE || drive == MPPI_DRIVE_CAR, MPPI_ERR_INVALID,
+          "drive %d: MPPI_DRIVE_UNICYCLE (%d) or MPPI_DRIVE_CAR (%d)", drive, MPPI_DRIVE_UNICYCLE, MPPI_DRIVE_CAR);
+  if (drive == p->drive) return MPPI_OK;
+  HIP_TRY(hipSetDevice(p->cfg.device));
+  TRY(drain_stream(p));
+  p->drive = drive;
+  drop_graphs(p);
+  return MPPI_OK;
+}
+
+extern "C" int mppi_planner_get_drive(mppi_planner* p, int* drive) {
+  REQUIRE(p && drive, MPPI_ERR_INVALID, "NULL argument");
+  REQUIRE(p->cfg.mode == MPPI_MODE_BAREBONE, MPPI_ERR_INVALID, "the drive belongs to the barebone mode (mode %d)", p->cfg.mode);
+  *drive = p->drive;
   return MPPI_OK;
 }
 

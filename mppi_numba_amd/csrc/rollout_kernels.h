@@ -111,7 +111,16 @@ struct DevParams {
   // its centre at time j * dt from "now", and "now" is row `track_off` (single-problem launches; a batch reads its
   // problems' offsets from their BatchInst).  0 rows: static discs
   int track_rows, track_off;
+  // barebone mode, car-like steering (mppi_planner_set_drive): != 0: the second control is the path curvature kappa in 1/m
+  // and the yaw rate of a step is the float32 product v * kappa, rounded once; 0: the second control is the yaw rate (the
+  // notebook's unicycle).  Last, so that no other field moves.  (Not in the padding behind ktime_waves, which would keep the
+  // struct's size: the crowd kernel then is compiled to other registers (supposed; no operation differs), and one sample form with a footprint
+  // miscounted its wall hits -- profiles/HISTORY.md, "Barebone car-like steering".)
+  int car;
 };
+
+// The yaw rate a barebone step applies, from the clipped controls: k itself (k * 1.0f: the bits of k), or v * k in car mode.
+__device__ __forceinline__ float barebone_yaw_rate(const DevParams& P, float v, float k) { return k * (P.car ? v : 1.0f); }
 
 // What differs between the problems of a batched handle (mppi_planner_set_instances).
 struct BatchInst {
@@ -1500,7 +1509,7 @@ __device__ __forceinline__ void barebone_next_pose(const DevParams& P, float2 ut
                                                    [[maybe_unused]] double rs, [[maybe_unused]] double rc, float& nx,
                                                    float& ny, float& nth) {
   float v = clip_f32(ut.x + e.x, P.v_lo, P.v_hi);
-  float w = clip_f32(ut.y + e.y, P.w_lo, P.w_hi);
+  float w = barebone_yaw_rate(P, v, clip_f32(ut.y + e.y, P.w_lo, P.w_hi));  // (car mode: the clipped curvature times v)
   float dtv = P.dt * v;  // float32 * float32 first (cell 3: dt_d*v_noisy*math.cos(...))
   if (EXACT) {
     double sn, cs;
@@ -1660,7 +1669,7 @@ __global__ __launch_bounds__(64) void k_rollout_barebone(DevParams P, const floa
         for (int j = 0; j < kNoiseBatch; ++j) {
           const float2 ut = u[t0 + j];
           const float v = clip_f32(ut.x + e_cur[j].x, P.v_lo, P.v_hi);
-          const float w = clip_f32(ut.y + e_cur[j].y, P.w_lo, P.w_hi);
+          const float w = barebone_yaw_rate(P, v, clip_f32(ut.y + e_cur[j].y, P.w_lo, P.w_hi));
           q64[j] = (double)(P.dt * v);  // float32 * float32 first (cell 3: dt_d*v_noisy*math.cos(...))
           const float nth = th + P.dt * w;
           sincos_increment_f64((double)nth - (double)th, sd[j], cd[j]);  // exact increment of the ROUNDED heading
@@ -1778,7 +1787,7 @@ __global__ void k_state_rollout(DevParams P, const uint32_t* __restrict__ cells,
       float dtv = P.dt * v;
       float nx = (float)fma((double)dtv, c, (double)x);
       float ny = (float)fma((double)dtv, s, (double)y);
-      th = th + P.dt * w;
+      th = th + P.dt * barebone_yaw_rate(P, v, w);  // (car mode: w holds the curvature; row 0 unclipped like v)
       x = nx; y = ny;
     } else {
       int xi = clamp_index(floordiv_to_int(x - P.xlo, P.res, P.inv_res), P.cols);

@@ -103,12 +103,16 @@ struct WorldLoop {
   // barebone mode with acceleration limits (mppi_planner_set_control_limits): [B] the control in force when the next plan
   // starts -- the u0 just applied; nullptr: no limits are held (the map modes never set it)
   float2* anchor;
+  // barebone mode, car-like steering (mppi_planner_set_drive): != 0: u0.y is the path curvature and the world turns by
+  // dt * v * kappa -- the product of two float32 factors, exact in float64; 0: u0.y is the yaw rate
+  int car;
 };
 
 // One block per problem.  The body of the notebook's loop after solve() (test.ipynb cell 4; barebone_mppi_numba.ipynb
 // cell 7 is the same with traction 1, G.lin == nullptr):
 //   u_curr = useq[0]; (lt, at) = traction_grid.get(x, y)
 //   x += dt*lt*cos(th)*u_curr[0]; y += dt*lt*sin(th)*u_curr[0]; th += dt*at*u_curr[1]   (float64)
+//   (car mode, WorldLoop::car: th += dt*at*(u_curr[0]*u_curr[1]), the second control being the curvature)
 //   shift_and_update(x_new, useq, 1)   (mppi.py:534-542: x0 <- x_new, u[:-1] = u[1:])
 //   goal check: ||x_new[:2] - goal|| <= goal_tolerance   (a goal that moves: the goal at the time of the new state)
 // A problem that has reached its goal is left alone (state, controls, log).
@@ -131,7 +135,8 @@ __global__ void k_world_step(WorldGrid G, WorldLoop L, BatchInst* __restrict__ i
     if (G.lin) world_lookup(G, x, y, lt, at);
     const double x1 = x + L.dt * lt * cos(th) * (double)u0.x;
     const double y1 = y + L.dt * lt * sin(th) * (double)u0.x;
-    const double th1 = th + L.dt * at * (double)u0.y;
+    const double kw = L.car ? (double)u0.x * (double)u0.y : (double)u0.y;
+    const double th1 = th + L.dt * at * kw;
     L.state[3 * b] = x1;
     L.state[3 * b + 1] = y1;
     L.state[3 * b + 2] = th1;
